@@ -37,6 +37,13 @@ probability rows travel to rank 0 in one RCCL gather per GATHER_EVERY steps (SUR
                   no staged copy is there): (i) in-process at its best thread count, (ii) one thread (how the
                   reference pipeline runs its workers) x usable cores;
   gt_concordance  arg-max of the gt21 and zygosity heads of the GPU rows vs the CPU baseline's rows on the same batch.
+
+A plain run measures the headline alone: the full-alignment workload, one handle, W warm-up steps and ONE block of exactly K
+timed steps, then the line (metric, value, unit, ms_per_step, dtype, ...).  Everything else above -- three batches in flight,
+the repeated blocks, host_inclusive, roofline, cpu_baseline, gt_concordance, the reference modules on the GPU, the pileup and
+dwell workloads and the complete record in a file -- runs only with --full.  --dump-outputs DIR writes the rows the timed path
+returned in its last step as DIR/<workload>.npy (float32; ranks > 0 as <workload>_rank<r>.npy): inputs and weights are seeded,
+so two builds run with the same arguments can be compared row for row.
 """
 import argparse
 import json
@@ -134,7 +141,7 @@ def run_workload(name, args, rank, world, local):
     # --streams S > 1: S model handles (own workspace each) on S HIP streams, steps issued round-robin -- a worker
     # that keeps S batches in flight, which is how the reference itself drives a GPU (free_MB // 8000 concurrent
     # workers per device, clair3/CallVariantsFromCffiGPU.py:55-56).  Every step is still one complete forward pass.
-    S = args.streams if args.streams > 0 else 3
+    S = (args.streams if args.streams > 0 else 3) if args.full else 1
     models = [model] + [build_model(kind, channels, indel, local)[0] for _ in range(S - 1)]
     streams = [torch.cuda.Stream(device=dev) for _ in models]
     # part of model set-up, like the weight upload: every handle sizes its device workspace on its first batch
@@ -223,6 +230,7 @@ def run_workload(name, args, rank, world, local):
 
     describe = lambda mi: mi.describe()
     single_blocks, single_own = timed(1)
+    dump_rows = last_rows[0].float().cpu().numpy() if args.dump_outputs else None  # the headline's last timed step
     variants = {"one_batch_in_flight": describe(model)}
     if S > 1:
         for mi in models:
@@ -249,18 +257,19 @@ def run_workload(name, args, rank, world, local):
         "value": n_total * args.steps / elapsed, "ms_per_step": 1e3 * elapsed / args.steps,
         "value_stats": stats(multi_blocks if in_flight > 1 else single_blocks),
         "one_batch_in_flight": {"value": n_total * args.steps / single, "ms_per_step": 1e3 * single / args.steps, **stats(single_blocks)},
-        f"{S}_batches_in_flight": {"value": n_total * args.steps / multi, "ms_per_step": 1e3 * multi / args.steps, **stats(multi_blocks)},
         "kernel_variants": variants,
         "flop_per_window": flop_w, "bytes_per_window": bytes_w,
         "range_flag_raised": any(f for f, _ in flags), "on_fp32_fallback": any(o for _, o in flags),
-        "rows_rank0": last_rows[0].cpu().numpy() if rank == 0 else None,
+        "rows_rank0": last_rows[0].cpu().numpy() if rank == 0 else None, "dump_rows": dump_rows,
     }
+    if S > 1:
+        res[f"{S}_batches_in_flight"] = {"value": n_total * args.steps / multi, "ms_per_step": 1e3 * multi / args.steps, **stats(multi_blocks)}
     if world > 1:
         res["multi_gpu"] = {**exchange.report(), "per_rank_windows_per_s": per_rank, "ranks": world,
                             "gather_every_steps": GATHER_EVERY}
 
     # ---- host-inclusive leg (H2D + kernels + D2H), N = 1 ----
-    if world == 1 and not args.no_host_leg:
+    if args.full and world == 1 and not args.no_host_leg:
         hl = {"slots_in_flight": HOST_SLOTS, "handles": 1,
               "path": "pageable numpy -> staging pool memcpy -> pinned -> H2D -> kernels -> D2H -> numpy (c3_predict_submit / _wait)"}
         # the supplementary host legs run >= 100 (B = 256 / 1024) and >= 25 (B = 1000) steps whatever --steps says: a ring of three
@@ -369,7 +378,7 @@ def run_workload(name, args, rank, world, local):
                                                    "slots_in_flight_per_handle": 2}
         res["host_inclusive"] = hl
 
-    if args.no_profiled_pass:
+    if args.no_profiled_pass or not args.full:
         return res
     # ---- profiled pass: HIP events around every kernel launch on the launch stream ----
     model.profile(True)
@@ -819,7 +828,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--workload", default="all", choices=["all"] + list(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="every leg of the record (see the module docstring); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows of the last timed step of every workload run as DIR/<workload>.npy (float32)")
+    ap.add_argument("--workload", default="all", choices=["all"] + list(WORKLOADS),
+                    help="all = full_alignment alone in a plain run, every workload with --full")
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch (parity/experiments only)")
     ap.add_argument("--streams", type=int, default=0,
                     help="batches kept in flight per GPU (model handles x HIP streams); 0 = 3")
@@ -828,12 +842,15 @@ def main():
     ap.add_argument("--no-host-leg", action="store_true")
     ap.add_argument("--no-profiled-pass", action="store_true", help="skip the HIP-event pass (for rocprofv3 runs of one leg)")
     ap.add_argument("--no-reference-gpu", action="store_true", help="skip the leg that times the reference's own modules on the GPU through PyTorch-ROCm")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of K steps each; value = the median block")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of K steps each; value = the median block (default: 5 with --full, else 1)")
     ap.add_argument("--gather-timeout", type=float, default=20.0, help="seconds RCCL's rendezvous / first gather may take before the rows go through torch.distributed (N > 1)")
     ap.add_argument("--torch-gather", action="store_true", help="N > 1: gather through torch.distributed from the start")
     ap.add_argument("--ref-gpu-worker", nargs=3, metavar=("WORKLOAD", "BUDGET", "BATCH"), help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker", nargs=5, metavar=("WORKLOAD", "THREADS", "BUDGET", "BATCH", "ROWS"), help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.cpu_worker:
         cpu_worker(args.cpu_worker[0], int(args.cpu_worker[1]), float(args.cpu_worker[2]), int(args.cpu_worker[3]),
                    args.cpu_worker[4])
@@ -866,13 +883,22 @@ def main():
                   f"--nproc-per-node {args.gpus}", file=sys.stderr)
         sys.exit(2)
 
-    names = ["full_alignment", "pileup", "full_alignment_dwell"] if args.workload == "all" else [args.workload]
+    if args.workload != "all":
+        names = [args.workload]
+    else:
+        names = ["full_alignment", "pileup", "full_alignment_dwell"] if args.full else ["full_alignment"]
     results = {n: run_workload(n, args, rank, world, local) for n in names}
     head = results[names[0]]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for n, r in results.items():
+            np.save(os.path.join(args.dump_outputs, n + (f"_rank{rank}" if rank else "") + ".npy"),
+                    r.pop("dump_rows").astype(np.float32))
 
     if rank == 0:
         def sub_line(n, r, budget):
             rows = r.pop("rows_rank0", None)
+            r.pop("dump_rows", None)
             sub = {"value": r["value"], "unit": "candidate-windows/s", "ms_per_step": r["ms_per_step"],
                    "batches_in_flight": r["batches_in_flight"], "one_batch_in_flight": r["one_batch_in_flight"],
                    **{k: v for k, v in r.items() if k.endswith("_batches_in_flight") and k != "one_batch_in_flight"},
@@ -884,9 +910,9 @@ def main():
                     sub[key] = r[key]
             if "host_inclusive" in r:
                 sub["host_inclusive"] = r["host_inclusive"]
-            if world == 1 and not args.no_reference_gpu and budget > 0:
+            if args.full and world == 1 and not args.no_reference_gpu and budget > 0:
                 sub["reference_on_this_gpu"] = reference_gpu(n, min(budget, 15.0), r)
-            if world == 1 and not args.no_cpu_baseline and budget > 0:
+            if args.full and world == 1 and not args.no_cpu_baseline and budget > 0:
                 sub["cpu_baseline"], sub["gt_concordance"] = cpu_baseline(n, budget, args.batch, rows)
                 if sub["cpu_baseline"]:
                     sub["speedup_vs_cpu_baseline"] = {
@@ -913,6 +939,9 @@ def main():
             full[n] = sub_line(n, results[n], args.cpu_budget / 2 if n == "pileup" else 0)
         if world > 1:
             full["placement_rank0"] = PLACEMENT  # dist.pin_to_device_numa: which NUMA node / how many CPUs rank 0's host side got
+    if rank == 0 and not args.full:  # a plain run: the line alone, no record file
+        print(json.dumps(short_line(full, names, None)), flush=True)
+    elif rank == 0:
         # everything measured goes to a file; stdout carries ONE short line the driver can parse (round 3's 21 KB line could not be)
         full_path = os.environ.get("C3_BENCH_FULL") or os.path.join(ROOT, "gpurun_out", "bench_full.json")
         try:

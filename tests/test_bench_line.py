@@ -3,6 +3,8 @@ ms_per_step and roofline on the same leg (one batch in flight)."""
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -131,3 +133,36 @@ def test_the_round_5_collections_are_consistent():
         assert min(abs(frac_csv / line["roofline"]["frac"] - 1), abs(scaled / line["roofline"]["frac"] - 1)) < 0.03, (tag, frac_csv, scaled, line["roofline"]["frac"])
         if "events" in line["roofline"]:
             assert line["roofline"]["events"]["frac"] < frac_csv < line["roofline"]["frac"] * 1.01, (tag, line["roofline"]["events"]["frac"], frac_csv)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_rows(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one block of exactly K steps of the headline workload, the line
+    without the legs that belong to --full, no record file; --dump-outputs writes the rows of the last timed step, which are the
+    oracle's rows of the seeded weights and windows"""
+    import subprocess
+    import sys
+    import numpy as np
+    from clair3_amd import synthetic as syn
+    from oracle import oracle
+    env = dict(os.environ, C3_BENCH_FULL=str(tmp_path / "full.json"))
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "candidate-windows/sec" and line["unit"] == "candidate-windows/s" and line["higher_is_better"] is True
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["value_stats"]["repeats"] == 1 and line["dtype"] == "f32(fp16x3)"
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 / line["config"]["windows_per_step"] - 1) < 1e-3
+    for key in ("roofline", "host_inclusive", "cpu_baseline", "gt_concordance", "pileup", "full_alignment_dwell", "3_batches_in_flight"):
+        assert key not in line, key
+    assert line["full_record"] is None and not (tmp_path / "full.json").exists()
+    assert sorted(os.listdir(tmp_path / "out")) == ["full_alignment.npy"]
+    y = np.load(tmp_path / "out" / "full_alignment.npy")
+    assert y.dtype == np.float32 and y.shape == (256, 90)
+    kind = syn.FULL_ALIGNMENT
+    x = syn.make_windows(kind, 256, seed=1000, channels=8)[:16]  # rows are per window: a slice keeps the fp64 oracle quick
+    y_ref = oracle.forward(kind, syn.make_state_dict(kind, 8, True, seed=0), x, True)
+    assert float(np.abs(y[:16] - y_ref).max()) < 1e-4

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for lib in "$@"; do
   for wl in ${WLS:-full_alignment pileup}; do
     echo "== $wl $lib"
-    C3_BENCH_FULL=/tmp/ab_full.json C3HIP_LIB=$PWD/$lib timeout 600 python bench.py --gpus 1 --workload $wl --no-cpu-baseline --no-host-leg --no-reference-gpu --steps ${STEPS:-200} --warmup 10 2> gpurun_out/ab.err > /dev/null; pyb < /dev/null
+    C3_BENCH_FULL=/tmp/ab_full.json C3HIP_LIB=$PWD/$lib timeout 600 python bench.py --gpus 1 --full --workload $wl --no-cpu-baseline --no-host-leg --no-reference-gpu --steps ${STEPS:-200} --warmup 10 2> "${TMPDIR:-/tmp}/ab.err" > /dev/null; pyb < /dev/null
   done
 done
 done

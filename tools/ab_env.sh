@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp; mkdir -p gpurun_out
 wl=$1; shift
 for rep in 1 2; do for setting in "$@"; do
   echo "== $wl $setting (run $rep)"
-  env $setting C3_BENCH_FULL=/tmp/ab_full.json timeout 300 python bench.py --gpus 1 --workload $wl --no-cpu-baseline --no-reference-gpu ${AB_FLAGS:-} --steps ${STEPS:-200} 2>> gpurun_out/ab_env.err > /dev/null; python -c "
+  env $setting C3_BENCH_FULL=/tmp/ab_full.json timeout 300 python bench.py --gpus 1 --full --workload $wl --no-cpu-baseline --no-reference-gpu ${AB_FLAGS:-} --steps ${STEPS:-200} 2>> "$TMPDIR/ab_env.err" > /dev/null; python -c "
 import sys,json
 d=json.load(open('/tmp/ab_full.json'))
 h=d.get('host_inclusive',{}); b=h.get('batch_1000',{})

@@ -15,7 +15,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 OUT="$PWD/gpurun_out"
 leg() {  # leg <workload>: the bench flags that run one workload's one-batch-in-flight leg and nothing else
-  echo "--gpus 1 --workload $1 --streams 1 --no-host-leg --no-cpu-baseline --no-reference-gpu --steps ${STEPS:-50} --warmup 5 --repeats 3"
+  echo "--gpus 1 --full --workload $1 --streams 1 --no-host-leg --no-cpu-baseline --no-reference-gpu --steps ${STEPS:-50} --warmup 5 --repeats 3"
 }
 prof() {  # prof <tag> <workload>: kernel trace + stats of the one-in-flight leg AND its HIP-event pass (the same kernels, the same one
           # batch in flight), so the roofline object of the JSON line comes from the very launches the CSV averages
@@ -29,8 +29,8 @@ for s in ${1:-test bench}; do
   case $s in
     test)    timeout 1200 python -m pytest tests -m gpu -q > gpurun_out/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -25 gpurun_out/pytest_gpu.txt ;;
     smoke)   timeout 600 python __graft_entry__.py --smoke > gpurun_out/smoke.txt 2>&1; echo "smoke rc=$?"; tail -5 gpurun_out/smoke.txt ;;
-    bench)   C3_BENCH_FULL="$OUT/bench_full.json" timeout 900 python bench.py --gpus 1 > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$?"; head -c 3000 gpurun_out/bench.json; echo ;;
-    bench20) C3_BENCH_FULL="$OUT/bench20_full.json" timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench20.json 2> gpurun_out/bench20.err; echo "bench20 rc=$?"; head -c 3000 gpurun_out/bench20.json; echo ;;
+    bench)   C3_BENCH_FULL="$OUT/bench_full.json" timeout 900 python bench.py --gpus 1 --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; head -c 3000 "$OUT/bench.json"; echo ;;
+    bench20) C3_BENCH_FULL="$OUT/bench20_full.json" timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench20.json" 2> "$OUT/bench20.err"; echo "bench20 rc=$?"; head -c 3000 "$OUT/bench20.json"; echo ;;
     prof_fa) prof prof_fa full_alignment ;;
     prof_p)  prof prof_p pileup ;;
     pmc_fa)  pmc pmc_fetch_fa full_alignment FETCH_SIZE; pmc pmc_write_fa full_alignment WRITE_SIZE ;;
