@@ -182,6 +182,7 @@ struct c3_model {
     // (tests/diag/sensitive_window.py), so such a handle STARTS on the fp32 matrix instructions.  C3HIP_FP32 set (0 or 1) is an explicit
     // choice and switches the automatism off; C3HIP_AUTO_FP32=<threshold> moves it (0 = never).
     bool precision_forced = false;   // C3HIP_FP32 was given
+    bool forced_f16 = true;          // ... and what it chose (0: fp16x3, 1: fp32): every c3_model_load starts from it again
     float auto_fp32_at = 4.0f;
     float lstm_wmax = 0.f;           // max |w| over W_hh of both LSTMs and W_ih of LSTM2 (what the decision looked at)
     float lstm_hh_norm = 0.f;        // max abs row sum of W_hh (reported, not decided on: ordinary LSTMs reach ~6)

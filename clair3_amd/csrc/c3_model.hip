@@ -90,7 +90,7 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     }
     if (getenv("C3HIP_KEEP_ACTIVATIONS")) m->keep = true;
     if (const char *e = getenv("C3HIP_FP32")) {  // an explicit choice: 1 = start on the fp32-MFMA forms (what the range guard falls back to), 0 = fp16x3, no automatism
-        m->f16_ok = atoi(e) == 0, m->precision_forced = true;
+        m->f16_ok = m->forced_f16 = atoi(e) == 0, m->precision_forced = true;
         if (!m->f16_ok) m->precision = "fp32-forced";
     }
     if (const char *e = getenv("C3HIP_AUTO_FP32")) m->auto_fp32_at = (float)atof(e);
@@ -168,7 +168,10 @@ int64_t c3_model_window_bytes(const c3_model *m, int x_dtype) {
 
 int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
     if (!m || (!tensors && n_tensors)) return fail("null argument");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
     HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());  // (the device-resident entries may still run the weights before on a caller's stream)
     TensorMap tm;
     for (int i = 0; i < n_tensors; ++i) {
         const c3_tensor_desc &t = tensors[i];
@@ -195,7 +198,6 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
             if (up)
                 fprintf(stderr, "libc3hip: LSTM weights reach |w| = %.3g (>= %.3g): this pileup handle runs on the fp32 matrix instructions "
                                 "(C3HIP_FP32=0 keeps the fp16x3 kernels)\n", (double)m->lstm_wmax, (double)m->auto_fp32_at);
-            // (new weights, new decision: a reload also ends what the range guard decided for the weights before)
             m->f16_ok = !up, m->precision = up ? "fp32-auto" : "fp16x3";
         }
     } else {
@@ -217,6 +219,12 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
         // strict like load_state_dict: report the first unexpected key
         return fail("Unexpected key(s) in state_dict: %zu tensors given, %zu expected", tm.size(), expected);
     }
+    // new weights, new start: what the range guard decided (f16_ok and the sticky device flag) was about the weights before.  The
+    // handle goes back to what C3HIP_FP32 chose, else to the load-time decision above (pileup) or to fp16x3 (full alignment).
+    if (m->precision_forced) m->f16_ok = m->forced_f16, m->precision = m->forced_f16 ? "fp16x3" : "fp32-forced";
+    else if (m->kind == C3_KIND_FULL_ALIGNMENT) m->f16_ok = true, m->precision = "fp16x3";
+    HIP_TRY(hipMemset(m->range_flag, 0, 256));
+    HIP_TRY(hipDeviceSynchronize());  // (the handle's streams are non-blocking: the flag is zero before any of them runs again)
     m->loaded = true;
     return 0;
 }

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <algorithm>
 #include <string>
 
@@ -860,10 +861,15 @@ extern "C" int c3_vcf_rows(const c3_rows_config *cfg, int64_t n, const char *pos
         const int bi = ref_base_index(refc);
         if (bi < 0) continue;
         const float *y = rows + i * row_stride_floats, *cols = y + cf.width;
-        const int cls = (int)cols[23 + bi];
-        if (cls < 0 || cls > 9) continue;
+        // (the class and entry columns are whole numbers the decoder wrote: a value that is not finite or does not fit an int -- a
+        // NaN row, a caller's own columns -- goes back to Python before any cast, which would be undefined behaviour)
+        const float fcls = cols[23 + bi];
+        if (!std::isfinite(fcls) || fcls < 0.f || fcls > 9.f) continue;
+        const int cls = (int)fcls;
         const int k = (cls > 0 ? cls : 1) - 1;
-        const int pos = (int)cols[13 + k];
+        const float fpos = cols[13 + k];
+        if (!std::isfinite(fpos) || fpos <= -2147483648.f || fpos >= 2147483648.f) continue;
+        const int pos = (int)fpos;
         const float prob = cls > 0 ? cols[k] : cols[9 + bi];
         if (!(prob == prob)) continue;
         if (cls > 0) {  // a maximum two classes share: output_with's flag chains are not output_from's

@@ -171,18 +171,23 @@ def _trained_like(sd, kind, rng):
         sd[f"{block}.conv2.weight"] /= s_inner[None, :, None, None]
 
 
-def make_pileup_windows(batch, seed=0, recipe="realistic", dtype=np.int8, channels=PILEUP_CHANNELS):
+def make_pileup_windows(batch, seed=0, recipe="realistic", dtype=np.int8, channels=PILEUP_CHANNELS, depth=None):
     """(batch, 33, 18) pileup count tensors.
 
     realistic: per-position strand-split base counts with the reference-base channel negated
     (src/clair3_pileup.c:370-371) and sparse indel channels; uniform: iid integers in [-60, 60].
+    depth: mean read depth of the realistic recipe (default: Poisson(50) clipped to [4, 127], what int8 holds); given, the
+    depths are Poisson(depth) without the upper clip -- counts of high-coverage regions, for int32 windows.
     """
     rng = np.random.default_rng(seed)
     if recipe == "uniform":
         x = rng.integers(-60, 61, size=(batch, NO_OF_POSITIONS, channels))
         return x.astype(dtype)
     x = np.zeros((batch, NO_OF_POSITIONS, channels), dtype=np.int64)
-    depth = np.clip(rng.poisson(50, size=(batch, 1)), 4, 127)
+    if depth is None:
+        depth = np.clip(rng.poisson(50, size=(batch, 1)), 4, 127)
+    else:
+        depth = np.maximum(rng.poisson(depth, size=(batch, 1)), 4)
     fwd = rng.binomial(depth, 0.5, size=(batch, NO_OF_POSITIONS))
     rev = depth - fwd
     ref = rng.integers(0, 4, size=(batch, NO_OF_POSITIONS))

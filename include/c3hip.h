@@ -88,7 +88,9 @@ int c3_device_pci_bus_id(int device, char *buf, int buf_bytes);
 c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int device);
 /* window geometry; defaults are the ONT shapes: depth 89 (ignored for pileup), 33 positions */
 int c3_model_set_geometry(c3_model *m, int depth, int positions);
-/* strict: every expected key must be present with the expected shape, unknown keys are an error */
+/* strict: every expected key must be present with the expected shape, unknown keys are an error.  A (re)load starts
+ * the handle afresh: the range guard's flag is cleared and the precision goes back to what C3HIP_FP32 chose, else to
+ * the load-time decision (pileup) or fp16x3.  Refused while a c3_predict_submit of the handle is pending. */
 int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors);
 /* 24 or 90 */
 int c3_model_output_size(const c3_model *m);
@@ -144,7 +146,10 @@ int c3_predict_submit_dev(c3_model *m, const void *x_host, int x_dtype, int64_t 
 /* device-resident forward: x_dev / y_dev are device pointers on the model's device, stream is a
  * hipStream_t (NULL = the HIP null stream, i.e. PyTorch's default stream).  Asynchronous with respect to the
  * host; ordered like any other work on that stream.  Calls on one handle must not overlap each other (one
- * workspace per handle): keep several batches in flight with several handles. */
+ * workspace per handle): keep several batches in flight with several handles.  x_dev may start at any byte address
+ * (a slice of a larger tensor, an odd base for 9-channel windows) and y_dev at any float: the kernels read no byte
+ * outside the batch*c3_model_window_bytes() window bytes and write no float outside the batch*c3_model_row_size() rows
+ * (tests/test_caller_inputs_gpu.py). */
 int c3_predict_device(c3_model *m, const void *x_dev, int x_dtype, int64_t batch, float *y_dev, void *stream);
 /* The same forward with the range guard of c3_predict_wait (the device-resident entry a sharded job uses,
  * clair3_amd/dist.py): after the kernels it scans the rows for non-finite values on the device, reads the range flag,
