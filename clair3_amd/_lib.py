@@ -20,7 +20,7 @@ EXPORTS = (
     "c3_version", "c3_last_error", "c3_device_count", "c3_mem_info", "c3_device_pci_bus_id", "c3_model_create", "c3_model_set_geometry",
     "c3_model_load", "c3_model_output_size", "c3_model_row_size", "c3_model_set_decode_columns", "c3_model_window_bytes", "c3_predict", "c3_predict_submit", "c3_predict_submit_dev",
     "c3_predict_wait", "c3_comm_unique_id", "c3_comm_create", "c3_comm_destroy", "c3_gather_rows", "c3_comm_count", "c3_comm_abort", "c3_stream_wait", "c3_model_describe", "c3_model_set_sharing", "c3_predict_device", "c3_predict_device_checked", "c3_model_range_status", "c3_predict_pileup_region", "c3_outcome_maxima", "c3_decode_columns", "c3_vcf_rows", "c3_model_synchronize", "c3_model_destroy", "c3_debug_fetch",
-    "c3_debug_keep_activations", "c3_profile_enable", "c3_profile_reset", "c3_profile_read",
+    "c3_debug_keep_activations", "c3_debug_tap", "c3_debug_tap_fetch", "c3_profile_enable", "c3_profile_reset", "c3_profile_read",
 )
 
 
@@ -128,6 +128,8 @@ def lib():
     L.c3_model_destroy.argtypes = [C.c_void_p]
     L.c3_debug_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
     L.c3_debug_keep_activations.argtypes = [C.c_void_p, C.c_int]
+    L.c3_debug_tap.argtypes = [C.c_void_p, C.c_char_p]
+    L.c3_debug_tap_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
     L.c3_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.c3_profile_reset.argtypes = [C.c_void_p]
     L.c3_profile_read.argtypes = [C.c_void_p, C.POINTER(KernelStat), C.c_int]

@@ -3,6 +3,33 @@
 #pragma once
 #include "c3_forward.h"
 
+// n floats of debug tensor `s` at src (device) as the checkpoint's fp32 values on the host: plane activations (c3_conv3.h) converted,
+// the channel powers of two of the full-alignment activations (channel equalisation, c3_pack.h) removed.  The caller has synchronised the device.
+static int to_host_values(c3_model *m, const std::string &s, const float *src, int64_t n, bool planes, float *host_out) {
+    const std::vector<int> *exps = nullptr;
+    if (m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) exps = &m->act_exp[s[3] - '0'];
+    if (m->kind == C3_KIND_FULL_ALIGNMENT && s == "spp") exps = &m->act_exp[8];
+    auto unscale = [&]() {
+        if (!exps || exps->empty()) return;
+        const size_t C = exps->size();
+        for (int64_t i = 0; i < n; ++i) host_out[i] = std::ldexp(host_out[i], -(*exps)[(size_t)i % C]);
+    };
+    if (planes) {
+        const int C = m->kind == C3_KIND_PILEUP ? 256 : kConvCout[s[3] - '0'];
+        float *tmp = nullptr;
+        HIP_TRY(hipMalloc((void **)&tmp, (size_t)n * sizeof(float)));
+        hipLaunchKernelGGL(planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const void *)src, tmp, n / C, C);
+        const int rc = d2h_staged(host_out, tmp, (size_t)n * sizeof(float));
+        (void)hipFree(tmp);
+        if (rc != 0) return rc;
+        unscale();
+        return 0;
+    }
+    TRY(d2h_staged(host_out, src, (size_t)n * sizeof(float)));
+    unscale();
+    return 0;
+}
+
 extern "C" {
 
 int c3_debug_keep_activations(c3_model *m, int enable) {
@@ -43,31 +70,61 @@ int c3_debug_fetch(c3_model *m, const char *name, float *host_out, int64_t n_flo
     if (!src) return fail("unknown debug tensor \"%s\"", name);
     if (n != n_floats) return fail("debug tensor %s has %lld floats, caller expects %lld", name, (long long)n, (long long)n_floats);
     HIP_TRY(hipDeviceSynchronize());
-    // activations of the full-alignment network live on the device with every channel times its power of two (channel
-    // equalisation, c3_pack.h): hand the caller the values of the checkpoint as given
-    const std::vector<int> *exps = nullptr;
-    if (m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) exps = &m->act_exp[s[3] - '0'];
-    if (m->kind == C3_KIND_FULL_ALIGNMENT && s == "spp") exps = &m->act_exp[8];
-    auto unscale = [&]() {
-        if (!exps || exps->empty()) return;
-        const size_t C = exps->size();
-        for (int64_t i = 0; i < n; ++i) host_out[i] = std::ldexp(host_out[i], -(*exps)[(size_t)i % C]);
-    };
-    if (m->last_planes && ((m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) || (m->kind == C3_KIND_PILEUP && s == "lstm1_out"))) {
-        // the layer holds plane activations (c3_conv3.h): hand the caller the fp32 values they stand for
-        const int C = m->kind == C3_KIND_PILEUP ? 256 : kConvCout[s[3] - '0'];
-        float *tmp = nullptr;
-        HIP_TRY(hipMalloc((void **)&tmp, (size_t)n * sizeof(float)));
-        hipLaunchKernelGGL(planes_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const void *)src, tmp, n / C, C);
-        const int rc = d2h_staged(host_out, tmp, (size_t)n * sizeof(float));
-        (void)hipFree(tmp);
-        if (rc != 0) return rc;
-        unscale();
-        return 0;
+    const bool planes = m->last_planes && ((m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) || (m->kind == C3_KIND_PILEUP && s == "lstm1_out"));
+    return to_host_values(m, s, src, n, planes, host_out);
+}
+
+// c3_debug_tap: tensors by name, comma separated ("" = none)
+int c3_debug_tap(c3_model *m, const char *names) {
+    if (!m || !names) return fail("null argument");
+    HIP_TRY(hipSetDevice(m->device));
+    uint32_t mask = 0;
+    std::string list = names;
+    for (size_t a = 0; a < list.size();) {
+        size_t b = list.find(',', a);
+        if (b == std::string::npos) b = list.size();
+        const std::string name = list.substr(a, b - a);
+        a = b + 1;
+        if (name.empty()) continue;
+        int id = -1;
+        for (int i = 0; i < kTapCount; ++i)
+            if (name == kTapName[i]) id = i;
+        const bool fa_tensor = id >= 0 && id <= kTapL4, p_tensor = id >= kTapL4;
+        if (id < 0 || (m->kind == C3_KIND_FULL_ALIGNMENT ? !fa_tensor : !p_tensor))
+            return fail("unknown tap tensor \"%s\" for the %s network", name.c_str(), m->kind == C3_KIND_PILEUP ? "pileup" : "full-alignment");
+        mask |= 1u << id;
     }
-    TRY(d2h_staged(host_out, src, (size_t)n * sizeof(float)));
-    unscale();
+    HIP_TRY(hipDeviceSynchronize());
+    for (int id = 0; id < kTapCount; ++id) {
+        if ((mask >> id & 1u) || !m->tap_dev[id]) continue;
+        (void)hipFree(m->tap_dev[id]);
+        m->tap_dev[id] = nullptr, m->tap_bytes[id] = 0;
+    }
+    m->tap_mask = mask;
+    m->tap_written = m->tap_skipped = m->tap_planes = 0, m->tap_n = 0;
     return 0;
+}
+
+int c3_debug_tap_fetch(c3_model *m, const char *name, int64_t first, int64_t windows, float *host_out, int64_t n_floats) {
+    if (!m || !name || (!host_out && n_floats > 0)) return fail("null argument");
+    HIP_TRY(hipSetDevice(m->device));
+    int id = -1;
+    for (int i = 0; i < kTapCount; ++i)
+        if (!strcmp(name, kTapName[i])) id = i;
+    if (id < 0 || !(m->tap_mask >> id & 1u)) return fail("%s is not tapped: c3_debug_tap first", name);
+    if (m->tap_skipped >> id & 1u) {
+        if (id == 0) return fail("act0 is computed inside res1a (conv1 inside the first residual block): the form writes no act0");
+        if (id == 8) return fail("act8 is pooled inside res3b (the pyramid pooling is its epilogue): the form writes no act8");
+        return fail("%s was not produced by the last call's form", name);
+    }
+    if (!(m->tap_written >> id & 1u) || m->tap_n <= 0) return fail("%s: no call since it was tapped", name);
+    if (first < 0 || windows < 0 || first + windows > m->tap_n)
+        return fail("windows %lld .. %lld of %s: the last call had %lld", (long long)first, (long long)(first + windows), name, (long long)m->tap_n);
+    const int64_t pw = tap_window_floats(m, id), n = windows * pw;
+    if (n != n_floats) return fail("%lld windows of %s are %lld floats, caller expects %lld", (long long)windows, name, (long long)n, (long long)n_floats);
+    if (n == 0) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    return to_host_values(m, name, m->tap_dev[id] + first * pw, n, (m->tap_planes >> id & 1u) != 0, host_out);
 }
 
 int c3_profile_enable(c3_model *m, int enable) {

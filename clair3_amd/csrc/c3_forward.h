@@ -4,6 +4,54 @@
 #pragma once
 #include "c3_model.h"
 
+// ------------------------------------------------------------------------------------------ debug taps (c3_debug.h c3_debug_tap)
+// floats of one window of tap tensor `id` (plane activations take the same bytes: two fp16 pieces per value)
+static int64_t tap_window_floats(const c3_model *m, int id) {
+    if (id < 9) {
+        int hh[10], ww[10];
+        fa_geometry(m, hh, ww);
+        return (int64_t)hh[id + 1] * ww[id + 1] * kConvCout[id];
+    }
+    switch (id) {
+        case kTapSpp: return m->K4;
+        case kTapL4: return m->FC;
+        case kTapLstm1: return (int64_t)m->positions * 256;
+        case kTapGx2: return (int64_t)m->positions * 1280;
+        default: return (int64_t)m->positions * 320;
+    }
+}
+// the n windows of tensor `id` that the launch just enqueued on s wrote at src: behind it on s, into the tap buffer at the part's windows
+static int tap(c3_model *m, hipStream_t s, int id, const void *src, int64_t n, bool planes = false) {
+    if (!(m->tap_mask >> id & 1u)) return 0;
+    const int64_t pw = tap_window_floats(m, id);
+    HIP_TRY(hipMemcpyAsync(m->tap_dev[id] + m->tap_base * pw, src, (size_t)(n * pw) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    m->tap_written |= 1u << id;
+    if (planes) m->tap_planes |= 1u << id;
+    return 0;
+}
+// the form of this part produces no tensor `id` (it is computed inside a fused kernel)
+static void tap_skip(c3_model *m, int id) {
+    if (m->tap_mask >> id & 1u) m->tap_skipped |= 1u << id;
+}
+// at the start of a call: tap buffers for `batch` windows
+static int tap_prepare(c3_model *m, int64_t batch) {
+    m->tap_written = m->tap_skipped = m->tap_planes = 0;
+    m->tap_n = 0, m->tap_base = 0;
+    if (!m->tap_mask) return 0;
+    for (int id = 0; id < kTapCount; ++id) {
+        if (!(m->tap_mask >> id & 1u)) continue;
+        const size_t bytes = (size_t)(batch * tap_window_floats(m, id)) * sizeof(float);
+        if (bytes <= m->tap_bytes[id]) continue;
+        HIP_TRY(hipDeviceSynchronize());  // (a buffer a previous call may still be copying into)
+        if (m->tap_dev[id]) (void)hipFree(m->tap_dev[id]);
+        m->tap_dev[id] = nullptr, m->tap_bytes[id] = 0;
+        HIP_TRY(hipMalloc((void **)&m->tap_dev[id], bytes));
+        m->tap_bytes[id] = bytes;
+    }
+    m->tap_n = batch;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ the FC chain on its own stream (ring only)
 // tail_begin: the stream the chain of THIS forward pass runs on -- tail_stream, behind everything queued on s so far, when the ring's
 // submit asked for it (m->tail_now), else s itself.  tail_end: marks the chain's end.  tail_guard: called on s right before the first
@@ -80,6 +128,7 @@ static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, in
         else
             hipLaunchKernelGGL(fc_tail_mfma_kernel<128>, grid, dim3(256), 0, s, tp);
         HIP_TRY(hipGetLastError());
+        TRY(tap(m, s, kTapL4, m->l4dbg, n));
     }
     if (m->row > m->nout) {  // decoder columns behind the probabilities of every row (c3_decode.h)
         ProfScope ps(m, s, m->kind == C3_KIND_PILEUP ? "p.decode" : "fa.decode", 0.0, 4.0 * n * m->row);
@@ -147,6 +196,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         // conv1 inside the first residual block (c3_conv3.h SRC8; 8-channel windows, or 9 with the dwell channel)
         const bool fuse1 = m->conv1_fused && (m->C == 8 || m->C == 9) && m->conv1_wfrag16 && !m->keep && ww[1] <= kPlMaxW && ww[0] >= 3;
         if (l == 0 && fuse1) {  // no launch, no conv1 planes: res1a computes its input rows, res1b its residual, from the windows
+            tap_skip(m, 0);
             cin = Cout;
             continue;
         }
@@ -249,6 +299,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                     else hipLaunchKernelGGL((conv3x3_wino_planes_kernel<256, false>), wgrid, wblock, 0, s, wp);
                 }
                 HIP_TRY(hipGetLastError());
+                TRY(tap(m, s, l, m->act[l], n, true));
                 m->choice_s1[(l / 3) * 2 + (l % 3 - 1)] = 'w';
                 cin = Cout;
                 continue;
@@ -277,7 +328,14 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                 else hipLaunchKernelGGL((conv3x3_planes_kernel<256, false>), grid, block, 0, s, cp);
             }
             HIP_TRY(hipGetLastError());
+            if (sppf) {  // the epilogue pooled the tiles: spp written, no act8
+                tap_skip(m, 8);
+                TRY(tap(m, s, kTapSpp, m->spp, n));
+                cin = Cout;
+                continue;
+            }
         }
+        TRY(tap(m, s, l, m->act[l], n, true));
         cin = Cout;
     }
     if (!sppf_ok) {
@@ -295,6 +353,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             hipLaunchKernelGGL(spp_planes_kernel, dim3(grid), dim3(256), 0, s, sp);
         }
         HIP_TRY(hipGetLastError());
+        TRY(tap(m, s, kTapSpp, m->spp, n));
     }
     m->last_planes = true;
     return run_tail(m, s, m->spp, m->K4, n, y, "fa.l4", "fa.tail");
@@ -331,6 +390,7 @@ static int run_fa_fp32(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, f
             else
                 TRY((launch_gemm<ConvLoader<4>, EPI_BIAS_RELU, 128, 64>(s, lp, m->conv_w[l], ldb, M, Cout, nk, 1, ep)));
         }
+        TRY(tap(m, s, l, m->act[l], n));
         cin = Cout;
     }
     {
@@ -342,6 +402,7 @@ static int run_fa_fp32(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, f
         const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
         hipLaunchKernelGGL(spp_kernel, dim3(grid), dim3(256), 0, s, sp);
         HIP_TRY(hipGetLastError());
+        TRY(tap(m, s, kTapSpp, m->spp, n));
     }
     return run_tail(m, s, m->spp, m->K4, n, y, "fa.l4", "fa.tail");
 }
@@ -399,6 +460,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             hipLaunchKernelGGL(lstm1_fused_kernel<T>, grid, dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());
+        TRY(tap(m, s, kTapLstm1, m->h1, n, h1_planes));
     }
     {
         ProfScope ps(m, s, "p.proj2", 2.0 * M * 1280.0 * 256.0, 4.0 * M * (256.0 + 1280.0));
@@ -430,6 +492,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             m->choice_proj2 = "fp32-mfma";
             TRY((launch_gemm<DenseLoader<4>, EPI_BIAS, 128, 128>(s, lp, m->proj_w[1], 256, M, 1280, 8, 1, ep)));
         }
+        TRY(tap(m, s, kTapGx2, m->gx2, n));
     }
     TRY(tail_guard(m, s));  // LSTM2 overwrites lstm2_out, which a chain still on tail_stream reads
     {
@@ -448,6 +511,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             hipLaunchKernelGGL(lstm_recurrent_kernel_v2<160>, dim3((unsigned)((n + 15) / 16), 2), dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());
+        TRY(tap(m, s, kTapLstm2, m->h2, n));
     }
     return run_tail(m, s, m->h2, m->K4, n, y, "p.l4", "p.tail");
 }
@@ -463,6 +527,7 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
     if (m->kind == C3_KIND_PILEUP && x_dtype != C3_DTYPE_I8 && x_dtype != C3_DTYPE_I32)
         return fail("pileup windows must be int8 or int32 (got dtype %d)", x_dtype);
     TRY(ensure_workspace(m, batch));
+    if (!m->tap_call) TRY(tap_prepare(m, batch));
     const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
     auto run = [&](hipStream_t st, const char *xp, const int32_t *sp, int64_t n, float *yp) -> int {
         if (m->kind == C3_KIND_FULL_ALIGNMENT) return run_fa(m, st, (const int8_t *)xp, n, yp);
@@ -489,6 +554,7 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
             const int64_t n0 = ((n / 2 + 15) / 16) * 16, n1 = n - n0;  // whole 16-window tiles in the first half
             HIP_TRY(hipEventRecord(m->duo_fork, s));
             HIP_TRY(hipStreamWaitEvent(m->duo_stream, m->duo_fork, 0));
+            m->tap_base = m->tap_call_off + off;
             TRY(run(s, xp, sp, n0, yp));
             // the second half: the same buffers, behind the first half's share of each
             float *const act0[9] = {m->act[0], m->act[1], m->act[2], m->act[3], m->act[4], m->act[5], m->act[6], m->act[7], m->act[8]};
@@ -505,6 +571,7 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
                 m->h1 = h10 + (size_t)n0 * T * 256, m->gx2 = gx20 + (size_t)n0 * T * 1280, m->h2 = h20 + (size_t)n0 * T * 320;
             }
             m->part = part0 + (size_t)l4_splits(m) * n0 * m->FC, m->l4dbg = dbg0 + (size_t)n0 * m->FC;
+            m->tap_base = m->tap_call_off + off + n0;
             const int rc = run(m->duo_stream, starts ? xp : xp + n0 * wbytes, sp ? sp + n0 : nullptr, n1, yp + n0 * m->row);
             for (int l = 0; l < 9; ++l) m->act[l] = act0[l];
             m->spp = spp0, m->part = part0, m->l4dbg = dbg0, m->h1 = h10, m->gx2 = gx20, m->h2 = h20;
@@ -514,6 +581,7 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
             m->last_n = n0;
             continue;
         }
+        m->tap_base = m->tap_call_off + off;
         TRY(run(s, xp, sp, n, yp));
         m->last_n = n;
     }

@@ -201,6 +201,7 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     sl.y_dev_out = y_dev_out;
     sl.lane = m->lane_cur;
     sl.y_host = y_host, sl.y_bytes = yb, sl.batch = batch, sl.x_dtype = x_dtype, sl.busy = true;
+    sl.tap_off = m->tap_call_off;
     return 0;
 }
 
@@ -218,7 +219,10 @@ int c3_predict_wait(c3_model *m, int slot) {
                 fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
-            TRY(forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out));
+            m->tap_call_off = sl.tap_off;
+            const int rc = forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out);
+            m->tap_call_off = 0;
+            TRY(rc);
             HIP_TRY(hipStreamSynchronize(m->stream));
         }
         return 0;
@@ -236,7 +240,10 @@ int c3_predict_wait(c3_model *m, int slot) {
                 fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
-            TRY(forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y));
+            m->tap_call_off = sl.tap_off;
+            const int rc = forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y);
+            m->tap_call_off = 0;
+            TRY(rc);
             HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, m->stream));
             HIP_TRY(hipStreamSynchronize(m->stream));
         }
@@ -296,6 +303,11 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
             }
         return v;
     }();
+    // debug taps (c3_debug_tap): every piece's windows at their place in this call
+    if (m->tap_mask) {
+        TRY(tap_prepare(m, batch));
+        m->tap_call = true;
+    }
     for (int64_t off = 0; off < batch && rc == 0; ++n_sub) {
         int64_t take = std::min(next, batch - off);
         if (batch - off - take < next / 2 || batch - off - take < chunk / 2) take = batch - off;
@@ -303,8 +315,10 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
         if (!forced.empty()) take = std::min<int64_t>(forced[std::min<size_t>((size_t)n_sub, forced.size() - 1)], batch - off);
         take = std::min(take, max_microbatch(m));
         if (n_sub - n_done == kRing) rc = c3_predict_wait(m, (int)(n_done++ % kRing));
+        m->tap_call_off = off;
         if (rc == 0)
             rc = predict_submit(m, (const char *)x_host + off * wbytes, x_dtype, take, y_host + off * m->row, (int)(n_sub % kRing));
+        m->tap_call_off = 0;
         if (rc != 0) break;
         off += take;
         next = std::min(3 * next, 4 * chunk);
@@ -314,6 +328,7 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
         const int r = c3_predict_wait(m, (int)(n_done % kRing));
         if (rc == 0) rc = r;
     }
+    if (m->tap_call) m->tap_call = false, m->tap_n = rc == 0 ? batch : 0;
     if (!first_error.empty()) g_err = first_error;
     return rc;
 }

@@ -83,6 +83,10 @@ static const int kConvCout[9] = {64, 64, 64, 128, 128, 128, 256, 256, 256};
 static const int kConvStride[9] = {2, 1, 1, 2, 1, 1, 2, 1, 1};
 static const char *kFaLayerTag[9] = {"fa.conv1", "fa.res1a", "fa.res1b", "fa.conv3", "fa.res2a",
                                      "fa.res2b", "fa.conv5", "fa.res3a", "fa.res3b"};
+// tensors c3_debug_tap can capture: full alignment act0 .. act8 (= their index), spp, l4_out; pileup l4_out, lstm1_out, gx2, lstm2_out
+enum { kTapSpp = 9, kTapL4 = 10, kTapLstm1 = 11, kTapGx2 = 12, kTapLstm2 = 13, kTapCount = 14 };
+static const char *kTapName[kTapCount] = {"act0", "act1", "act2", "act3", "act4", "act5", "act6", "act7", "act8",
+                                          "spp",  "l4_out", "lstm1_out", "gx2", "lstm2_out"};
 
 struct DevBuf {
     void *p = nullptr;
@@ -110,6 +114,7 @@ struct HostSlot {
     int64_t batch = 0;  // what is in flight (for the fp32 re-run of c3_predict_wait)
     uint32_t *pin_flag = nullptr;  // pinned copy of the model's range_flag after this batch
     int x_dtype = 0;
+    int64_t tap_off = 0;  // first window of this batch in the c3_predict call it is a piece of (debug taps)
     bool busy = false;
     bool used_f16 = false;  // the batch in flight was computed by the fp16x3 kernels (c3_predict_wait then checks its range)
     int lane = 0;           // the lane (c3_model::Lane) the batch in flight runs in
@@ -233,6 +238,16 @@ struct c3_model {
     float *spp = nullptr, *part = nullptr, *l4dbg = nullptr;
     float *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
     int64_t last_n = 0;  // windows of the last micro-batch (for debug fetch)
+
+    // ---- debug taps (c3_debug_tap): layer outputs of the forms a call really runs, each copied on its producing stream right behind
+    // the producing launch into a buffer of the handle, at the window's position in the call (micro-batches, duo halves, ring lanes) ----
+    uint32_t tap_mask = 0;                                // bit per kTap* tensor; 0 = off: no copy, no allocation, the launches of an untapped call
+    uint32_t tap_written = 0, tap_skipped = 0, tap_planes = 0;  // of the last call: copied / not produced by its form / held as planes
+    float *tap_dev[kTapCount] = {};
+    size_t tap_bytes[kTapCount] = {};
+    int64_t tap_n = 0, tap_base = 0;  // windows of the last call; first window of the part being enqueued
+    bool tap_call = false;            // inside a c3_predict that runs its batch as pieces: the taps are sized for the whole call
+    int64_t tap_call_off = 0;         // ... and the piece being enqueued starts at this window of it
 
     HostSlot slot[kHostSlots];
 

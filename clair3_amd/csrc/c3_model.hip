@@ -10,7 +10,7 @@
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.3.0 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.4.0 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -329,6 +329,8 @@ int c3_model_destroy(c3_model *m) {
     for (float *p : ws)
         if (p) (void)hipFree(p);
     if (m->decode_dev) (void)hipFree(m->decode_dev);
+    for (float *p : m->tap_dev)
+        if (p) (void)hipFree(p);
     if (m->range_flag) (void)hipFree(m->range_flag);
     if (m->pin_flag) (void)hipHostFree(m->pin_flag);
     for (int l = 0; l < 9; ++l) {

@@ -40,6 +40,7 @@ class _HipModel:
         self._device = None
         self._pending_sd = None
         self._keep = False
+        self._taps = ""
         self._geometry = None
         self._decode_cols = False
         if device is not None:
@@ -61,6 +62,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_geometry(self._handle, *self._geometry), "c3_model_set_geometry")
         if self._keep:
             _lib.check(_lib.lib().c3_debug_keep_activations(self._handle, 1), "c3_debug_keep_activations")
+        if self._taps:
+            _lib.check(_lib.lib().c3_debug_tap(self._handle, self._taps.encode()), "c3_debug_tap")
         if self._decode_cols:
             _lib.check(_lib.lib().c3_model_set_decode_columns(self._handle, 1), "c3_model_set_decode_columns")
         if sd is not None:
@@ -264,6 +267,22 @@ class _HipModel:
     def debug_fetch(self, name, shape):
         out = np.empty(shape, dtype=np.float32)
         _lib.check(_lib.lib().c3_debug_fetch(self._handle, name.encode(), out.ctypes.data, out.size), "c3_debug_fetch")
+        return out
+
+    def tap(self, names):
+        """capture these layer outputs of every later call on the forms it really runs (c3_debug_tap); names: iterable or
+        comma-separated string, empty = off"""
+        names = names if isinstance(names, str) else ",".join(names)
+        self._taps = names
+        if self._handle is not None:
+            _lib.check(_lib.lib().c3_debug_tap(self._handle, names.encode()), "c3_debug_tap")
+        return self
+
+    def tap_fetch(self, name, first, shape):
+        """windows first .. first + shape[0] of a tapped tensor of the last call (c3_debug_tap_fetch)"""
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(_lib.lib().c3_debug_tap_fetch(self._handle, name.encode(), int(first), int(shape[0]), out.ctypes.data, out.size),
+                   "c3_debug_tap_fetch")
         return out
 
     def profile(self, enable=True):

@@ -264,6 +264,16 @@ int c3_debug_fetch(c3_model *m, const char *name, float *host_out, int64_t n_flo
  * non-recycled tensors can be fetched).  Also enabled by the environment variable C3HIP_KEEP_ACTIVATIONS. */
 int c3_debug_keep_activations(c3_model *m, int enable);
 
+/* Taps: layer outputs of the kernel forms a call really runs (keep mode switches the fused forms off; taps do not).
+ * names: comma separated, "" = none.  full-aln "act0".."act8", "spp", "l4_out"; pileup "lstm1_out", "gx2" (B,33,1280: both directions'
+ * x-projections of LSTM2 with both biases, PyTorch gate order), "lstm2_out", "l4_out".  Every later call copies each tapped tensor
+ * behind the launch that produced it, on that launch's stream, for ALL its windows (micro-batches, two halves, ring lanes); with no
+ * tap set a call launches exactly what it did before.  Calls on the handle must not overlap while taps are read. */
+int c3_debug_tap(c3_model *m, const char *names);
+/* windows [first, first + windows) of tapped tensor `name` of the last call, as the checkpoint's fp32 values.  Fails, naming the
+ * fusing kernel, when the call's form produced no such tensor (act0 inside res1a, act8 inside res3b). */
+int c3_debug_tap_fetch(c3_model *m, const char *name, int64_t first, int64_t windows, float *host_out, int64_t n_floats);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);

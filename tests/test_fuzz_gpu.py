@@ -5,7 +5,10 @@ trained-like / peaked) for the five model shapes through the C ABI, gated agains
 windows travelling as two batches give bit-identical rows.  EVERY row of every batch is checked against the reference, pileup included
 (round 6; until then a pileup batch met the reference at both ends and 16 random rows), and trained-like pileup weight sets -- which the
 load-time precision decision starts on the fp32 matrix instructions -- are run a second time on the fp16x3 kernels (C3HIP_FP32=0).
-Fixed seeds 7 and 11 (the seeds of tests/diag/fuzz_parity.py, whose
+Every row is also held to the fp64 oracle at 2e-5 (3e-5 for trained-like pileup weights on the fp16x3 kernels, the margin
+test_parity_gpu.py::test_sensitive_recurrence justifies), and the first batch of every weight set is checked layer by layer against
+the oracle on the forms the call really ran (debug taps).  The oracle part runs without the staged reference; only the comparison with
+the reference's fp32 modules needs it.  Fixed seeds 7 and 11 (the seeds of tests/diag/fuzz_parity.py, whose
 open-ended form stays a diagnostic), a fixed number of batches each, so the run is reproducible and bounded."""
 import os
 
@@ -13,6 +16,8 @@ import numpy as np
 import pytest
 
 from clair3_amd import synthetic as syn
+from oracle import oracle
+from oracle.stage_reference import reference_root
 from tests import refmodels, util
 from tests.test_parity_gpu import make_model
 
@@ -23,19 +28,33 @@ SHAPES = [(syn.PILEUP, 18, False), (syn.PILEUP, 18, True), (syn.FULL_ALIGNMENT, 
 EDGE_SIZES = [1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 184, 185, 186, 255, 256, 257]
 
 
+def _tapped_layer_errors(m, d, kind, sd, n):
+    """the layers a debug tap caught on the call's own forms vs the oracle: FA per tensor and worst channel (util.layer_errors),
+    pileup relative to max(1, range)"""
+    if kind == syn.PILEUP:
+        return {name: float(np.abs(m.tap_fetch(name, 0, d[name].shape) - d[name]).max()) / max(1.0, float(np.abs(d[name]).max()))
+                for name in ("lstm1_out", "lstm2_out", "l4_out")}
+    names = [f"act{i}" for i in range(1, 8)] + ["spp", "l4_out"]
+    whole, chan = util.layer_errors(lambda name: m.tap_fetch(name, 0, d[name].shape), d, names, sd)
+    return {**whole, **{k + "/channel": v for k, v in chan.items()}}
+
+
 @pytest.mark.parametrize("seed,batches", [(7, 36), (11, 36)])
 def test_random_batches_and_weight_sets_against_the_reference_rows(seed, batches):
-    root = refmodels.reference_root_or_skip()
-    import torch
-    torch.set_num_threads(8)
+    root = reference_root()  # None: the oracle part alone
+    if root is not None:
+        import torch
+        torch.set_num_threads(8)
     rng = np.random.default_rng(seed)
     models = {}
     worst, rows_checked, windows, weight_sets = 0.0, 0, 0, 0
     worst_case = None
+    worst_o, worst_o_case, worst_layer = {}, {}, 0.0
     for _ in range(batches):
         kind, ch, indel = SHAPES[int(rng.integers(len(SHAPES)))]
         s = int(rng.integers(1 << 30))
         key = (kind, ch, indel)
+        fresh = False
         if key not in models or rng.random() < 0.25:
             flags = dict(seed=s, peaked=bool(rng.random() < 0.25), trained_like=bool(rng.random() < 0.5))
             sd = syn.make_state_dict(kind, ch, indel, **flags)
@@ -49,9 +68,12 @@ def test_random_batches_and_weight_sets_against_the_reference_rows(seed, batches
                     m16 = make_model(kind, ch, indel, sd)
                 finally:
                     del os.environ["C3HIP_FP32"]
-            models[key] = (make_model(kind, ch, indel, sd), refmodels.reference_model(root, kind, sd, indel, ch), flags, m16)
+            m_ref = refmodels.reference_model(root, kind, sd, indel, ch) if root is not None else None
+            taps = ("lstm1_out", "lstm2_out", "l4_out") if kind == syn.PILEUP else tuple(f"act{i}" for i in range(1, 8)) + ("spp", "l4_out")
+            models[key] = (make_model(kind, ch, indel, sd).tap(taps), m_ref, flags, m16, sd)
             weight_sets += 1
-        m, m_ref, flags, m16 = models[key]
+            fresh = True
+        m, m_ref, flags, m16, sd = models[key]
         hi = 1300 if kind == syn.PILEUP else 330
         n = int(rng.integers(1, hi)) if rng.random() < 0.7 else int(rng.choice(EDGE_SIZES))
         recipe = "uniform" if rng.random() < 0.3 else "realistic"
@@ -59,21 +81,47 @@ def test_random_batches_and_weight_sets_against_the_reference_rows(seed, batches
             syn.make_fa_windows(n, seed=s, recipe=recipe, channels=ch)
         y = m.predict_numpy(x)
         assert y.dtype == np.float32 and np.isfinite(y).all()
-        # EVERY row of every batch, pileup included (until round 5: both ends and 16 random rows of a pileup batch)
+        what = f"seed {seed}: kind={kind} ch={ch} indel={indel} n={n} recipe={recipe} input_seed={s} weights={flags}"
+        # EVERY row against the exact (fp64 oracle) rows; the first batch of a weight set also layer by layer, on its own forms
+        if fresh:
+            y_o, d = oracle.forward(kind, sd, x, indel, debug=True)
+            layers = _tapped_layer_errors(m, d, kind, sd, n)
+            print(f"  layers of the first batch ({what}): " + ", ".join(f"{k} {v:.1e}" for k, v in layers.items()))
+            assert max(layers.values()) <= 2e-5, (what, layers)
+            worst_layer = max(worst_layer, max(layers.values()))
+        else:
+            y_o = oracle.forward(kind, sd, x, indel)
+        forms = [("default", m, 2e-5)]
+        if m16 is not None:  # the fp16x3 kernels on trained-like LSTM weights: test_parity_gpu.py::test_sensitive_recurrence's 3e-5
+            forms.append(("C3HIP_FP32=0", m16, 3e-5))
+        y16 = None
+        for label, mm, tol in forms:
+            yy = y if mm is m else mm.predict_numpy(x)
+            if mm is m16:
+                y16 = yy
+            e = util.assert_rows_match(yy, y_o, tol=tol, what=f"{what} [{label}] vs the oracle")
+            if e > worst_o.get(label, -1.0):
+                worst_o[label], worst_o_case[label] = e, what
+        # EVERY row of every batch against the reference's fp32 modules, pileup included (until round 5: both ends and 16 random rows)
         rng.integers(0, n, size=min(n, 16))  # (the sample is no longer used; drawn so that the random stream stays round 4's)
         idx = np.arange(n)
-        y_ref = refmodels.reference_rows(m_ref, x[idx])
-        what = f"seed {seed}: kind={kind} ch={ch} indel={indel} n={n} recipe={recipe} input_seed={s} weights={flags}"
-        err = util.assert_rows_match(y[idx], y_ref, tol=util.PROB_TOL, what=what)  # 1e-4 + labels outside near-ties
-        if m16 is not None:  # the fp16x3 kernels on the same trained-like weights
-            err = max(err, util.assert_rows_match(m16.predict_numpy(x), y_ref, tol=util.PROB_TOL, what=what + " [C3HIP_FP32=0]"))
-        if err > worst:
-            worst, worst_case = err, what
+        if m_ref is not None:
+            y_ref = refmodels.reference_rows(m_ref, x[idx])
+            err = util.assert_rows_match(y[idx], y_ref, tol=util.PROB_TOL, what=what)  # 1e-4 + labels outside near-ties
+            if y16 is not None:  # the fp16x3 kernels on the same trained-like weights
+                err = max(err, util.assert_rows_match(y16, y_ref, tol=util.PROB_TOL, what=what + " [C3HIP_FP32=0]"))
+            if err > worst:
+                worst, worst_case = err, what
         rows_checked += len(idx)
         windows += n
         if n > 3:  # the same windows in another batch composition: bit-identical rows
             k = int(rng.integers(1, n))
             y2 = np.concatenate([m.predict_numpy(x[:k]), m.predict_numpy(x[k:])])
             assert np.array_equal(y, y2), f"rows depend on the batch they travel in ({what}, split at {k})"
-    print(f"fuzz seed {seed}: {batches} batches, {windows} windows, {weight_sets} weight sets, {rows_checked} rows against the "
-          f"reference's fp32 modules: worst |dY| = {worst:.2e} ({worst_case})")
+    print(f"fuzz seed {seed}: {batches} batches, {windows} windows, {weight_sets} weight sets, {rows_checked} rows; against the fp64 oracle: "
+          + ", ".join(f"{k} worst |dY| {v:.2e} ({worst_o_case[k]})" for k, v in worst_o.items())
+          + f"; first batches layer by layer: worst {worst_layer:.2e}")
+    if root is None:
+        print("  (no staged reference: the comparison with its fp32 modules did not run)")
+    else:
+        print(f"  against the reference's fp32 modules: worst |dY| = {worst:.2e} ({worst_case})")

@@ -422,21 +422,25 @@ def test_model_handles_release_their_device_memory():
 
 
 def test_plane_pipeline_stays_at_fp32_level(monkeypatch, oracle_mod):
-    """the default full-alignment path: plane activations (every value kept as its two fp16 pieces) and direct fp16x3
-    convolutions (c3_conv3.h).  Every layer output against the fp64 oracle, next to the all-fp32-MFMA kernels on fp32
-    activations (C3HIP_FP32=1: the forms the range guard falls back to): the same order of rounding noise, 100x inside the
+    """the plane pipeline in keep mode: plane activations (every value kept as its two fp16 pieces), conv1 on its own launch, the
+    stride-1 convolutions as F(2,3) along H (c3_conv3w.h, the default C3HIP_WINO=2) and -- with C3HIP_WINO=0 -- as the direct plane
+    kernel (c3_conv3.h) on every one of the six.  Every layer output against the fp64 oracle, next to the all-fp32-MFMA kernels on
+    fp32 activations (C3HIP_FP32=1: the forms the range guard falls back to): the same order of rounding noise, 100x inside the
     1e-4 gate on the probabilities.  Also the dwell model (conv1 through the tiled contraction with the plane epilogue) and a
-    batch that is not a multiple of any tile."""
+    batch that is not a multiple of any tile.  The fused forms a default call runs (conv1 inside res1a / res1b, the pooling inside
+    res3b) are checked layer by layer through debug taps in tests/test_product_layers_gpu.py."""
     errs = {}
     for ch, seed in ((8, 41), (9, 43)):
         sd = syn.make_state_dict(syn.FULL_ALIGNMENT, ch, True, seed=seed, peaked=True)
         x = syn.make_fa_windows(7, seed=42, channels=ch)
         y_o, d = oracle_mod.fa_forward(sd, x, True, debug=True)
-        for mode, env in (("planes", {}), ("fp32", {"C3HIP_FP32": "1"})):
+        for mode, env in (("planes", {}), ("direct", {"C3HIP_WINO": "0"}), ("fp32", {"C3HIP_FP32": "1"})):
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
             m = make_model(syn.FULL_ALIGNMENT, ch, True, sd, keep=True)
             y = m.predict_numpy(x)
+            if mode != "fp32":
+                assert ("stride1=dddddd" if mode == "direct" else "stride1=wwwwww") in m.describe(), (mode, m.describe())
             e = {}
             for l in range(9):
                 a = m.debug_fetch(f"act{l}", d[f"act{l}"].shape)
@@ -446,31 +450,17 @@ def test_plane_pipeline_stays_at_fp32_level(monkeypatch, oracle_mod):
             errs[(ch, mode)] = e
             for k in env:
                 monkeypatch.delenv(k)
-        print(f"C={ch}:", {k: (round(errs[(ch, 'planes')][k] * 1e6, 2), round(errs[(ch, 'fp32')][k] * 1e6, 2)) for k in errs[(ch, "fp32")]},
-              "(x1e-6: planes, fp32)")
-        for k, v in errs[(ch, "planes")].items():
-            assert v < 1e-5, (ch, k, v)
-            assert v <= 5 * errs[(ch, "fp32")][k] + 3e-7, (ch, k, errs)
+        print(f"C={ch}:", {k: tuple(round(errs[(ch, mode)][k] * 1e6, 2) for mode in ("planes", "direct", "fp32")) for k in errs[(ch, "fp32")]},
+              "(x1e-6: planes F(2,3), planes direct, fp32)")
+        for mode in ("planes", "direct"):
+            for k, v in errs[(ch, mode)].items():
+                assert v < 1e-5, (ch, mode, k, v)
+                assert v <= 5 * errs[(ch, "fp32")][k] + 3e-7, (ch, mode, k, errs)
 
 
 def _layer_errors(m, d, names, sd):
-    """per layer: max |a - d| over the tensor relative to the tensor's range, and the worst CHANNEL relative to that channel's own
-    scale (a channel whose values are 1e-3 of the tensor's is invisible in the first number and is what the next layer's
-    large weights amplify).  A channel's scale is what its BatchNorm gives it, |gamma| + |beta| (the larger of the two
-    producers behind a residual add) -- its observed range if that is larger: a channel the ReLU leaves almost dead on these
-    nine windows is the clipped tail of a sum of that scale, and so is its rounding noise"""
-    whole, chan = {}, {}
-    for name in names:
-        l = int(name[3:])
-        a = m.debug_fetch(name, d[name].shape)
-        assert np.isfinite(a).all(), name
-        err = np.abs(a - d[name]).reshape(-1, a.shape[-1]).max(0)
-        rng = np.abs(d[name]).reshape(-1, a.shape[-1]).max(0)
-        whole[name] = float(err.max()) / max(1.0, float(rng.max()))
-        mag = lambda k: np.abs(sd[syn.FA_CONV_LAYERS[k][1] + ".weight"]) + np.abs(sd[syn.FA_CONV_LAYERS[k][1] + ".bias"])
-        scale = np.maximum(rng, np.maximum(mag(l), mag(l - 2)) if l % 3 == 2 else mag(l))
-        chan[name] = float((err / np.maximum(scale, 1e-30)).max())
-    return whole, chan
+    """util.layer_errors on the tensors of a keep-mode handle's last call"""
+    return util.layer_errors(lambda name: m.debug_fetch(name, d[name].shape), d, names, sd)
 
 
 @pytest.mark.parametrize("channels", [8, 9])
@@ -868,17 +858,28 @@ def test_conv1_inside_the_first_residual_block(channels, monkeypatch, oracle_mod
 def test_pyramid_pooling_inside_the_last_convolution(monkeypatch, oracle_mod):
     """12 x 5 windows: res3b runs on window-aligned tiles (four whole windows each) and pools its own output (c3_conv3.h SPPF).  Batches
     that are not a multiple of four windows, more tiles than workgroups (1100 windows: 1100 tiles on 256 workgroups), against the
-    oracle and against the separate pooling launch (which pools the two fp16 pieces instead of the fp32 value: ~1e-7 apart)"""
+    oracle and against the separate pooling launch (which pools the two fp16 pieces instead of the fp32 value: ~1e-7 apart).  The pooled
+    tensor itself (a debug tap: the fused form writes spp and no act8) against the oracle's, per tensor and per channel."""
     sd = syn.make_state_dict(syn.FULL_ALIGNMENT, 8, True, seed=91)
     for n in (1, 3, 6, 1100):
         x = syn.make_fa_windows(n, seed=92 + n)
-        y = make_model(syn.FULL_ALIGNMENT, 8, True, sd).predict_numpy(x)
+        m = make_model(syn.FULL_ALIGNMENT, 8, True, sd).tap(["spp", "act8"])
+        y = m.predict_numpy(x)
         sel = np.unique(np.r_[0:min(n, 8), max(0, n - 8):n])
-        util.assert_rows_match(y[sel], oracle_mod.fa_forward(sd, x[sel], True), what=f"pooling inside res3b, {n} windows")
+        y_o, d = oracle_mod.fa_forward(sd, x[sel], True, debug=True)
+        util.assert_rows_match(y[sel], y_o, what=f"pooling inside res3b, {n} windows")
+        with pytest.raises(_lib.C3Error, match="act8 is pooled inside res3b"):
+            m.tap_fetch("act8", 0, (1, 12, 5, 256))
+        spp = np.concatenate([m.tap_fetch("spp", i, (1, 3584)) for i in sel])
+        whole, chan = util.layer_errors(lambda name: spp, d, ["spp"], sd)
+        assert whole["spp"] < 2e-5 and chan["spp"] < 2e-5, (n, whole, chan)
         monkeypatch.setenv("C3HIP_SPP_FUSED", "0")
-        y0 = make_model(syn.FULL_ALIGNMENT, 8, True, sd).predict_numpy(x)
+        m0 = make_model(syn.FULL_ALIGNMENT, 8, True, sd).tap(["spp"])
+        y0 = m0.predict_numpy(x)
         monkeypatch.delenv("C3HIP_SPP_FUSED")
         assert np.abs(y - y0).max() < 2e-6
+        spp0 = np.concatenate([m0.tap_fetch("spp", i, (1, 3584)) for i in sel])
+        assert np.abs(spp - spp0).max() < 2e-6 * max(1.0, float(np.abs(d["spp"]).max()))
 
 
 def test_two_handles_side_by_side_give_the_same_rows(oracle_mod):

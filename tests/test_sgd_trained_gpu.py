@@ -47,6 +47,19 @@ def test_rows_on_weights_that_went_through_an_optimizer(kind, channels, steps, b
     print("   layer: error relative to the layer's range (range): " + ", ".join(f"{k_} {e:.1e} ({s:.3g})" for k_, (e, s) in worst.items()))
     assert err < 2e-5 and float(np.abs(yk - y_o).max()) < 2e-5
     assert all(e < 2e-5 for e, _ in worst.values()), worst
+    # the same layers on the forms a default call runs (keep mode switches the fused ones off), through debug taps
+    taps = ("lstm1_out", "lstm2_out", "l4_out") if kind == syn.PILEUP else tuple(f"act{i}" for i in range(1, 8)) + ("spp", "l4_out")
+    mt = make_model(kind, channels, True, sd).tap(taps)
+    assert np.array_equal(mt.wait(mt.submit(x[:k], slot=0)), y[:k])
+    product = {}
+    for name in taps:
+        a = mt.tap_fetch(name, 0, d[name].shape)
+        product[name] = float(np.abs(a - d[name]).max()) / max(float(np.abs(d[name]).max()), 1e-30)
+    print("   product forms (taps): " + ", ".join(f"{k_} {e:.1e}" for k_, e in product.items()))
+    assert all(e < 2e-5 for e in product.values()), product
+    if kind == syn.FULL_ALIGNMENT:
+        whole, chan = util.layer_errors(lambda name: mt.tap_fetch(name, 0, d[name].shape), d, taps[:-1], sd)
+        assert max(chan.values()) < 2e-5, chan
     if kind == syn.FULL_ALIGNMENT:  # headroom of the activations to the range guard's 16000 (fp16 pieces need |x| < 65504)
         assert max(s for k_, (_, s) in worst.items() if k_.startswith("act")) < 16000
     # the same windows in another batch composition: bit-identical rows

@@ -62,3 +62,29 @@ def assert_rows_match(y, y_ref, tol=PROB_TOL, what=""):
     bad = label_mismatches(y, y_ref)
     assert not bad, f"{what}: arg-max label differs outside near-ties at (head_start, window) {bad[:8]}"
     return err
+
+
+def layer_errors(get, d, names, sd):
+    """Full-alignment layer outputs against the oracle's.  get(name) -> the library's tensor of the same windows as d[name].
+    Per tensor: max |a - d| relative to the tensor's range (at least 1).  Per channel (act0 .. act8, spp): the worst CHANNEL relative
+    to that channel's own scale (a channel whose values are 1e-3 of the tensor's is invisible in the first number and is what the
+    next layer's large weights amplify).  A channel's scale is what its BatchNorm gives it, |gamma| + |beta| (the larger of the two
+    producers behind a residual add; spp pools act8's channels) -- its observed range if that is larger: a channel the ReLU leaves
+    almost dead on the windows at hand is the clipped tail of a sum of that scale, and so is its rounding noise.  l4_out has
+    no per-channel number (no BatchNorm behind it)."""
+    whole, chan = {}, {}
+    for name in names:
+        a, ref = get(name), d[name]
+        assert a.shape == ref.shape, (name, a.shape, ref.shape)
+        assert np.isfinite(a).all(), name
+        C = ref.shape[-1] if name.startswith("act") else 256
+        err = np.abs(a.astype(np.float64) - ref).reshape(-1, C).max(0)
+        rng = np.abs(ref).reshape(-1, C).max(0)
+        whole[name] = float(err.max()) / max(1.0, float(rng.max()))
+        if name == "l4_out":
+            continue
+        l = 8 if name == "spp" else int(name[3:])
+        mag = lambda k: np.abs(sd[syn.FA_CONV_LAYERS[k][1] + ".weight"]) + np.abs(sd[syn.FA_CONV_LAYERS[k][1] + ".bias"])
+        scale = np.maximum(rng, np.maximum(mag(l), mag(l - 2)) if l % 3 == 2 else mag(l))
+        chan[name] = float((err / np.maximum(scale, 1e-30)).max())
+    return whole, chan
