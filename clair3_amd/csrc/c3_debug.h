@@ -36,8 +36,8 @@ int c3_debug_keep_activations(c3_model *m, int enable) {
     if (!m) return fail("null model");
     HIP_TRY(hipSetDevice(m->device));
     if (m->keep != (enable != 0)) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        free_workspace(m);
+        HIP_TRY(hipStreamSynchronize(lane(m).stream));
+        free_workspace(lane(m));
         m->keep = enable != 0;
     }
     return 0;
@@ -46,31 +46,32 @@ int c3_debug_keep_activations(c3_model *m, int enable) {
 int c3_debug_fetch(c3_model *m, const char *name, float *host_out, int64_t n_floats) {
     if (!m || !name || !host_out) return fail("null argument");
     HIP_TRY(hipSetDevice(m->device));
-    if (m->last_n <= 0) return fail("nothing has been predicted yet");
+    const Lane &L = lane(m);
+    if (L.last_n <= 0) return fail("nothing has been predicted yet");
     const std::string s = name;
     const float *src = nullptr;
     int64_t n = 0;
     if (m->kind == C3_KIND_PILEUP) {
-        if (s == "lstm1_out") src = m->h1, n = m->last_n * m->positions * 256;
-        else if (s == "lstm2_out") src = m->h2, n = m->last_n * m->positions * 320;
-        else if (s == "gx2") src = m->gx2, n = m->last_n * m->positions * 1280;
+        if (s == "lstm1_out") src = L.h1, n = L.last_n * m->positions * 256;
+        else if (s == "lstm2_out") src = L.h2, n = L.last_n * m->positions * 320;
+        else if (s == "gx2") src = L.gx2, n = L.last_n * m->positions * 1280;
     } else {
         int hh[10], ww[10];
         fa_geometry(m, hh, ww);
         if (s.size() == 4 && s.compare(0, 3, "act") == 0 && s[3] >= '0' && s[3] <= '8') {
             if (!m->keep) return fail("activations are recycled: enable c3_debug_keep_activations first");
             const int l = s[3] - '0';
-            src = m->act[l], n = m->last_n * hh[l + 1] * ww[l + 1] * kConvCout[l];
-        } else if (s == "spp") src = m->spp, n = m->last_n * m->K4;
+            src = L.act[l], n = L.last_n * hh[l + 1] * ww[l + 1] * kConvCout[l];
+        } else if (s == "spp") src = L.spp, n = L.last_n * m->K4;
     }
     if (s == "l4_out") {
         if (!m->keep) return fail("l4_out is only written with c3_debug_keep_activations enabled");
-        src = m->l4dbg, n = m->last_n * m->FC;
+        src = L.l4dbg, n = L.last_n * m->FC;
     }
     if (!src) return fail("unknown debug tensor \"%s\"", name);
     if (n != n_floats) return fail("debug tensor %s has %lld floats, caller expects %lld", name, (long long)n, (long long)n_floats);
     HIP_TRY(hipDeviceSynchronize());
-    const bool planes = m->last_planes && ((m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) || (m->kind == C3_KIND_PILEUP && s == "lstm1_out"));
+    const bool planes = L.last_planes && ((m->kind == C3_KIND_FULL_ALIGNMENT && s.compare(0, 3, "act") == 0) || (m->kind == C3_KIND_PILEUP && s == "lstm1_out"));
     return to_host_values(m, s, src, n, planes, host_out);
 }
 

@@ -256,8 +256,8 @@ struct DenseWresParams {
 };
 
 // ABL (tools/dense_probe.hip only; 0 in the product): 1 no activation loads, 2 no LDS staging writes, 4 no matrix instructions,
-// 8 no fragment reads, 16 no result stores, 32 no barriers; 64 (product A/B knob C3HIP_GX2_NT): non-temporal result stores; 128 / 256
-// (probe only) the results stored in two / three bytes per value.
+// 8 no fragment reads, 16 no result stores, 32 no barriers; 128 / 256 the results stored in two / three bytes per value.  (Non-temporal
+// result stores were measured and not kept: profiles/r05_c_ab_gx2_nontemporal_not_kept.txt.)
 template <int ABL = 0>
 __global__ __launch_bounds__(kDnThreads, 2) void dense_planes_wres_kernel(DenseWresParams p) {
     __shared__ __attribute__((aligned(16))) char smem[4 * kWrStage + 8192];
@@ -342,8 +342,6 @@ __global__ __launch_bounds__(kDnThreads, 2) void dense_planes_wres_kernel(DenseW
             const pl_u32x4 w = __builtin_bit_cast(pl_u32x4, val);
             typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
             __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, crsrc, rowoff == kPlOob ? kPlOob : (rowoff + 32 * q) / 4 * 3, 0, 0);
-        } else if constexpr (ABL & 64) {  // A/B knob (C3HIP_GX2_NT=1): the 173 MB of pre-activations leave with the non-temporal hint
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pl_u32x4, val), crsrc, rowoff + 32 * q, 0, 2);
         } else {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pl_u32x4, val), crsrc, rowoff + 32 * q, 0, 0);
         }

@@ -52,44 +52,11 @@ static int tap_prepare(c3_model *m, int64_t batch) {
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------ the FC chain on its own stream (ring only)
-// tail_begin: the stream the chain of THIS forward pass runs on -- tail_stream, behind everything queued on s so far, when the ring's
-// submit asked for it (m->tail_now), else s itself.  tail_end: marks the chain's end.  tail_guard: called on s right before the first
-// launch that overwrites what a chain reads (the pooled tensor / lstm2_out of the handle's one workspace): waits for the chain that may
-// still be running -- by then it finished a whole network ago, so the wait costs nothing.
-static int tail_guard(c3_model *m, hipStream_t s);
-static int tail_begin(c3_model *m, hipStream_t s, hipStream_t *ts) {
-    *ts = s;
-    if (!m->tail_now) return tail_guard(m, s);  // (a chain on s itself: behind one that may still be running on tail_stream -- they share the partials)
-    if (!m->tail_stream) {
-        HIP_TRY(new_stream(m, &m->tail_stream));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_body_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_tail_done, hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventRecord(m->ev_body_done, s));
-    HIP_TRY(hipStreamWaitEvent(m->tail_stream, m->ev_body_done, 0));
-    *ts = m->tail_stream;
-    return 0;
-}
-static int tail_end(c3_model *m, hipStream_t ts) {
-    if (ts != m->tail_stream || !m->tail_stream) return 0;
-    HIP_TRY(hipEventRecord(m->ev_tail_done, ts));
-    m->tail_pending = true;
-    return 0;
-}
-static int tail_guard(c3_model *m, hipStream_t s) {
-    if (!m->tail_pending) return 0;
-    HIP_TRY(hipStreamWaitEvent(s, m->ev_tail_done, 0));
-    m->tail_pending = false;
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------ FC tail (both networks)
 // L4 as a split-K contraction -> splitk_reduce_selu_kernel -> fc_tail_mfma_kernel (c3_tail.h); the decoder columns behind it
-static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, int64_t n, float *y, const char *tag_l4,
+static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int64_t n, float *y, const char *tag_l4,
                     const char *tag_tail) {
-    hipStream_t s;
-    TRY(tail_begin(m, s0, &s));  // (the ring: the chain on its own stream, behind the layers queued on s0)
+    Lane &L = lane(m);
     const int FC = m->FC, K4 = m->K4;
     const int nk_total = K4 / kBK;
     const int S = l4_splits(m);
@@ -97,13 +64,13 @@ static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, in
     {
         ProfScope ps(m, s, tag_l4, 2.0 * n * FC * K4, 4.0 * (n * K4 + (double)FC * K4 + (double)S * n * FC));
         if (l4_f16) {  // partials carry the features' powers of two (l4_pre)
-            L4Params lp{a, lda, m->l4_wf, m->part, (int)n, FC, K4 / 64, S, (int)((n + kL4BM - 1) / kL4BM), FC / kL4BN};
+            L4Params lp{a, lda, m->l4_wf, L.part, (int)n, FC, K4 / 64, S, (int)((n + kL4BM - 1) / kL4BM), FC / kL4BN};
             ps.mfma(2.0 * lp.m_tiles * kL4BM * FC * K4 * 3, true);
             hipLaunchKernelGGL(l4_stream_kernel<0>, dim3((unsigned)(lp.m_tiles * lp.n_tiles * S)), dim3(kL4Threads), 0, s, lp);
             HIP_TRY(hipGetLastError());
         } else {
             DenseLoaderParams lp{a, lda};
-            EpilogueParams ep{m->part, nullptr, nullptr, FC, n * FC};
+            EpilogueParams ep{L.part, nullptr, nullptr, FC, n * FC};
             ps.mfma(2.0 * ((n + 127) / 128 * 128) * FC * K4, false);
             TRY((launch_gemm<DenseLoader<4>, EPI_PARTIAL, 128, 64>(s, lp, m->l4_w, K4, (int)n, FC, nk_total / S, S, ep)));
         }
@@ -112,12 +79,12 @@ static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, in
         const double fl = 2.0 * n * (FC * 128.0 * m->nb + 128.0 * m->nout);
         ProfScope ps(m, s, tag_tail, fl, 4.0 * ((double)S * n * FC + n * m->nout));
         ps.mfma(2.0 * ((n + 15) / 16 * 16) * m->nb * (FC * 128.0 + 128.0 * 48.0), false);
-        Tail2Params tp{m->l4dbg, m->w5f, m->b5, m->whf, m->bh48, y, (int)n, m->nb, m->row};
+        Tail2Params tp{L.l4dbg, m->w5f, m->b5, m->whf, m->bh48, y, (int)n, m->nb, m->row};
         if (m->tail_fused) {  // the split-K sum inside the tail kernel: two launches behind the last convolution / recurrence, not three
-            tp.part = m->part, tp.S = S, tp.bias4 = m->l4_b, tp.l4out = m->l4dbg;
+            tp.part = L.part, tp.S = S, tp.bias4 = m->l4_b, tp.l4out = L.l4dbg;
             if (l4_f16) tp.pre = m->l4_pre, tp.post = m->l4_post;
         } else {
-            ReduceParams rp{m->part, m->l4_b, m->l4dbg, (int)n, FC, S};
+            ReduceParams rp{L.part, m->l4_b, L.l4dbg, (int)n, FC, S};
             if (l4_f16) rp.pre = m->l4_pre, rp.post = m->l4_post;
             hipLaunchKernelGGL(splitk_reduce_selu_kernel, dim3((unsigned)((n * FC + 255) / 256)), dim3(256), 0, s, rp);
             HIP_TRY(hipGetLastError());
@@ -128,7 +95,7 @@ static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, in
         else
             hipLaunchKernelGGL(fc_tail_mfma_kernel<128>, grid, dim3(256), 0, s, tp);
         HIP_TRY(hipGetLastError());
-        TRY(tap(m, s, kTapL4, m->l4dbg, n));
+        TRY(tap(m, s, kTapL4, L.l4dbg, n));
     }
     if (m->row > m->nout) {  // decoder columns behind the probabilities of every row (c3_decode.h)
         ProfScope ps(m, s, m->kind == C3_KIND_PILEUP ? "p.decode" : "fa.decode", 0.0, 4.0 * n * m->row);
@@ -136,7 +103,7 @@ static int run_tail(c3_model *m, hipStream_t s0, const float *a, int64_t lda, in
         hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dp);
         HIP_TRY(hipGetLastError());
     }
-    return tail_end(m, s);
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------ full alignment
@@ -186,6 +153,7 @@ static bool fa_planes_ok(const c3_model *m) {
 // activations as fp16 piece planes (c3_conv3.h), 8 convolution launches: conv1 inside res1a / res1b, the stride-2 convolutions
 // on the chunk stream of c3_dense.h, the pyramid pooling as the epilogue of res3b
 static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float *y) {
+    Lane &L = lane(m);
     int hh[10], ww[10];
     fa_geometry(m, hh, ww);
     int cin = m->C;
@@ -200,7 +168,6 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             cin = Cout;
             continue;
         }
-        if (l == 8) TRY(tail_guard(m, s));  // res3b (and the pooling behind it) overwrites what a chain still on tail_stream reads
         double flops = 2.0 * M * Cout * 9.0 * cin;
         double bytes = (l == 0 ? 1.0 : 4.0) * n * hh[l] * ww[l] * cin + 4.0 * M * Cout * (l % 3 == 2 ? 2 : 1) + 4.0 * Cout * 9.0 * cin;
         if (fuse1 && l == 1) flops += 2.0 * M * 64.0 * 9.0 * m->C, bytes += 1.0 * n * hh[0] * ww[0] * m->C - 4.0 * M * 64;  // conv1's algorithmic work rides here
@@ -209,7 +176,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         if (l == 0 && cin == 8) {
             ps.mfma(2.0 * ((M + 31) / 32 * 32) * 64.0 * 80.0 * 2, true);
             Conv1F16Params cp;
-            cp.x = x, cp.wfrag = reinterpret_cast<const uint32_t *>(m->conv1_wfrag16), cp.bias = m->conv_b[0], cp.out = m->act[0];
+            cp.x = x, cp.wfrag = reinterpret_cast<const uint32_t *>(m->conv1_wfrag16), cp.bias = m->conv_b[0], cp.out = L.act[0];
             cp.range_flag = m->range_flag, cp.post = m->conv1_post;
             cp.B = (int)n, cp.H = hh[0], cp.W = ww[0], cp.OH = hh[1], cp.OW = ww[1], cp.M = M, cp.groups = (M + 31) / 32;
             const int grid = std::min((cp.groups + 3) / 4, m->wg_slots);
@@ -218,12 +185,12 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         } else if (l == 0) {
             ps.mfma(2.0 * ((M + 127) / 128 * 128) * 64.0 * 96.0 * 3, true);
             Conv1LoaderParams lp{x, (const int8_t *)m->zeros, hh[0], ww[0], cin, hh[1], ww[1]};
-            EpilogueParams ep{m->act[0], m->conv_b[0], nullptr, Cout, 0};
+            EpilogueParams ep{L.act[0], m->conv_b[0], nullptr, Cout, 0};
             ep.post = m->conv1_w16_post, ep.range_flag = m->range_flag;
             TRY((launch_gemm<Conv1Loader<4>, EPI_BIAS_RELU_PLANES, 128, 64, 2>(s, lp, m->conv_w[0], 96, M, Cout, 3, 1, ep, m->conv1_w16)));
         } else if (kConvStride[l] == 2) {
             S2ConvParams sp;
-            sp.a = m->act[l - 1], sp.wf = m->pconv_w[l], sp.bias = m->conv_b[l], sp.post = m->pconv_post[l], sp.c = m->act[l], sp.range_flag = m->range_flag;
+            sp.a = L.act[l - 1], sp.wf = m->pconv_w[l], sp.bias = m->conv_b[l], sp.post = m->pconv_post[l], sp.c = L.act[l], sp.range_flag = m->range_flag;
             sp.M = M, sp.N = Cout, sp.NK = 9 * cin / 64, sp.tiles_n = Cout / kS2BN, sp.tiles = (M + kS2BM - 1) / kS2BM * sp.tiles_n;
             sp.Hin = hh[l], sp.Win = ww[l], sp.Cin = cin, sp.Ho = hh[l + 1], sp.Wo = ww[l + 1];
             TRY(div_magic(hh[l + 1] * ww[l + 1], (int64_t)M + 2 * kS2BM, &sp.mg_hw));
@@ -242,7 +209,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         } else {
             const bool res = l % 3 == 2;
             PlaneConvParams cp;
-            cp.x = m->act[l - 1], cp.wf = m->pconv_w[l], cp.bias = m->conv_b[l], cp.res = res ? m->act[l - 2] : nullptr, cp.out = m->act[l];
+            cp.x = L.act[l - 1], cp.wf = m->pconv_w[l], cp.bias = m->conv_b[l], cp.res = res ? L.act[l - 2] : nullptr, cp.out = L.act[l];
             cp.range_flag = m->range_flag, cp.post = m->pconv_post[l], cp.pre = m->pconv_pre[l];
             cp.M = M, cp.H = hh[l], cp.W = ww[l];
             TRY(div_magic(hh[l] * ww[l], (int64_t)M + 2 * kPlBM, &cp.mg_hw));
@@ -254,7 +221,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             const bool sppf = l == 8 && sppf_ok;
             constexpr int wpt = kPlBM / 60;  // windows per tile
             if (sppf) {
-                cp.spp = m->spp;
+                cp.spp = L.spp;
                 cp.tiles = (int)((n + wpt - 1) / wpt) * (Cout / 64);
             }
             if (src8) {
@@ -276,8 +243,8 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             const bool wino_layer = m->wino >= 2 || (m->wino == 1 && (Cout == 64 || Cout == 128));
             if (wino_layer && !src8 && !sppf && m->wconv_w[l]) {
                 WinoConvParams wp;
-                wp.x = m->act[l - 1], wp.wf = m->wconv_w[l], wp.bias = m->conv_b[l], wp.post = m->wconv_post[l];
-                wp.res = res ? m->act[l - 2] : nullptr, wp.out = m->act[l], wp.range_flag = m->range_flag;
+                wp.x = L.act[l - 1], wp.wf = m->wconv_w[l], wp.bias = m->conv_b[l], wp.post = m->wconv_post[l];
+                wp.res = res ? L.act[l - 2] : nullptr, wp.out = L.act[l], wp.range_flag = m->range_flag;
                 wp.M = M, wp.H = hh[l], wp.W = ww[l], wp.Hj = (hh[l] + 1) / 2, wp.Mp = (int)(n * wp.Hj * ww[l]);
                 TRY(div_magic(wp.Hj * ww[l], (int64_t)wp.Mp + 2 * kWTM, &wp.mg_hjw));
                 TRY(div_magic(ww[l], wp.Hj * ww[l], &wp.mg_w));
@@ -299,7 +266,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                     else hipLaunchKernelGGL((conv3x3_wino_planes_kernel<256, false>), wgrid, wblock, 0, s, wp);
                 }
                 HIP_TRY(hipGetLastError());
-                TRY(tap(m, s, l, m->act[l], n, true));
+                TRY(tap(m, s, l, L.act[l], n, true));
                 m->choice_s1[(l / 3) * 2 + (l % 3 - 1)] = 'w';
                 cin = Cout;
                 continue;
@@ -330,12 +297,12 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             HIP_TRY(hipGetLastError());
             if (sppf) {  // the epilogue pooled the tiles: spp written, no act8
                 tap_skip(m, 8);
-                TRY(tap(m, s, kTapSpp, m->spp, n));
+                TRY(tap(m, s, kTapSpp, L.spp, n));
                 cin = Cout;
                 continue;
             }
         }
-        TRY(tap(m, s, l, m->act[l], n, true));
+        TRY(tap(m, s, l, L.act[l], n, true));
         cin = Cout;
     }
     if (!sppf_ok) {
@@ -343,45 +310,45 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         if (hh[9] == 12 && ww[9] == 5) {
             if (14 * 256 != m->K4) return fail("unsupported geometry: L4 expects %d inputs", m->K4);
             const int grid = (int)std::min<int64_t>(n, 8192);
-            hipLaunchKernelGGL((spp_planes_fixed_kernel<12, 5>), dim3(grid), dim3(256), 0, s, (const void *)m->act[8], m->spp, (int)n, 256);
+            hipLaunchKernelGGL((spp_planes_fixed_kernel<12, 5>), dim3(grid), dim3(256), 0, s, (const void *)L.act[8], L.spp, (int)n, 256);
         } else {
             SppParams sp;
             TRY(spp_bins(m, hh[9], ww[9], sp));
-            sp.in = m->act[8], sp.out = m->spp, sp.B = (int)n;
+            sp.in = L.act[8], sp.out = L.spp, sp.B = (int)n;
             const int64_t total = n * m->K4;
             const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
             hipLaunchKernelGGL(spp_planes_kernel, dim3(grid), dim3(256), 0, s, sp);
         }
         HIP_TRY(hipGetLastError());
-        TRY(tap(m, s, kTapSpp, m->spp, n));
+        TRY(tap(m, s, kTapSpp, L.spp, n));
     }
-    m->last_planes = true;
-    return run_tail(m, s, m->spp, m->K4, n, y, "fa.l4", "fa.tail");
+    L.last_planes = true;
+    return run_tail(m, s, L.spp, m->K4, n, y, "fa.l4", "fa.tail");
 }
 
 // The fp32 form of the full-alignment network (range-guard fallback, C3HIP_FP32=1, geometries the plane kernels are not
 // sized for): fp32 NHWC activations, every convolution an implicit GEMM on v_mfma_f32_32x32x2_f32 (c3_gemm.h ConvLoader /
 // Conv1Loader), pooling and tail on fp32.
 static int run_fa_fp32(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float *y) {
-    m->last_planes = false;
+    Lane &L = lane(m);
+    L.last_planes = false;
     int hh[10], ww[10];
     fa_geometry(m, hh, ww);
     int cin = m->C;
     for (int l = 0; l < 9; ++l) {
         const int Cout = kConvCout[l];
         const int M = (int)(n * hh[l + 1] * ww[l + 1]);
-        if (l == 8) TRY(tail_guard(m, s));
         const double flops = 2.0 * M * Cout * 9.0 * cin;
         const double bytes = (l == 0 ? 1.0 : 4.0) * n * hh[l] * ww[l] * cin + 4.0 * M * Cout * (l % 3 == 2 ? 2 : 1) + 4.0 * Cout * 9.0 * cin;
         ProfScope ps(m, s, kFaLayerTag[l], flops, bytes);
         const bool res = l % 3 == 2;
-        EpilogueParams ep{m->act[l], m->conv_b[l], res ? m->act[l - 2] : nullptr, Cout, 0};
+        EpilogueParams ep{L.act[l], m->conv_b[l], res ? L.act[l - 2] : nullptr, Cout, 0};
         if (l == 0) {
             Conv1LoaderParams lp{x, (const int8_t *)m->zeros, hh[0], ww[0], cin, hh[1], ww[1]};
             ps.mfma(2.0 * ((M + 127) / 128 * 128) * 64.0 * 96.0, false);
             TRY((launch_gemm<Conv1Loader<4>, EPI_BIAS_RELU, 128, 64>(s, lp, m->conv_w[0], 96, M, Cout, 3, 1, ep)));
         } else {
-            ConvLoaderParams lp{m->act[l - 1], m->zeros, hh[l], ww[l], cin, hh[l + 1], ww[l + 1], kConvStride[l], cin / kBK};
+            ConvLoaderParams lp{L.act[l - 1], m->zeros, hh[l], ww[l], cin, hh[l + 1], ww[l + 1], kConvStride[l], cin / kBK};
             const int nk = 9 * cin / kBK;
             const int64_t ldb = 9 * cin;
             ps.mfma(2.0 * ((M + 127) / 128 * 128) * (double)Cout * 9.0 * cin, false);
@@ -390,21 +357,21 @@ static int run_fa_fp32(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, f
             else
                 TRY((launch_gemm<ConvLoader<4>, EPI_BIAS_RELU, 128, 64>(s, lp, m->conv_w[l], ldb, M, Cout, nk, 1, ep)));
         }
-        TRY(tap(m, s, l, m->act[l], n));
+        TRY(tap(m, s, l, L.act[l], n));
         cin = Cout;
     }
     {
         SppParams sp;
         TRY(spp_bins(m, hh[9], ww[9], sp));
-        sp.in = m->act[8], sp.out = m->spp, sp.B = (int)n;
+        sp.in = L.act[8], sp.out = L.spp, sp.B = (int)n;
         ProfScope ps(m, s, "fa.spp", 0.0, 4.0 * n * (hh[9] * ww[9] * 256.0 + m->K4));
         const int64_t total = n * m->K4;
         const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
         hipLaunchKernelGGL(spp_kernel, dim3(grid), dim3(256), 0, s, sp);
         HIP_TRY(hipGetLastError());
-        TRY(tap(m, s, kTapSpp, m->spp, n));
+        TRY(tap(m, s, kTapSpp, L.spp, n));
     }
-    return run_tail(m, s, m->spp, m->K4, n, y, "fa.l4", "fa.tail");
+    return run_tail(m, s, L.spp, m->K4, n, y, "fa.l4", "fa.tail");
 }
 
 static int run_fa(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float *y) {
@@ -421,6 +388,7 @@ static int run_fa(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float 
 // LSTM2 recurrence -> tail.  With `starts` the windows are gathered out of one region matrix (c3_predict_pileup_region).
 template <typename T>
 static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float *y, const int32_t *starts = nullptr) {
+    Lane &L = lane(m);
     const int Tn = m->positions;
     const int M = (int)(n * Tn);
     // int8 windows feed the fp16 projection fragments (counts are exact in fp16); int32 windows keep an fp32 projection inside
@@ -428,7 +396,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
     const bool l1_f16 = m->f16_ok && m->whh16[0] && (sizeof(T) != 1 || m->l1_wih16);
     const int beside = std::max(m->sharing, m->lane_sharing);  // other batches on the chip: the caller's handles, or this handle's other lanes (c3_model.h)
     const bool h1_planes = l1_f16 && m->proj2_pw;  // h1 leaves LSTM1 as fp16 piece planes for c3_dense.h
-    m->last_planes = h1_planes;
+    L.last_planes = h1_planes;
     {
         ProfScope ps(m, s, "p.lstm1", 2.0 * M * 1024.0 * m->C + 2.0 * M * 2.0 * 512.0 * 128.0, sizeof(T) * (double)M * m->C + 4.0 * M * 256.0);
         // half tiles (8 windows per workgroup, c3_lstm_fused.h OPT bit 2) while the full tiles would leave half the CUs without a
@@ -438,11 +406,11 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
         const double tiles = (double)(half1 ? (n + 7) / 8 * 16 : (n + 15) / 16 * 16) * Tn * 2;  // (window, step, direction) rows of the 16-row tiles
         // recurrent part 512 x 128 as fp16x3 (or fp32); input part: int8 windows 512 x 32 against two weight pieces, else 512 x 20 fp32
         ps.mfma(l1_f16 ? tiles * 2.0 * 512 * (128 * 3 + (sizeof(T) == 1 ? 32 * 2 : 0)) : tiles * 2.0 * 512 * (128 + 20), l1_f16);
-        LstmFusedParams<T> lp{x, starts, m->l1_wih, m->l1_bias, m->whh[0], reinterpret_cast<const uint32_t *>(m->l1_wih16), m->h1, (int)n, Tn, m->C};
+        LstmFusedParams<T> lp{x, starts, m->l1_wih, m->l1_bias, m->whh[0], reinterpret_cast<const uint32_t *>(m->l1_wih16), L.h1, (int)n, Tn, m->C};
         const dim3 grid((unsigned)((n + 15) / 16), 2);
         if (l1_f16) {
             lp.whh = m->whh16[0];
-            if (h1_planes) lp.hplanes = m->h1;
+            if (h1_planes) lp.hplanes = L.h1;
             m->choice_lstm1 = half1 ? "fused-f16x3-half-tiles" : "fused-f16x3-full-tiles";
             bool launched = false;
             if constexpr (sizeof(T) == 1) {
@@ -460,7 +428,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             hipLaunchKernelGGL(lstm1_fused_kernel<T>, grid, dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());
-        TRY(tap(m, s, kTapLstm1, m->h1, n, h1_planes));
+        TRY(tap(m, s, kTapLstm1, L.h1, n, h1_planes));
     }
     {
         ProfScope ps(m, s, "p.proj2", 2.0 * M * 1280.0 * 256.0, 4.0 * M * (256.0 + 1280.0));
@@ -468,39 +436,36 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
         if (h1_planes && m->proj2_pwr && (M + kWrBM - 1) / kWrBM >= 2 * 8 * std::max(1, m->wg_slots / 16 / (1280 / kWrBN))) {
             // weights resident in registers (c3_dense.h): 8 XCDs x lanes x 5 column tiles of workgroups, each walking the row tiles of its lane
             DenseWresParams wp;
-            wp.a = m->h1, wp.w = m->proj2_pwr, wp.bias = m->proj_b[1], wp.c = m->gx2, wp.post_scale = m->proj2_post_scale;
+            wp.a = L.h1, wp.w = m->proj2_pwr, wp.bias = m->proj_b[1], wp.c = L.gx2, wp.post_scale = m->proj2_post_scale;
             wp.M = M, wp.N = 1280, wp.tiles_m = (M + kWrBM - 1) / kWrBM, wp.tiles_n = 1280 / kWrBN;
             wp.lanes_per_xcd = std::max(1, m->wg_slots / 16 / wp.tiles_n);  // CUs per XCD / column tiles (32 / 5 = 6)
             // beside other handles half as many, twice as long workgroups: 120 of them leave room for the 128 of another batch's
             // LSTM launch (three batches in flight 5.46 M -> 5.59 M windows/s; alone 4.9 M -> 4.3 M, hence the caller's hint)
             if (beside > 1) wp.lanes_per_xcd = std::max(1, wp.lanes_per_xcd / 2);
             m->choice_proj2 = beside > 1 ? "weights-resident-half-grid" : "weights-resident";
-            static const bool gx2_nt = getenv("C3HIP_GX2_NT") && atoi(getenv("C3HIP_GX2_NT")) != 0;  // A/B knob (profiles/r05_*_ab_gx2_nt.txt)
-            if (gx2_nt) hipLaunchKernelGGL(dense_planes_wres_kernel<64>, dim3(8 * wp.lanes_per_xcd * wp.tiles_n), dim3(kDnThreads), 0, s, wp);
-            else hipLaunchKernelGGL(dense_planes_wres_kernel<0>, dim3(8 * wp.lanes_per_xcd * wp.tiles_n), dim3(kDnThreads), 0, s, wp);
+            hipLaunchKernelGGL(dense_planes_wres_kernel<0>, dim3(8 * wp.lanes_per_xcd * wp.tiles_n), dim3(kDnThreads), 0, s, wp);
             HIP_TRY(hipGetLastError());
         } else if (h1_planes) {  // batches below ~190 windows: fewer than two row tiles per lane
             DensePlanesParams dp;
-            dp.a = m->h1, dp.w = m->proj2_pw, dp.bias = m->proj_b[1], dp.c = m->gx2, dp.post = m->proj2_post;
+            dp.a = L.h1, dp.w = m->proj2_pw, dp.bias = m->proj_b[1], dp.c = L.gx2, dp.post = m->proj2_post;
             dp.M = M, dp.N = 1280, dp.K = 256, dp.tiles_n = 1280 / kDnBN, dp.tiles = ((M + kDnBM - 1) / kDnBM) * dp.tiles_n;
             m->choice_proj2 = "128x128-chunk-stream";
             hipLaunchKernelGGL(dense_planes_pipe_kernel<0>, dim3(std::min(dp.tiles, m->wg_slots / 2)), dim3(kDnThreads), 0, s, dp);
             HIP_TRY(hipGetLastError());
         } else {
-            DenseLoaderParams lp{m->h1, 256};
-            EpilogueParams ep{m->gx2, m->proj_b[1], nullptr, 1280, 0};
+            DenseLoaderParams lp{L.h1, 256};
+            EpilogueParams ep{L.gx2, m->proj_b[1], nullptr, 1280, 0};
             m->choice_proj2 = "fp32-mfma";
             TRY((launch_gemm<DenseLoader<4>, EPI_BIAS, 128, 128>(s, lp, m->proj_w[1], 256, M, 1280, 8, 1, ep)));
         }
-        TRY(tap(m, s, kTapGx2, m->gx2, n));
+        TRY(tap(m, s, kTapGx2, L.gx2, n));
     }
-    TRY(tail_guard(m, s));  // LSTM2 overwrites lstm2_out, which a chain still on tail_stream reads
     {
         ProfScope ps(m, s, "p.lstm2", 2.0 * M * 2.0 * 640.0 * 160.0, 4.0 * M * (1280.0 + 320.0));
         const bool l2_f16 = m->f16_ok && m->whh16[1];
         const bool half2 = l2_f16 && m->half_tiles && beside <= 1 && 2 * ((n + 15) / 16) <= m->wg_slots / 4;
         ps.mfma((double)(half2 ? (n + 7) / 8 * 16 : (n + 15) / 16 * 16) * Tn * 2 * 2.0 * 640 * 160 * (l2_f16 ? 3 : 1), l2_f16);
-        Lstm2Params lp{m->gx2, m->whh[1], m->h2, (int)n, Tn, 1280};
+        Lstm2Params lp{L.gx2, m->whh[1], L.h2, (int)n, Tn, 1280};
         if (l2_f16) {
             lp.whh = m->whh16[1];
             m->choice_lstm2 = half2 ? "f16x3-half-tiles" : "f16x3-full-tiles";
@@ -511,9 +476,9 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             hipLaunchKernelGGL(lstm_recurrent_kernel_v2<160>, dim3((unsigned)((n + 15) / 16), 2), dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());
-        TRY(tap(m, s, kTapLstm2, m->h2, n));
+        TRY(tap(m, s, kTapLstm2, L.h2, n));
     }
-    return run_tail(m, s, m->h2, m->K4, n, y, "p.l4", "p.tail");
+    return run_tail(m, s, L.h2, m->K4, n, y, "p.l4", "p.tail");
 }
 
 // ------------------------------------------------------------------------------------------ both
@@ -529,61 +494,17 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
     TRY(ensure_workspace(m, batch));
     if (!m->tap_call) TRY(tap_prepare(m, batch));
     const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
-    auto run = [&](hipStream_t st, const char *xp, const int32_t *sp, int64_t n, float *yp) -> int {
-        if (m->kind == C3_KIND_FULL_ALIGNMENT) return run_fa(m, st, (const int8_t *)xp, n, yp);
-        if (x_dtype == C3_DTYPE_I8) return run_pileup_t<int8_t>(m, st, (const int8_t *)xp, n, yp, sp);
-        return run_pileup_t<int32_t>(m, st, (const int32_t *)xp, n, yp, sp);
-    };
-    for (int64_t off = 0; off < batch; off += m->cap) {
-        const int64_t n = std::min<int64_t>(m->cap, batch - off);
+    Lane &L = lane(m);
+    for (int64_t off = 0; off < batch; off += L.cap) {
+        const int64_t n = std::min<int64_t>(L.cap, batch - off);
         const char *xp = starts ? (const char *)x : (const char *)x + off * wbytes;  // region matrix is shared
         const int32_t *sp = starts ? starts + off : nullptr;
         float *yp = y + off * m->row;
-        // DUO (C3HIP_DUO=1): the micro-batch as two halves on two streams.  Every layer is its own launch and every workgroup of a
-        // launch is in the same phase, so ~10 us of head and tail per launch overlap nothing when one batch is alone on the chip
-        // (DESIGN.md 3.8); windows are independent, so the second half's launches -- enqueued behind the first half's, i.e. half a
-        // step out of phase -- fill them.  Each half works in its own part of the workspace (the buffers are sized for the whole
-        // micro-batch); a window's row does not depend on the batch it travels in, so the rows are the undivided call's bit for bit.
-        const int64_t duo_min = m->kind == C3_KIND_FULL_ALIGNMENT ? 192 : 768;
-        if (m->duo > 0 && !m->keep && m->sharing <= 1 && n >= duo_min) {
-            if (!m->duo_stream) {
-                HIP_TRY(new_stream(m, &m->duo_stream));
-                HIP_TRY(hipEventCreateWithFlags(&m->duo_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&m->duo_join, hipEventDisableTiming));
-            }
-            const int64_t n0 = ((n / 2 + 15) / 16) * 16, n1 = n - n0;  // whole 16-window tiles in the first half
-            HIP_TRY(hipEventRecord(m->duo_fork, s));
-            HIP_TRY(hipStreamWaitEvent(m->duo_stream, m->duo_fork, 0));
-            m->tap_base = m->tap_call_off + off;
-            TRY(run(s, xp, sp, n0, yp));
-            // the second half: the same buffers, behind the first half's share of each
-            float *const act0[9] = {m->act[0], m->act[1], m->act[2], m->act[3], m->act[4], m->act[5], m->act[6], m->act[7], m->act[8]};
-            float *const spp0 = m->spp, *const part0 = m->part, *const dbg0 = m->l4dbg, *const h10 = m->h1, *const gx20 = m->gx2, *const h20 = m->h2;
-            if (m->kind == C3_KIND_FULL_ALIGNMENT) {
-                int hh[10], ww[10];
-                fa_geometry(m, hh, ww);
-                size_t biggest = 0;
-                for (int l = 0; l < 9; ++l) biggest = std::max(biggest, (size_t)hh[l + 1] * ww[l + 1] * kConvCout[l]);
-                for (int l = 0; l < 9; ++l) m->act[l] = act0[l] + biggest * (size_t)n0;
-                m->spp = spp0 + (size_t)n0 * m->K4;
-            } else {
-                const size_t T = (size_t)m->positions;
-                m->h1 = h10 + (size_t)n0 * T * 256, m->gx2 = gx20 + (size_t)n0 * T * 1280, m->h2 = h20 + (size_t)n0 * T * 320;
-            }
-            m->part = part0 + (size_t)l4_splits(m) * n0 * m->FC, m->l4dbg = dbg0 + (size_t)n0 * m->FC;
-            m->tap_base = m->tap_call_off + off + n0;
-            const int rc = run(m->duo_stream, starts ? xp : xp + n0 * wbytes, sp ? sp + n0 : nullptr, n1, yp + n0 * m->row);
-            for (int l = 0; l < 9; ++l) m->act[l] = act0[l];
-            m->spp = spp0, m->part = part0, m->l4dbg = dbg0, m->h1 = h10, m->gx2 = gx20, m->h2 = h20;
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(m->duo_join, m->duo_stream));
-            HIP_TRY(hipStreamWaitEvent(s, m->duo_join, 0));
-            m->last_n = n0;
-            continue;
-        }
         m->tap_base = m->tap_call_off + off;
-        TRY(run(s, xp, sp, n, yp));
-        m->last_n = n;
+        if (m->kind == C3_KIND_FULL_ALIGNMENT) TRY(run_fa(m, s, (const int8_t *)xp, n, yp));
+        else if (x_dtype == C3_DTYPE_I8) TRY(run_pileup_t<int8_t>(m, s, (const int8_t *)xp, n, yp, sp));
+        else TRY(run_pileup_t<int32_t>(m, s, (const int32_t *)xp, n, yp, sp));
+        L.last_n = n;
     }
     return 0;
 }

@@ -19,9 +19,10 @@
 // Rows always leave through a copy kernel on the COMPUTE stream (host_copy_kernel writes the pinned, device-mapped result
 // buffer): handing them to a transfer stream -- event, cross-queue wait, DMA copies, event -- cost the compute queue ~75 us per
 // batch (profiles/r03_e_d2h_by_kernel.txt).  Windows come in on the transfer stream (DMA engine; the compute stream's wait for
-// that event is free, the transfer finished batches ago) -- except a small batch with nothing else in flight (the blocking call
-// of one chunk): there a copy kernel on the compute stream reading the pinned staging buffer is the shorter way, up to
-// kKernelCopyMax bytes (4000 pileup windows = 2.4 MB, ~50 us at PCIe Gen5 rates).
+// that event is free, the transfer finished batches ago) -- except a batch in a lane, which stages them on its lane's own stream,
+// and a small batch with nothing else in flight (the blocking call of one chunk): there a copy kernel on the compute stream
+// reading the pinned staging buffer is the shorter way, up to kKernelCopyMax bytes (4000 pileup windows = 2.4 MB, ~50 us at
+// PCIe Gen5 rates).
 constexpr size_t kKernelCopyMax = (size_t)4 << 20;
 __global__ __launch_bounds__(256) void host_copy_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16,
                                                        const uint32_t *flag_src, uint32_t *flag_dst) {
@@ -49,17 +50,6 @@ static int stage_h2d(void *dev, void *pin, const void *src, size_t bytes, hipStr
         HIP_TRY(hipMemcpyAsync((char *)dev + off, (char *)pin + off, n, hipMemcpyHostToDevice, s));
     }
     return 0;
-}
-
-// The forward pass of a batch of the ring on the handle's stream, its FC chain on tail_stream (c3_forward.h tail_begin): *outs is the stream the
-// rows are complete on -- where the copy-out kernel and the slot's event go.  The next batch's layers are queued on m->stream right behind this
-// batch's LAST LAYER, not behind its chain.
-static int ring_forward(c3_model *m, const void *x_dev, int x_dtype, int64_t batch, float *y_dev, hipStream_t *outs) {
-    m->tail_now = m->tail_split && !m->keep && m->duo == 0 && !m->prof;
-    const int rc = forward_device(m, m->stream, x_dev, x_dtype, batch, y_dev);
-    *outs = (m->tail_now && m->tail_stream && batch > 0) ? m->tail_stream : m->stream;
-    m->tail_now = false;
-    return rc;
 }
 
 extern "C" {
@@ -120,28 +110,26 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     if (sl.busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
     HIP_TRY(hipSetDevice(m->device));
     if (!m->loaded) return fail("model has no weights: call c3_model_load first");
-    // the batch in slot k runs in lane k % lanes (c3_model.h Lane): its own workspace and kernel stream, so that it overlaps the batch of the
-    // neighbouring slot on the chip; keep mode, the two-halves knob and profiling stay in one lane
-    // -- and so does a batch that fills the chip by itself: two of those side by side only get in each other's way (same-box A/B,
-    // profiles/r06_i_ab_ring_lanes.txt: full alignment ring +5.5 % at B = 256, -4 % at B = 1000)
-    const bool in_lane = m->ring_lanes > 1 && batch <= m->lane_max_batch && !m->keep && m->duo == 0 && !m->prof;
+    // a small batch runs in the next lane (c3_model.h Lane): its own workspace and kernel stream, so that it overlaps the batches before it
+    // on the chip; keep mode and profiling stay in one lane -- and so does a batch that fills the chip by itself: two of those side by side
+    // only get in each other's way (same-box A/B, profiles/r06_i_ab_ring_lanes.txt: full alignment ring +5.5 % at B = 256, -4 % at B = 1000)
+    const bool in_lane = m->ring_lanes > 1 && batch <= m->lane_max_batch && !m->keep && !m->prof;
     // lanes are dealt in the ORDER of the submits, not by slot number: three slots on two lanes (the pileup network) would put two of every
-    // three batches behind each other in lane 0 (C3HIP_LANE_ORDER=slot: the slot's number, as before)
-    TRY(use_lane(m, in_lane ? (m->lane_by_slot ? slot : (int)(m->lane_next++ % (unsigned)m->ring_lanes)) % m->ring_lanes : 0));
+    // three batches behind each other in lane 0 (profiles/r06_n_ab_lane_sharing.txt)
+    TRY(use_lane(m, in_lane ? (int)(m->lane_next++ % (unsigned)m->ring_lanes) : 0));
+    Lane &L = lane(m);
     const size_t xb = (size_t)(batch * c3_model_window_bytes(m, x_dtype));
     const size_t yb = (size_t)batch * m->row * sizeof(float);
-    // C3HIP_HOST_COPY_KERNEL: 0 = never, 1 = up to kKernelCopyMax, n > 1 = up to n KB (A/B of the threshold)
-    const size_t kcopy_max = m->host_copy_kernel > 1 ? (size_t)m->host_copy_kernel << 10 : kKernelCopyMax;
-    // ... and only while no other batch of this handle is in flight: behind a running batch the transfer stream brings the windows
-    // in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s), alone the copy kernel is the shorter way (blocking call of one
-    // chunk 3.87 M against 3.64 M)
+    // windows of up to kKernelCopyMax bytes come in through the copy kernel only while no other batch of this handle is in flight: behind a
+    // running batch the transfer stream brings the windows in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s), alone the copy
+    // kernel is the shorter way (blocking call of one chunk 3.87 M against 3.64 M)
     bool alone = true;
     for (int k = 0; k < kHostSlots; ++k) alone &= !m->slot[k].busy;
     // beside batches in the other lanes: the kernel forms for a shared chip (c3_model.h lane_sharing; rows bit-identical either way) -- when this
     // batch and the largest ones in flight in the other lanes would, on half tiles (two workgroups per 8 windows), ask for more workgroups than
     // the chip has CUs (ring of 1024-window batches: yes; the blocking call's 250 + 750 pieces: no, 252 half-tile workgroups fit side by side)
     int64_t beside_windows = 0;
-    if (in_lane && !alone && m->lane_sharing_ok) {
+    if (in_lane && !alone) {
         int64_t other[kHostSlots];
         int no = 0;
         for (int k = 0; k < kHostSlots; ++k)
@@ -154,48 +142,35 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
         LaneSharing(c3_model *m_, int v) : m(m_) { m->lane_sharing = v; }
         ~LaneSharing() { m->lane_sharing = 1; }
     } lane_sharing(m, (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1);
-    if (batch > 0 && m->host_copy_kernel && alone && xb <= kcopy_max && yb <= kcopy_max) {
-        TRY(ensure_slot(m, sl, (xb + 255) & ~(size_t)255, y_dev_out ? 0 : (yb + 255) & ~(size_t)255));  // (rows that stay on the device need no slot buffers)
-        StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
-        hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, m->stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xb + 15) / 16,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
-        const bool f16 = m->f16_ok;
-        hipStream_t outs;
-        TRY(ring_forward(m, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, &outs));
-        if (y_dev_out && f16)
-            hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, outs, y_dev_out, batch * m->row, m->range_flag);
-        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(yb)), dim3(256), 0, outs, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                           y_dev_out ? 0 : (yb + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(sl.ev_out, outs));
-        sl.used_f16 = f16;
-    } else
     if (batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
         TRY(ensure_slot(m, sl, xb, y_dev_out ? 0 : yb));  // (rows that stay on the device need no slot buffers)
-        if (in_lane && m->lane_h2d) {
+        if (alone && xb <= kKernelCopyMax && yb <= kKernelCopyMax) {
+            StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
+            hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xb + 15) / 16,
+                               (const uint32_t *)nullptr, (uint32_t *)nullptr);
+            HIP_TRY(hipGetLastError());
+        } else if (in_lane) {
             // a small batch in a lane brings its windows in on the lane's OWN stream: copy, kernels and the copy-out in order in one queue, no
-            // event between two streams -- the batches of the other lanes are what the copy runs under (c3_model.h lane_h2d)
-            TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, m->stream));
+            // event between two streams -- the batches of the other lanes are what the copy runs under (c3_model.h, the streams)
+            TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, L.stream));
         } else {
-            if (!m->h2d_stream) HIP_TRY(new_stream(m, &m->h2d_stream));
+            if (!m->h2d_stream) HIP_TRY(hipStreamCreateWithFlags(&m->h2d_stream, hipStreamNonBlocking));
             TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, m->h2d_stream));
             HIP_TRY(hipEventRecord(sl.ev_h2d, m->h2d_stream));
-            HIP_TRY(hipStreamWaitEvent(m->stream, sl.ev_h2d, 0));
+            HIP_TRY(hipStreamWaitEvent(L.stream, sl.ev_h2d, 0));
         }
         const bool f16 = m->f16_ok;
-        hipStream_t outs;
-        TRY(ring_forward(m, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, &outs));
+        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y));
         if (y_dev_out && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
-            hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, outs, y_dev_out, batch * m->row, m->range_flag);
+            hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, L.stream, y_dev_out, batch * m->row, m->range_flag);
         // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
         // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
         // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
-        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(yb)), dim3(256), 0, outs, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
+        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(yb)), dim3(256), 0, L.stream, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
                            y_dev_out ? 0 : (yb + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(sl.ev_out, outs));
+        HIP_TRY(hipEventRecord(sl.ev_out, L.stream));
         sl.used_f16 = f16;
     }
     sl.y_dev_out = y_dev_out;
@@ -220,10 +195,10 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out);
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out);
             m->tap_call_off = 0;
             TRY(rc);
-            HIP_TRY(hipStreamSynchronize(m->stream));
+            HIP_TRY(hipStreamSynchronize(lane(m).stream));
         }
         return 0;
     }
@@ -241,11 +216,11 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, m->stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y);
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y);
             m->tap_call_off = 0;
             TRY(rc);
-            HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, m->stream));
-            HIP_TRY(hipStreamSynchronize(m->stream));
+            HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, lane(m).stream));
+            HIP_TRY(hipStreamSynchronize(lane(m).stream));
         }
     }
     memcpy(sl.y_host, sl.pin_y, sl.y_bytes);
@@ -284,25 +259,11 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
     next = std::max<int64_t>(next, 1);
     // A batch that fits the ring's lanes as EQUAL pieces -- one lane-sized piece per lane: 334 + 333 + 333 full-alignment windows for the
     // reference's batch of 1000 -- is cut that way: every piece brings its windows in on its own lane's stream and runs beside the others
-    // (profiles/r06_o_*: 656 - 667 k -> 700 - 721 k windows/s same-box; with the lanes' first form -- up to three streams each -- the same cut
-    // LOST 4 %, profiles/r06_i_ab_ring_lanes.txt).  C3HIP_PREDICT_EQUAL=0: the growing pieces below for every batch.
-    static const bool equal_ok = !(getenv("C3HIP_PREDICT_EQUAL") && atoi(getenv("C3HIP_PREDICT_EQUAL")) == 0);
-    const bool lanes_on = m->ring_lanes > 1 && !m->keep && m->duo == 0 && !m->prof;
-    const int64_t equal = (equal_ok && lanes_on && m->kind == C3_KIND_FULL_ALIGNMENT && batch <= (int64_t)m->ring_lanes * m->lane_max_batch)
+    // (profiles/r06_o_*: 656 - 667 k -> 700 - 721 k windows/s same-box against the growing pieces; with the lanes' first form -- up to three
+    // streams each -- the same cut LOST 4 %, profiles/r06_i_ab_ring_lanes.txt, r06_j_blocking_call_pieces.txt).
+    const bool lanes_on = m->ring_lanes > 1 && !m->keep && !m->prof;
+    const int64_t equal = (lanes_on && m->kind == C3_KIND_FULL_ALIGNMENT && batch <= (int64_t)m->ring_lanes * m->lane_max_batch)
                               ? (batch + m->ring_lanes - 1) / m->ring_lanes : 0;
-    // C3HIP_PREDICT_PIECES=a,b,c: A/B knob -- the piece sizes themselves (the last one repeats)
-    static const std::vector<int64_t> forced = [] {
-        std::vector<int64_t> v;
-        if (const char *e = getenv("C3HIP_PREDICT_PIECES"))
-            for (const char *q = e; *q;) {
-                char *end = nullptr;
-                const long long n = strtoll(q, &end, 10);
-                if (end == q) break;
-                if (n > 0) v.push_back(n);
-                q = *end ? end + 1 : end;
-            }
-        return v;
-    }();
     // debug taps (c3_debug_tap): every piece's windows at their place in this call
     if (m->tap_mask) {
         TRY(tap_prepare(m, batch));
@@ -312,7 +273,6 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
         int64_t take = std::min(next, batch - off);
         if (batch - off - take < next / 2 || batch - off - take < chunk / 2) take = batch - off;
         if (equal > 0) take = std::min(equal, batch - off);
-        if (!forced.empty()) take = std::min<int64_t>(forced[std::min<size_t>((size_t)n_sub, forced.size() - 1)], batch - off);
         take = std::min(take, max_microbatch(m));
         if (n_sub - n_done == kRing) rc = c3_predict_wait(m, (int)(n_done++ % kRing));
         m->tap_call_off = off;
@@ -367,10 +327,10 @@ int c3_predict_pileup_region(c3_model *m, const void *region_host, int x_dtype, 
         memcpy(sl.pin_x, region_host, (size_t)n_cols * m->C * item);
     }
     memcpy((char *)sl.pin_x + rb, starts_host, sb);
-    HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, rb + sb, hipMemcpyHostToDevice, m->stream));
-    TRY(forward_device(m, m->stream, sl.dev_x, x_dtype, batch, sl.dev_y, (const int32_t *)((char *)sl.dev_x + rb)));
-    HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, yb, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, rb + sb, hipMemcpyHostToDevice, lane(m).stream));
+    TRY(forward_device(m, lane(m).stream, sl.dev_x, x_dtype, batch, sl.dev_y, (const int32_t *)((char *)sl.dev_x + rb)));
+    HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, yb, hipMemcpyDeviceToHost, lane(m).stream));
+    HIP_TRY(hipStreamSynchronize(lane(m).stream));
     memcpy(y_host, sl.pin_y, yb);
     return 0;
 }
@@ -400,14 +360,14 @@ int c3_outcome_maxima(c3_model *m, const float *y_host, int64_t batch, const uin
     float *maxp = (float *)(base + yb + rb);
     int32_t *arg = (int32_t *)(base + yb + rb + mb);
     uint8_t *early = (uint8_t *)(base + yb + rb + 2 * mb);
-    TRY(h2d_staged(y, y_host, yb, m->stream));  // (pageable rows: through the bounce buffer, c3_model.h)
-    TRY(h2d_staged(ref, ref21_host, (size_t)batch, m->stream));
+    TRY(h2d_staged(y, y_host, yb, lane(m).stream));  // (pageable rows: through the bounce buffer, c3_model.h)
+    TRY(h2d_staged(ref, ref21_host, (size_t)batch, lane(m).stream));
     DecodeParams dp{y, m->nout, ref, maxp, arg, early, nullptr, (int)batch, m->nout == 90 ? 1 : 0};
-    hipLaunchKernelGGL(outcome_maxima_kernel<false>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, m->stream, dp);
+    hipLaunchKernelGGL(outcome_maxima_kernel<false>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, lane(m).stream, dp);
     HIP_TRY(hipGetLastError());
-    TRY(d2h_staged(maxp_host, maxp, mb, m->stream));
-    TRY(d2h_staged(argmax_host, arg, mb, m->stream));
-    TRY(d2h_staged(early_host, early, (size_t)batch, m->stream));
+    TRY(d2h_staged(maxp_host, maxp, mb, lane(m).stream));
+    TRY(d2h_staged(argmax_host, arg, mb, lane(m).stream));
+    TRY(d2h_staged(early_host, early, (size_t)batch, lane(m).stream));
     return 0;
 }
 
@@ -435,14 +395,14 @@ int c3_decode_columns(c3_model *m, const float *y_host, int64_t batch, float *ro
             const int64_t nr = std::min(per, batch - r0);
             for (int64_t r = 0; r < nr; ++r)
                 memcpy((float *)b.pin + r * wide, y_host + (r0 + r) * m->nout, (size_t)m->nout * sizeof(float));
-            HIP_TRY(hipMemcpyAsync(rows + r0 * wide, b.pin, (size_t)nr * wide * sizeof(float), hipMemcpyHostToDevice, m->stream));
-            HIP_TRY(hipStreamSynchronize(m->stream));
+            HIP_TRY(hipMemcpyAsync(rows + r0 * wide, b.pin, (size_t)nr * wide * sizeof(float), hipMemcpyHostToDevice, lane(m).stream));
+            HIP_TRY(hipStreamSynchronize(lane(m).stream));
         }
     }
     DecodeParams dp{rows, wide, nullptr, nullptr, nullptr, nullptr, rows + m->nout, (int)batch, m->nout == 90 ? 1 : 0};
-    hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, m->stream, dp);
+    hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, lane(m).stream, dp);
     HIP_TRY(hipGetLastError());
-    TRY(d2h_staged(rows_host, rows, total, m->stream));
+    TRY(d2h_staged(rows_host, rows, total, lane(m).stream));
     return 0;
 }
 

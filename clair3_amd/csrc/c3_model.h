@@ -117,10 +117,28 @@ struct HostSlot {
     int64_t tap_off = 0;  // first window of this batch in the c3_predict call it is a piece of (debug taps)
     bool busy = false;
     bool used_f16 = false;  // the batch in flight was computed by the fp16x3 kernels (c3_predict_wait then checks its range)
-    int lane = 0;           // the lane (c3_model::Lane) the batch in flight runs in
+    int lane = 0;           // the lane (Lane) the batch in flight runs in
 };
 
 constexpr int kHostSlots = 4;  // batches in flight per handle through c3_predict_submit / _wait (C3_HOST_SLOTS)
+
+// ---- the ring's lanes (round 6) ----
+// Batches of the submit / wait ring used to run strictly one after the other: ONE workspace and ONE kernel stream per handle.  A lane is
+// everything a forward pass writes -- the workspace and the kernel stream: with two or three of them consecutive small batches (dealt to the
+// lanes in submit order, c3_hostring.h) overlap on the chip (what three HANDLES in flight do, 876 k against 735 k windows/s at B = 256,
+// without a second copy of the weights) and fill each other's under-filled launches.  Rows do not depend on the lane
+// (same kernels, same data).  env C3HIP_RING_LANES=1: one lane.
+struct Lane {
+    hipStream_t stream = nullptr;  // kernels (and the rows on their way out)
+    int64_t cap = 0;               // windows per micro-batch the workspace can hold
+    bool last_planes = false;      // the last forward pass left plane activations in act[] / h1 (c3_debug_fetch converts)
+    std::vector<DevBuf> bufs;
+    float *act[9] = {};
+    float *spp = nullptr, *part = nullptr, *l4dbg = nullptr;
+    float *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
+    int64_t last_n = 0;  // windows of the last micro-batch (for debug fetch)
+};
+constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
 
 struct c3_model {
     int kind = 0, C = 0, add_indel = 0, device = 0;
@@ -128,20 +146,7 @@ struct c3_model {
     int nb = 2, nout = 24;
     int row = 24;  // floats per output row: nout, + kDecodeCols when c3_model_set_decode_columns is on
     bool loaded = false;
-    hipStream_t stream = nullptr, h2d_stream = nullptr;  // kernels (and the rows on their way out); staged windows on their way in
-    hipStream_t duo_stream = nullptr;                    // the second half of a micro-batch (c3_forward.h forward_device, C3HIP_DUO)
-    // The FC chain of a batch of the submit / wait ring on a stream of its own (round 6, c3_forward.h tail_split): L4, the split-K sum and
-    // the tail are three small launches (224 / few / 64 workgroups, 20 - 30 us) behind which the NEXT batch's first layers would wait
-    // although they depend on nothing of them; on their own stream they run in the slots the next batch's under-filled launches leave
-    // free.  ev_body_done: the last layer in front of the chain; ev_tail_done: the chain (the next batch waits for it before it overwrites
-    // what the chain reads: the pooled tensor / lstm2_out).  Default: on for full alignment, off for pileup (c3_model_create says why); env
-    // C3HIP_TAIL_STREAM=0 / 1.
-    hipStream_t tail_stream = nullptr;
-    hipEvent_t ev_body_done = nullptr, ev_tail_done = nullptr;
-    bool tail_split = false;   // allowed (set in c3_model_create: the kind's default, or env)
-    bool tail_pending = false;  // a chain is (or may still be) running on tail_stream
-    bool tail_now = false;      // this forward pass puts its chain on tail_stream (set by the ring's submit around forward_device)
-    hipEvent_t duo_fork = nullptr, duo_join = nullptr;
+    hipStream_t h2d_stream = nullptr;  // staged windows on their way in (the kernel streams are the lanes', below)
 
     // ---- packed weights (device) ----
     // pileup
@@ -205,42 +210,33 @@ struct c3_model {
     // a batch of the ring that runs in a lane NEXT TO another batch of the same handle (c3_hostring.h predict_submit) is in the same position
     // as one beside another handle: its recurrences take full 16-window tiles (128 workgroups per 1024 windows, so that two batches fill the 256
     // CUs between them -- a half-tile launch alone owns every CU: 144 KB of LDS per workgroup, and the second lane's batch waits), the
-    // LSTM2 projection half its grid.  Set around forward_device by the ring; 1 everywhere else.  C3HIP_LANE_SHARING=0: never.
+    // LSTM2 projection half its grid (profiles/r06_n_ab_lane_sharing.txt).  Set around forward_device by the ring; 1 everywhere else.
     int lane_sharing = 1;
-    bool lane_sharing_ok = true;
     unsigned lane_next = 0;     // the lane of the ring's next small batch (round robin over the submits)
-    int stream_priority = 0;    // env C3HIP_STREAM_PRIORITY=-1/0/1: the priority every stream of this handle is created with (new_stream below)
     // As few streams as the work needs.  The runtime gives a process FOUR hardware queues (GPU_MAX_HW_QUEUES) and places every stream on the
     // least-used one; two streams on one queue run in submission order, and a wait between streams on two queues costs tens of microseconds.
     // Which streams meet on a queue depends on everything else the process created before -- measured (profiles/r06_o_*): the same ring of
     // 256-window batches ran at 650 k windows/s on the first handle of a fresh process and at 800 k on a second one, 620 k with 8 or 16 queues
     // (every stream alone: every dependency crosses queues).  So a small batch of the ring lives on its lane's stream ALONE -- staged windows in,
-    // kernels, FC chain, rows out, in order, no event (lane_h2d; the batches of the other lanes are what its copy runs under) -- and the transfer
-    // stream exists only from the first large batch on (lazy_h2d): three lanes + the null stream are the four queues.
-    bool lazy_h2d = true;       // env C3HIP_LAZY_H2D_STREAM=0: the transfer stream is created with the handle
-    bool lane_h2d = true;       // env C3HIP_LANE_H2D=0: a lane batch's staged windows travel on the transfer stream, an event in between
-    bool lane_by_slot = false;  // env C3HIP_LANE_ORDER=slot: lane = slot % lanes (round 6's first form)
-    int host_copy_kernel = 1;  // env C3HIP_HOST_COPY_KERNEL=0: every batch through the DMA engines on the transfer streams
+    // kernels, FC chain, rows out, in order, no event (the batches of the other lanes are what its copy runs under) -- and the transfer stream
+    // exists only from the first batch on that stages outside a lane: three lanes + the null stream are the four queues.  (The FC chain on a
+    // stream of its own gained 1.5 - 2 % in one placement of the streams and lost in another: profiles/r06_h_ab_tail_stream.txt, r06_o_*.)
     bool tail_fused = false;  // the split-K sum of L4 inside fc_tail_mfma_kernel (c3_tail.h) instead of its own launch: on for the pileup network (+0.7 %:
-                              // 15 partials of 128 features), off for full alignment (-1 %: four branch workgroups re-read 28 partials of 256); env C3HIP_TAIL_FUSED
-    int duo = 0;              // a micro-batch as two halves on two streams inside one call (c3_forward.h forward_device); env C3HIP_DUO
+                              // 15 partials of 128 features), off for full alignment (-1 %: four branch workgroups re-read 28 partials of 256)
     int wg_slots = 512;       // co-resident 256-thread / 64 KiB-LDS workgroups on the device (2 per CU)
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
 
-    // ---- workspace ----
-    int64_t cap = 0;    // windows per micro-batch the workspace can hold
+    // ---- workspaces and kernel streams: the lanes (Lane above; lane(m) is the active one) ----
+    Lane lanes[kMaxLanes];
+    int lane_cur = 0;
+    int ring_lanes = 1;  // 1 .. kMaxLanes (set in c3_model_create: the kind's default, or env)
+    int64_t lane_max_batch = 0;  // batches up to this many windows take the next lane, larger ones the first lane (env C3HIP_RING_LANES_MAX_BATCH)
     bool keep = false;  // debug: one buffer per layer instead of the 3-buffer rotation
-    bool last_planes = false;  // the last forward pass left plane activations in act[] / h1 (c3_debug_fetch converts)
-    std::vector<DevBuf> bufs;
-    float *act[9] = {};
-    float *spp = nullptr, *part = nullptr, *l4dbg = nullptr;
-    float *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
-    int64_t last_n = 0;  // windows of the last micro-batch (for debug fetch)
 
     // ---- debug taps (c3_debug_tap): layer outputs of the forms a call really runs, each copied on its producing stream right behind
-    // the producing launch into a buffer of the handle, at the window's position in the call (micro-batches, duo halves, ring lanes) ----
+    // the producing launch into a buffer of the handle, at the window's position in the call (micro-batches, ring lanes) ----
     uint32_t tap_mask = 0;                                // bit per kTap* tensor; 0 = off: no copy, no allocation, the launches of an untapped call
     uint32_t tap_written = 0, tap_skipped = 0, tap_planes = 0;  // of the last call: copied / not produced by its form / held as planes
     float *tap_dev[kTapCount] = {};
@@ -250,29 +246,6 @@ struct c3_model {
     int64_t tap_call_off = 0;         // ... and the piece being enqueued starts at this window of it
 
     HostSlot slot[kHostSlots];
-
-    // ---- the ring's second lane (round 6) ----
-    // Batches of the submit / wait ring used to run strictly one after the other: ONE workspace and ONE kernel stream per handle.  A lane is
-    // everything a forward pass writes -- the workspace, the kernel stream, the tail stream and its events: with two of them consecutive
-    // small batches (dealt to the lanes in submit order, c3_hostring.h) overlap on the chip (what three HANDLES in flight do, 876 k against 735 k windows/s at
-    // B = 256, without a second copy of the weights) and fill each other's under-filled launches.  The fields above ARE the
-    // active lane; use_lane() parks them and takes another lane's out of `parked`.  Rows do not depend on the lane (same kernels, same data).
-    // env C3HIP_RING_LANES=1: one lane.
-    struct Lane {
-        int64_t cap = 0;
-        bool last_planes = false, tail_pending = false;
-        std::vector<DevBuf> bufs;
-        float *act[9] = {};
-        float *spp = nullptr, *part = nullptr, *l4dbg = nullptr, *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
-        int64_t last_n = 0;
-        hipStream_t stream = nullptr, tail_stream = nullptr;
-        hipEvent_t ev_body_done = nullptr, ev_tail_done = nullptr;
-    };
-    static constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
-    Lane parked[kMaxLanes];  // the lanes that are NOT active live here (parked[lane_cur] is stale: its contents ARE the fields above)
-    int lane_cur = 0;  // which lane the fields above hold
-    int ring_lanes = 1;  // 1 .. kMaxLanes (set in c3_model_create: the kind's default, or env)
-    int64_t lane_max_batch = 0;  // batches up to this many windows take the lane of their slot, larger ones the first lane (env C3HIP_RING_LANES_MAX_BATCH)
 
     // which kernel forms the last forward pass took (c3_model_describe; bench.py reports it)
     const char *choice_lstm1 = "-", *choice_proj2 = "-", *choice_lstm2 = "-", *choice_fa = "-";
@@ -285,30 +258,13 @@ struct c3_model {
 
 static int conv_out(int n, int s) { return (n - 1) / s + 1; }
 
-// Every stream of a handle: non-blocking, at the handle's priority.  The runtime keeps one pool of at most GPU_MAX_HW_QUEUES (4) hardware queues
-// per priority and hands a new stream the least-used queue of its pool; two streams on one hardware queue run in submission order.
-static hipError_t new_stream(const c3_model *m, hipStream_t *s) {
-    return m->stream_priority ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, m->stream_priority) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}
-
-
-// make lane k the active one (c3_model::Lane): park everything a forward pass writes and take lane k's out of the parking lot
-static void lane_exchange(c3_model *m, c3_model::Lane &o) {
-    std::swap(m->cap, o.cap), std::swap(m->last_planes, o.last_planes), std::swap(m->tail_pending, o.tail_pending);
-    m->bufs.swap(o.bufs);
-    for (int l = 0; l < 9; ++l) std::swap(m->act[l], o.act[l]);
-    std::swap(m->spp, o.spp), std::swap(m->part, o.part), std::swap(m->l4dbg, o.l4dbg);
-    std::swap(m->h1, o.h1), std::swap(m->gx2, o.gx2), std::swap(m->h2, o.h2), std::swap(m->last_n, o.last_n);
-    std::swap(m->stream, o.stream), std::swap(m->tail_stream, o.tail_stream);
-    std::swap(m->ev_body_done, o.ev_body_done), std::swap(m->ev_tail_done, o.ev_tail_done);
-}
+// the active lane: the workspace and the kernel stream of the forward pass being enqueued
+static Lane &lane(c3_model *m) { return m->lanes[m->lane_cur]; }
+// make lane k the active one; its kernel stream is created on first use (every stream of a handle: non-blocking, default priority)
 static int use_lane(c3_model *m, int k) {
-    if (k == m->lane_cur) return 0;
-    if (k < 0 || k >= c3_model::kMaxLanes) return fail("lane %d out of range", k);
-    lane_exchange(m, m->parked[m->lane_cur]);  // the active fields -> their parking place (which held nothing that matters)
-    lane_exchange(m, m->parked[k]);            // lane k's -> the active fields
+    if (k < 0 || k >= kMaxLanes) return fail("lane %d out of range", k);
     m->lane_cur = k;
-    if (!m->stream) HIP_TRY(new_stream(m, &m->stream));  // (a further lane's kernel stream, on first use)
+    if (!m->lanes[k].stream) HIP_TRY(hipStreamCreateWithFlags(&m->lanes[k].stream, hipStreamNonBlocking));
     return 0;
 }
 
@@ -363,8 +319,7 @@ static int launch_gemm(hipStream_t s, const typename Loader::Params &lp, const f
 // order by the reduce kernel, so a window's probabilities are bit-identical whatever batch it travels in.
 static int l4_splits(const c3_model *m) {
     const int nk = m->K4 % 64 == 0 ? m->K4 / 64 : m->K4 / kBK;  // l4_stream_kernel (c3_l4.h) walks chunks of 64 inputs, the fp32 form chunks of kBK
-    static const int env = getenv("C3HIP_L4_SPLITS") ? atoi(getenv("C3HIP_L4_SPLITS")) : 0;  // A/B knob
-    const int want = env > 0 ? env : m->kind == C3_KIND_PILEUP ? 15 : 28;  // measured against 22 / 30 / 33 (pileup) and 14 / 56 (full alignment)
+    const int want = m->kind == C3_KIND_PILEUP ? 15 : 28;  // measured against 22 / 30 / 33 (pileup) and 14 / 56 (full alignment)
     int best = 1;
     for (int s = 1; s <= nk && s <= want; ++s)
         if (nk % s == 0) best = s;
@@ -372,11 +327,11 @@ static int l4_splits(const c3_model *m) {
 }
 
 // ------------------------------------------------------------------------------------------ memory
-static int dev_alloc(c3_model *m, void **p, size_t bytes) {
+static int dev_alloc(Lane &L, void **p, size_t bytes) {
     DevBuf b;
     b.bytes = bytes;
     HIP_TRY(hipMalloc(&b.p, std::max<size_t>(bytes, 256)));
-    m->bufs.push_back(b);
+    L.bufs.push_back(b);
     *p = b.p;
     return 0;
 }
@@ -478,28 +433,23 @@ static int upload(c3_model *m, float **dst, const std::vector<float> &src) {
     return 0;
 }
 
-static void free_workspace(c3_model *m) {  // the active lane's
-    for (auto &b : m->bufs) (void)hipFree(b.p);
-    m->bufs.clear();
-    m->cap = 0;
+static void free_workspace(Lane &L) {
+    for (auto &b : L.bufs) (void)hipFree(b.p);
+    L.bufs.clear();
+    L.cap = 0;
 }
-static void free_all_workspaces(c3_model *m) {  // both lanes' (geometry change, destruction)
-    free_workspace(m);
-    for (int k = 0; k < c3_model::kMaxLanes; ++k) {
-        if (k == m->lane_cur) continue;
-        for (auto &b : m->parked[k].bufs) (void)hipFree(b.p);
-        m->parked[k].bufs.clear();
-        m->parked[k].cap = 0;
-    }
+static void free_all_workspaces(c3_model *m) {  // every lane's (geometry change, destruction)
+    for (Lane &L : m->lanes) free_workspace(L);
 }
 
 static int64_t max_microbatch(const c3_model *m) { return m->kind == C3_KIND_PILEUP ? 16384 : 2048; }
 
-static int ensure_workspace(c3_model *m, int64_t n) {
+static int ensure_workspace(c3_model *m, int64_t n) {  // the active lane's
+    Lane &L = lane(m);
     n = std::min<int64_t>(n, max_microbatch(m));
-    if (n <= m->cap) return 0;
+    if (n <= L.cap) return 0;
     HIP_TRY(hipDeviceSynchronize());
-    free_workspace(m);
+    free_workspace(L);
     if (m->kind == C3_KIND_FULL_ALIGNMENT) {
         int hh[10], ww[10];
         fa_geometry(m, hh, ww);
@@ -510,21 +460,21 @@ static int ensure_workspace(c3_model *m, int64_t n) {
             biggest = std::max(biggest, act_elems[l]);
         }
         if (m->keep) {
-            for (int l = 0; l < 9; ++l) TRY(dev_alloc(m, (void **)&m->act[l], act_elems[l] * n * sizeof(float)));
+            for (int l = 0; l < 9; ++l) TRY(dev_alloc(L, (void **)&L.act[l], act_elems[l] * n * sizeof(float)));
         } else {
             float *rot[3];
-            for (int i = 0; i < 3; ++i) TRY(dev_alloc(m, (void **)&rot[i], biggest * n * sizeof(float)));
-            for (int l = 0; l < 9; ++l) m->act[l] = rot[l % 3];
+            for (int i = 0; i < 3; ++i) TRY(dev_alloc(L, (void **)&rot[i], biggest * n * sizeof(float)));
+            for (int l = 0; l < 9; ++l) L.act[l] = rot[l % 3];
         }
-        TRY(dev_alloc(m, (void **)&m->spp, (size_t)n * m->K4 * sizeof(float)));
+        TRY(dev_alloc(L, (void **)&L.spp, (size_t)n * m->K4 * sizeof(float)));
     } else {
         const int T = m->positions;
-        TRY(dev_alloc(m, (void **)&m->h1, (size_t)n * T * 256 * sizeof(float)));
-        TRY(dev_alloc(m, (void **)&m->gx2, (size_t)n * T * 1280 * sizeof(float)));
-        TRY(dev_alloc(m, (void **)&m->h2, (size_t)n * T * 320 * sizeof(float)));
+        TRY(dev_alloc(L, (void **)&L.h1, (size_t)n * T * 256 * sizeof(float)));
+        TRY(dev_alloc(L, (void **)&L.gx2, (size_t)n * T * 1280 * sizeof(float)));
+        TRY(dev_alloc(L, (void **)&L.h2, (size_t)n * T * 320 * sizeof(float)));
     }
-    TRY(dev_alloc(m, (void **)&m->part, (size_t)l4_splits(m) * n * m->FC * sizeof(float)));  // [S][n][FC]
-    TRY(dev_alloc(m, (void **)&m->l4dbg, (size_t)n * m->FC * sizeof(float)));
-    m->cap = n;
+    TRY(dev_alloc(L, (void **)&L.part, (size_t)l4_splits(m) * n * m->FC * sizeof(float)));  // [S][n][FC]
+    TRY(dev_alloc(L, (void **)&L.l4dbg, (size_t)n * m->FC * sizeof(float)));
+    L.cap = n;
     return 0;
 }

@@ -81,9 +81,7 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     m->row = m->nout;
     m->FC = kind == C3_KIND_PILEUP ? 128 : 256;
     m->K4 = kind == C3_KIND_PILEUP ? m->positions * 320 : 14 * 256;
-    if (const char *e = getenv("C3HIP_STREAM_PRIORITY")) m->stream_priority = atoi(e);
-    if (const char *e = getenv("C3HIP_LAZY_H2D_STREAM")) m->lazy_h2d = atoi(e) != 0;
-    if (new_stream(m, &m->stream) != hipSuccess || (!m->lazy_h2d && new_stream(m, &m->h2d_stream) != hipSuccess)) {
+    if (hipStreamCreateWithFlags(&m->lanes[0].stream, hipStreamNonBlocking) != hipSuccess) {  // (a further lane's: use_lane; the transfer stream: c3_hostring.h)
         fail("hipStreamCreate failed");
         delete m;
         return nullptr;
@@ -96,18 +94,9 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     if (const char *e = getenv("C3HIP_AUTO_FP32")) m->auto_fp32_at = (float)atof(e);
     if (const char *e = getenv("C3HIP_CONV1_FUSED")) m->conv1_fused = atoi(e) != 0;
     if (const char *e = getenv("C3HIP_WINO")) m->wino = atoi(e);
-    if (const char *e = getenv("C3HIP_DUO")) m->duo = atoi(e);
     if (const char *e = getenv("C3HIP_SPP_FUSED")) m->spp_fused = atoi(e) != 0;
-    m->tail_fused = kind == C3_KIND_PILEUP;
-    if (const char *e = getenv("C3HIP_TAIL_FUSED")) m->tail_fused = atoi(e) != 0;
+    m->tail_fused = kind == C3_KIND_PILEUP;  // (profiles/r04_e_ab_tail_pileup.txt, r04_e_ab_tail_fa.txt)
     if (const char *e = getenv("C3HIP_HALF_TILES")) m->half_tiles = atoi(e) != 0;
-    // the ring's FC chain on its own stream: on for full alignment (same-box A/B, profiles/r06_h_ab_tail_stream.txt: ring 680 - 685 k -> 696 k windows/s at
-    // B = 256, 687 -> 705 - 709 k over the driver's 100 steps, 768 -> 778 - 780 k at B = 1000), off for the pileup network (4.09 - 4.14 M -> 4.03 M: a chain
-    // beside the next batch's latency-bound LSTM1 slows the recurrence more than it hides)
-    // (round 6, later: OFF for both.  The +1.5 - 2 % of that A/B was one placement of the handle's streams on the runtime's four hardware queues;
-    // another placement of the same streams loses 15 %, and a handle with FEWER streams is what holds everywhere: see lane_h2d in c3_model.h and
-    // profiles/r06_o_ring_streams_and_hardware_queues.txt)
-    m->tail_split = false;
     // two lanes for the ring (c3_model.h Lane): the kind's default follows the same-box A/B of profiles/r06_i_ab_ring_lanes.txt
     // (one MI355X, alternating: full alignment ring 728 - 732 k -> 768 - 775 k windows/s at B = 256 but 807 - 809 k -> 768 - 778 k at B = 1000; pileup
     // 4.24 M -> 4.32 - 4.33 M at B = 1024): more than one lane, for batches that do not fill the chip by themselves
@@ -115,13 +104,8 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     // pileup 4.11 - 4.14 M -> 4.23 - 4.26 M (two) -> 4.07 - 4.08 M (three: three recurrences side by side starve each other)
     m->ring_lanes = kind == C3_KIND_FULL_ALIGNMENT ? 3 : 2;
     m->lane_max_batch = kind == C3_KIND_FULL_ALIGNMENT ? 512 : 1024;
-    if (const char *e = getenv("C3HIP_RING_LANES")) m->ring_lanes = std::min(std::max(atoi(e), 1), (int)c3_model::kMaxLanes);
+    if (const char *e = getenv("C3HIP_RING_LANES")) m->ring_lanes = std::min(std::max(atoi(e), 1), kMaxLanes);
     if (const char *e = getenv("C3HIP_RING_LANES_MAX_BATCH")) m->lane_max_batch = atoll(e);
-    if (const char *e = getenv("C3HIP_TAIL_STREAM")) m->tail_split = atoi(e) != 0;
-    if (const char *e = getenv("C3HIP_LANE_SHARING")) m->lane_sharing_ok = atoi(e) != 0;
-    if (const char *e = getenv("C3HIP_LANE_ORDER")) m->lane_by_slot = strcmp(e, "slot") == 0;
-    if (const char *e = getenv("C3HIP_LANE_H2D")) m->lane_h2d = atoi(e) != 0;
-    if (const char *e = getenv("C3HIP_HOST_COPY_KERNEL")) m->host_copy_kernel = atoi(e);
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -288,25 +272,20 @@ int c3_model_set_sharing(c3_model *m, int handles) {
 int c3_model_describe(c3_model *m, char *buf, int n) {
     if (!m || !buf || n <= 0) return fail("null argument");
     if (m->kind == C3_KIND_PILEUP)
-        snprintf(buf, (size_t)n, "sharing=%d duo=%d lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
-                 "ring_lanes=%d lane_max_batch=%lld tail_stream=%d", m->sharing,
-                 m->duo, m->choice_lstm1, m->choice_proj2, m->choice_lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
-                 (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, (int)m->tail_split);
+        snprintf(buf, (size_t)n, "sharing=%d lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
+                 "ring_lanes=%d lane_max_batch=%lld", m->sharing,
+                 m->choice_lstm1, m->choice_proj2, m->choice_lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
+                 (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch);
     else
-        snprintf(buf, (size_t)n, "sharing=%d duo=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld tail_stream=%d", m->sharing,
-                 m->duo, m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch, (int)m->tail_split);
+        snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld", m->sharing,
+                 m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch);
     return 0;
 }
 
 int c3_model_synchronize(c3_model *m) {
     if (!m) return fail("null model");
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (m->tail_stream) HIP_TRY(hipStreamSynchronize(m->tail_stream));
-    for (int k = 0; k < c3_model::kMaxLanes; ++k) {
-        if (k == m->lane_cur) continue;
-        if (m->parked[k].stream) HIP_TRY(hipStreamSynchronize(m->parked[k].stream));
-        if (m->parked[k].tail_stream) HIP_TRY(hipStreamSynchronize(m->parked[k].tail_stream));
-    }
+    for (const Lane &L : m->lanes)
+        if (L.stream) HIP_TRY(hipStreamSynchronize(L.stream));
     return 0;
 }
 
@@ -315,13 +294,8 @@ int c3_model_destroy(c3_model *m) {
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
     free_all_workspaces(m);
-    for (int k = 0; k < c3_model::kMaxLanes; ++k) {
-        if (k == m->lane_cur) continue;
-        if (m->parked[k].stream) (void)hipStreamDestroy(m->parked[k].stream);
-        if (m->parked[k].tail_stream) (void)hipStreamDestroy(m->parked[k].tail_stream);
-        if (m->parked[k].ev_body_done) (void)hipEventDestroy(m->parked[k].ev_body_done);
-        if (m->parked[k].ev_tail_done) (void)hipEventDestroy(m->parked[k].ev_tail_done);
-    }
+    for (const Lane &L : m->lanes)
+        if (L.stream) (void)hipStreamDestroy(L.stream);
     float *ws[] = {m->proj_w[0], m->proj_w[1], m->proj_b[0], m->proj_b[1], m->whh[0], m->whh[1], m->whh16[0], m->whh16[1],
                    m->l4_w, m->l4_b, m->l4_wf, m->b5, m->zeros, m->l1_wih, m->l1_wih16, m->l1_bias, m->conv1_w16,
                    m->conv1_wfrag16, m->w5f, m->whf, m->bh48, m->proj2_pw, m->proj2_pwr, m->proj2_post, m->conv1_post,
@@ -355,14 +329,7 @@ int c3_model_destroy(c3_model *m) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
     }
-    if (m->stream) (void)hipStreamDestroy(m->stream);
     if (m->h2d_stream) (void)hipStreamDestroy(m->h2d_stream);
-    if (m->duo_stream) (void)hipStreamDestroy(m->duo_stream);
-    if (m->tail_stream) (void)hipStreamDestroy(m->tail_stream);
-    if (m->ev_body_done) (void)hipEventDestroy(m->ev_body_done);
-    if (m->ev_tail_done) (void)hipEventDestroy(m->ev_tail_done);
-    if (m->duo_fork) (void)hipEventDestroy(m->duo_fork);
-    if (m->duo_join) (void)hipEventDestroy(m->duo_join);
     delete m;
     return 0;
 }

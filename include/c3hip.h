@@ -125,7 +125,7 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
 #define C3_HOST_SLOTS 4
 /* asynchronous pair, slot in [0, C3_HOST_SLOTS): submit copies x into pinned staging and enqueues H2D + kernels + D2H;
  * wait blocks until y_host of that slot is complete. x_host may be reused as soon as submit returns.  Batches in different slots
- * may run side by side on the device (the handle keeps up to three lanes -- workspace + streams -- for batches that do not fill the
+ * may run side by side on the device (the handle keeps up to three lanes -- workspace + kernel stream -- for batches that do not fill the
  * chip by themselves; C3HIP_RING_LANES): rows never depend on the slot, the lane or the batch a window travels in. */
 int c3_predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot);
 int c3_predict_wait(c3_model *m, int slot);
@@ -267,7 +267,7 @@ int c3_debug_keep_activations(c3_model *m, int enable);
 /* Taps: layer outputs of the kernel forms a call really runs (keep mode switches the fused forms off; taps do not).
  * names: comma separated, "" = none.  full-aln "act0".."act8", "spp", "l4_out"; pileup "lstm1_out", "gx2" (B,33,1280: both directions'
  * x-projections of LSTM2 with both biases, PyTorch gate order), "lstm2_out", "l4_out".  Every later call copies each tapped tensor
- * behind the launch that produced it, on that launch's stream, for ALL its windows (micro-batches, two halves, ring lanes); with no
+ * behind the launch that produced it, on that launch's stream, for ALL its windows (micro-batches, ring lanes); with no
  * tap set a call launches exactly what it did before.  Calls on the handle must not overlap while taps are read. */
 int c3_debug_tap(c3_model *m, const char *names);
 /* windows [first, first + windows) of tapped tensor `name` of the last call, as the checkpoint's fp32 values.  Fails, naming the

@@ -171,34 +171,26 @@ def test_async_submit_wait_and_device_paths_agree():
     assert yd.is_cuda and np.array_equal(yd.cpu().numpy(), ya)
 
 
-@pytest.mark.parametrize("kind,lane_h2d", [(syn.FULL_ALIGNMENT, "1"), (syn.PILEUP, "1"), (syn.FULL_ALIGNMENT, "0")])
-def test_the_fc_chain_of_a_ring_batch_on_its_own_stream(kind, lane_h2d, monkeypatch):
-    """Round 6: a batch of the submit / wait ring runs its FC chain (L4, the split-K sum, the tail, the decoder columns, the copy-out) on
-    the handle's tail stream, so that the NEXT batch's first layers are queued behind this batch's last layer, not behind three small
-    launches they do not depend on; the next batch waits for the chain only before it overwrites what the chain reads (the pooled tensor /
-    lstm2_out); and the ring has TWO lanes (workspace + streams): the batch in slot k runs in lane k & 1 and overlaps its neighbour.  Same
-    kernels on the same data: rows bit-identical to C3HIP_TAIL_STREAM=0 C3HIP_RING_LANES=1 and to the blocking call, for batches of
-    different sizes kept in flight on every slot, micro-batches beyond the workspace cap, decoder columns, and with the device-resident
-    entry (whose chain stays on the caller's stream) called between rounds."""
+@pytest.mark.parametrize("kind", [syn.FULL_ALIGNMENT, syn.PILEUP])
+def test_ring_lanes_give_the_one_lane_rows(kind, monkeypatch):
+    """Round 6: the submit / wait ring has LANES (a workspace and one kernel stream each): consecutive batches are dealt to the lanes in
+    submit order and overlap on the chip; a batch in a lane stages its windows, runs its layers and FC chain and copies its rows out on its
+    lane's stream, in order.  Same kernels on the same data: rows bit-identical to C3HIP_RING_LANES=1 and to the blocking call, for batches
+    of different sizes kept in flight on every slot, micro-batches beyond the workspace cap, decoder columns, and with the device-resident
+    entry (on the caller's stream, in the first lane) called between rounds."""
     import torch
     ch, indel = (8, True) if kind == syn.FULL_ALIGNMENT else (18, False)
     sd = syn.make_state_dict(kind, ch, indel, seed=91)
     sizes = [300, 17, 256, 1, 129, 64, 511, 33, 256, 256] if kind == syn.FULL_ALIGNMENT else [1024, 9, 4097, 16, 2000, 1, 777, 1024, 1024, 31]
     xs = [syn.make_windows(kind, n, seed=92 + i, channels=ch) for i, n in enumerate(sizes)]
-    monkeypatch.setenv("C3HIP_TAIL_STREAM", "0")
     monkeypatch.setenv("C3HIP_RING_LANES", "1")
     m0 = make_model(kind, ch, indel, sd)  # round 5's ring: one workspace, one kernel stream, every batch strictly behind the one before
     want = [m0.predict_numpy(x) for x in xs]
-    monkeypatch.setenv("C3HIP_TAIL_STREAM", "1")  # (the default for full alignment; off by default for the pileup network, where it measured a loss)
-    monkeypatch.setenv("C3HIP_RING_LANES", "3")   # the batch in slot k in lane k % 3: consecutive batches overlap on the chip
+    monkeypatch.setenv("C3HIP_RING_LANES", "3")   # consecutive batches in lanes 0, 1, 2, 0, ...: they overlap on the chip
     monkeypatch.setenv("C3HIP_RING_LANES_MAX_BATCH", "100000")  # (by default only batches that leave the chip under-filled: here every size)
-    # (the end of round 6 made both of these knobs: by default a lane batch is ONE stream -- no tail stream, its staged windows on the lane's own
-    # stream -- because of the runtime's four hardware queues, DESIGN.md 3.8-9; "0": the windows on the transfer stream, an event in between)
-    monkeypatch.setenv("C3HIP_LANE_H2D", lane_h2d)
-    monkeypatch.setenv("C3HIP_LAZY_H2D_STREAM", lane_h2d)
     m = make_model(kind, ch, indel, sd)
-    assert "ring_lanes=1" in m0.describe() and "tail_stream=0" in m0.describe()
-    assert "ring_lanes=3 lane_max_batch=100000 tail_stream=1" in m.describe(), m.describe()
+    assert "ring_lanes=1" in m0.describe()
+    assert "ring_lanes=3 lane_max_batch=100000" in m.describe(), m.describe()
     for rounds in range(3):
         tickets = []
         got = [None] * len(xs)
@@ -209,8 +201,8 @@ def test_the_fc_chain_of_a_ring_batch_on_its_own_stream(kind, lane_h2d, monkeypa
             tickets.append((i, m.submit(x, slot=i % 3)))
         for j, t in tickets:
             got[j] = m.wait(t)
-        # the device-resident entry between two rounds of the ring (calls on one handle must not overlap: the ring is drained): its chain
-        # runs on the CALLER's stream, behind the ring's last chain
+        # the device-resident entry between two rounds of the ring (calls on one handle must not overlap: the ring is drained): it runs
+        # on the CALLER's stream, in the first lane
         yd = m(torch.from_numpy(xs[1]).cuda())
         torch.cuda.synchronize()
         assert np.array_equal(yd.cpu().numpy(), want[1])
@@ -230,7 +222,7 @@ def test_ring_batches_beside_each_other_take_the_shared_chip_forms(monkeypatch):
     batches beside each other and the blocking call's pieces keep the half tiles.  Lanes are dealt in submit order.  Rows: bit-identical to
     the one-lane ring whatever the form (the property every tile form of these kernels is held to)."""
     sd = syn.make_state_dict(syn.PILEUP, 18, True, seed=93)
-    xs = [syn.make_windows(syn.PILEUP, n, seed=94 + i, channels=18) for i, n in enumerate([1024, 1024, 1000, 1024, 300, 200, 1024])]
+    xs = [syn.make_windows(syn.PILEUP, n, seed=94 + i, channels=18) for i, n in enumerate([1024, 1024, 1000, 1024, 300, 200])]
     monkeypatch.setenv("C3HIP_RING_LANES", "1")
     m0 = make_model(syn.PILEUP, 18, True, sd)
     want = [m0.predict_numpy(x) for x in xs]
@@ -252,11 +244,6 @@ def test_ring_batches_beside_each_other_take_the_shared_chip_forms(monkeypatch):
     assert np.array_equal(m.wait(ta), want[4]) and np.array_equal(m.wait(tb), want[5]) and np.array_equal(m.wait(tc), want[3])
     assert np.array_equal(m.predict_numpy(xs[2]), want[2])  # the blocking call of 1000 windows: its pieces side by side on half tiles
     assert "lstm2=f16x3-half-tiles" in m.describe(), m.describe()
-    monkeypatch.setenv("C3HIP_LANE_SHARING", "0")
-    m2 = make_model(syn.PILEUP, 18, True, sd)
-    u, v = m2.submit(xs[0], slot=0), m2.submit(xs[6], slot=1)
-    assert "lstm2=f16x3-half-tiles" in m2.describe()
-    assert np.array_equal(m2.wait(u), want[0]) and np.array_equal(m2.wait(v), want[6])
 
 
 def test_strict_state_dict_loading():
@@ -657,7 +644,7 @@ def test_every_switch_keeps_the_calls(monkeypatch, oracle_mod):
     y_p = oracle_mod.pileup_forward(sd_p, x_p, False)
     for env in [{"C3HIP_CONV1_FUSED": "0"},  # conv1 as its own launch, its planes read by res1a / res1b
                 {"C3HIP_SPP_FUSED": "0"},    # res3b writes its planes, pyramid pooling as its own launch
-                {"C3HIP_FP32": "1"}, {"C3HIP_HOST_COPY_KERNEL": "0"}]:
+                {"C3HIP_FP32": "1"}]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         m = make_model(syn.FULL_ALIGNMENT, 8, True, sd_f)
@@ -665,7 +652,7 @@ def test_every_switch_keeps_the_calls(monkeypatch, oracle_mod):
         assert m.range_status()[1] == ("C3HIP_FP32" in env)
         for k in env:
             monkeypatch.delenv(k)
-    for env in [{"C3HIP_HALF_TILES": "0"}, {"C3HIP_FP32": "1"}, {"C3HIP_HOST_COPY_KERNEL": "0"}]:
+    for env in [{"C3HIP_HALF_TILES": "0"}, {"C3HIP_FP32": "1"}]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         util.assert_rows_match(make_model(syn.PILEUP, 18, False, sd_p).predict_numpy(x_p), y_p, what=f"pileup {env}")
@@ -947,35 +934,3 @@ def test_rows_winograd_convolutions_against_the_direct_ones(monkeypatch, oracle_
     monkeypatch.setenv("C3HIP_WINO", "2"), monkeypatch.setenv("C3HIP_CONV1_FUSED", "0"), monkeypatch.setenv("C3HIP_SPP_FUSED", "0")
     xt = syn.make_fa_windows(41, seed=139, channels=9)
     util.assert_rows_match(make_model(syn.FULL_ALIGNMENT, 9, True, sdt).predict_numpy(xt), oracle_mod.fa_forward(sdt, xt, True), what="trained-like, all six")
-
-
-def test_a_micro_batch_as_two_halves_on_two_streams(monkeypatch, oracle_mod):
-    """C3HIP_DUO=1 (c3_forward.h forward_device): from 192 full-alignment / 768 pileup windows on, a micro-batch runs as two halves on
-    two streams inside the call, each half in its own part of the workspace.  A window's row does not depend on the batch it travels
-    in, so the rows must be the undivided call's bit for bit: at the thresholds, at sizes whose halves are ragged, across several
-    micro-batches (2100 full-alignment windows = 2048 + 52), for int32 pileup windows, through the blocking call, the ring and the
-    device-resident entry; and against the oracle."""
-    import torch
-    for kind, ch, indel, sizes in ((syn.FULL_ALIGNMENT, 8, True, (191, 192, 333, 2100)), (syn.PILEUP, 18, False, (767, 768, 1024, 1501))):
-        sd = syn.make_state_dict(kind, ch, indel, seed=141)
-        for n in sizes:
-            x = syn.make_windows(kind, n, seed=142 + n, channels=ch)
-            monkeypatch.setenv("C3HIP_DUO", "0")
-            m0 = make_model(kind, ch, indel, sd)
-            y0 = m0.predict_numpy(x)
-            assert "duo=0" in m0.describe()
-            monkeypatch.setenv("C3HIP_DUO", "1")
-            m1 = make_model(kind, ch, indel, sd)
-            y1 = m1.predict_numpy(x)
-            assert "duo=1" in m1.describe()
-            assert np.array_equal(y0, y1), (kind, n)
-            t = m1.wait(m1.submit(x, slot=0))
-            assert np.array_equal(t, y0), (kind, n, "ring")
-            yd = m1(torch.from_numpy(x).to("cuda:0")).cpu().numpy()
-            assert np.array_equal(yd, y0), (kind, n, "device-resident")
-            if kind == syn.PILEUP and n == 1024:
-                assert np.array_equal(m1.predict_numpy(x.astype(np.int32)), m0.predict_numpy(x.astype(np.int32)))
-            monkeypatch.delenv("C3HIP_DUO")
-        sel = np.r_[0:8, n // 2 - 8:n // 2 + 8, n - 8:n]
-        ref = oracle_mod.fa_forward(sd, x[sel], True) if kind == syn.FULL_ALIGNMENT else oracle_mod.pileup_forward(sd, x[sel], False)
-        util.assert_rows_match(y1[sel], ref, what=f"{kind}, two halves")

@@ -1,6 +1,6 @@
 """Layer by layer on the kernel forms the product runs (needs an MI355X).  Keep mode (c3_debug_keep_activations) switches the fused forms
-off -- conv1 inside res1a / res1b (the SRC8 direct plane kernel), the pyramid pooling as res3b's epilogue, the two halves on two streams,
-the ring's lanes and tail stream -- so the keep-mode parity tests see every layer of OTHER forms than a default call runs.  Debug taps
+off -- conv1 inside res1a / res1b (the SRC8 direct plane kernel), the pyramid pooling as res3b's epilogue, the ring's lanes -- so the
+keep-mode parity tests see every layer of OTHER forms than a default call runs.  Debug taps
 (c3_debug_tap) copy a layer's output right behind the launch that produced it without changing the form: every tapped tensor of the
 default forms, at batch sizes that cross each form boundary, against the fp64 oracle, next to the fp32-MFMA forms (C3HIP_FP32=1) on
 the same windows.  Bounds are the ones the keep-mode tests meet: 2e-5 of a tensor's range and of a channel's own scale, and no worse
@@ -22,16 +22,12 @@ TABLE = []  # (what, per tensor, per channel) of every run, printed at the end o
 
 @pytest.fixture(autouse=True)
 def _clean_env(monkeypatch):
-    for k in ("C3HIP_FP32", "C3HIP_WINO", "C3HIP_DUO", "C3HIP_KEEP_ACTIVATIONS"):
+    for k in ("C3HIP_FP32", "C3HIP_WINO", "C3HIP_KEEP_ACTIVATIONS"):
         monkeypatch.delenv(k, raising=False)
 
 
-def _duo_split(n):
-    return ((n // 2 + 15) // 16) * 16  # c3_forward.h forward_device: whole 16-window tiles in the first half
-
-
 def sample(n, splits=()):
-    """every window of a batch up to 64; else both ends, 8 on each side of every split (duo halves, micro-batches) and 16 random"""
+    """every window of a batch up to 64; else both ends, 8 on each side of every split (micro-batches) and 16 random"""
     if n <= 64:
         return np.arange(n)
     idx = set(range(8)) | set(range(n - 8, n))
@@ -84,10 +80,10 @@ def _print_table(title):
 # ------------------------------------------------------------------------------------------ full alignment
 # (weights, channels, depth) -> [(env, batch sizes)]: together every form of the product stack
 FA_POOLS = {
-    ("plain", 8, 89): [({}, [1, 7, 17, 158, 159, 273, 274, 330, 1100, FA_MICRO + 37]), ({"C3HIP_DUO": "1"}, [191, 192, 333]),
+    ("plain", 8, 89): [({}, [1, 7, 17, 158, 159, 191, 192, 273, 274, 330, 333, 1100, FA_MICRO + 37]),
                        ({"C3HIP_WINO": "0"}, [17, 330]), ({"C3HIP_WINO": "1"}, [330])],
-    ("peaked", 9, 55): [({}, [1, 17, 159, 274, 1100]), ({"C3HIP_WINO": "0"}, [330]), ({"C3HIP_DUO": "1"}, [333])],
-    ("trained_like", 8, 89): [({}, [7, 330, FA_MICRO + 37]), ({"C3HIP_WINO": "0"}, [159]), ({"C3HIP_DUO": "1"}, [192])],
+    ("peaked", 9, 55): [({}, [1, 17, 159, 274, 333, 1100]), ({"C3HIP_WINO": "0"}, [330])],
+    ("trained_like", 8, 89): [({}, [7, 192, 330, FA_MICRO + 37]), ({"C3HIP_WINO": "0"}, [159])],
     ("trained_like", 9, 89): [({}, [17, 1100]), ({"C3HIP_WINO": "0"}, [274])],
 }
 FORMS_SEEN = set()
@@ -117,8 +113,7 @@ def test_full_alignment_product_layers(weights, ch, depth, monkeypatch):
     plan = []
     for env, sizes in FA_POOLS[(weights, ch, depth)]:
         for n in sizes:
-            splits = [FA_MICRO] + ([_duo_split(n)] if env.get("C3HIP_DUO") == "1" else [])
-            plan.append((env, n, sample(n, splits)))
+            plan.append((env, n, sample(n, [FA_MICRO])))
     # the comparison form: fp32 MFMA on fp32 activations, every layer written, one forward pass over the whole pool
     every = np.array(sorted(set().union(*[set(p[2].tolist()) for p in plan])))
     monkeypatch.setenv("C3HIP_FP32", "1")
@@ -186,7 +181,7 @@ def test_full_alignment_forms_seen(monkeypatch):
                     monkeypatch.delenv(k)
     seen = " | ".join(sorted(FORMS_SEEN))
     for want in ("stride1=ddwwwd", "stride1=dddddd", "stride1=ddwwdd", "conv3=one-workgroup-per-cu", "conv3=two-workgroups-per-cu",
-                 "conv5=one-workgroup-per-cu", "conv5=two-workgroups-per-cu", "duo=1", "conv_stack=planes-f16x3"):
+                 "conv5=one-workgroup-per-cu", "conv5=two-workgroups-per-cu", "conv_stack=planes-f16x3"):
         assert want in seen, (want, seen)
     print("forms seen:\n  " + "\n  ".join(sorted(FORMS_SEEN)))
 
@@ -203,9 +198,8 @@ def _gx2(sd, h1):
 
 
 P_PLAN = [  # (weights, env, sharing hint, dtype, sizes)
-    ("plain", {}, 1, np.int8, [1, 17, 189, 190, 191, 1024, 8192, P_MICRO + 37]),
+    ("plain", {}, 1, np.int8, [1, 17, 189, 190, 191, 767, 768, 1024, 8192, P_MICRO + 37]),
     ("plain", {}, 2, np.int8, [8192]),
-    ("plain", {"C3HIP_DUO": "1"}, 1, np.int8, [767, 768]),
     ("plain", {}, 1, np.int32, [17, 1024]),
     ("trained_like", {}, 1, np.int8, [17, 1024]),
     ("trained_like", {"C3HIP_FP32": "0"}, 1, np.int8, [17, 1024]),
@@ -228,7 +222,7 @@ def test_pileup_product_layers(weights, monkeypatch):
         if sharing > 1:
             m.sharing(sharing)
         for n in sizes:
-            idx = sample(n, [P_MICRO] + ([_duo_split(n)] if env.get("C3HIP_DUO") == "1" else []))
+            idx = sample(n, [P_MICRO])
             y = m.wait(m.submit(x8[:n].astype(dt), slot=0))
             form = m.describe()
             forms.add(form.split(" on_fp32")[0] + f" precision={form.split('precision=')[1].split()[0]}")
@@ -251,15 +245,15 @@ def test_pileup_product_layers(weights, monkeypatch):
     print("forms seen:\n  " + "\n  ".join(sorted(forms)))
     if weights == "plain":
         for want in ("lstm1=fused-f16x3-half-tiles", "lstm1=fused-f16x3-full-tiles", "proj2=128x128-chunk-stream", "proj2=weights-resident ",
-                     "proj2=weights-resident-half-grid", "duo=1"):
+                     "proj2=weights-resident-half-grid"):
             assert want in seen + " ", (want, seen)
     else:
         assert "precision=fp32-auto" in seen and "precision=fp16x3" in seen, seen
 
 
 # ------------------------------------------------------------------------------------------ taps change nothing
-@pytest.mark.parametrize("kind,env,n", [(syn.FULL_ALIGNMENT, {}, 330), (syn.FULL_ALIGNMENT, {"C3HIP_DUO": "1"}, FA_MICRO + 37),
-                                        (syn.PILEUP, {}, 1024), (syn.PILEUP, {"C3HIP_DUO": "1"}, P_MICRO + 37)])
+@pytest.mark.parametrize("kind,env,n", [(syn.FULL_ALIGNMENT, {}, 330), (syn.FULL_ALIGNMENT, {}, FA_MICRO + 37),
+                                        (syn.PILEUP, {}, 1024), (syn.PILEUP, {}, P_MICRO + 37)])
 def test_taps_change_no_form(kind, env, n, monkeypatch):
     """with taps set the call takes the same forms (describe()) and gives bit-identical rows; with the taps off again the
     handle launches the kernels it launched before any tap was set (c3_profile_read lists the same families and launches)"""
@@ -282,7 +276,7 @@ def test_taps_change_no_form(kind, env, n, monkeypatch):
     m.tap(FA_TAPS[1:8] + ("spp", "l4_out") if kind == syn.FULL_ALIGNMENT else P_TAPS)
     y1, d1, p1 = call()
     assert d1 == d0 and np.array_equal(y1, y0) and p1 == p0, (d0, d1, p0, p1)
-    y2 = m.wait(m.submit(x, slot=0))  # ... and without the profiler (the ring's lanes and tail stream)
+    y2 = m.wait(m.submit(x, slot=0))  # ... and without the profiler (the ring's lanes)
     assert np.array_equal(y2, y0) and m.describe() == d0
     m.tap("")
     y3, d3, p3 = call()
