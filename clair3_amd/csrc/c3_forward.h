@@ -482,8 +482,10 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
 }
 
 // ------------------------------------------------------------------------------------------ both
+// With `depth` (pileup, int32 counts; one per window, device): the reference's rescaling of very deep windows (c3_rescale.h) as a pre-pass
+// into the lane's buffer of sliced windows, then the int32 forms on that buffer -- x (and the region matrix behind `starts`) stays as it came.
 static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype, int64_t batch, float *y,
-                          const int32_t *starts = nullptr) {
+                          const int32_t *starts = nullptr, const int32_t *depth = nullptr) {
     if (!m->loaded) return fail("model has no weights: call c3_model_load first");
     if (batch < 0) return fail("negative batch");
     if (batch == 0) return 0;
@@ -491,7 +493,9 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
         return fail("full-alignment windows must be int8 (got dtype %d)", x_dtype);
     if (m->kind == C3_KIND_PILEUP && x_dtype != C3_DTYPE_I8 && x_dtype != C3_DTYPE_I32)
         return fail("pileup windows must be int8 or int32 (got dtype %d)", x_dtype);
+    if (depth && (m->kind != C3_KIND_PILEUP || x_dtype != C3_DTYPE_I32)) return fail("internal: depths need int32 pileup counts");
     TRY(ensure_workspace(m, batch));
+    if (depth) TRY(ensure_rescale_buf(m));
     if (!m->tap_call) TRY(tap_prepare(m, batch));
     const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
     Lane &L = lane(m);
@@ -503,7 +507,18 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
         m->tap_base = m->tap_call_off + off;
         if (m->kind == C3_KIND_FULL_ALIGNMENT) TRY(run_fa(m, s, (const int8_t *)xp, n, yp));
         else if (x_dtype == C3_DTYPE_I8) TRY(run_pileup_t<int8_t>(m, s, (const int8_t *)xp, n, yp, sp));
-        else TRY(run_pileup_t<int32_t>(m, s, (const int32_t *)xp, n, yp, sp));
+        else if (depth) {
+            {
+                const int TC = m->positions * m->C;
+                ProfScope ps(m, s, "p.rescale", 0.0, 2.0 * sizeof(int32_t) * (double)n * TC);
+                RescaleParams rp{(const int32_t *)xp, sp, depth + off, L.xr, (int)n, TC, m->C, m->max_depth};
+                const dim3 grid((unsigned)((n + kRescaleWindows - 1) / kRescaleWindows));
+                if (m->C % 2 == 0) hipLaunchKernelGGL(rescale_windows_kernel<2>, grid, dim3(kRescaleThreads), 0, s, rp);
+                else hipLaunchKernelGGL(rescale_windows_kernel<1>, grid, dim3(kRescaleThreads), 0, s, rp);
+                HIP_TRY(hipGetLastError());
+            }
+            TRY(run_pileup_t<int32_t>(m, s, L.xr, n, yp));
+        } else TRY(run_pileup_t<int32_t>(m, s, (const int32_t *)xp, n, yp, sp));
         L.last_n = n;
     }
     return 0;

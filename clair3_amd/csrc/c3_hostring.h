@@ -91,7 +91,16 @@ static int ensure_slot(c3_model *m, HostSlot &sl, size_t xb, size_t yb) {
     return 0;
 }
 
-static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out = nullptr);
+// what a batch of the ring reads besides (or instead of) sliced windows
+struct RingInput {
+    int64_t n_cols = -1;              // >= 0: x_host is ONE region matrix of n_cols columns and window b starts at column starts[b]
+    const int32_t *starts = nullptr;  // (checked against n_cols by the caller)
+    bool narrow = false;              // the region holds int64 / size_t counts: narrowed to int32 on their way into the staging buffer
+    const int32_t *depth = nullptr;   // per-window depths: windows deeper than 1.5 x max_depth are rescaled on the device (c3_rescale.h)
+    bool piece = false;               // a piece of a blocking call: its rescaled windows add to the call's count
+};
+static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out = nullptr,
+                          const RingInput *in = nullptr);
 int c3_predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot) {
     return predict_submit(m, x_host, x_dtype, batch, y_host, slot);
 }
@@ -101,7 +110,7 @@ int c3_predict_submit_dev(c3_model *m, const void *x_host, int x_dtype, int64_t 
     if (batch > 0 && !y_dev) return fail("null device buffer");
     return predict_submit(m, x_host, x_dtype, batch, nullptr, slot, y_dev);
 }
-static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out) {
+static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out, const RingInput *in) {
     if (!m) return fail("null model");
     if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
     if (batch < 0) return fail("negative batch");
@@ -118,7 +127,19 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     // three batches behind each other in lane 0 (profiles/r06_n_ab_lane_sharing.txt)
     TRY(use_lane(m, in_lane ? (int)(m->lane_next++ % (unsigned)m->ring_lanes) : 0));
     Lane &L = lane(m);
-    const size_t xb = (size_t)(batch * c3_model_window_bytes(m, x_dtype));
+    // the staged input: the windows (or the region matrix), then -- each from a multiple of 256 bytes -- the window starts and the depths
+    const bool region = in && in->n_cols >= 0;
+    int64_t n_deep = 0;  // windows the rule rescales: depth > 0 and depth > 1.5 x max_depth
+    if (in && in->depth)
+        for (int64_t i = 0; i < batch; ++i) n_deep += in->depth[i] > 0 && (double)in->depth[i] > 1.5 * (double)m->max_depth;
+    m->rescaled = (in && in->piece ? m->rescaled : 0) + n_deep;
+    // a batch without a deep window runs exactly what it runs without depths: no pre-pass, no copy
+    const int32_t *depth_host = n_deep > 0 ? in->depth : nullptr;
+    const size_t xb = region ? (size_t)in->n_cols * m->C * (x_dtype == C3_DTYPE_I32 ? 4 : 1) : (size_t)(batch * c3_model_window_bytes(m, x_dtype));
+    const size_t xb_al = (xb + 255) & ~(size_t)255;
+    const size_t sb = region ? (size_t)batch * sizeof(int32_t) : 0, sb_al = (sb + 255) & ~(size_t)255;
+    const size_t db = depth_host ? (size_t)batch * sizeof(int32_t) : 0;
+    const size_t xtot = sb + db ? xb_al + sb_al + db : xb;
     const size_t yb = (size_t)batch * m->row * sizeof(float);
     // windows of up to kKernelCopyMax bytes come in through the copy kernel only while no other batch of this handle is in flight: behind a
     // running batch the transfer stream brings the windows in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s), alone the copy
@@ -144,24 +165,43 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     } lane_sharing(m, (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1);
     if (batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(m, sl, xb, y_dev_out ? 0 : yb));  // (rows that stay on the device need no slot buffers)
-        if (alone && xb <= kKernelCopyMax && yb <= kKernelCopyMax) {
-            StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
-            hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xb + 15) / 16,
+        TRY(ensure_slot(m, sl, xtot, y_dev_out ? 0 : yb));  // (rows that stay on the device need no slot buffers)
+        if (region) memcpy((char *)sl.pin_x + xb_al, in->starts, sb);
+        if (depth_host) memcpy((char *)sl.pin_x + xb_al + sb_al, depth_host, db);
+        // int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
+        // buffer, which is what the reference's PIPE mode feeds the model (CreateTensorPileupFromCffi.py:143-146 -> int32 windows)
+        const bool narrow = region && in->narrow;
+        if (narrow) {
+            const int64_t *src = static_cast<const int64_t *>(x_host);
+            int32_t *dst = static_cast<int32_t *>(sl.pin_x);
+            for (size_t i = 0, e = (size_t)in->n_cols * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
+        }
+        // the counts through the pinned buffer onto stream st, the starts and depths (already in the pinned buffer) behind them
+        auto stage = [&](hipStream_t st) -> int {
+            if (narrow) HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, xb, hipMemcpyHostToDevice, st));
+            else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
+            if (xtot > xb) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + xb_al, (char *)sl.pin_x + xb_al, xtot - xb_al, hipMemcpyHostToDevice, st));
+            return 0;
+        };
+        if (alone && xtot <= kKernelCopyMax && yb <= kKernelCopyMax) {
+            if (!narrow) StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
+            hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xtot + 15) / 16,
                                (const uint32_t *)nullptr, (uint32_t *)nullptr);
             HIP_TRY(hipGetLastError());
         } else if (in_lane) {
             // a small batch in a lane brings its windows in on the lane's OWN stream: copy, kernels and the copy-out in order in one queue, no
             // event between two streams -- the batches of the other lanes are what the copy runs under (c3_model.h, the streams)
-            TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, L.stream));
+            TRY(stage(L.stream));
         } else {
             if (!m->h2d_stream) HIP_TRY(hipStreamCreateWithFlags(&m->h2d_stream, hipStreamNonBlocking));
-            TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, m->h2d_stream));
+            TRY(stage(m->h2d_stream));
             HIP_TRY(hipEventRecord(sl.ev_h2d, m->h2d_stream));
             HIP_TRY(hipStreamWaitEvent(L.stream, sl.ev_h2d, 0));
         }
+        sl.dev_starts = region ? (const int32_t *)((char *)sl.dev_x + xb_al) : nullptr;
+        sl.dev_depth = depth_host ? (const int32_t *)((char *)sl.dev_x + xb_al + sb_al) : nullptr;
         const bool f16 = m->f16_ok;
-        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y));
+        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, sl.dev_starts, sl.dev_depth));
         if (y_dev_out && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
             hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, L.stream, y_dev_out, batch * m->row, m->range_flag);
         // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
@@ -195,7 +235,7 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out);
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out, sl.dev_starts, sl.dev_depth);
             m->tap_call_off = 0;
             TRY(rc);
             HIP_TRY(hipStreamSynchronize(lane(m).stream));
@@ -216,7 +256,8 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y);
+            // (a region batch gathers again, a batch with depths rescales again -- from the staged ORIGINAL counts: nothing has written dev_x)
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y, sl.dev_starts, sl.dev_depth);
             m->tap_call_off = 0;
             TRY(rc);
             HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, lane(m).stream));
@@ -238,13 +279,16 @@ static int64_t predict_chunk(const c3_model *m) {
     return m->kind == C3_KIND_PILEUP ? 4096 : 256;
 }
 
-int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host) {
+static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host) {
     if (!m) return fail("null model");
     const int64_t chunk = predict_chunk(m);
+    RingInput in;
+    in.depth = depth_host;
     if (chunk <= 0 || batch < 2 * chunk) {
-        TRY(c3_predict_submit(m, x_host, x_dtype, batch, y_host, 0));
+        TRY(predict_submit(m, x_host, x_dtype, batch, y_host, 0, nullptr, depth_host ? &in : nullptr));
         return c3_predict_wait(m, 0);
     }
+    m->rescaled = 0, in.piece = true;
     constexpr int kRing = 3;
     const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
     // A blocking call cannot hide its FIRST staging copy behind a previous batch (pageable -> pinned, ~16 GB/s with the staging pool);
@@ -276,8 +320,10 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
         take = std::min(take, max_microbatch(m));
         if (n_sub - n_done == kRing) rc = c3_predict_wait(m, (int)(n_done++ % kRing));
         m->tap_call_off = off;
+        if (depth_host) in.depth = depth_host + off;
         if (rc == 0)
-            rc = predict_submit(m, (const char *)x_host + off * wbytes, x_dtype, take, y_host + off * m->row, (int)(n_sub % kRing));
+            rc = predict_submit(m, (const char *)x_host + off * wbytes, x_dtype, take, y_host + off * m->row, (int)(n_sub % kRing), nullptr,
+                                depth_host ? &in : nullptr);
         m->tap_call_off = 0;
         if (rc != 0) break;
         off += take;
@@ -293,46 +339,85 @@ int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, floa
     return rc;
 }
 
-int c3_predict_pileup_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
-                             int64_t batch, float *y_host) {
+int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host) {
+    return predict_blocking(m, x_host, x_dtype, batch, nullptr, y_host);
+}
+
+// ---- depths: the reference's CPU-branch meaning of a pileup window (c3_rescale.h) ----
+// what the *_depth entries refuse before anything is staged
+static int depth_args_ok(c3_model *m, int x_dtype, int64_t batch, const int32_t *depth_host, bool region) {
     if (!m) return fail("null model");
-    if (m->kind != C3_KIND_PILEUP) return fail("c3_predict_pileup_region needs a pileup model");
+    if (m->kind != C3_KIND_PILEUP) return fail("depths belong to pileup windows: a full-alignment model has no rescaling rule");
+    if (batch < 0) return fail("negative batch");
+    if (x_dtype == C3_DTYPE_I8)
+        return fail("depths are refused for int8 counts: int8 tensor files are the reference's GPU branch, which does not rescale, and counts "
+                    "above 127 have already wrapped in them -- pass int32%s counts", region ? " / int64" : "");
+    if (x_dtype != C3_DTYPE_I32 && !(region && x_dtype == C3_DTYPE_I64))
+        return fail("windows with depths must be int32%s (got dtype %d)", region ? " or int64 / size_t" : "", x_dtype);
+    if (!depth_host && batch > 0) return fail("null depths (the entries without depths are c3_predict / c3_predict_submit / c3_predict_pileup_region)");
+    return 0;
+}
+
+int c3_model_set_max_depth(c3_model *m, int max_depth) {
+    if (!m) return fail("null model");
+    if (m->kind != C3_KIND_PILEUP) return fail("max_depth belongs to the pileup network");
+    if (max_depth <= 0) return fail("max_depth must be positive (got %d)", max_depth);
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    m->max_depth = max_depth;
+    return 0;
+}
+
+int c3_predict_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host) {
+    TRY(depth_args_ok(m, x_dtype, batch, depth_host, false));
+    return predict_blocking(m, x_host, x_dtype, batch, depth_host, y_host);
+}
+
+int c3_predict_submit_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host, int slot) {
+    TRY(depth_args_ok(m, x_dtype, batch, depth_host, false));
+    RingInput in;
+    in.depth = depth_host;
+    return predict_submit(m, x_host, x_dtype, batch, y_host, slot, nullptr, &in);
+}
+
+// ---- the region form of the pileup call on the ring ----
+static int region_submit(c3_model *m, const char *who, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
+                         int64_t batch, const int32_t *depth_host, float *y_host, int slot) {
+    if (!m) return fail("null model");
+    if (m->kind != C3_KIND_PILEUP) return fail("%s needs a pileup model", who);
     if (batch < 0 || n_cols < 0) return fail("negative size");
-    if (batch == 0) return 0;
-    if (!region_host || !starts_host || !y_host) return fail("null buffer");
+    if (batch > 0 && (!region_host || !starts_host || !y_host)) return fail("null buffer");
     if (x_dtype != C3_DTYPE_I8 && x_dtype != C3_DTYPE_I32 && x_dtype != C3_DTYPE_I64)
         return fail("pileup regions must be int8, int32 or int64 / size_t (got dtype %d)", x_dtype);
-    // int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
-    // buffer, which is what the reference's PIPE mode feeds the model (CreateTensorPileupFromCffi.py:143-146 -> int32 windows)
-    const bool narrow = x_dtype == C3_DTYPE_I64;
-    if (narrow) x_dtype = C3_DTYPE_I32;
     for (int64_t i = 0; i < batch; ++i)
         if (starts_host[i] < 0 || (int64_t)starts_host[i] + m->positions > n_cols)
             return fail("window %lld starts at column %d: outside the %lld-column region", (long long)i, starts_host[i], (long long)n_cols);
-    HostSlot &sl = m->slot[0];
-    if (sl.busy) return fail("slot 0 still in flight: call c3_predict_wait first");
-    HIP_TRY(hipSetDevice(m->device));
-    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
-    TRY(use_lane(m, 0));
-    const size_t item = x_dtype == C3_DTYPE_I32 ? 4 : 1;
-    const size_t rb = ((size_t)n_cols * m->C * item + 255) & ~(size_t)255;
-    const size_t sb = (size_t)batch * sizeof(int32_t);
-    const size_t yb = (size_t)batch * m->row * sizeof(float);
-    TRY(ensure_slot(m, sl, rb + sb, yb));
-    if (narrow) {
-        const int64_t *src = static_cast<const int64_t *>(region_host);
-        int32_t *dst = static_cast<int32_t *>(sl.pin_x);
-        for (size_t i = 0, e = (size_t)n_cols * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
-    } else {
-        memcpy(sl.pin_x, region_host, (size_t)n_cols * m->C * item);
-    }
-    memcpy((char *)sl.pin_x + rb, starts_host, sb);
-    HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, rb + sb, hipMemcpyHostToDevice, lane(m).stream));
-    TRY(forward_device(m, lane(m).stream, sl.dev_x, x_dtype, batch, sl.dev_y, (const int32_t *)((char *)sl.dev_x + rb)));
-    HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, yb, hipMemcpyDeviceToHost, lane(m).stream));
-    HIP_TRY(hipStreamSynchronize(lane(m).stream));
-    memcpy(y_host, sl.pin_y, yb);
-    return 0;
+    RingInput in;
+    in.n_cols = n_cols, in.starts = starts_host, in.depth = depth_host;
+    in.narrow = x_dtype == C3_DTYPE_I64;
+    return predict_submit(m, region_host, in.narrow ? C3_DTYPE_I32 : x_dtype, batch, y_host, slot, nullptr, &in);
+}
+
+int c3_predict_submit_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host, int64_t batch,
+                             const int32_t *depth_host, float *y_host, int slot) {
+    if (depth_host) TRY(depth_args_ok(m, x_dtype, batch, depth_host, true));
+    return region_submit(m, "c3_predict_submit_region", region_host, x_dtype, n_cols, starts_host, batch, depth_host, y_host, slot);
+}
+
+// the two blocking region entries: submit + wait on slot 0 (so they pass through the range guard of c3_predict_wait like every other batch)
+int c3_predict_pileup_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
+                             int64_t batch, float *y_host) {
+    if (m && m->kind == C3_KIND_PILEUP && batch == 0 && n_cols >= 0) return 0;
+    TRY(region_submit(m, "c3_predict_pileup_region", region_host, x_dtype, n_cols, starts_host, batch, nullptr, y_host, 0));
+    return c3_predict_wait(m, 0);
+}
+
+int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
+                                   int64_t batch, const int32_t *depth_host, float *y_host) {
+    TRY(depth_args_ok(m, x_dtype, batch, depth_host, true));
+    if (batch == 0 && n_cols >= 0) return 0;
+    TRY(region_submit(m, "c3_predict_pileup_region_depth", region_host, x_dtype, n_cols, starts_host, batch, depth_host, y_host, 0));
+    return c3_predict_wait(m, 0);
 }
 
 int c3_outcome_maxima(c3_model *m, const float *y_host, int64_t batch, const uint8_t *ref21_host, float *maxp_host,

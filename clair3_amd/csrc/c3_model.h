@@ -5,7 +5,8 @@
 //   c3_model.h     this file
 //   c3_pack.h      c3_model_load: BatchNorm folding, gate re-ordering, matrix-instruction fragment layouts, fp16 pieces
 //   c3_forward.h   the launch sequences of the two forward passes (clair3/model.py:130-161 and :377-416)
-//   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait (staging, transfers, range guard)
+//   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait (staging, transfers, range guard), the region
+//                  entries and the entries that take per-window depths (c3_rescale.h: the pre-pass that rescales very deep windows)
 //   c3_comm.h      the gather of a sharded job on RCCL
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
@@ -38,6 +39,7 @@
 #include "c3_tail.h"
 #include "c3_decode.h"
 #include "c3_lstm_fused.h"
+#include "c3_rescale.h"
 #include "c3_host.h"
 #include "c3_conv3.h"
 #include "c3_conv3s2.h"
@@ -118,6 +120,9 @@ struct HostSlot {
     bool busy = false;
     bool used_f16 = false;  // the batch in flight was computed by the fp16x3 kernels (c3_predict_wait then checks its range)
     int lane = 0;           // the lane (Lane) the batch in flight runs in
+    // a region batch / a batch with depths keeps its window starts and depths on the device with the slot (behind the counts in dev_x): the
+    // range guard's re-run gathers and rescales again from the ORIGINAL counts (c3_rescale.h never writes dev_x)
+    const int32_t *dev_starts = nullptr, *dev_depth = nullptr;
 };
 
 constexpr int kHostSlots = 4;  // batches in flight per handle through c3_predict_submit / _wait (C3_HOST_SLOTS)
@@ -137,6 +142,8 @@ struct Lane {
     float *spp = nullptr, *part = nullptr, *l4dbg = nullptr;
     float *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
     int64_t last_n = 0;  // windows of the last micro-batch (for debug fetch)
+    int32_t *xr = nullptr;  // rescaled sliced int32 windows of a micro-batch that carries depths (c3_rescale.h); allocated on first use
+    int64_t xr_cap = 0;     // windows it holds
 };
 constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
 
@@ -224,6 +231,10 @@ struct c3_model {
     bool tail_fused = false;  // the split-K sum of L4 inside fc_tail_mfma_kernel (c3_tail.h) instead of its own launch: on for the pileup network (+0.7 %:
                               // 15 partials of 128 features), off for full alignment (-1 %: four branch workgroups re-read 28 partials of 256)
     int wg_slots = 512;       // co-resident 256-thread / 64 KiB-LDS workgroups on the device (2 per CU)
+
+    // the reference's rescaling of very deep pileup windows (c3_rescale.h; the *_depth entries and c3_predict_submit_region)
+    int max_depth = 144;   // shared/param_p.py:15 max_depth_dict: 144 on every platform (c3_model_set_max_depth)
+    int64_t rescaled = 0;  // windows rescaled in the last call (c3_model_describe)
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
@@ -437,6 +448,8 @@ static void free_workspace(Lane &L) {
     for (auto &b : L.bufs) (void)hipFree(b.p);
     L.bufs.clear();
     L.cap = 0;
+    if (L.xr) (void)hipFree(L.xr);
+    L.xr = nullptr, L.xr_cap = 0;
 }
 static void free_all_workspaces(c3_model *m) {  // every lane's (geometry change, destruction)
     for (Lane &L : m->lanes) free_workspace(L);
@@ -476,5 +489,17 @@ static int ensure_workspace(c3_model *m, int64_t n) {  // the active lane's
     TRY(dev_alloc(L, (void **)&L.part, (size_t)l4_splits(m) * n * m->FC * sizeof(float)));  // [S][n][FC]
     TRY(dev_alloc(L, (void **)&L.l4dbg, (size_t)n * m->FC * sizeof(float)));
     L.cap = n;
+    return 0;
+}
+
+// the active lane's buffer of rescaled windows (c3_rescale.h), as many as its workspace holds; only a handle that is given depths has one
+static int ensure_rescale_buf(c3_model *m) {
+    Lane &L = lane(m);
+    if (L.xr && L.xr_cap >= L.cap) return 0;
+    HIP_TRY(hipDeviceSynchronize());  // (a batch in flight in this lane may still read the smaller one)
+    if (L.xr) (void)hipFree(L.xr);
+    L.xr = nullptr, L.xr_cap = 0;
+    HIP_TRY(hipMalloc((void **)&L.xr, std::max<size_t>((size_t)L.cap * m->positions * m->C * sizeof(int32_t), 256)));
+    L.xr_cap = L.cap;
     return 0;
 }

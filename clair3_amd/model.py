@@ -195,26 +195,45 @@ class _HipModel:
             raise _lib.C3Error(f"window shape {shape[1:]} does not match the model "
                                f"({wbytes // item} elements per window, {self.input_channels} channels)")
 
-    def predict_numpy(self, x):
+    @staticmethod
+    def _depths(depths, n):
+        """one int32 depth per window, as the C ABI takes them"""
+        d = np.ascontiguousarray(depths, dtype=np.int32)
+        if d.shape != (n,):
+            raise _lib.C3Error(f"depths must hold one entry per window: shape {d.shape} for {n} windows")
+        return d
+
+    def predict_numpy(self, x, depths=None):
+        """depths: per-window read depths (predict.depths_from_alt_info); given, windows deeper than 1.5 x max_depth are rescaled on the
+        device the way the reference's in-process loops do before their model call (c3_predict_depth; pileup, int32 windows)."""
         x = np.ascontiguousarray(x)
         dt = _NP_DTYPE.get(x.dtype)
         if dt is None:
             raise _lib.C3Error(f"unsupported window dtype {x.dtype} (int8 / int32 expected)")
         self._check_shape(x.shape, dt)
         y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
-        _lib.check(_lib.lib().c3_predict(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data), "c3_predict")
+        if depths is None:
+            _lib.check(_lib.lib().c3_predict(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data), "c3_predict")
+        else:
+            d = self._depths(depths, x.shape[0])
+            _lib.check(_lib.lib().c3_predict_depth(self._handle, x.ctypes.data, dt, x.shape[0], d.ctypes.data, y.ctypes.data), "c3_predict_depth")
         return y
 
-    def submit(self, x, slot=0):
-        """Asynchronous half of predict_numpy (c3_predict_submit); returns a handle for wait()."""
+    def submit(self, x, slot=0, depths=None):
+        """Asynchronous half of predict_numpy (c3_predict_submit / c3_predict_submit_depth); returns a handle for wait()."""
         x = np.ascontiguousarray(x)
         dt = _NP_DTYPE.get(x.dtype)
         if dt is None:
             raise _lib.C3Error(f"unsupported window dtype {x.dtype} (int8 / int32 expected)")
         self._check_shape(x.shape, dt)
         y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
-        _lib.check(_lib.lib().c3_predict_submit(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data, slot),
-                   "c3_predict_submit")
+        if depths is None:
+            _lib.check(_lib.lib().c3_predict_submit(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data, slot),
+                       "c3_predict_submit")
+        else:
+            d = self._depths(depths, x.shape[0])
+            _lib.check(_lib.lib().c3_predict_submit_depth(self._handle, x.ctypes.data, dt, x.shape[0], d.ctypes.data, y.ctypes.data, slot),
+                       "c3_predict_submit_depth")
         return slot, y
 
     def submit_dev(self, x, y_dev_ptr, slot=0):
@@ -317,10 +336,14 @@ class Clair3_P(_HipModel):
     KIND = _lib.KIND_PILEUP
     DEFAULT_CHANNELS = 18  # shared/param_p.py:32-36
 
-    def predict_region(self, region, starts):
-        """Rows for the windows region[starts[b] : starts[b] + 33] without materialising them: ``region`` is the
-        (n_cols, 18) matrix of one pileup region, ``starts`` the per-candidate offsets the reference slices at
-        (preprocess/CreateTensorPileupFromCffi.py:362-364).  Same rows, bit for bit, as predict_numpy on the slices."""
+    def set_max_depth(self, n):
+        """param.max_depth_dict[platform] of the rescaling rule (c3_model_set_max_depth; default 144, shared/param_p.py:15)"""
+        if self._handle is None:
+            self.to(0)
+        _lib.check(_lib.lib().c3_model_set_max_depth(self._handle, int(n)), "c3_model_set_max_depth")
+        return self
+
+    def _region_args(self, region, starts):
         region = np.ascontiguousarray(region)
         # int64 / uint64: the size_t matrix of plp_data viewed in place (np.frombuffer(ffi.buffer(plp_data.matrix, ...)),
         # CreateTensorPileupFromCffi.py:140-146) -- no .copy(), no astype
@@ -328,11 +351,33 @@ class Clair3_P(_HipModel):
         if dt is None or region.ndim != 2 or region.shape[1] != self.input_channels:
             raise _lib.C3Error(f"region must be (n_cols, {self.input_channels}) int8/int32/int64, got {region.dtype} {region.shape}")
         starts = np.ascontiguousarray(starts, dtype=np.int32)
-        y = np.empty((len(starts), self.row_size), dtype=np.float32)
-        _lib.check(_lib.lib().c3_predict_pileup_region(self._handle, region.ctypes.data, dt, region.shape[0],
-                                                       starts.ctypes.data, len(starts), y.ctypes.data),
-                   "c3_predict_pileup_region")
+        return region, dt, starts, np.empty((len(starts), self.row_size), dtype=np.float32)
+
+    def predict_region(self, region, starts, depths=None):
+        """Rows for the windows region[starts[b] : starts[b] + 33] without materialising them: ``region`` is the
+        (n_cols, 18) matrix of one pileup region, ``starts`` the per-candidate offsets the reference slices at
+        (preprocess/CreateTensorPileupFromCffi.py:362-364).  Same rows, bit for bit, as predict_numpy on the slices -- with ``depths``
+        (one per window) as predict_numpy(slices, depths): every window is rescaled by the factor of its own candidate."""
+        region, dt, starts, y = self._region_args(region, starts)
+        if depths is None:
+            _lib.check(_lib.lib().c3_predict_pileup_region(self._handle, region.ctypes.data, dt, region.shape[0],
+                                                           starts.ctypes.data, len(starts), y.ctypes.data),
+                       "c3_predict_pileup_region")
+        else:
+            d = self._depths(depths, len(starts))
+            _lib.check(_lib.lib().c3_predict_pileup_region_depth(self._handle, region.ctypes.data, dt, region.shape[0],
+                                                                 starts.ctypes.data, len(starts), d.ctypes.data, y.ctypes.data),
+                       "c3_predict_pileup_region_depth")
         return y
+
+    def submit_region(self, region, starts, slot=0, depths=None):
+        """Asynchronous half of predict_region (c3_predict_submit_region); returns a handle for wait()."""
+        region, dt, starts, y = self._region_args(region, starts)
+        d = None if depths is None else self._depths(depths, len(starts))
+        _lib.check(_lib.lib().c3_predict_submit_region(self._handle, region.ctypes.data, dt, region.shape[0], starts.ctypes.data, len(starts),
+                                                       None if d is None else d.ctypes.data, y.ctypes.data, slot),
+                   "c3_predict_submit_region")
+        return slot, y
 
 
 class Clair3_F(_HipModel):

@@ -88,6 +88,19 @@ def _hip_predict(model, device, X):
 _torch_predict = _hip_predict  # the name the reference call sites use
 
 
+def depths_from_alt_info(alt_info_list):
+    """The per-window depths of a batch as the reference's loops read them before they rescale deep pileup windows
+    (clair3/CallVariantsFromCffi.py:280, clair3/utils.py:106: ``int(alt_info.split('-', maxsplit=1)[0])``), as the int32 array
+    ``Clair3_P.predict_numpy(x, depths=...)`` / ``predict_region`` / ``submit`` take."""
+    out = np.empty(len(alt_info_list), dtype=np.int32)
+    for i, alt_info in enumerate(alt_info_list):
+        try:
+            out[i] = int(alt_info.split('-', maxsplit=1)[0])
+        except (ValueError, AttributeError, OverflowError) as e:
+            raise _lib.C3Error(f"alt_info {i} does not start with an integer depth: {alt_info!r}") from e
+    return out
+
+
 def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=False, device=0, chkpnt_fn=None):
     """Model factory block of call_variants_from_cffi (clair3/CallVariantsFromCffi.py:223-248)."""
     if platform != "ont":

@@ -171,17 +171,21 @@ def _trained_like(sd, kind, rng):
         sd[f"{block}.conv2.weight"] /= s_inner[None, :, None, None]
 
 
-def make_pileup_windows(batch, seed=0, recipe="realistic", dtype=np.int8, channels=PILEUP_CHANNELS, depth=None):
+def make_pileup_windows(batch, seed=0, recipe="realistic", dtype=np.int8, channels=PILEUP_CHANNELS, depth=None, return_depth=False):
     """(batch, 33, 18) pileup count tensors.
 
     realistic: per-position strand-split base counts with the reference-base channel negated
     (src/clair3_pileup.c:370-371) and sparse indel channels; uniform: iid integers in [-60, 60].
     depth: mean read depth of the realistic recipe (default: Poisson(50) clipped to [4, 127], what int8 holds); given, the
     depths are Poisson(depth) without the upper clip -- counts of high-coverage regions, for int32 windows.
+    return_depth: also return the per-window depth the recipe drew, (windows, int32 depths) -- what the leading integer of a
+    candidate's alt_info says; the windows of a seed are the same either way.
     """
     rng = np.random.default_rng(seed)
     if recipe == "uniform":
         x = rng.integers(-60, 61, size=(batch, NO_OF_POSITIONS, channels))
+        if return_depth:
+            raise ValueError("the uniform recipe draws no read depth")
         return x.astype(dtype)
     x = np.zeros((batch, NO_OF_POSITIONS, channels), dtype=np.int64)
     if depth is None:
@@ -211,7 +215,37 @@ def make_pileup_windows(batch, seed=0, recipe="realistic", dtype=np.int8, channe
         x[..., strand + 4:strand + 9] = np.where(indel, amt, 0)
     if channels != PILEUP_CHANNELS:
         x = np.resize(x, (batch, NO_OF_POSITIONS, channels))
+    if return_depth:
+        return x.astype(dtype), depth.ravel().astype(np.int32)
     return x.astype(dtype)  # int8 wraps like the reference's GPU .npy path (CreateTensorPileupFromCffi.py:447)
+
+
+MAX_DEPTH = 144  # shared/param_p.py:15 max_depth_dict, every platform
+
+
+def rescale_deep_windows(x, depths, max_depth=MAX_DEPTH):
+    """What both in-process loops of the reference do to int32 pileup windows before their model call
+    (clair3/CallVariantsFromCffi.py:278-285, clair3/utils.py:104-111), in numpy, for tests and callers without a GPU.  Window b with
+    depths[b] > 0 and depths[b] > 1.5 * max_depth becomes trunc(x / s) with s = depths[b] / max_depth: one rounding for s (a double,
+    as Python's int / int), a second one for every quotient (double), then towards zero into int32.  Deliberately not the exact
+    rational x * max_depth / depths[b] (x = 217, depth = 248: 125 here, 126 there).  Every other window is returned as it came.
+    Returns a new int32 array; ``x`` is not modified."""
+    x = np.asarray(x)
+    if x.dtype != np.int32:
+        raise TypeError(f"the rescaling rule is defined on int32 counts, got {x.dtype}")
+    depths = np.asarray(depths)
+    if depths.shape != (x.shape[0],):
+        raise ValueError(f"one depth per window: {depths.shape} for {x.shape[0]} windows")
+    if max_depth <= 0:
+        raise ValueError("max_depth must be positive")
+    out = x.copy()
+    d = depths.astype(np.int64)
+    deep = (d > 0) & (d.astype(np.float64) > 1.5 * float(max_depth))
+    if deep.any():
+        s = d[deep].astype(np.float64) / np.float64(max_depth)
+        q = x[deep].astype(np.float64) / s.reshape((-1,) + (1,) * (x.ndim - 1))
+        out[deep] = np.trunc(q).astype(np.int32)
+    return out
 
 
 def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, depth=FA_DEPTH_ONT):

@@ -165,9 +165,40 @@ int c3_model_range_status(c3_model *m, int *flag_out, int *on_fp32_out);
  * (src/clair3_pileup.h:113; preprocess/CreateTensorPileupFromCffi.py:143-146) -- C3_DTYPE_I64 is plp_data.matrix itself
  * (size_t), narrowed to int32 while it is staged, so the numpy copy of :143-146 is not needed either; starts_host[b] = first column of window
  * b, i.e. the `offset` the reference slices at (CreateTensorPileupFromCffi.py:362-364: result[0][offset:offset+33]).
- * Equivalent to c3_predict on the sliced windows, bit for bit; candidate filtering stays with the caller. */
+ * Equivalent to c3_predict on the sliced windows, bit for bit (neither rescales deep windows: c3_predict_pileup_region_depth below does);
+ * candidate filtering stays with the caller.  Blocks on slot 0 of the ring (c3_predict_submit_region + c3_predict_wait). */
 int c3_predict_pileup_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
                              int64_t batch, float *y_host);
+/* The region entry on the ring: c3_predict_pileup_region split like c3_predict_submit / c3_predict_wait, on the same slots and lanes
+ * (the lane follows `batch`, as for windows); region_host, starts_host and depth_host may be reused as soon as submit returns.
+ * depth_host may be NULL (no rescaling) or carry one depth per window (see c3_predict_depth below).  The slot keeps the starts and
+ * depths on the device with the region, so the range guard of c3_predict_wait gathers -- and rescales -- again from the original
+ * matrix.  The two blocking region entries are this submit + c3_predict_wait on slot 0: same rows as before, now with the guard. */
+int c3_predict_submit_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host, int64_t batch,
+                             const int32_t *depth_host, float *y_host, int slot);
+/* ---- windows of very deep coverage: the reference's CPU-branch meaning of a pileup window ----
+ * Both in-process loops of the reference bring a window of very deep coverage down to max_depth before the network sees it
+ * (clair3/CallVariantsFromCffi.py:278-285, the loop of the default pipeline; clair3/utils.py:104-111, the stdin worker's generator):
+ *     depth = int(alt_info.split('-', 1)[0])
+ *     if depth > 0 and depth > max_depth * 1.5:  X[i] = X[i] / (depth / max_depth)     (int32 array: truncated towards zero)
+ * with max_depth = shared/param_p.py:15 (144 on every platform: windows from depth 217 on).  The *_depth entries apply exactly that
+ * on the device, for all 33 x C counts of window b with depth_host[b]: two roundings in double (s = depth / max_depth, then x / s),
+ * then towards zero -- numpy's statement, not the exact rational x * max_depth / depth (x = 217, depth = 248: 125, not 126).  A window
+ * that is not rescaled passes through bit for bit; a batch without any deep window runs what the entry without depths runs.  The
+ * reference's GPU branch (int8 tensor files, CallVariantsFromCffiGPU.py) does NOT rescale and stays mirrored as it is: C3_DTYPE_I8 is
+ * refused here, because counts above 127 have already wrapped in such files.  Pileup handles only.
+ *   c3_model_set_max_depth         param.max_depth_dict[platform]; default 144; <= 0 is an error
+ *   c3_predict_depth               c3_predict with depths; x_dtype C3_DTYPE_I32
+ *   c3_predict_submit_depth        c3_predict_submit with depths (wait: c3_predict_wait); depth_host may be reused when it returns
+ *   c3_predict_pileup_region_depth c3_predict_pileup_region with depths; C3_DTYPE_I32 | C3_DTYPE_I64.  A column belongs to up to 33
+ *                                  windows, each rescaled by the factor of its own candidate: the matrix cannot be pre-scaled
+ * depth_host == NULL is an error in these three (the entries without depths keep their names and their behaviour).
+ * c3_model_describe reports max_depth= and rescaled=<windows rescaled in the last call>. */
+int c3_model_set_max_depth(c3_model *m, int max_depth);
+int c3_predict_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host);
+int c3_predict_submit_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host, int slot);
+int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
+                                   int64_t batch, const int32_t *depth_host, float *y_host);
 /* SURVEY 8f N1 (first slice): the arithmetic of the reference decoder, clair3/CallVariants.py:510-659
  * (possible_outcome_probabilites_from).  For every probability row y_host[b] (24 or 90 floats, as produced by
  * c3_predict) and the gt21 index of its reference base pair ref21_host[b] (0 AA, 4 CC, 7 GG, 9 TT -- reference_gt21 at
