@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("C3HIP_LIB", os.path.join(_HERE, "lib", "libc3hip.so")
 KIND_PILEUP = 0
 KIND_FULL_ALIGNMENT = 1
 DTYPE_I8, DTYPE_I32, DTYPE_F32, DTYPE_I64 = 0, 1, 2, 3
+# status of a candidate (C3_CAND_* in include/c3hip.h)
+CAND_NO_WINDOW, CAND_MAIN, CAND_EMPTY_COLUMN, CAND_HEAD, CAND_TAIL = 0, 1, 2, 3, 4
 
 # every symbol include/c3hip.h declares (tests/test_abi.py checks the header against this list)
 EXPORTS = (
@@ -22,6 +24,7 @@ EXPORTS = (
     "c3_predict_wait", "c3_comm_unique_id", "c3_comm_create", "c3_comm_destroy", "c3_gather_rows", "c3_comm_count", "c3_comm_abort", "c3_stream_wait", "c3_model_describe", "c3_model_set_sharing", "c3_predict_device", "c3_predict_device_checked", "c3_model_range_status", "c3_predict_pileup_region", "c3_outcome_maxima", "c3_decode_columns", "c3_vcf_rows", "c3_model_synchronize", "c3_model_destroy", "c3_debug_fetch",
     "c3_debug_keep_activations", "c3_debug_tap", "c3_debug_tap_fetch", "c3_profile_enable", "c3_profile_reset", "c3_profile_read",
     "c3_model_set_max_depth", "c3_predict_depth", "c3_predict_submit_depth", "c3_predict_pileup_region_depth", "c3_predict_submit_region",
+    "c3_predict_submit_candidates", "c3_predict_pileup_candidates",
 )
 
 
@@ -128,6 +131,10 @@ def lib():
     L.c3_predict_submit_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.c3_predict_pileup_region_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.c3_predict_submit_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    L.c3_predict_submit_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+    L.c3_predict_pileup_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -52,6 +52,21 @@ static int stage_h2d(void *dev, void *pin, const void *src, size_t bytes, hipStr
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ candidate selection (c3_select.h)
+static int run_select(c3_model *m, hipStream_t s, const SelectParams &sp) {
+    ProfScope ps(m, s, "p.select", 0.0, 4.0 * sp.n_cand * (double)(sp.T * sp.C));
+    const dim3 grid((unsigned)((sp.n_cand + kSelectThreads / 64 - 1) / (kSelectThreads / 64)));
+    if (sp.C % 2 == 0) hipLaunchKernelGGL(candidate_status_kernel<2>, grid, dim3(kSelectThreads), 0, s, sp);
+    else hipLaunchKernelGGL(candidate_status_kernel<1>, grid, dim3(kSelectThreads), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    const dim3 tiles((unsigned)((sp.n_cand + kCompactTile - 1) / kCompactTile));
+    hipLaunchKernelGGL(kept_count_kernel, tiles, dim3(kCompactTile), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(compact_kept_kernel, tiles, dim3(kCompactTile), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 // Pinned staging memory stays out of forked children (keep_out_of_children, c3_model.h: the staging copies of the 40 groups after
@@ -98,6 +113,17 @@ struct RingInput {
     bool narrow = false;              // the region holds int64 / size_t counts: narrowed to int32 on their way into the staging buffer
     const int32_t *depth = nullptr;   // per-window depths: windows deeper than 1.5 x max_depth are rescaled on the device (c3_rescale.h)
     bool piece = false;               // a piece of a blocking call: its rescaled windows add to the call's count
+    const struct CandInput *cand = nullptr;  // a candidate batch: the starts are worked out on the device (c3_select.h); n_cols = columns of the device image
+};
+// candidate positions instead of window starts (c3_predict_submit_candidates): what the host knows of the region before it is staged
+struct CandInput {
+    const int64_t *pos = nullptr;     // [batch]
+    bool head_tail = false;           // the device image carries positions - 1 zero columns in front of and behind every chunk
+    int64_t n_cols = 0;               // columns of the caller's matrix
+    std::vector<SelectChunk> chunks;  // col: the chunk's first column in the device image
+    std::vector<int64_t> src_col;     // ... and in the caller's matrix
+    uint8_t *status_host = nullptr;
+    int64_t *n_rows_host = nullptr;
 };
 static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out = nullptr,
                           const RingInput *in = nullptr);
@@ -139,8 +165,20 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     const size_t xb_al = (xb + 255) & ~(size_t)255;
     const size_t sb = region ? (size_t)batch * sizeof(int32_t) : 0, sb_al = (sb + 255) & ~(size_t)255;
     const size_t db = depth_host ? (size_t)batch * sizeof(int32_t) : 0;
-    const size_t xtot = sb + db ? xb_al + sb_al + db : xb;
+    const CandInput *cand = in ? in->cand : nullptr;
+    // a candidate batch stages, behind the image, the positions, the depths and the chunk table; the arrays the selection kernels write
+    // (compacted starts and depths, every candidate's start, the tiles' counts) follow and are never staged
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t c_pos = xb_al, c_din = c_pos + al((size_t)batch * sizeof(int64_t)), c_chk = c_din + al(db);
+    const size_t c_staged = cand ? c_chk + cand->chunks.size() * sizeof(SelectChunk) : 0;
+    const size_t c_starts = al(c_staged), c_dep = c_starts + sb_al, c_all = c_dep + al(db), c_tiles = c_all + sb_al;
+    const size_t n_tiles = (size_t)((batch + kCompactTile - 1) / kCompactTile);
+    const size_t c_end = cand ? c_tiles + al(n_tiles * sizeof(uint32_t)) : 0;
+    const size_t xtot = cand ? c_staged : (sb + db ? xb_al + sb_al + db : xb);
     const size_t yb = (size_t)batch * m->row * sizeof(float);
+    // ... and its statuses and the count of kept candidates leave behind the rows
+    const size_t y_status = al(yb), y_count = y_status + (((size_t)batch + 15) & ~(size_t)15);
+    const size_t ytot = cand ? y_count + 16 : yb;
     // windows of up to kKernelCopyMax bytes come in through the copy kernel only while no other batch of this handle is in flight: behind a
     // running batch the transfer stream brings the windows in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s), alone the copy
     // kernel is the shorter way (blocking call of one chunk 3.87 M against 3.64 M)
@@ -165,26 +203,49 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     } lane_sharing(m, (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1);
     if (batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(m, sl, xtot, y_dev_out ? 0 : yb));  // (rows that stay on the device need no slot buffers)
-        if (region) memcpy((char *)sl.pin_x + xb_al, in->starts, sb);
-        if (depth_host) memcpy((char *)sl.pin_x + xb_al + sb_al, depth_host, db);
+        TRY(ensure_slot(m, sl, cand ? c_end : xtot, y_dev_out ? 0 : ytot));  // (rows that stay on the device need no slot buffers)
+        if (cand) {
+            memcpy((char *)sl.pin_x + c_pos, cand->pos, (size_t)batch * sizeof(int64_t));
+            if (depth_host) memcpy((char *)sl.pin_x + c_din, depth_host, db);
+            memcpy((char *)sl.pin_x + c_chk, cand->chunks.data(), cand->chunks.size() * sizeof(SelectChunk));
+        } else {
+            if (region) memcpy((char *)sl.pin_x + xb_al, in->starts, sb);
+            if (depth_host) memcpy((char *)sl.pin_x + xb_al + sb_al, depth_host, db);
+        }
         // int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
         // buffer, which is what the reference's PIPE mode feeds the model (CreateTensorPileupFromCffi.py:143-146 -> int32 windows)
         const bool narrow = region && in->narrow;
-        if (narrow) {
+        // a candidate batch with head / tail windows: the image is laid out in the staging buffer chunk by chunk, positions - 1 zero
+        // columns in front of and behind each (c3_select.h)
+        const bool laid_out = cand && cand->head_tail;
+        if (laid_out) {
+            const size_t colb = (size_t)m->C * sizeof(int32_t), pad = (size_t)(m->positions - 1);
+            for (size_t k = 0; k < cand->chunks.size(); ++k) {
+                const SelectChunk &ch = cand->chunks[k];
+                const size_t n = (size_t)(ch.last - ch.first + 1), c0 = (size_t)ch.col, s0 = (size_t)cand->src_col[k];
+                int32_t *dst = (int32_t *)((char *)sl.pin_x + c0 * colb);
+                memset((char *)sl.pin_x + (c0 - pad) * colb, 0, pad * colb);
+                if (narrow) {
+                    const int64_t *src = static_cast<const int64_t *>(x_host) + s0 * m->C;
+                    for (size_t i = 0, e = n * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
+                } else StagePool::get().copy(dst, (const char *)x_host + s0 * colb, n * colb);
+                memset((char *)sl.pin_x + (c0 + n) * colb, 0, pad * colb);
+            }
+        } else if (narrow) {
             const int64_t *src = static_cast<const int64_t *>(x_host);
             int32_t *dst = static_cast<int32_t *>(sl.pin_x);
             for (size_t i = 0, e = (size_t)in->n_cols * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
         }
+        const bool prebuilt = narrow || laid_out;  // the image is already in the pinned buffer
         // the counts through the pinned buffer onto stream st, the starts and depths (already in the pinned buffer) behind them
         auto stage = [&](hipStream_t st) -> int {
-            if (narrow) HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, xb, hipMemcpyHostToDevice, st));
+            if (prebuilt) HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, xb, hipMemcpyHostToDevice, st));
             else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
             if (xtot > xb) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + xb_al, (char *)sl.pin_x + xb_al, xtot - xb_al, hipMemcpyHostToDevice, st));
             return 0;
         };
-        if (alone && xtot <= kKernelCopyMax && yb <= kKernelCopyMax) {
-            if (!narrow) StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
+        if (alone && xtot <= kKernelCopyMax && ytot <= kKernelCopyMax) {
+            if (!prebuilt) StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
             hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xtot + 15) / 16,
                                (const uint32_t *)nullptr, (uint32_t *)nullptr);
             HIP_TRY(hipGetLastError());
@@ -200,6 +261,20 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
         }
         sl.dev_starts = region ? (const int32_t *)((char *)sl.dev_x + xb_al) : nullptr;
         sl.dev_depth = depth_host ? (const int32_t *)((char *)sl.dev_x + xb_al + sb_al) : nullptr;
+        if (cand) {  // the selection, on the batch's stream in front of the forward pass; the slot keeps the compacted starts / depths for a re-run
+            char *d = (char *)sl.dev_x;
+            sl.dev_starts = (const int32_t *)(d + c_starts);
+            sl.dev_depth = depth_host ? (const int32_t *)(d + c_dep) : nullptr;
+            SelectParams sp;
+            sp.x = (const int32_t *)d, sp.chunks = (const SelectChunk *)(d + c_chk);
+            sp.pos = (const int64_t *)(d + c_pos), sp.depth_in = depth_host ? (const int32_t *)(d + c_din) : nullptr;
+            sp.status = (uint8_t *)sl.dev_y + y_status, sp.start_all = (int32_t *)(d + c_all), sp.starts = (int32_t *)(d + c_starts);
+            sp.depth = depth_host ? (int32_t *)(d + c_dep) : nullptr, sp.block_kept = (uint32_t *)(d + c_tiles);
+            sp.n_rows = (uint32_t *)((char *)sl.dev_y + y_count);
+            sp.n_cand = (int)batch, sp.n_chunks = (int)cand->chunks.size(), sp.C = m->C, sp.T = m->positions, sp.head_tail = cand->head_tail;
+            sp.img_cols = in->n_cols;
+            TRY(run_select(m, L.stream, sp));
+        }
         const bool f16 = m->f16_ok;
         TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, sl.dev_starts, sl.dev_depth));
         if (y_dev_out && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
@@ -207,8 +282,8 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
         // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
         // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
         // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
-        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(yb)), dim3(256), 0, L.stream, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                           y_dev_out ? 0 : (yb + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(ytot)), dim3(256), 0, L.stream, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
+                           y_dev_out ? 0 : (ytot + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(sl.ev_out, L.stream));
         sl.used_f16 = f16;
@@ -217,6 +292,11 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     sl.lane = m->lane_cur;
     sl.y_host = y_host, sl.y_bytes = yb, sl.batch = batch, sl.x_dtype = x_dtype, sl.busy = true;
     sl.tap_off = m->tap_call_off;
+    sl.cand = cand != nullptr, sl.cand_none = false;
+    if (cand) {
+        sl.status_host = cand->status_host, sl.n_rows_host = cand->n_rows_host, sl.tail_bytes = ytot - y_status;
+        sl.pin_depth = depth_host ? (const int32_t *)((char *)sl.pin_x + c_din) : nullptr, sl.n_chunks = (int64_t)cand->chunks.size();
+    }
     return 0;
 }
 
@@ -226,6 +306,13 @@ int c3_predict_wait(c3_model *m, int slot) {
     HostSlot &sl = m->slot[slot];
     if (!sl.busy) return fail("slot %d has nothing in flight", slot);
     sl.busy = false;
+    if (sl.cand && sl.cand_none) {  // nothing was launched: no candidate has a window
+        if (sl.batch > 0) memset(sl.status_host, kCandNoWindow, (size_t)sl.batch);
+        *sl.n_rows_host = 0;
+        m->cand_n = sl.batch, m->cand_kept = 0, m->cand_chunks = sl.n_chunks, m->rescaled = 0;
+        sl.cand = false;
+        return 0;
+    }
     if (sl.y_bytes == 0) return 0;
     HIP_TRY(hipEventSynchronize(sl.ev_out));
     if (sl.y_dev_out) {  // rows stayed on the device: the flag (range bit + the device-side scan for non-finite rows) is all there is to read
@@ -263,6 +350,23 @@ int c3_predict_wait(c3_model *m, int slot) {
             HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, lane(m).stream));
             HIP_TRY(hipStreamSynchronize(lane(m).stream));
         }
+    }
+    if (sl.cand) {  // rows [0, kept) are the result; the rest belong to the surplus windows of dropped candidates
+        const char *tail = (const char *)sl.pin_y + ((sl.y_bytes + 255) & ~(size_t)255);
+        const int64_t kept = (int64_t)*(const uint32_t *)(tail + sl.tail_bytes - 16);
+        if (kept < 0 || kept > sl.batch) return fail("internal: %lld of %lld candidates kept", (long long)kept, (long long)sl.batch);
+        memcpy(sl.status_host, tail, (size_t)sl.batch);
+        memcpy(sl.y_host, sl.pin_y, (size_t)kept * m->row * sizeof(float));
+        *sl.n_rows_host = kept;
+        int64_t deep = 0;
+        if (sl.pin_depth)
+            for (int64_t i = 0; i < sl.batch; ++i) {
+                const uint8_t st = sl.status_host[i];
+                deep += (st == kCandMain || st == kCandHead || st == kCandTail) && sl.pin_depth[i] > 0 && (double)sl.pin_depth[i] > 1.5 * (double)m->max_depth;
+            }
+        m->cand_n = sl.batch, m->cand_kept = kept, m->cand_chunks = sl.n_chunks, m->rescaled = deep;
+        sl.cand = false;
+        return 0;
     }
     memcpy(sl.y_host, sl.pin_y, sl.y_bytes);
     return 0;
@@ -417,6 +521,60 @@ int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_d
     TRY(depth_args_ok(m, x_dtype, batch, depth_host, true));
     if (batch == 0 && n_cols >= 0) return 0;
     TRY(region_submit(m, "c3_predict_pileup_region_depth", region_host, x_dtype, n_cols, starts_host, batch, depth_host, y_host, 0));
+    return c3_predict_wait(m, 0);
+}
+
+// ---- candidate positions instead of window starts (c3_select.h) ----
+int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
+                                 const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
+                                 uint8_t *status_host, int64_t *n_rows_host, int slot) {
+    if (!m) return fail("null model");
+    if (m->kind != C3_KIND_PILEUP) return fail("candidate selection needs a pileup model: a full-alignment handle has no region matrix");
+    if (n_cand < 0 || n_cols < 0) return fail("negative size");
+    if (x_dtype == C3_DTYPE_I8)
+        return fail("candidate selection is refused for int8 counts: int8 tensor files are the reference's GPU branch, whose windows are already "
+                    "sliced -- pass the int32 / int64 region matrix");
+    if (x_dtype != C3_DTYPE_I32 && x_dtype != C3_DTYPE_I64) return fail("the region matrix must be int32 or int64 / size_t (got dtype %d)", x_dtype);
+    if (!n_rows_host) return fail("null buffer: n_rows_host");
+    if (n_cols > 0 && (!region_host || !major_host)) return fail("null buffer: region / major");
+    if (n_cand > 0 && (!pos_host || !y_host || !status_host)) return fail("null buffer: positions / rows / status");
+    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
+    if (m->slot[slot].busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
+    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
+    if (n_cand > INT32_MAX) return fail("too many candidates for one call (%lld)", (long long)n_cand);
+    // the chunk table: one pass over major (8 bytes a column); the image column of a chunk's first follows from the layout
+    CandInput ci;
+    ci.pos = pos_host, ci.head_tail = head_tail != 0, ci.n_cols = n_cols, ci.status_host = status_host, ci.n_rows_host = n_rows_host;
+    const int64_t pad = ci.head_tail ? m->positions - 1 : 0;
+    for (int64_t c = 0; c < n_cols; ++c) {
+        if (c > 0 && major_host[c] <= major_host[c - 1])
+            return fail("major must be strictly increasing: column %lld holds %lld after %lld", (long long)c, (long long)major_host[c],
+                        (long long)major_host[c - 1]);
+        if (c == 0 || major_host[c] != major_host[c - 1] + 1) {
+            const int64_t k = (int64_t)ci.chunks.size();
+            ci.chunks.push_back(SelectChunk{major_host[c], major_host[c], c + (2 * k + 1) * pad});
+            ci.src_col.push_back(c);
+        } else ci.chunks.back().last = major_host[c];
+    }
+    const int64_t img_cols = n_cols + 2 * pad * (int64_t)ci.chunks.size();
+    if (img_cols > INT32_MAX - m->positions) return fail("region too large: %lld columns on the device", (long long)img_cols);
+    if (depth_host) TRY(depth_args_ok(m, x_dtype, n_cand, depth_host, true));
+    HostSlot &sl = m->slot[slot];
+    if (n_cand == 0 || img_cols < m->positions) {  // no candidate, or no window fits: nothing to launch, every status is "no window"
+        sl.cand = sl.cand_none = true, sl.status_host = status_host, sl.n_rows_host = n_rows_host, sl.n_chunks = (int64_t)ci.chunks.size();
+        sl.y_host = y_host, sl.y_bytes = 0, sl.batch = n_cand, sl.y_dev_out = nullptr, sl.busy = true;
+        return 0;
+    }
+    RingInput in;
+    in.n_cols = img_cols, in.depth = depth_host, in.narrow = x_dtype == C3_DTYPE_I64, in.cand = &ci;
+    return predict_submit(m, region_host, C3_DTYPE_I32, n_cand, y_host, slot, nullptr, &in);
+}
+
+int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
+                                 const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
+                                 uint8_t *status_host, int64_t *n_rows_host) {
+    TRY(c3_predict_submit_candidates(m, region_host, x_dtype, n_cols, major_host, pos_host, depth_host, n_cand, head_tail, y_host, status_host,
+                                     n_rows_host, 0));
     return c3_predict_wait(m, 0);
 }
 

@@ -6,7 +6,8 @@
 //   c3_pack.h      c3_model_load: BatchNorm folding, gate re-ordering, matrix-instruction fragment layouts, fp16 pieces
 //   c3_forward.h   the launch sequences of the two forward passes (clair3/model.py:130-161 and :377-416)
 //   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait (staging, transfers, range guard), the region
-//                  entries and the entries that take per-window depths (c3_rescale.h: the pre-pass that rescales very deep windows)
+//                  entries, the entries that take per-window depths (c3_rescale.h: the pre-pass that rescales very deep windows) and the
+//                  candidate entries (c3_select.h: window selection from candidate positions in front of the forward pass)
 //   c3_comm.h      the gather of a sharded job on RCCL
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
@@ -40,6 +41,7 @@
 #include "c3_decode.h"
 #include "c3_lstm_fused.h"
 #include "c3_rescale.h"
+#include "c3_select.h"
 #include "c3_host.h"
 #include "c3_conv3.h"
 #include "c3_conv3s2.h"
@@ -123,6 +125,15 @@ struct HostSlot {
     // a region batch / a batch with depths keeps its window starts and depths on the device with the slot (behind the counts in dev_x): the
     // range guard's re-run gathers and rescales again from the ORIGINAL counts (c3_rescale.h never writes dev_x)
     const int32_t *dev_starts = nullptr, *dev_depth = nullptr;
+    // a candidate batch (c3_select.h; c3_predict_submit_candidates): the statuses and the count of kept candidates leave behind the rows
+    // (tail_bytes of dev_y / pin_y from y_bytes rounded up to 256 on: n_cand status bytes, then -- from the next multiple of 16 -- the count)
+    bool cand = false;
+    bool cand_none = false;        // nothing was launched: no candidate, or a region in which no window fits -- every status is "no window"
+    uint8_t *status_host = nullptr;
+    int64_t *n_rows_host = nullptr;
+    size_t tail_bytes = 0;
+    const int32_t *pin_depth = nullptr;  // the candidates' depths as staged (the count of rescaled windows among the kept, for c3_model_describe)
+    int64_t n_chunks = 0;
 };
 
 constexpr int kHostSlots = 4;  // batches in flight per handle through c3_predict_submit / _wait (C3_HOST_SLOTS)
@@ -235,6 +246,7 @@ struct c3_model {
     // the reference's rescaling of very deep pileup windows (c3_rescale.h; the *_depth entries and c3_predict_submit_region)
     int max_depth = 144;   // shared/param_p.py:15 max_depth_dict: 144 on every platform (c3_model_set_max_depth)
     int64_t rescaled = 0;  // windows rescaled in the last call (c3_model_describe)
+    int64_t cand_n = 0, cand_kept = 0, cand_chunks = 0;  // of the last candidate call that completed (c3_model_describe)
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;

@@ -10,7 +10,7 @@
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.0 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.1 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -273,10 +273,10 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
     if (!m || !buf || n <= 0) return fail("null argument");
     if (m->kind == C3_KIND_PILEUP)
         snprintf(buf, (size_t)n, "sharing=%d lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
-                 "ring_lanes=%d lane_max_batch=%lld max_depth=%d rescaled=%lld", m->sharing,
+                 "ring_lanes=%d lane_max_batch=%lld max_depth=%d rescaled=%lld candidates=%lld kept=%lld chunks=%lld", m->sharing,
                  m->choice_lstm1, m->choice_proj2, m->choice_lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
-                 (long long)m->rescaled);
+                 (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else
         snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld", m->sharing,
                  m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch);

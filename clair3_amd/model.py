@@ -27,6 +27,15 @@ def _device_index(device):
     raise _lib.C3Error(f"clair3_amd models only run on an MI355X HIP device, not on {s!r} (there is no CPU path)")
 
 
+class _CandidateBatch:
+    """what a candidate batch in flight writes into (Clair3_P.submit_candidates): c3_predict_wait fills all three"""
+
+    def __init__(self, n, row_size):
+        self.rows = np.empty((n, row_size), dtype=np.float32)
+        self.status = np.empty(n, dtype=np.uint8)
+        self.n_rows = C.c_int64(-1)
+
+
 class _HipModel:
     KIND = None
     DEFAULT_CHANNELS = None
@@ -252,6 +261,8 @@ class _HipModel:
     def wait(self, ticket):
         slot, y = ticket
         _lib.check(_lib.lib().c3_predict_wait(self._handle, slot), "c3_predict_wait")
+        if isinstance(y, _CandidateBatch):  # submit_candidates: the rows of the kept candidates and every candidate's status
+            return y.rows[:y.n_rows.value], y.status
         return y
 
     def sharing(self, handles=1):
@@ -378,6 +389,42 @@ class Clair3_P(_HipModel):
                                                        None if d is None else d.ctypes.data, y.ctypes.data, slot),
                    "c3_predict_submit_region")
         return slot, y
+
+    def _candidate_args(self, region, major, positions, depths):
+        region = np.ascontiguousarray(region)
+        dt = _lib.DTYPE_I64 if region.dtype in (np.dtype(np.int64), np.dtype(np.uint64)) else _NP_DTYPE.get(region.dtype)
+        if dt is None or region.ndim != 2 or region.shape[1] != self.input_channels:
+            raise _lib.C3Error(f"region must be (n_cols, {self.input_channels}) int32/int64, got {region.dtype} {region.shape}")
+        major = np.ascontiguousarray(major, dtype=np.int64)
+        if major.shape != (region.shape[0],):
+            raise _lib.C3Error(f"major must hold one entry per column: shape {major.shape} for {region.shape[0]} columns")
+        positions = np.ascontiguousarray(positions, dtype=np.int64)
+        if positions.ndim != 1:
+            raise _lib.C3Error(f"positions must be one-dimensional, got shape {positions.shape}")
+        d = None if depths is None else self._depths(depths, len(positions))
+        return region, dt, major, positions, d, _CandidateBatch(len(positions), self.row_size)
+
+    def predict_candidates(self, region, major, positions, depths=None, head_tail=False):
+        """The rows of the windows the reference's pileup producer would have fed the model for these candidates
+        (preprocess/CreateTensorPileupFromCffi.py:343-397), selected on the device: ``region`` is the (n_cols, 18) matrix of one pileup
+        region (int32, or the int64 plp_data.matrix itself), ``major`` its plp_data.major, ``positions`` the candidates' positions in the
+        caller's order, ``head_tail`` the reference's --enable_variant_calling_at_sequence_head_and_tail.  Returns (rows, status): the rows
+        of the kept candidates in candidate order and one _lib.CAND_* byte per candidate (synthetic.select_pileup_windows states the rule).
+        Same rows, bit for bit, as predict_numpy(windows[, depths of the kept]) on the materialised windows."""
+        region, dt, major, positions, d, out = self._candidate_args(region, major, positions, depths)
+        _lib.check(_lib.lib().c3_predict_pileup_candidates(
+            self._handle, region.ctypes.data, dt, region.shape[0], major.ctypes.data, positions.ctypes.data, None if d is None else d.ctypes.data,
+            len(positions), int(bool(head_tail)), out.rows.ctypes.data, out.status.ctypes.data, C.byref(out.n_rows)), "c3_predict_pileup_candidates")
+        return out.rows[:out.n_rows.value], out.status
+
+    def submit_candidates(self, region, major, positions, slot=0, depths=None, head_tail=False):
+        """Asynchronous half of predict_candidates (c3_predict_submit_candidates); wait() on the ticket returns (rows, status)."""
+        region, dt, major, positions, d, out = self._candidate_args(region, major, positions, depths)
+        _lib.check(_lib.lib().c3_predict_submit_candidates(
+            self._handle, region.ctypes.data, dt, region.shape[0], major.ctypes.data, positions.ctypes.data, None if d is None else d.ctypes.data,
+            len(positions), int(bool(head_tail)), out.rows.ctypes.data, out.status.ctypes.data, C.byref(out.n_rows), slot),
+            "c3_predict_submit_candidates")
+        return slot, out
 
 
 class Clair3_F(_HipModel):

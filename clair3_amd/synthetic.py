@@ -248,6 +248,105 @@ def rescale_deep_windows(x, depths, max_depth=MAX_DEPTH):
     return out
 
 
+# status of a candidate in select_pileup_windows (C3_CAND_* in include/c3hip.h)
+CAND_NO_WINDOW, CAND_MAIN, CAND_EMPTY_COLUMN, CAND_HEAD, CAND_TAIL = 0, 1, 2, 3, 4
+CAND_KEPT = (CAND_MAIN, CAND_HEAD, CAND_TAIL)
+
+
+def pileup_chunks(major):
+    """(first column, one-past-last column) of the chunks of a region: the maximal runs of ``major`` with steps of exactly 1
+    (preprocess/CreateTensorPileupFromCffi.py:180-236 cuts wherever major jumps by more than 1; major is strictly increasing)."""
+    major = np.asarray(major, dtype=np.int64)
+    if major.ndim != 1:
+        raise ValueError("major must be one-dimensional")
+    if len(major) > 1 and (np.diff(major) <= 0).any():
+        raise ValueError("major must be strictly increasing")
+    if len(major) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    cuts = np.flatnonzero(np.diff(major) != 1) + 1
+    return np.r_[0, cuts].astype(np.int64), np.r_[cuts, len(major)].astype(np.int64)
+
+
+def select_pileup_starts(region, major, positions, head_tail=False):
+    """The selection rule of select_pileup_windows without the windows: (status uint8 [n_cand], chunk index int64 [n_cand], offset int64
+    [n_cand]) -- the window of candidate i is columns offset[i] .. offset[i] + 32 of its chunk, where columns outside the chunk (head / tail
+    windows only) are zero rows; for a main window chunk start + offset is its first column in ``region``."""
+    region = np.asarray(region)
+    major = np.asarray(major, dtype=np.int64)
+    pos = np.asarray(positions, dtype=np.int64)
+    if region.ndim != 2 or len(major) != len(region) or pos.ndim != 1:
+        raise ValueError("region (n_cols, C), major (n_cols,), positions (n_cand,) expected")
+    T, F = NO_OF_POSITIONS, (NO_OF_POSITIONS - 1) // 2
+    a, b = pileup_chunks(major)
+    status = np.zeros(len(pos), np.uint8)
+    chunk = np.zeros(len(pos), np.int64)
+    off = np.zeros(len(pos), np.int64)
+    if len(a) == 0 or len(pos) == 0:
+        return status, chunk, off
+    first, last = major[a], major[b - 1]
+    k = np.searchsorted(first, pos, side="right") - 1
+    inside = (k >= 0) & (pos <= last[np.maximum(k, 0)])
+    k = np.maximum(k, 0)
+    lo = pos - F - 1  # first position of the window (the reference's offset = start - first - 1 with start = pos - F)
+    main = inside & (lo >= first[k]) & (pos + F + 1 <= last[k])
+    empty = np.r_[0, np.cumsum((region == 0).all(axis=1))]
+    col = np.where(main, a[k] + lo - first[k], 0)
+    has_empty = main & (empty[np.minimum(col + T, len(region))] - empty[col] > 0)
+    status[main] = CAND_MAIN
+    status[has_empty] = CAND_EMPTY_COLUMN
+    if head_tail:
+        rest = inside & ~main
+        head = rest & (lo < first[k])
+        status[head & (lo + T - 1 <= last[k])] = CAND_HEAD
+        status[rest & ~head] = CAND_TAIL
+    kept = np.isin(status, CAND_KEPT)
+    chunk[kept], off[kept] = k[kept], (lo - first[k])[kept]
+    return status, chunk, off
+
+
+def select_pileup_windows(region, major, positions, head_tail=False):
+    """Which windows the reference's pileup producer feeds the model (preprocess/CreateTensorPileupFromCffi.py:343-397), in numpy: for
+    callers without a GPU and for the tests.  region: (n_cols, C) counts; major: plp_data.major (strictly increasing; `minor` is not read:
+    the Clair3 pileup emits no insertion columns); positions: the candidates' positions, in the caller's order.
+
+    Chunks are the maximal runs of major with steps of 1 (first .. last).  A candidate's window covers positions pos-17 .. pos+15.  Main
+    (pos-17 >= first and pos+17 <= last): 33 in-chunk columns, CAND_MAIN, or CAND_EMPTY_COLUMN (dropped) when one of them is all zero.  With
+    head_tail, where the main test failed and first <= pos <= last: pos-17 < first gives CAND_HEAD iff pos+15 <= last (zero rows before
+    first), else CAND_TAIL (zero rows after last); neither is tested for empty columns.  Everything else: CAND_NO_WINDOW.
+
+    Returns (status uint8 [n_cand], windows int32 [n_kept, 33, C]) -- the windows of the kept candidates in candidate order."""
+    region = np.asarray(region)
+    status, chunk, off = select_pileup_starts(region, major, positions, head_tail)
+    a, b = pileup_chunks(major)
+    kept = np.flatnonzero(np.isin(status, CAND_KEPT))
+    T = NO_OF_POSITIONS
+    windows = np.zeros((len(kept), T, region.shape[1]), dtype=np.int32)
+    for j, i in enumerate(kept):
+        c0, c1 = a[chunk[i]], b[chunk[i]]
+        lo, hi = c0 + off[i], c0 + off[i] + T  # columns of the region; the part outside [c0, c1) stays zero
+        s, e = max(lo, c0), min(hi, c1)
+        windows[j, s - lo:e - lo] = region[s:e]
+    return status, windows
+
+
+def make_pileup_region(n_cols, n_chunks=1, seed=0, empty_fraction=0.0, empty_runs=(), depth=None, first=100000):
+    """A region as calculate_clair3_pileup returns it, for select_pileup_windows / Clair3_P.predict_candidates: (region int32 (n_cols, 18),
+    major int64 (n_cols,)).  Counts of the realistic window recipe laid end to end; ``n_chunks`` runs of consecutive positions separated by
+    1 .. 49 missing ones, cut at seeded columns; ``empty_fraction`` of the columns, and the ``empty_runs`` (first column, columns), all zero."""
+    rng = np.random.default_rng(seed)
+    region = make_pileup_windows(n_cols // NO_OF_POSITIONS + 1, seed=seed + 1, dtype=np.int32, depth=depth).reshape(-1, PILEUP_CHANNELS)[:n_cols].copy()
+    step = np.ones(n_cols, dtype=np.int64)
+    if n_chunks > 1:
+        cuts = rng.choice(np.arange(1, n_cols), size=n_chunks - 1, replace=False)
+        step[cuts] += rng.integers(1, 50, size=n_chunks - 1)
+    step[0] = first
+    if empty_fraction > 0:
+        region[rng.random(n_cols) < empty_fraction] = 0
+    for c0, n in empty_runs:
+        region[c0:c0 + n] = 0
+    return region, np.cumsum(step)
+
+
 def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, depth=FA_DEPTH_ONT):
     """(batch, 89, 33, 8|9) int8 full-alignment tensors."""
     rng = np.random.default_rng(seed)

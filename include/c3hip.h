@@ -26,6 +26,9 @@
  *   c3_vcf_rows                     the per-row Python of the decoder: batch_output -> output_with -> output_from with its allele
  *                                   lookups (clair3/CallVariants.py:1069-1394, :676-1016, :117-201, :662-673) for rows that carry the
  *                                   decoder columns -- one pass of plain host code per batch.
+ *   c3_predict_pileup_candidates    the loop that slices a region's pileup into windows, preprocess/CreateTensorPileupFromCffi.py:343-397
+ *                                   with __enforce_pileup_chunk_contiguity :180-236 (chunk lookup, offsets, the empty-column test, head /
+ *                                   tail padding), followed by the model call: candidate positions in, rows and statuses out.
  *   c3_device_pci_bus_id            where a GPU slot's worker belongs on the host (the reference leaves placement to the OS,
  *                                   clair3/CallVariantsFromCffiGPU.py:138-156).
  *
@@ -166,7 +169,7 @@ int c3_model_range_status(c3_model *m, int *flag_out, int *on_fp32_out);
  * (size_t), narrowed to int32 while it is staged, so the numpy copy of :143-146 is not needed either; starts_host[b] = first column of window
  * b, i.e. the `offset` the reference slices at (CreateTensorPileupFromCffi.py:362-364: result[0][offset:offset+33]).
  * Equivalent to c3_predict on the sliced windows, bit for bit (neither rescales deep windows: c3_predict_pileup_region_depth below does);
- * candidate filtering stays with the caller.  Blocks on slot 0 of the ring (c3_predict_submit_region + c3_predict_wait). */
+ * candidate filtering stays with the caller here (c3_predict_pileup_candidates below takes positions and filters).  Blocks on slot 0 of the ring (c3_predict_submit_region + c3_predict_wait). */
 int c3_predict_pileup_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
                              int64_t batch, float *y_host);
 /* The region entry on the ring: c3_predict_pileup_region split like c3_predict_submit / c3_predict_wait, on the same slots and lanes
@@ -199,6 +202,44 @@ int c3_predict_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch
 int c3_predict_submit_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host, int slot);
 int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host,
                                    int64_t batch, const int32_t *depth_host, float *y_host);
+/* ---- candidate POSITIONS instead of window starts: the reference's selection of pileup windows on the device ----
+ * Replaces the loop over all_alt_info_list in preprocess/CreateTensorPileupFromCffi.py:343-397 together with
+ * __enforce_pileup_chunk_contiguity (:180-236): the caller hands over the region matrix, plp_data.major and the candidates' positions
+ * (the first field of each alt-info string, in the caller's order -- after its own bed / known-VCF filters and the len(alt_info) < 4 skip)
+ * and gets the rows of the windows the reference would have fed the model, in the reference's order, plus a status per candidate.
+ *   region_host  (n_cols, C) C3_DTYPE_I32, or C3_DTYPE_I64 = plp_data.matrix itself (narrowed while it is staged); C3_DTYPE_I8 is refused
+ *   major_host   [n_cols] plp_data.major, strictly increasing.  Only `major` is read: the Clair3 pileup emits no minor (insertion) columns
+ *   pos_host     [n_cand] candidate positions; depth_host [n_cand] or NULL: with depths, kept windows deeper than 1.5 x max_depth are
+ *                rescaled exactly as c3_predict_*_depth does (after selection; zero rows stay zero)
+ *   head_tail    != 0: --enable_variant_calling_at_sequence_head_and_tail
+ * The rule.  Chunks are the maximal runs of major with steps of exactly 1, first / last a chunk's first and last major; a candidate belongs to
+ * the one chunk with first <= pos <= last.  Its window covers positions pos-17 .. pos+15 (the reference's offset = start - first - 1 with
+ * start = pos - 16; the asymmetry is the reference's).
+ *   main (pos-17 >= first and pos+17 <= last): 33 in-chunk columns; C3_CAND_MAIN unless one of them is all zero over its C counts:
+ *        C3_CAND_EMPTY_COLUMN, no row;
+ *   with head_tail, where the main test failed:  pos-17 < first: C3_CAND_HEAD iff pos+15 <= last, the columns before first are zero rows;
+ *        else (pos+17 > last): C3_CAND_TAIL, the columns after last are zero rows.  These windows are not tested for empty columns;
+ *   everything else: C3_CAND_NO_WINDOW, no row.  No candidate yields two windows.
+ * Results: status_host[n_cand] (C3_CAND_*), *n_rows_host = number of kept candidates (MAIN, HEAD, TAIL), y_host rows [0, *n_rows_host) in
+ * candidate order, c3_model_row_size() floats each (decoder columns apply); y_host must hold n_cand rows.  Rows are bit-identical to c3_predict
+ * (c3_predict_depth) on the materialised windows.  The forward pass runs on n_cand windows (the host does not know the count when it
+ * submits; a dropped candidate costs one surplus window); n_cand == 0 launches nothing.
+ * c3_predict_submit_candidates is completed by c3_predict_wait(slot), which writes rows, statuses and *n_rows_host: same ring, lanes and range
+ * guard as c3_predict_submit_region (the slot keeps the selected starts and depths on the device for a re-run on fp32); region, major,
+ * positions and depths may be reused as soon as submit returns.  c3_predict_pileup_candidates = submit + wait on slot 0.
+ * Errors: a full-alignment handle, C3_DTYPE_I8, major not strictly increasing, null buffers, a busy slot.
+ * c3_model_describe reports candidates=, kept=, chunks= of the last completed candidate call. */
+#define C3_CAND_NO_WINDOW 0
+#define C3_CAND_MAIN 1
+#define C3_CAND_EMPTY_COLUMN 2
+#define C3_CAND_HEAD 3
+#define C3_CAND_TAIL 4
+int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
+                                 const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
+                                 uint8_t *status_host, int64_t *n_rows_host, int slot);
+int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
+                                 const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
+                                 uint8_t *status_host, int64_t *n_rows_host);
 /* SURVEY 8f N1 (first slice): the arithmetic of the reference decoder, clair3/CallVariants.py:510-659
  * (possible_outcome_probabilites_from).  For every probability row y_host[b] (24 or 90 floats, as produced by
  * c3_predict) and the gt21 index of its reference base pair ref21_host[b] (0 AA, 4 CC, 7 GG, 9 TT -- reference_gt21 at
