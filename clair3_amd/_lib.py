@@ -25,6 +25,7 @@ EXPORTS = (
     "c3_debug_keep_activations", "c3_debug_tap", "c3_debug_tap_fetch", "c3_profile_enable", "c3_profile_reset", "c3_profile_read",
     "c3_model_set_max_depth", "c3_predict_depth", "c3_predict_submit_depth", "c3_predict_pileup_region_depth", "c3_predict_submit_region",
     "c3_predict_submit_candidates", "c3_predict_pileup_candidates",
+    "c3_predict_submit_rows", "c3_predict_rows", "c3_pack_rows",
 )
 
 
@@ -135,6 +136,10 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
     L.c3_predict_pileup_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    L.c3_predict_submit_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+    L.c3_predict_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.c3_pack_rows.restype = C.c_int64
+    L.c3_pack_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -13,7 +13,11 @@ LIB = os.path.join(LIBDIR, "libc3hip.so")
 SOURCES = ["c3_model.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "c3hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-         "-fgpu-flush-denormals-to-zero" if False else "-fno-gpu-flush-denormals-to-zero"]
+         "-fgpu-flush-denormals-to-zero" if False else "-fno-gpu-flush-denormals-to-zero",
+         # the device code starts on a page of its own.  Without this the kernels sit wherever the code object's symbol tables and notes end,
+         # so ADDING a kernel moves every other one by some multiple of 256 bytes: the same res1a .. res3b code ran 0.3 - 0.4 % slower
+         # after two small kernels had been added (profiles/fa_rows_transport.txt, same box, alternating) and no slower with this
+         "-Xoffload-linker", "-z", "-Xoffload-linker", "separate-code"]
 
 
 def hipcc():

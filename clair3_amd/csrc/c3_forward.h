@@ -484,8 +484,10 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
 // ------------------------------------------------------------------------------------------ both
 // With `depth` (pileup, int32 counts; one per window, device): the reference's rescaling of very deep windows (c3_rescale.h) as a pre-pass
 // into the lane's buffer of sliced windows, then the int32 forms on that buffer -- x (and the region matrix behind `starts`) stays as it came.
+// With `rows` (full alignment; one table entry per window, device): x holds the occupied rows of the windows and the pre-pass of
+// c3_expand.h writes the dense windows of every micro-batch into the lane's buffer in front of the unchanged forward pass.
 static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype, int64_t batch, float *y,
-                          const int32_t *starts = nullptr, const int32_t *depth = nullptr) {
+                          const int32_t *starts = nullptr, const int32_t *depth = nullptr, const ExpandEntry *rows = nullptr) {
     if (!m->loaded) return fail("model has no weights: call c3_model_load first");
     if (batch < 0) return fail("negative batch");
     if (batch == 0) return 0;
@@ -496,6 +498,8 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
     if (depth && (m->kind != C3_KIND_PILEUP || x_dtype != C3_DTYPE_I32)) return fail("internal: depths need int32 pileup counts");
     TRY(ensure_workspace(m, batch));
     if (depth) TRY(ensure_rescale_buf(m));
+    if (rows && (m->kind != C3_KIND_FULL_ALIGNMENT || x_dtype != C3_DTYPE_I8)) return fail("internal: rows need int8 full-alignment windows");
+    if (rows) TRY(ensure_expand_buf(m));
     if (!m->tap_call) TRY(tap_prepare(m, batch));
     const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
     Lane &L = lane(m);
@@ -505,7 +509,16 @@ static int forward_device(c3_model *m, hipStream_t s, const void *x, int x_dtype
         const int32_t *sp = starts ? starts + off : nullptr;
         float *yp = y + off * m->row;
         m->tap_base = m->tap_call_off + off;
-        if (m->kind == C3_KIND_FULL_ALIGNMENT) TRY(run_fa(m, s, (const int8_t *)xp, n, yp));
+        if (m->kind == C3_KIND_FULL_ALIGNMENT && rows) {
+            {
+                ExpandParams ep{(const int8_t *)x, rows + off, L.xe, (int)n, m->positions * m->C, (int)wbytes};
+                ProfScope ps(m, s, "fa.expand", 0.0, 2.0 * (double)n * (double)wbytes);
+                if (ep.row_bytes % 8 == 0) hipLaunchKernelGGL(expand_rows_kernel<8>, dim3((unsigned)n), dim3(kExpandThreads), 0, s, ep);
+                else hipLaunchKernelGGL(expand_rows_kernel<1>, dim3((unsigned)n), dim3(kExpandThreads), 0, s, ep);
+                HIP_TRY(hipGetLastError());
+            }
+            TRY(run_fa(m, s, L.xe, n, yp));
+        } else if (m->kind == C3_KIND_FULL_ALIGNMENT) TRY(run_fa(m, s, (const int8_t *)xp, n, yp));
         else if (x_dtype == C3_DTYPE_I8) TRY(run_pileup_t<int8_t>(m, s, (const int8_t *)xp, n, yp, sp));
         else if (depth) {
             {

@@ -14,6 +14,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -49,13 +50,37 @@ public:
         std::unique_lock<std::mutex> lk(mu_);
         done_.wait(lk, [&] { return left_ == 0; });
     }
+    static constexpr int kHelpers = 3;  // measured against 1, 2, 5 and 7 in round 2: the copy is memory-bound beyond four threads
+    int helpers() const { return kHelpers; }
+    // fn(0) .. fn(parts - 1), split over the helpers and the caller (part 0); returns when all have run.  For staging work that is more
+    // than a memcpy: packing full-alignment windows into the pinned buffer by window ranges (c3_hostring.h)
+    void run(int parts, const std::function<void(int)> &fn) {
+        if (parts <= 1) {
+            if (parts == 1) fn(0);
+            return;
+        }
+        std::lock_guard<std::mutex> one_call(call_mu_);
+        ensure_started();
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            fn_ = &fn, parts_ = parts;
+            next_.store(1, std::memory_order_relaxed);
+            left_ = parts - 1;
+            ++gen_;
+        }
+        cv_.notify_all();
+        fn(0);
+        std::unique_lock<std::mutex> lk(mu_);
+        done_.wait(lk, [&] { return left_ == 0; });
+        fn_ = nullptr;
+    }
 
 private:
     StagePool() = default;
     int ensure_started() {
         if (started_) return (int)threads_.size();
         started_ = true;
-        const int n = 3;  // measured against 1, 2, 5 and 7 in round 2: the copy is memory-bound beyond four threads
+        const int n = kHelpers;
         for (int i = 0; i < n; ++i) {
             threads_.emplace_back([this] { run(); });
             threads_.back().detach();
@@ -76,8 +101,10 @@ private:
                 char *d = dst_;
                 const char *s = src_;
                 const size_t len = off < n_ ? std::min(per_, n_ - off) : 0;
+                const std::function<void(int)> *fn = fn_;
                 lk.unlock();
-                if (len) memcpy(d + off, s + off, len);
+                if (fn) (*fn)(part);
+                else if (len) memcpy(d + off, s + off, len);
                 lk.lock();
                 if (--left_ == 0) done_.notify_one();
             }
@@ -93,6 +120,7 @@ private:
     size_t n_ = 0, per_ = 0;
     int parts_ = 0, left_ = 0;
     std::atomic<int> next_{0};
+    const std::function<void(int)> *fn_ = nullptr;  // run(): the parts' work (nullptr: a copy)
 };
 
 }  // namespace c3

@@ -52,6 +52,44 @@ static int stage_h2d(void *dev, void *pin, const void *src, size_t bytes, hipStr
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ occupied rows of full-alignment windows (c3_expand.h)
+// entry i of a caller's int32 table that may sit at any byte address
+static inline int32_t table_i32(const int32_t *p, int64_t i) {
+    int32_t v;
+    memcpy(&v, (const char *)p + 4 * i, 4);
+    return v;
+}
+// wide ORs over a row; stops at the first 32 bytes that hold a set bit (p may sit at any byte address)
+static inline bool row_is_zero(const uint8_t *p, size_t n) {
+    size_t i = 0;
+    for (; i + 32 <= n; i += 32) {
+        uint64_t a, b, c, d;
+        memcpy(&a, p + i, 8), memcpy(&b, p + i + 8, 8), memcpy(&c, p + i + 16, 8), memcpy(&d, p + i + 24, 8);
+        if ((a | b) | (c | d)) return false;
+    }
+    uint64_t acc = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t a;
+        memcpy(&a, p + i, 8);
+        acc |= a;
+    }
+    for (; i < n; ++i) acc |= p[i];
+    return acc == 0;
+}
+// the run from the first to the last non-zero row of a dense window (interior zero rows stay inside it; an all-zero window: count 0, first
+// 0): scanned from the top and from the bottom, so only zero rows and the two boundary rows are read
+static inline void occupied_run(const uint8_t *w, int depth, size_t row_bytes, int32_t *first, int32_t *count) {
+    int top = 0;
+    while (top < depth && row_is_zero(w + (size_t)top * row_bytes, row_bytes)) ++top;
+    if (top == depth) {
+        *first = 0, *count = 0;
+        return;
+    }
+    int bot = depth - 1;
+    while (row_is_zero(w + (size_t)bot * row_bytes, row_bytes)) --bot;
+    *first = top, *count = bot - top + 1;
+}
+
 // ------------------------------------------------------------------------------------------ candidate selection (c3_select.h)
 static int run_select(c3_model *m, hipStream_t s, const SelectParams &sp) {
     ProfScope ps(m, s, "p.select", 0.0, 4.0 * sp.n_cand * (double)(sp.T * sp.C));
@@ -114,6 +152,11 @@ struct RingInput {
     const int32_t *depth = nullptr;   // per-window depths: windows deeper than 1.5 x max_depth are rescaled on the device (c3_rescale.h)
     bool piece = false;               // a piece of a blocking call: its rescaled windows add to the call's count
     const struct CandInput *cand = nullptr;  // a candidate batch: the starts are worked out on the device (c3_select.h); n_cols = columns of the device image
+    // full alignment: x_host holds the occupied rows of the windows back to back, row_count[b] of them for window b from dense row row_first[b]
+    // on (nullptr: centred, (depth - row_count[b]) / 2); checked by the caller, which also adds the counts up (c3_expand.h)
+    bool rows = false;
+    const int32_t *row_first = nullptr, *row_count = nullptr;
+    int64_t rows_total = 0;
 };
 // candidate positions instead of window starts (c3_predict_submit_candidates): what the host knows of the region before it is staged
 struct CandInput {
@@ -161,7 +204,14 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     m->rescaled = (in && in->piece ? m->rescaled : 0) + n_deep;
     // a batch without a deep window runs exactly what it runs without depths: no pre-pass, no copy
     const int32_t *depth_host = n_deep > 0 ? in->depth : nullptr;
-    const size_t xb = region ? (size_t)in->n_cols * m->C * (x_dtype == C3_DTYPE_I32 ? 4 : 1) : (size_t)(batch * c3_model_window_bytes(m, x_dtype));
+    // occupied rows instead of dense full-alignment windows (c3_expand.h): handed over as such, or -- C3HIP_PACK_ROWS=1 -- packed here while the
+    // dense windows are staged
+    const bool rows_given = in && in->rows;
+    const bool pack = !in && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && x_dtype == C3_DTYPE_I8;
+    const bool rows = rows_given || pack;
+    const size_t row_bytes = (size_t)m->positions * m->C;
+    const size_t xb = region ? (size_t)in->n_cols * m->C * (x_dtype == C3_DTYPE_I32 ? 4 : 1)
+                      : rows_given ? (size_t)in->rows_total * row_bytes : (size_t)(batch * c3_model_window_bytes(m, x_dtype));
     const size_t xb_al = (xb + 255) & ~(size_t)255;
     const size_t sb = region ? (size_t)batch * sizeof(int32_t) : 0, sb_al = (sb + 255) & ~(size_t)255;
     const size_t db = depth_host ? (size_t)batch * sizeof(int32_t) : 0;
@@ -174,7 +224,8 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
     const size_t c_starts = al(c_staged), c_dep = c_starts + sb_al, c_all = c_dep + al(db), c_tiles = c_all + sb_al;
     const size_t n_tiles = (size_t)((batch + kCompactTile - 1) / kCompactTile);
     const size_t c_end = cand ? c_tiles + al(n_tiles * sizeof(uint32_t)) : 0;
-    const size_t xtot = cand ? c_staged : (sb + db ? xb_al + sb_al + db : xb);
+    // (a rows batch: the table behind the rows; a batch packed here may need less than this bound -- settled once it is packed)
+    size_t xtot = cand ? c_staged : rows ? xb_al + (size_t)batch * sizeof(ExpandEntry) : (sb + db ? xb_al + sb_al + db : xb);
     const size_t yb = (size_t)batch * m->row * sizeof(float);
     // ... and its statuses and the count of kept candidates leave behind the rows
     const size_t y_status = al(yb), y_count = y_status + (((size_t)batch + 15) & ~(size_t)15);
@@ -236,15 +287,68 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
             int32_t *dst = static_cast<int32_t *>(sl.pin_x);
             for (size_t i = 0, e = (size_t)in->n_cols * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
         }
-        const bool prebuilt = narrow || laid_out;  // the image is already in the pinned buffer
+        // rows: the table of {source byte offset, first dense row, rows} per window, filled in one pass over the counts -- or, packing here, by
+        // the scan of c3_pack_rows writing every window's run straight into the pinned buffer, split over the staging pool by window ranges:
+        // range k packs back to back from where its first window would start in the dense layout (an 8-byte boundary for an even C), so no
+        // range waits for the count of the one before it and the runs cross PCIe as one transfer per range
+        struct Seg {
+            size_t off, bytes;
+            int64_t rows;
+        } seg[8];
+        int nseg = 0;
+        size_t tab_off = 0;
+        int64_t shipped = 0;
+        if (rows) {
+            std::vector<ExpandEntry> tab((size_t)batch);
+            if (pack) {
+                const size_t wbytes = (size_t)m->depth * row_bytes;
+                nseg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(StagePool::get().helpers() + 1, (int64_t)(xb / ((size_t)512 << 10))), batch));
+                StagePool::get().run(nseg, [&](int k) {
+                    const int64_t b0 = batch * k / nseg, b1 = batch * (k + 1) / nseg;
+                    size_t o = (size_t)b0 * wbytes;
+                    int64_t nr = 0;
+                    for (int64_t b = b0; b < b1; ++b) {
+                        const uint8_t *w = (const uint8_t *)x_host + (size_t)b * wbytes;
+                        int32_t first, count;
+                        occupied_run(w, m->depth, row_bytes, &first, &count);
+                        tab[(size_t)b] = ExpandEntry{(int64_t)o, first, count};
+                        memcpy((char *)sl.pin_x + o, w + (size_t)first * row_bytes, (size_t)count * row_bytes);
+                        o += (size_t)count * row_bytes, nr += count;
+                    }
+                    seg[k] = Seg{(size_t)b0 * wbytes, o - (size_t)b0 * wbytes, nr};
+                });
+                tab_off = nseg == 1 ? al(seg[0].bytes) : xb_al;
+            } else {
+                int64_t o = 0;
+                for (int64_t b = 0; b < batch; ++b) {
+                    const int32_t c = table_i32(in->row_count, b);
+                    tab[(size_t)b] = ExpandEntry{o, in->row_first ? table_i32(in->row_first, b) : (m->depth - c) / 2, c};
+                    o += (int64_t)c * (int64_t)row_bytes;
+                }
+                nseg = 1, seg[0] = Seg{0, xb, in->rows_total};
+                tab_off = xb_al;
+            }
+            for (int k = 0; k < nseg; ++k) shipped += seg[k].rows;
+            memcpy((char *)sl.pin_x + tab_off, tab.data(), (size_t)batch * sizeof(ExpandEntry));
+            xtot = tab_off + (size_t)batch * sizeof(ExpandEntry);
+        }
+        const bool prebuilt = narrow || laid_out || pack;  // the image is already in the pinned buffer
         // the counts through the pinned buffer onto stream st, the starts and depths (already in the pinned buffer) behind them
         auto stage = [&](hipStream_t st) -> int {
+            if (rows) {
+                if (pack) {
+                    for (int k = 0; k < nseg; ++k)
+                        if (seg[k].bytes) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + seg[k].off, (char *)sl.pin_x + seg[k].off, seg[k].bytes, hipMemcpyHostToDevice, st));
+                } else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
+                HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + tab_off, (char *)sl.pin_x + tab_off, xtot - tab_off, hipMemcpyHostToDevice, st));
+                return 0;
+            }
             if (prebuilt) HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, xb, hipMemcpyHostToDevice, st));
             else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
             if (xtot > xb) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + xb_al, (char *)sl.pin_x + xb_al, xtot - xb_al, hipMemcpyHostToDevice, st));
             return 0;
         };
-        if (alone && xtot <= kKernelCopyMax && ytot <= kKernelCopyMax) {
+        if (alone && xtot <= kKernelCopyMax && ytot <= kKernelCopyMax && nseg <= 1) {  // (the copy kernel moves ONE run: rows packed by several ranges take the transfers)
             if (!prebuilt) StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
             hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xtot + 15) / 16,
                                (const uint32_t *)nullptr, (uint32_t *)nullptr);
@@ -261,6 +365,8 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
         }
         sl.dev_starts = region ? (const int32_t *)((char *)sl.dev_x + xb_al) : nullptr;
         sl.dev_depth = depth_host ? (const int32_t *)((char *)sl.dev_x + xb_al + sb_al) : nullptr;
+        sl.dev_rows = rows ? (const ExpandEntry *)((char *)sl.dev_x + tab_off) : nullptr;
+        sl.rows_shipped = shipped;
         if (cand) {  // the selection, on the batch's stream in front of the forward pass; the slot keeps the compacted starts / depths for a re-run
             char *d = (char *)sl.dev_x;
             sl.dev_starts = (const int32_t *)(d + c_starts);
@@ -276,7 +382,7 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
             TRY(run_select(m, L.stream, sp));
         }
         const bool f16 = m->f16_ok;
-        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, sl.dev_starts, sl.dev_depth));
+        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, sl.dev_starts, sl.dev_depth, sl.dev_rows));
         if (y_dev_out && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
             hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, L.stream, y_dev_out, batch * m->row, m->range_flag);
         // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
@@ -288,6 +394,8 @@ static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t 
         HIP_TRY(hipEventRecord(sl.ev_out, L.stream));
         sl.used_f16 = f16;
     }
+    if (batch == 0) sl.rows_shipped = 0;
+    if (!rows) sl.rows_shipped = -1;
     sl.y_dev_out = y_dev_out;
     sl.lane = m->lane_cur;
     sl.y_host = y_host, sl.y_bytes = yb, sl.batch = batch, sl.x_dtype = x_dtype, sl.busy = true;
@@ -306,6 +414,9 @@ int c3_predict_wait(c3_model *m, int slot) {
     HostSlot &sl = m->slot[slot];
     if (!sl.busy) return fail("slot %d has nothing in flight", slot);
     sl.busy = false;
+    // windows that travelled as occupied rows in the call this completes, and their rows (c3_model_describe)
+    if (!m->rows_call) m->rows_windows = m->rows_shipped = 0;
+    if (sl.rows_shipped >= 0) m->rows_windows += sl.batch, m->rows_shipped += sl.rows_shipped;
     if (sl.cand && sl.cand_none) {  // nothing was launched: no candidate has a window
         if (sl.batch > 0) memset(sl.status_host, kCandNoWindow, (size_t)sl.batch);
         *sl.n_rows_host = 0;
@@ -322,7 +433,7 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out, sl.dev_starts, sl.dev_depth);
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out, sl.dev_starts, sl.dev_depth, sl.dev_rows);
             m->tap_call_off = 0;
             TRY(rc);
             HIP_TRY(hipStreamSynchronize(lane(m).stream));
@@ -343,8 +454,9 @@ int c3_predict_wait(c3_model *m, int slot) {
             m->f16_ok = false, m->precision = "fp32-range-guard";
             TRY(use_lane(m, sl.lane));
             m->tap_call_off = sl.tap_off;
-            // (a region batch gathers again, a batch with depths rescales again -- from the staged ORIGINAL counts: nothing has written dev_x)
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y, sl.dev_starts, sl.dev_depth);
+            // (a region batch gathers again, a batch with depths rescales again, a rows batch expands again -- from what was staged: nothing has
+            // written dev_x)
+            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y, sl.dev_starts, sl.dev_depth, sl.dev_rows);
             m->tap_call_off = 0;
             TRY(rc);
             HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, lane(m).stream));
@@ -417,6 +529,7 @@ static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_
         TRY(tap_prepare(m, batch));
         m->tap_call = true;
     }
+    m->rows_windows = m->rows_shipped = 0, m->rows_call = true;  // (C3HIP_PACK_ROWS=1: the pieces' counts add up)
     for (int64_t off = 0; off < batch && rc == 0; ++n_sub) {
         int64_t take = std::min(next, batch - off);
         if (batch - off - take < next / 2 || batch - off - take < chunk / 2) take = batch - off;
@@ -438,6 +551,7 @@ static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_
         const int r = c3_predict_wait(m, (int)(n_done % kRing));
         if (rc == 0) rc = r;
     }
+    m->rows_call = false;
     if (m->tap_call) m->tap_call = false, m->tap_n = rc == 0 ? batch : 0;
     if (!first_error.empty()) g_err = first_error;
     return rc;
@@ -522,6 +636,54 @@ int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_d
     if (batch == 0 && n_cols >= 0) return 0;
     TRY(region_submit(m, "c3_predict_pileup_region_depth", region_host, x_dtype, n_cols, starts_host, batch, depth_host, y_host, 0));
     return c3_predict_wait(m, 0);
+}
+
+// ---- full-alignment windows as their occupied rows (c3_expand.h) ----
+int c3_predict_submit_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, float *y_host,
+                           int slot) {
+    if (!m) return fail("null model");
+    if (m->kind != C3_KIND_FULL_ALIGNMENT)
+        return fail("rows belong to full-alignment windows: a pileup model has no zero rows to restore (c3_predict_submit takes its windows)");
+    if (batch < 0) return fail("negative batch");
+    if (batch > 0 && (!rows_host || !row_count || !y_host)) return fail("null buffer: rows / row_count / y_host");
+    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
+    if (m->slot[slot].busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
+    RingInput in;
+    in.rows = true, in.row_first = row_first, in.row_count = row_count;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int32_t c = table_i32(row_count, b);
+        if (c < 0) return fail("window %lld: negative row_count %d", (long long)b, c);
+        const int32_t first = row_first ? table_i32(row_first, b) : (m->depth - c) / 2;
+        if (first < 0) return fail("window %lld: negative row_first %d", (long long)b, first);
+        if ((int64_t)first + c > m->depth)
+            return fail("window %lld: rows [%d, %lld) reach beyond the depth of %d rows", (long long)b, first, (long long)first + c, m->depth);
+        in.rows_total += c;
+    }
+    return predict_submit(m, rows_host, C3_DTYPE_I8, batch, y_host, slot, nullptr, &in);
+}
+
+int c3_predict_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, float *y_host) {
+    TRY(c3_predict_submit_rows(m, rows_host, row_first, row_count, batch, y_host, 0));
+    return c3_predict_wait(m, 0);
+}
+
+// plain host code (no device): what a caller that holds dense windows does to hand them over as rows
+int64_t c3_pack_rows(int depth, int positions, int channels, const void *x_host, int64_t batch, void *rows_out, int32_t *row_first_out,
+                     int32_t *row_count_out) {
+    if (depth < 1 || positions < 1 || channels < 1) return fail("bad geometry %dx%dx%d", depth, positions, channels), -1;
+    if (batch < 0) return fail("negative batch"), -1;
+    if (batch > 0 && (!x_host || !row_first_out || !row_count_out)) return fail("null buffer: windows / row_first_out / row_count_out"), -1;
+    const size_t row_bytes = (size_t)positions * channels, wbytes = (size_t)depth * row_bytes;
+    int64_t total = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        const uint8_t *w = (const uint8_t *)x_host + (size_t)b * wbytes;
+        int32_t first, count;
+        occupied_run(w, depth, row_bytes, &first, &count);
+        row_first_out[b] = first, row_count_out[b] = count;
+        if (rows_out) memcpy((char *)rows_out + (size_t)total * row_bytes, w + (size_t)first * row_bytes, (size_t)count * row_bytes);
+        total += count;
+    }
+    return total;
 }
 
 // ---- candidate positions instead of window starts (c3_select.h) ----

@@ -7,7 +7,8 @@
 //   c3_forward.h   the launch sequences of the two forward passes (clair3/model.py:130-161 and :377-416)
 //   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait (staging, transfers, range guard), the region
 //                  entries, the entries that take per-window depths (c3_rescale.h: the pre-pass that rescales very deep windows) and the
-//                  candidate entries (c3_select.h: window selection from candidate positions in front of the forward pass)
+//                  candidate entries (c3_select.h: window selection from candidate positions in front of the forward pass), and the rows
+//                  entries of the full-alignment network (c3_expand.h: the pre-pass that restores the zero rows of a window)
 //   c3_comm.h      the gather of a sharded job on RCCL
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
@@ -42,6 +43,7 @@
 #include "c3_lstm_fused.h"
 #include "c3_rescale.h"
 #include "c3_select.h"
+#include "c3_expand.h"
 #include "c3_host.h"
 #include "c3_conv3.h"
 #include "c3_conv3s2.h"
@@ -125,6 +127,10 @@ struct HostSlot {
     // a region batch / a batch with depths keeps its window starts and depths on the device with the slot (behind the counts in dev_x): the
     // range guard's re-run gathers and rescales again from the ORIGINAL counts (c3_rescale.h never writes dev_x)
     const int32_t *dev_starts = nullptr, *dev_depth = nullptr;
+    // a rows batch (c3_expand.h; c3_predict_submit_rows, or C3HIP_PACK_ROWS=1): dev_x holds the occupied rows, and behind them the table the
+    // pre-pass expands them by -- kept, never written, so that the range guard's re-run expands again
+    const ExpandEntry *dev_rows = nullptr;
+    int64_t rows_shipped = -1;  // rows staged for the batch in flight (-1: a dense batch)
     // a candidate batch (c3_select.h; c3_predict_submit_candidates): the statuses and the count of kept candidates leave behind the rows
     // (tail_bytes of dev_y / pin_y from y_bytes rounded up to 256 on: n_cand status bytes, then -- from the next multiple of 16 -- the count)
     bool cand = false;
@@ -155,6 +161,8 @@ struct Lane {
     int64_t last_n = 0;  // windows of the last micro-batch (for debug fetch)
     int32_t *xr = nullptr;  // rescaled sliced int32 windows of a micro-batch that carries depths (c3_rescale.h); allocated on first use
     int64_t xr_cap = 0;     // windows it holds
+    int8_t *xe = nullptr;   // dense int8 windows of a micro-batch that came as occupied rows (c3_expand.h); allocated on first use
+    int64_t xe_cap = 0;     // windows it holds
 };
 constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
 
@@ -247,6 +255,10 @@ struct c3_model {
     int max_depth = 144;   // shared/param_p.py:15 max_depth_dict: 144 on every platform (c3_model_set_max_depth)
     int64_t rescaled = 0;  // windows rescaled in the last call (c3_model_describe)
     int64_t cand_n = 0, cand_kept = 0, cand_chunks = 0;  // of the last candidate call that completed (c3_model_describe)
+    // full-alignment windows as occupied rows (c3_expand.h)
+    bool pack_rows = false;  // env C3HIP_PACK_ROWS=1: c3_predict / c3_predict_submit pack int8 windows while they stage them
+    int64_t rows_windows = 0, rows_shipped = 0;  // windows that travelled as rows in the last completed call, and their rows (c3_model_describe)
+    bool rows_call = false;  // inside a c3_predict that runs its batch as pieces: the two counts add up over the pieces
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
@@ -462,6 +474,8 @@ static void free_workspace(Lane &L) {
     L.cap = 0;
     if (L.xr) (void)hipFree(L.xr);
     L.xr = nullptr, L.xr_cap = 0;
+    if (L.xe) (void)hipFree(L.xe);
+    L.xe = nullptr, L.xe_cap = 0;
 }
 static void free_all_workspaces(c3_model *m) {  // every lane's (geometry change, destruction)
     for (Lane &L : m->lanes) free_workspace(L);
@@ -513,5 +527,18 @@ static int ensure_rescale_buf(c3_model *m) {
     L.xr = nullptr, L.xr_cap = 0;
     HIP_TRY(hipMalloc((void **)&L.xr, std::max<size_t>((size_t)L.cap * m->positions * m->C * sizeof(int32_t), 256)));
     L.xr_cap = L.cap;
+    return 0;
+}
+
+// the active lane's buffer of expanded full-alignment windows (c3_expand.h), as many as its workspace holds (2048 windows x 23.5 KB = 48 MB
+// at most); only a handle that is given rows has one
+static int ensure_expand_buf(c3_model *m) {
+    Lane &L = lane(m);
+    if (L.xe && L.xe_cap >= L.cap) return 0;
+    HIP_TRY(hipDeviceSynchronize());  // (a batch in flight in this lane may still read the smaller one)
+    if (L.xe) (void)hipFree(L.xe);
+    L.xe = nullptr, L.xe_cap = 0;
+    HIP_TRY(hipMalloc((void **)&L.xe, std::max<size_t>((size_t)L.cap * m->depth * m->positions * m->C, 256)));
+    L.xe_cap = L.cap;
     return 0;
 }

@@ -97,6 +97,7 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     if (const char *e = getenv("C3HIP_SPP_FUSED")) m->spp_fused = atoi(e) != 0;
     m->tail_fused = kind == C3_KIND_PILEUP;  // (profiles/r04_e_ab_tail_pileup.txt, r04_e_ab_tail_fa.txt)
     if (const char *e = getenv("C3HIP_HALF_TILES")) m->half_tiles = atoi(e) != 0;
+    if (const char *e = getenv("C3HIP_PACK_ROWS")) m->pack_rows = kind == C3_KIND_FULL_ALIGNMENT && atoi(e) != 0;  // (c3_expand.h; default off)
     // two lanes for the ring (c3_model.h Lane): the kind's default follows the same-box A/B of profiles/r06_i_ab_ring_lanes.txt
     // (one MI355X, alternating: full alignment ring 728 - 732 k -> 768 - 775 k windows/s at B = 256 but 807 - 809 k -> 768 - 778 k at B = 1000; pileup
     // 4.24 M -> 4.32 - 4.33 M at B = 1024): more than one lane, for batches that do not fill the chip by themselves
@@ -278,8 +279,10 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else
-        snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld", m->sharing,
-                 m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch);
+        snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
+                 "precision=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
+                 m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
+                 m->precision, (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
     return 0;
 }
 

@@ -431,3 +431,40 @@ class Clair3_F(_HipModel):
     """Full-alignment network: residual 3x3-conv stack + pyramid pooling + FC heads (clair3/model.py:282-416)."""
     KIND = _lib.KIND_FULL_ALIGNMENT
     DEFAULT_CHANNELS = 8  # shared/param_f.py:24-31 (9 with --enable_dwell_time)
+
+    def _rows_args(self, rows, counts, firsts):
+        """(rows int8 (n_rows, positions, C), counts int32 [B], firsts int32 [B] | None) as the C ABI takes them; the geometry is the handle's"""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        depth, positions = self._geometry or (89, 33)
+        rows = np.ascontiguousarray(rows)
+        if rows.dtype != np.int8 or rows.ndim != 3 or rows.shape[1:] != (positions, self.input_channels):
+            raise _lib.C3Error(f"rows must be (n_rows, {positions}, {self.input_channels}) int8, got {rows.dtype} {rows.shape}")
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if counts.ndim != 1:
+            raise _lib.C3Error(f"counts must be one-dimensional, got shape {counts.shape}")
+        if firsts is not None:
+            firsts = np.ascontiguousarray(firsts, dtype=np.int32)
+            if firsts.shape != counts.shape:
+                raise _lib.C3Error(f"firsts must hold one entry per window: shape {firsts.shape} for {len(counts)} windows")
+        # the library checks every count against the depth; the sum against the rows handed over is checked here, where the array's length is known
+        if (counts >= 0).all() and int(counts.sum(dtype=np.int64)) != rows.shape[0]:
+            raise _lib.C3Error(f"counts add up to {int(counts.sum(dtype=np.int64))} rows, {rows.shape[0]} given")
+        return rows, counts, firsts, np.empty((len(counts), self.row_size), dtype=np.float32)
+
+    def predict_rows(self, rows, counts, firsts=None):
+        """Rows of probabilities for windows handed over as their occupied read rows (c3_predict_rows): ``rows`` holds the rows of all windows
+        back to back, window b owns counts[b] of them; its dense form is zero except rows [first, first + counts[b]) with first =
+        (depth - counts[b]) // 2 -- the padding rule of the reference's generator (clair3/utils.py:113-121) -- or firsts[b] where ``firsts`` is
+        given.  The zero rows are restored on the device: same rows, bit for bit, as predict_numpy(synthetic.pad_fa_rows(rows, counts, firsts))."""
+        rows, counts, firsts, y = self._rows_args(rows, counts, firsts)
+        _lib.check(_lib.lib().c3_predict_rows(self._handle, rows.ctypes.data, None if firsts is None else firsts.ctypes.data, counts.ctypes.data,
+                                              len(counts), y.ctypes.data), "c3_predict_rows")
+        return y
+
+    def submit_rows(self, rows, counts, firsts=None, slot=0):
+        """Asynchronous half of predict_rows (c3_predict_submit_rows); returns a handle for wait()."""
+        rows, counts, firsts, y = self._rows_args(rows, counts, firsts)
+        _lib.check(_lib.lib().c3_predict_submit_rows(self._handle, rows.ctypes.data, None if firsts is None else firsts.ctypes.data,
+                                                     counts.ctypes.data, len(counts), y.ctypes.data, slot), "c3_predict_submit_rows")
+        return slot, y

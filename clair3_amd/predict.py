@@ -101,6 +101,22 @@ def depths_from_alt_info(alt_info_list):
     return out
 
 
+def pack_rows(x):
+    """(rows, firsts, counts) of dense full-alignment windows ``x`` (B, depth, positions, C) int8, as ``Clair3_F.predict_rows(rows, counts,
+    firsts)`` takes them (c3_pack_rows; plain host code, no device): for every window the run from its first to its last non-zero row --
+    interior zero rows stay inside the run, an all-zero window gives count 0 and first 0.  ``x`` is not written."""
+    x = np.ascontiguousarray(x)
+    if x.dtype != np.int8 or x.ndim != 4:
+        raise _lib.C3Error(f"windows must be (B, depth, positions, C) int8, got {x.dtype} {x.shape}")
+    b, depth, positions, channels = x.shape
+    firsts, counts = np.empty(b, dtype=np.int32), np.empty(b, dtype=np.int32)
+    rows = np.empty((b * depth, positions, channels), dtype=np.int8)
+    n = _lib.lib().c3_pack_rows(depth, positions, channels, x.ctypes.data, b, rows.ctypes.data, firsts.ctypes.data, counts.ctypes.data)
+    if n < 0:
+        raise _lib.C3Error(f"c3_pack_rows: {_lib.last_error()}")
+    return rows[:n], firsts, counts
+
+
 def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=False, device=0, chkpnt_fn=None):
     """Model factory block of call_variants_from_cffi (clair3/CallVariantsFromCffi.py:223-248)."""
     if platform != "ont":

@@ -385,6 +385,46 @@ def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, dep
     return x.astype(np.int8)
 
 
+def pad_fa_rows(rows, counts, firsts=None, depth=FA_DEPTH_ONT):
+    """Dense full-alignment windows (B, depth, positions, C) int8 from their occupied rows, in numpy, for tests and callers without a GPU:
+    ``rows`` (n_rows, positions, C) holds the rows of all windows back to back, window b owns counts[b] of them and is zero except rows
+    [first, first + counts[b]).  firsts=None: first = (depth - counts[b]) // 2, what the reference's generator pads by
+    (clair3/utils.py:113-121: prefix = int(padding_depth / 2), the rest behind) and its C producer lays out
+    (src/clair3_full_alignment_dwell.c:139-150); else first = firsts[b]."""
+    rows = np.asarray(rows)
+    counts = np.asarray(counts, dtype=np.int64)
+    if rows.ndim != 3 or counts.ndim != 1:
+        raise ValueError("rows (n_rows, positions, C) and counts (B,) expected")
+    if (counts < 0).any() or (counts > depth).any() or int(counts.sum()) != len(rows):
+        raise ValueError(f"counts must lie in [0, {depth}] and add up to the {len(rows)} rows given")
+    first = (depth - counts) // 2 if firsts is None else np.asarray(firsts, dtype=np.int64)
+    if first.shape != counts.shape or (first < 0).any() or (first + counts > depth).any():
+        raise ValueError(f"every run must lie inside the {depth} rows of a window")
+    x = np.zeros((len(counts), depth) + rows.shape[1:], dtype=rows.dtype)
+    src = np.r_[0, np.cumsum(counts)]
+    for b in range(len(counts)):
+        x[b, first[b]:first[b] + counts[b]] = rows[src[b]:src[b + 1]]
+    return x
+
+
+def pack_fa_rows(x):
+    """The inverse, as c3_pack_rows states it: (rows, firsts int32, counts int32) of dense windows (B, depth, positions, C) -- for every
+    window the run from its first to its last non-zero row (interior zero rows stay inside the run; an all-zero window: count 0, first 0)."""
+    x = np.asarray(x)
+    if x.ndim != 4:
+        raise ValueError("windows (B, depth, positions, C) expected")
+    occupied = (x != 0).any(axis=(2, 3))
+    firsts, counts = np.zeros(len(x), np.int32), np.zeros(len(x), np.int32)
+    parts = []
+    for b in range(len(x)):
+        nz = np.flatnonzero(occupied[b])
+        if len(nz):
+            firsts[b], counts[b] = nz[0], nz[-1] - nz[0] + 1
+            parts.append(x[b, nz[0]:nz[-1] + 1])
+    rows = np.concatenate(parts) if parts else np.zeros((0,) + x.shape[2:], dtype=x.dtype)
+    return rows, firsts, counts
+
+
 def make_windows(kind, batch, seed=0, recipe="realistic", channels=None):
     if kind == PILEUP:
         return make_pileup_windows(batch, seed, recipe, channels=channels or PILEUP_CHANNELS)

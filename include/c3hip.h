@@ -29,6 +29,10 @@
  *   c3_predict_pileup_candidates    the loop that slices a region's pileup into windows, preprocess/CreateTensorPileupFromCffi.py:343-397
  *                                   with __enforce_pileup_chunk_contiguity :180-236 (chunk lookup, offsets, the empty-column test, head /
  *                                   tail padding), followed by the model call: candidate positions in, rows and statuses out.
+ *   c3_predict_rows / _submit_rows  the zero rows of a full-alignment window: the stream format carries the reads' rows only and the generator
+ *                                   pads them to the matrix depth on the host before the model call, clair3/utils.py:113-121 (its C producer
+ *                                   lays the dense matrix out by the same rule, src/clair3_full_alignment_dwell.c:139-150): rows in, padded on
+ *                                   the device.
  *   c3_device_pci_bus_id            where a GPU slot's worker belongs on the host (the reference leaves placement to the OS,
  *                                   clair3/CallVariantsFromCffiGPU.py:138-156).
  *
@@ -240,6 +244,36 @@ int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dty
 int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
                                  const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
                                  uint8_t *status_host, int64_t *n_rows_host);
+/* ---- full-alignment windows as their OCCUPIED ROWS: the zero rows are restored on the device ----
+ * A full-alignment window is depth x positions x C int8, but only the reads that overlap the candidate fill rows.  The reference's stream
+ * format carries just those rows and its generator pads them to the matrix depth on the host before the model call (clair3/utils.py:113-121:
+ * padding_depth = depth - tensor_depth, prefix = int(padding_depth / 2), the rest behind); its C producer lays the dense matrix out by the same
+ * rule (src/clair3_full_alignment_dwell.c:139-150, prefix_padding_depth = padding_depth >> 1).  These entries take the rows and restore the
+ * zero rows on the device, bit for bit what c3_predict computes on the padded windows -- and stage, per window, its rows instead of depth rows.
+ *   rows_host   the occupied rows of all windows, back to back, positions x C int8 bytes each; window b owns row_count[b] rows starting at
+ *               row sum(row_count[0 .. b)).  Full-alignment handles, int8 only
+ *   meaning     dense window b is zero except rows [first, first + row_count[b]), which are window b's rows in order.
+ *               row_first == NULL: first = (depth - row_count[b]) / 2 (integer division) -- the reference's rule;
+ *               row_first != NULL: first = row_first[b], the caller says where the run sits (any dense window can be carried losslessly)
+ *   errors      before anything is queued, the slot left free: a pileup handle, null buffers with batch > 0, row_count[b] < 0, first < 0,
+ *               first + row_count[b] > depth, a busy slot.  row_count[b] == 0 is a legal all-zero window; batch == 0 launches nothing
+ * Same ring, lanes, decoder columns and range guard as c3_predict_submit: the slot keeps the rows and their table on the device, never writes
+ * them, and a re-run on fp32 expands again from them.  rows_host, row_first and row_count may be reused as soon as submit returns.
+ *   c3_predict_submit_rows   completed by c3_predict_wait(slot)
+ *   c3_predict_rows          submit + wait on slot 0
+ *   c3_pack_rows             plain host code (no device, like c3_vcf_rows): for each of `batch` dense windows at x_host the run from its first
+ *                            to its last non-zero row (interior zero rows stay inside the run; an all-zero window: count 0, first 0) copied
+ *                            to rows_out (may be sized for batch x depth rows; NULL: only the counts), row_first_out / row_count_out filled.
+ *                            Returns the number of rows, < 0 on error.  Only zero rows and the two boundary rows are read besides the copy.
+ * C3HIP_PACK_ROWS=1 (read at c3_model_create; default off): c3_predict / c3_predict_submit of a full-alignment handle pack the int8 windows
+ * they are given while they stage them and continue as c3_predict_submit_rows with explicit firsts; rows are bit-identical either way.
+ * c3_model_describe of a full-alignment handle ends on rows_windows=<windows that travelled as rows> rows_shipped=<their rows>
+ * pack_rows=<0|1> for the last completed call. */
+int c3_predict_submit_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch,
+                           float *y_host, int slot);
+int c3_predict_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, float *y_host);
+int64_t c3_pack_rows(int depth, int positions, int channels, const void *x_host, int64_t batch, void *rows_out, int32_t *row_first_out,
+                     int32_t *row_count_out);
 /* SURVEY 8f N1 (first slice): the arithmetic of the reference decoder, clair3/CallVariants.py:510-659
  * (possible_outcome_probabilites_from).  For every probability row y_host[b] (24 or 90 floats, as produced by
  * c3_predict) and the gt21 index of its reference base pair ref21_host[b] (0 AA, 4 CC, 7 GG, 9 TT -- reference_gt21 at
