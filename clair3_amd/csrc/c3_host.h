@@ -27,44 +27,21 @@ public:
         static StagePool *p = new StagePool;  // never destroyed: the helpers may outlive static destruction at exit
         return *p;
     }
-    // memcpy(dst, src, n) split over the helpers and the caller; returns when every byte has been copied
-    void copy(void *dst, const void *src, size_t n) {
-        std::lock_guard<std::mutex> one_call(call_mu_);  // handles on different threads share the pool
-        const int helpers = ensure_started();
-        const size_t kMin = (size_t)512 << 10;  // below 512 KiB per part the hand-off costs more than it saves
-        int parts = (int)std::min<size_t>((size_t)helpers + 1, n / kMin);
-        if (parts <= 1) {
-            memcpy(dst, src, n);
-            return;
-        }
-        const size_t per = ((n / parts) + 4095) & ~(size_t)4095;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            dst_ = (char *)dst, src_ = (const char *)src, n_ = n, per_ = per, parts_ = parts;
-            next_.store(1, std::memory_order_relaxed);  // part 0 is the caller's
-            left_ = parts - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        memcpy(dst, src, std::min(per, n));
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [&] { return left_ == 0; });
-    }
     static constexpr int kHelpers = 3;  // measured against 1, 2, 5 and 7 in round 2: the copy is memory-bound beyond four threads
     int helpers() const { return kHelpers; }
-    // fn(0) .. fn(parts - 1), split over the helpers and the caller (part 0); returns when all have run.  For staging work that is more
-    // than a memcpy: packing full-alignment windows into the pinned buffer by window ranges (c3_hostring.h)
+    // fn(0) .. fn(parts - 1), split over the helpers and the caller (part 0); returns when all have run: the pool's ONE hand-off.  For
+    // staging work that is more than a memcpy: packing full-alignment windows into the pinned buffer by window ranges (c3_hostring.h)
     void run(int parts, const std::function<void(int)> &fn) {
+        std::lock_guard<std::mutex> one_call(call_mu_);  // handles on different threads share the pool
+        ensure_started();
         if (parts <= 1) {
             if (parts == 1) fn(0);
             return;
         }
-        std::lock_guard<std::mutex> one_call(call_mu_);
-        ensure_started();
         {
             std::lock_guard<std::mutex> lk(mu_);
             fn_ = &fn, parts_ = parts;
-            next_.store(1, std::memory_order_relaxed);
+            next_.store(1, std::memory_order_relaxed);  // part 0 is the caller's
             left_ = parts - 1;
             ++gen_;
         }
@@ -73,6 +50,16 @@ public:
         std::unique_lock<std::mutex> lk(mu_);
         done_.wait(lk, [&] { return left_ == 0; });
         fn_ = nullptr;
+    }
+    // memcpy(dst, src, n) split over the helpers and the caller; returns when every byte has been copied
+    void copy(void *dst, const void *src, size_t n) {
+        const size_t kMin = (size_t)512 << 10;  // below 512 KiB per part the hand-off costs more than it saves
+        const int parts = (int)std::max<size_t>(1, std::min<size_t>((size_t)kHelpers + 1, n / kMin));
+        const size_t per = parts > 1 ? ((n / parts) + 4095) & ~(size_t)4095 : n;
+        run(parts, [&](int part) {
+            const size_t off = (size_t)part * per;
+            if (off < n) memcpy((char *)dst + off, (const char *)src + off, std::min(per, n - off));
+        });
     }
 
 private:
@@ -97,14 +84,9 @@ private:
             for (;;) {
                 const int part = next_.fetch_add(1, std::memory_order_relaxed);
                 if (part >= parts_) break;
-                const size_t off = (size_t)part * per_;
-                char *d = dst_;
-                const char *s = src_;
-                const size_t len = off < n_ ? std::min(per_, n_ - off) : 0;
                 const std::function<void(int)> *fn = fn_;
                 lk.unlock();
-                if (fn) (*fn)(part);
-                else if (len) memcpy(d + off, s + off, len);
+                (*fn)(part);
                 lk.lock();
                 if (--left_ == 0) done_.notify_one();
             }
@@ -115,12 +97,9 @@ private:
     std::vector<std::thread> threads_;
     bool started_ = false, stop_ = false;
     unsigned long long gen_ = 0;
-    char *dst_ = nullptr;
-    const char *src_ = nullptr;
-    size_t n_ = 0, per_ = 0;
     int parts_ = 0, left_ = 0;
     std::atomic<int> next_{0};
-    const std::function<void(int)> *fn_ = nullptr;  // run(): the parts' work (nullptr: a copy)
+    const std::function<void(int)> *fn_ = nullptr;  // the parts' work of the call being served
 };
 
 }  // namespace c3

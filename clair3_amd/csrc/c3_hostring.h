@@ -109,7 +109,7 @@ extern "C" {
 
 // Pinned staging memory stays out of forked children (keep_out_of_children, c3_model.h: the staging copies of the 40 groups after
 // eight forks 155 -> 97 ms, profiles/r05_k_host_loop_feeder_not_kept.txt).
-static int ensure_slot(c3_model *m, HostSlot &sl, size_t xb, size_t yb) {
+static int ensure_slot(HostSlot &sl, size_t xb, size_t yb) {
     // host_copy_kernel moves whole 16-byte pieces ((bytes + 15) / 16 of them): every buffer it touches is sized to a multiple of
     // 256 bytes here, for every path (90-column rows of an odd batch, 121-float decoder rows: yb % 16 != 0) -- and to whole pages, so that
     // the pinned halves can be kept out of forked children page by page (keep_out_of_children)
@@ -140,280 +140,343 @@ static int ensure_slot(c3_model *m, HostSlot &sl, size_t xb, size_t yb) {
         HIP_TRY(hipMalloc((void **)&sl.dev_y, yb));
         sl.cap_y = yb;
     }
-    (void)m;
     return 0;
 }
 
-// what a batch of the ring reads besides (or instead of) sliced windows
-struct RingInput {
-    int64_t n_cols = -1;              // >= 0: x_host is ONE region matrix of n_cols columns and window b starts at column starts[b]
-    const int32_t *starts = nullptr;  // (checked against n_cols by the caller)
-    bool narrow = false;              // the region holds int64 / size_t counts: narrowed to int32 on their way into the staging buffer
-    const int32_t *depth = nullptr;   // per-window depths: windows deeper than 1.5 x max_depth are rescaled on the device (c3_rescale.h)
-    bool piece = false;               // a piece of a blocking call: its rescaled windows add to the call's count
-    const struct CandInput *cand = nullptr;  // a candidate batch: the starts are worked out on the device (c3_select.h); n_cols = columns of the device image
-    // full alignment: x_host holds the occupied rows of the windows back to back, row_count[b] of them for window b from dense row row_first[b]
-    // on (nullptr: centred, (depth - row_count[b]) / 2); checked by the caller, which also adds the counts up (c3_expand.h)
-    bool rows = false;
-    const int32_t *row_first = nullptr, *row_count = nullptr;
-    int64_t rows_total = 0;
+// ------------------------------------------------------------------------------------------ what a batch of the ring reads
+enum class InKind {
+    Sliced,      // x: the windows themselves
+    Region,      // x: ONE region matrix of n_cols columns, window b starts at column starts[b] (checked against n_cols by the caller)
+    Candidates,  // x: the region matrix, the starts are worked out on the device (c3_select.h); n_cols = columns of the device image
+    Rows,        // full alignment: x holds the occupied rows of the windows back to back, row_count[b] of them for window b from dense row
+                 // row_first[b] on (nullptr: centred, (depth - row_count[b]) / 2); checked by the caller, which also adds the counts up
+    PackedHere,  // C3HIP_PACK_ROWS=1: sliced int8 full-alignment windows, packed into their occupied rows while they are staged (c3_expand.h)
 };
 // candidate positions instead of window starts (c3_predict_submit_candidates): what the host knows of the region before it is staged
 struct CandInput {
     const int64_t *pos = nullptr;     // [batch]
     bool head_tail = false;           // the device image carries positions - 1 zero columns in front of and behind every chunk
-    int64_t n_cols = 0;               // columns of the caller's matrix
     std::vector<SelectChunk> chunks;  // col: the chunk's first column in the device image
     std::vector<int64_t> src_col;     // ... and in the caller's matrix
     uint8_t *status_host = nullptr;
     int64_t *n_rows_host = nullptr;
 };
-static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out = nullptr,
-                          const RingInput *in = nullptr);
+struct RingInput {
+    InKind kind = InKind::Sliced;
+    const void *x = nullptr;
+    int x_dtype = C3_DTYPE_I8;  // of the STAGED counts
+    int64_t batch = 0;
+    float *y_host = nullptr, *y_dev = nullptr;  // where the rows go: this host, or (c3_predict_submit_dev) the caller's device buffer
+    const int32_t *depth = nullptr;  // per-window depths: windows deeper than 1.5 x max_depth are rescaled on the device (c3_rescale.h)
+    bool piece = false;              // a piece of a blocking call: its rescaled windows add to the call's count
+    int64_t n_cols = 0;                                         // Region / Candidates
+    const int32_t *starts = nullptr;                            // Region
+    bool narrow = false;  // Region / Candidates: x holds int64 / size_t counts, narrowed to int32 on their way into the staging buffer
+    const CandInput *cand = nullptr;                            // Candidates
+    const int32_t *row_first = nullptr, *row_count = nullptr;  // Rows
+    int64_t rows_total = 0;
+};
+static RingInput ring_input(InKind kind, const void *x, int x_dtype, int64_t batch, float *y_host, const int32_t *depth = nullptr, float *y_dev = nullptr) {
+    RingInput in;
+    in.kind = kind, in.x = x, in.x_dtype = x_dtype, in.batch = batch, in.y_host = y_host, in.depth = depth, in.y_dev = y_dev;
+    return in;
+}
+static bool is_rows(InKind k) { return k == InKind::Rows || k == InKind::PackedHere; }
+
+// what every entry of the ring refuses first: a handle or slot that cannot take a batch (c3_predict_wait: that cannot hold one)
+static int ring_ready(const c3_model *m, int slot, bool to_submit = true) {
+    if (!m) return fail("null model");
+    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
+    if (!to_submit) return 0;
+    if (m->slot[slot].busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
+    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ submit, step by step
+// Beside batches in the other lanes: the kernel forms for a shared chip (c3_model.h lane_sharing; rows bit-identical either way) -- when this
+// batch and the largest ones in flight in the other lanes would, on half tiles (two workgroups per 8 windows), ask for more workgroups than
+// the chip has CUs (ring of 1024-window batches: yes; the blocking call's 250 + 750 pieces: no, 252 half-tile workgroups fit side by side).
+// In force from here until submit returns, on any path.
+struct LaneSharing {
+    c3_model *m;
+    LaneSharing(c3_model *m_, int64_t batch, bool beside) : m(m_) {
+        int64_t other[kHostSlots], beside_windows = 0;
+        int no = 0;
+        for (int k = 0; beside && k < kHostSlots; ++k)
+            if (m->slot[k].busy && m->slot[k].batch <= m->lane_max_batch) other[no++] = m->slot[k].batch;
+        std::sort(other, other + no, std::greater<int64_t>());
+        for (int k = 0; k < no && k < m->ring_lanes - 1; ++k) beside_windows += other[k];
+        m->lane_sharing = (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1;
+    }
+    ~LaneSharing() { m->lane_sharing = 1; }
+};
+
+// the depths the batch stages; counts the windows the rule rescales (depth > 0 and depth > 1.5 x max_depth) for c3_model_describe.  A batch
+// without a deep window runs exactly what it runs without depths: no pre-pass, no copy
+static const int32_t *deep_depths(c3_model *m, const RingInput &in) {
+    int64_t n_deep = 0;
+    for (int64_t i = 0; in.depth && i < in.batch; ++i) n_deep += in.depth[i] > 0 && (double)in.depth[i] > 1.5 * (double)m->max_depth;
+    m->rescaled = (in.piece ? m->rescaled : 0) + n_deep;
+    return n_deep > 0 ? in.depth : nullptr;
+}
+
+// THE layout of a staged batch (c3_model.h StagedBatch), for every kind: nothing else computes an offset.  The kernels' alignment
+// assumptions hang on it: sections from multiples of 256 bytes, the 8-byte pieces of expand_rows_kernel, the 16-byte pieces of host_copy_kernel
+static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth) {
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const bool cand = in.kind == InKind::Candidates, region = cand || in.kind == InKind::Region, rows = is_rows(in.kind);
+    const size_t n = (size_t)in.batch, db = with_depth ? n * sizeof(int32_t) : 0;
+    StagedBatch p;
+    p.image.bytes = region ? (size_t)in.n_cols * m->C * (in.x_dtype == C3_DTYPE_I32 ? 4 : 1)
+                    : in.kind == InKind::Rows ? (size_t)in.rows_total * m->positions * m->C : (size_t)(in.batch * c3_model_window_bytes(m, in.x_dtype));
+    if (cand) p.cand_pos.bytes = n * sizeof(int64_t), p.depth_in.bytes = db, p.chunks.bytes = in.cand->chunks.size() * sizeof(SelectChunk);
+    if (cand) p.start_all.bytes = n * sizeof(int32_t), p.tiles.bytes = (size_t)((in.batch + kCompactTile - 1) / kCompactTile) * sizeof(uint32_t);
+    p.starts.bytes = region ? n * sizeof(int32_t) : 0, p.depth.bytes = db;
+    if (rows) p.rows_tab.bytes = n * sizeof(ExpandEntry);  // (a batch packed here may need less than this bound: fill_packed_rows)
+    size_t end = 0;
+    for (Section *s : {&p.image, &p.cand_pos, &p.depth_in, &p.chunks, &p.starts, &p.depth, &p.start_all, &p.tiles, &p.rows_tab})
+        s->off = al(end), end = s->off + s->bytes;
+    // a candidate batch stages up to its chunk table: the arrays behind it are written by the selection kernels
+    p.tail = rows ? p.rows_tab.off : p.cand_pos.off;
+    p.staged = cand ? p.chunks.off + p.chunks.bytes
+               : rows ? end : (p.starts.bytes + p.depth.bytes ? p.depth.off + p.depth.bytes : p.image.bytes);
+    p.x_cap = cand ? end : p.staged;
+    // ... and its statuses and the count of kept candidates leave behind the rows
+    p.y.bytes = n * m->row * sizeof(float);
+    p.status.off = al(p.y.bytes), p.status.bytes = cand ? n : 0;
+    p.kept.off = p.status.off + ((n + 15) & ~(size_t)15), p.kept.bytes = cand ? 16 : 0;
+    p.y_total = cand ? p.kept.off + p.kept.bytes : p.y.bytes;
+    return p;
+}
+
+// ---- fill the pinned buffer: one function per kind.  What is left for the transport: the image either still sits in the caller's memory
+// (src: it passes through the pinned buffer piece by piece, every piece's transfer queued as soon as it is copied, stage_h2d) or is
+// already in the pinned buffer as nrun runs
+struct Filled {
+    const void *src = nullptr;
+    int nrun = 0;
+    struct Run { size_t off, bytes; } run[8];
+    int64_t rows_shipped = 0;
+    void prebuilt(size_t bytes) { nrun = 1, run[0] = Run{0, bytes}; }
+};
+// int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
+// buffer, which is what the reference's PIPE mode feeds the model (CreateTensorPileupFromCffi.py:143-146 -> int32 windows)
+static void narrow_counts(int32_t *dst, const int64_t *src, size_t n) {
+    for (size_t i = 0; i < n; ++i) dst[i] = (int32_t)src[i];
+}
+// the region matrix as ONE image: narrowed here, or left to the transport
+static void fill_region_image(const c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p, Filled &f) {
+    if (!in.narrow) f.src = in.x;
+    else narrow_counts(static_cast<int32_t *>(sl.pin_x), static_cast<const int64_t *>(in.x), (size_t)in.n_cols * m->C), f.prebuilt(p.image.bytes);
+}
+static void fill_sliced(const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
+    if (depth) memcpy(sl.pin<char>(p.depth), depth, p.depth.bytes);
+    f.src = in.x;
+}
+static void fill_region(const c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
+    memcpy(sl.pin<char>(p.starts), in.starts, p.starts.bytes);
+    if (depth) memcpy(sl.pin<char>(p.depth), depth, p.depth.bytes);
+    fill_region_image(m, sl, in, p, f);
+}
+static void fill_candidates(const c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
+    const CandInput &ci = *in.cand;
+    memcpy(sl.pin<char>(p.cand_pos), ci.pos, p.cand_pos.bytes);
+    if (depth) memcpy(sl.pin<char>(p.depth_in), depth, p.depth_in.bytes);
+    memcpy(sl.pin<char>(p.chunks), ci.chunks.data(), p.chunks.bytes);
+    if (!ci.head_tail) return fill_region_image(m, sl, in, p, f);
+    // head / tail windows: the image is laid out in the staging buffer chunk by chunk, positions - 1 zero columns in front of and behind
+    // each (c3_select.h)
+    const size_t colb = (size_t)m->C * sizeof(int32_t), pad = (size_t)(m->positions - 1);
+    for (size_t k = 0; k < ci.chunks.size(); ++k) {
+        const SelectChunk &ch = ci.chunks[k];
+        const size_t n = (size_t)(ch.last - ch.first + 1), c0 = (size_t)ch.col, s0 = (size_t)ci.src_col[k];
+        int32_t *dst = (int32_t *)((char *)sl.pin_x + c0 * colb);
+        memset((char *)sl.pin_x + (c0 - pad) * colb, 0, pad * colb);
+        if (in.narrow) narrow_counts(dst, static_cast<const int64_t *>(in.x) + s0 * m->C, n * m->C);
+        else StagePool::get().copy(dst, (const char *)in.x + s0 * colb, n * colb);
+        memset((char *)sl.pin_x + (c0 + n) * colb, 0, pad * colb);
+    }
+    f.prebuilt(p.image.bytes);
+}
+// rows handed over: the table of {source byte offset, first dense row, rows} per window, filled in one pass over the counts
+static void fill_rows(const c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p, Filled &f) {
+    ExpandEntry *tab = sl.pin<ExpandEntry>(p.rows_tab);
+    int64_t o = 0, row_bytes = (int64_t)m->positions * m->C;
+    for (int64_t b = 0; b < in.batch; ++b) {
+        const int32_t c = table_i32(in.row_count, b);
+        tab[b] = ExpandEntry{o, in.row_first ? table_i32(in.row_first, b) : (m->depth - c) / 2, c};
+        o += (int64_t)c * row_bytes;
+    }
+    f.src = in.x, f.rows_shipped = in.rows_total;
+}
+// rows packed here: the scan of c3_pack_rows writes every window's run straight into the pinned buffer, split over the staging pool by window
+// ranges: range k packs back to back from where its first window would start in the dense layout (an 8-byte boundary for an even C), so no
+// range waits for the count of the one before it and the runs cross PCIe as one transfer per range.  ONE range: the table moves up behind
+// its rows (the plan is settled here)
+static void fill_packed_rows(const c3_model *m, const HostSlot &sl, const RingInput &in, StagedBatch &p, Filled &f) {
+    const size_t row_bytes = (size_t)m->positions * m->C, wbytes = (size_t)m->depth * row_bytes;
+    std::vector<ExpandEntry> tab((size_t)in.batch);
+    int64_t rows[8] = {};
+    const int nrun = f.nrun = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(StagePool::get().helpers() + 1, (int64_t)(p.image.bytes / ((size_t)512 << 10))), in.batch));
+    StagePool::get().run(nrun, [&](int k) {
+        const int64_t b0 = in.batch * k / nrun, b1 = in.batch * (k + 1) / nrun;
+        size_t o = (size_t)b0 * wbytes;
+        for (int64_t b = b0; b < b1; ++b) {
+            const uint8_t *w = (const uint8_t *)in.x + (size_t)b * wbytes;
+            int32_t first, count;
+            occupied_run(w, m->depth, row_bytes, &first, &count);
+            tab[(size_t)b] = ExpandEntry{(int64_t)o, first, count};
+            memcpy((char *)sl.pin_x + o, w + (size_t)first * row_bytes, (size_t)count * row_bytes);
+            o += (size_t)count * row_bytes, rows[k] += count;
+        }
+        f.run[k] = Filled::Run{(size_t)b0 * wbytes, o - (size_t)b0 * wbytes};
+    });
+    for (int k = 0; k < nrun; ++k) f.rows_shipped += rows[k];
+    if (nrun == 1) {  // the layout of these rows handed over
+        RingInput found = in;
+        found.kind = InKind::Rows, found.rows_total = rows[0];
+        p = plan_batch(m, found, false);
+    }
+    memcpy((char *)sl.pin_x + p.rows_tab.off, tab.data(), p.rows_tab.bytes);
+}
+
+// ---- queue the input.  Windows of up to kKernelCopyMax bytes come in through the copy kernel only while no other batch of this handle is
+// in flight: behind a running batch the transfer stream brings the windows in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s),
+// alone the copy kernel is the shorter way (blocking call of one chunk 3.87 M against 3.64 M)
+static int transfer_input(const HostSlot &sl, const StagedBatch &p, const Filled &f, hipStream_t st) {
+    if (f.src) TRY(stage_h2d(sl.dev_x, sl.pin_x, f.src, p.image.bytes, st));
+    for (int k = 0; k < f.nrun; ++k)
+        if (f.run[k].bytes)
+            HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + f.run[k].off, (char *)sl.pin_x + f.run[k].off, f.run[k].bytes, hipMemcpyHostToDevice, st));
+    if (p.staged > p.tail) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + p.tail, (char *)sl.pin_x + p.tail, p.staged - p.tail, hipMemcpyHostToDevice, st));
+    return 0;
+}
+static int queue_input(c3_model *m, const HostSlot &sl, const StagedBatch &p, const Filled &f, bool alone, bool in_lane) {
+    hipStream_t s = lane(m).stream;
+    if (alone && p.staged <= kKernelCopyMax && p.y_total <= kKernelCopyMax && f.nrun <= 1) {  // (the copy kernel moves ONE run: rows packed by several ranges take the transfers)
+        if (f.src) StagePool::get().copy(sl.pin_x, f.src, p.image.bytes);  // (plain memcpy below 1 MB, split over the helpers above)
+        hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, s, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (p.staged + 15) / 16,
+                           (const uint32_t *)nullptr, (uint32_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+    } else if (in_lane) {
+        // a small batch in a lane brings its windows in on the lane's OWN stream: copy, kernels and the copy-out in order in one queue, no
+        // event between two streams -- the batches of the other lanes are what the copy runs under (c3_model.h, the streams)
+        TRY(transfer_input(sl, p, f, s));
+    } else {
+        if (!m->h2d_stream) HIP_TRY(hipStreamCreateWithFlags(&m->h2d_stream, hipStreamNonBlocking));
+        TRY(transfer_input(sl, p, f, m->h2d_stream));
+        HIP_TRY(hipEventRecord(sl.ev_h2d, m->h2d_stream));
+        HIP_TRY(hipStreamWaitEvent(s, sl.ev_h2d, 0));
+    }
+    return 0;
+}
+
+// ---- launch, on the active lane's stream: the selection in front of a candidate batch, the forward pass, the rows on their way out
+static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p) {
+    hipStream_t s = lane(m).stream;
+    if (in.kind == InKind::Candidates) {
+        SelectParams sp;
+        sp.x = (const int32_t *)sl.dev_x, sp.chunks = sl.dev<const SelectChunk>(p.chunks);
+        sp.pos = sl.dev<const int64_t>(p.cand_pos), sp.depth_in = sl.dev<const int32_t>(p.depth_in);
+        sp.status = (uint8_t *)sl.dev_y + p.status.off, sp.start_all = sl.dev<int32_t>(p.start_all), sp.starts = sl.dev<int32_t>(p.starts);
+        sp.depth = sl.dev<int32_t>(p.depth), sp.block_kept = sl.dev<uint32_t>(p.tiles), sp.n_rows = (uint32_t *)((char *)sl.dev_y + p.kept.off);
+        sp.n_cand = (int)in.batch, sp.n_chunks = (int)in.cand->chunks.size(), sp.C = m->C, sp.T = m->positions, sp.head_tail = in.cand->head_tail;
+        sp.img_cols = in.n_cols;
+        TRY(run_select(m, s, sp));
+    }
+    const bool f16 = m->f16_ok;
+    TRY(forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, sl.dev<const int32_t>(p.starts),
+                       sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
+    if (in.y_dev && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
+        hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, in.y_dev, in.batch * m->row, m->range_flag);
+    // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
+    // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
+    // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
+    hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
+                       in.y_dev ? 0 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sl.ev_out, s));
+    sl.used_f16 = f16;
+    return 0;
+}
+
+// ---- record: the slot becomes busy, with everything c3_predict_wait needs (launched: false -- a candidate batch with nothing to launch)
+static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p, int64_t rows_shipped, bool launched = true) {
+    sl.plan = p, sl.batch = in.batch, sl.x_dtype = in.x_dtype, sl.y_host = in.y_host, sl.y_dev_out = in.y_dev;
+    sl.lane = m->lane_cur, sl.tap_off = m->tap_call_off, sl.rows_shipped = rows_shipped;
+    sl.cand = in.cand != nullptr, sl.cand_none = !launched;
+    if (in.cand) sl.status_host = in.cand->status_host, sl.n_rows_host = in.cand->n_rows_host, sl.n_chunks = (int64_t)in.cand->chunks.size();
+    sl.busy = true;
+}
+
+static int predict_submit(c3_model *m, RingInput in, int slot) {
+    TRY(ring_ready(m, slot));
+    if (in.batch < 0) return fail("negative batch");
+    if (in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev))) return fail("null buffer");
+    HIP_TRY(hipSetDevice(m->device));
+    if (in.kind == InKind::Sliced && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && in.x_dtype == C3_DTYPE_I8) in.kind = InKind::PackedHere;
+    HostSlot &sl = m->slot[slot];
+    // A small batch runs in the next lane (c3_model.h Lane): its own workspace and kernel stream, so that it overlaps the batches before it
+    // on the chip; keep mode and profiling stay in one lane -- and so does a batch that fills the chip by itself: two of those side by side
+    // only get in each other's way (same-box A/B, profiles/r06_i_ab_ring_lanes.txt: full alignment ring +5.5 % at B = 256, -4 % at B = 1000).
+    // Lanes are dealt in the ORDER of the submits, not by slot number: three slots on two lanes (the pileup network) would put two of every
+    // three batches behind each other in lane 0 (profiles/r06_n_ab_lane_sharing.txt)
+    const bool in_lane = m->ring_lanes > 1 && in.batch <= m->lane_max_batch && !m->keep && !m->prof;
+    TRY(use_lane(m, in_lane ? (int)(m->lane_next++ % (unsigned)m->ring_lanes) : 0));
+    bool alone = true;
+    for (int k = 0; k < kHostSlots; ++k) alone &= !m->slot[k].busy;
+    const LaneSharing shared_chip_forms(m, in.batch, in_lane && !alone);
+    const int32_t *depth = deep_depths(m, in);
+    StagedBatch p = plan_batch(m, in, depth != nullptr);
+    Filled f;
+    if (in.batch > 0) {
+        // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
+        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? 0 : p.y_total));  // (rows that stay on the device need no slot buffers)
+        switch (in.kind) {
+        case InKind::Sliced: fill_sliced(sl, in, p, depth, f); break;
+        case InKind::Region: fill_region(m, sl, in, p, depth, f); break;
+        case InKind::Candidates: fill_candidates(m, sl, in, p, depth, f); break;
+        case InKind::Rows: fill_rows(m, sl, in, p, f); break;
+        case InKind::PackedHere: fill_packed_rows(m, sl, in, p, f); break;
+        }
+        TRY(queue_input(m, sl, p, f, alone, in_lane));
+        TRY(launch_batch(m, sl, in, p));
+    }
+    record_batch(m, sl, in, p, is_rows(in.kind) ? f.rows_shipped : -1);
+    return 0;
+}
+
 int c3_predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot) {
-    return predict_submit(m, x_host, x_dtype, batch, y_host, slot);
+    return predict_submit(m, ring_input(InKind::Sliced, x_host, x_dtype, batch, y_host), slot);
 }
 // the ring with the rows LEFT ON THE DEVICE (a rank of a sharded job: its rows go to the RCCL gather, not to this host): the
 // forward pass writes them straight into the caller's device buffer, only the range flag crosses PCIe
 int c3_predict_submit_dev(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_dev, int slot) {
     if (batch > 0 && !y_dev) return fail("null device buffer");
-    return predict_submit(m, x_host, x_dtype, batch, nullptr, slot, y_dev);
-}
-static int predict_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host, int slot, float *y_dev_out, const RingInput *in) {
-    if (!m) return fail("null model");
-    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
-    if (batch < 0) return fail("negative batch");
-    if (batch > 0 && (!x_host || (!y_host && !y_dev_out))) return fail("null buffer");
-    HostSlot &sl = m->slot[slot];
-    if (sl.busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
-    HIP_TRY(hipSetDevice(m->device));
-    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
-    // a small batch runs in the next lane (c3_model.h Lane): its own workspace and kernel stream, so that it overlaps the batches before it
-    // on the chip; keep mode and profiling stay in one lane -- and so does a batch that fills the chip by itself: two of those side by side
-    // only get in each other's way (same-box A/B, profiles/r06_i_ab_ring_lanes.txt: full alignment ring +5.5 % at B = 256, -4 % at B = 1000)
-    const bool in_lane = m->ring_lanes > 1 && batch <= m->lane_max_batch && !m->keep && !m->prof;
-    // lanes are dealt in the ORDER of the submits, not by slot number: three slots on two lanes (the pileup network) would put two of every
-    // three batches behind each other in lane 0 (profiles/r06_n_ab_lane_sharing.txt)
-    TRY(use_lane(m, in_lane ? (int)(m->lane_next++ % (unsigned)m->ring_lanes) : 0));
-    Lane &L = lane(m);
-    // the staged input: the windows (or the region matrix), then -- each from a multiple of 256 bytes -- the window starts and the depths
-    const bool region = in && in->n_cols >= 0;
-    int64_t n_deep = 0;  // windows the rule rescales: depth > 0 and depth > 1.5 x max_depth
-    if (in && in->depth)
-        for (int64_t i = 0; i < batch; ++i) n_deep += in->depth[i] > 0 && (double)in->depth[i] > 1.5 * (double)m->max_depth;
-    m->rescaled = (in && in->piece ? m->rescaled : 0) + n_deep;
-    // a batch without a deep window runs exactly what it runs without depths: no pre-pass, no copy
-    const int32_t *depth_host = n_deep > 0 ? in->depth : nullptr;
-    // occupied rows instead of dense full-alignment windows (c3_expand.h): handed over as such, or -- C3HIP_PACK_ROWS=1 -- packed here while the
-    // dense windows are staged
-    const bool rows_given = in && in->rows;
-    const bool pack = !in && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && x_dtype == C3_DTYPE_I8;
-    const bool rows = rows_given || pack;
-    const size_t row_bytes = (size_t)m->positions * m->C;
-    const size_t xb = region ? (size_t)in->n_cols * m->C * (x_dtype == C3_DTYPE_I32 ? 4 : 1)
-                      : rows_given ? (size_t)in->rows_total * row_bytes : (size_t)(batch * c3_model_window_bytes(m, x_dtype));
-    const size_t xb_al = (xb + 255) & ~(size_t)255;
-    const size_t sb = region ? (size_t)batch * sizeof(int32_t) : 0, sb_al = (sb + 255) & ~(size_t)255;
-    const size_t db = depth_host ? (size_t)batch * sizeof(int32_t) : 0;
-    const CandInput *cand = in ? in->cand : nullptr;
-    // a candidate batch stages, behind the image, the positions, the depths and the chunk table; the arrays the selection kernels write
-    // (compacted starts and depths, every candidate's start, the tiles' counts) follow and are never staged
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t c_pos = xb_al, c_din = c_pos + al((size_t)batch * sizeof(int64_t)), c_chk = c_din + al(db);
-    const size_t c_staged = cand ? c_chk + cand->chunks.size() * sizeof(SelectChunk) : 0;
-    const size_t c_starts = al(c_staged), c_dep = c_starts + sb_al, c_all = c_dep + al(db), c_tiles = c_all + sb_al;
-    const size_t n_tiles = (size_t)((batch + kCompactTile - 1) / kCompactTile);
-    const size_t c_end = cand ? c_tiles + al(n_tiles * sizeof(uint32_t)) : 0;
-    // (a rows batch: the table behind the rows; a batch packed here may need less than this bound -- settled once it is packed)
-    size_t xtot = cand ? c_staged : rows ? xb_al + (size_t)batch * sizeof(ExpandEntry) : (sb + db ? xb_al + sb_al + db : xb);
-    const size_t yb = (size_t)batch * m->row * sizeof(float);
-    // ... and its statuses and the count of kept candidates leave behind the rows
-    const size_t y_status = al(yb), y_count = y_status + (((size_t)batch + 15) & ~(size_t)15);
-    const size_t ytot = cand ? y_count + 16 : yb;
-    // windows of up to kKernelCopyMax bytes come in through the copy kernel only while no other batch of this handle is in flight: behind a
-    // running batch the transfer stream brings the windows in under its kernels (pileup ring 4.22 M -> 4.37 M windows/s), alone the copy
-    // kernel is the shorter way (blocking call of one chunk 3.87 M against 3.64 M)
-    bool alone = true;
-    for (int k = 0; k < kHostSlots; ++k) alone &= !m->slot[k].busy;
-    // beside batches in the other lanes: the kernel forms for a shared chip (c3_model.h lane_sharing; rows bit-identical either way) -- when this
-    // batch and the largest ones in flight in the other lanes would, on half tiles (two workgroups per 8 windows), ask for more workgroups than
-    // the chip has CUs (ring of 1024-window batches: yes; the blocking call's 250 + 750 pieces: no, 252 half-tile workgroups fit side by side)
-    int64_t beside_windows = 0;
-    if (in_lane && !alone) {
-        int64_t other[kHostSlots];
-        int no = 0;
-        for (int k = 0; k < kHostSlots; ++k)
-            if (m->slot[k].busy && m->slot[k].batch <= m->lane_max_batch) other[no++] = m->slot[k].batch;
-        std::sort(other, other + no, std::greater<int64_t>());
-        for (int k = 0; k < no && k < m->ring_lanes - 1; ++k) beside_windows += other[k];
-    }
-    struct LaneSharing {
-        c3_model *m;
-        LaneSharing(c3_model *m_, int v) : m(m_) { m->lane_sharing = v; }
-        ~LaneSharing() { m->lane_sharing = 1; }
-    } lane_sharing(m, (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1);
-    if (batch > 0) {
-        // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(m, sl, cand ? c_end : xtot, y_dev_out ? 0 : ytot));  // (rows that stay on the device need no slot buffers)
-        if (cand) {
-            memcpy((char *)sl.pin_x + c_pos, cand->pos, (size_t)batch * sizeof(int64_t));
-            if (depth_host) memcpy((char *)sl.pin_x + c_din, depth_host, db);
-            memcpy((char *)sl.pin_x + c_chk, cand->chunks.data(), cand->chunks.size() * sizeof(SelectChunk));
-        } else {
-            if (region) memcpy((char *)sl.pin_x + xb_al, in->starts, sb);
-            if (depth_host) memcpy((char *)sl.pin_x + xb_al + sb_al, depth_host, db);
-        }
-        // int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
-        // buffer, which is what the reference's PIPE mode feeds the model (CreateTensorPileupFromCffi.py:143-146 -> int32 windows)
-        const bool narrow = region && in->narrow;
-        // a candidate batch with head / tail windows: the image is laid out in the staging buffer chunk by chunk, positions - 1 zero
-        // columns in front of and behind each (c3_select.h)
-        const bool laid_out = cand && cand->head_tail;
-        if (laid_out) {
-            const size_t colb = (size_t)m->C * sizeof(int32_t), pad = (size_t)(m->positions - 1);
-            for (size_t k = 0; k < cand->chunks.size(); ++k) {
-                const SelectChunk &ch = cand->chunks[k];
-                const size_t n = (size_t)(ch.last - ch.first + 1), c0 = (size_t)ch.col, s0 = (size_t)cand->src_col[k];
-                int32_t *dst = (int32_t *)((char *)sl.pin_x + c0 * colb);
-                memset((char *)sl.pin_x + (c0 - pad) * colb, 0, pad * colb);
-                if (narrow) {
-                    const int64_t *src = static_cast<const int64_t *>(x_host) + s0 * m->C;
-                    for (size_t i = 0, e = n * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
-                } else StagePool::get().copy(dst, (const char *)x_host + s0 * colb, n * colb);
-                memset((char *)sl.pin_x + (c0 + n) * colb, 0, pad * colb);
-            }
-        } else if (narrow) {
-            const int64_t *src = static_cast<const int64_t *>(x_host);
-            int32_t *dst = static_cast<int32_t *>(sl.pin_x);
-            for (size_t i = 0, e = (size_t)in->n_cols * m->C; i < e; ++i) dst[i] = (int32_t)src[i];
-        }
-        // rows: the table of {source byte offset, first dense row, rows} per window, filled in one pass over the counts -- or, packing here, by
-        // the scan of c3_pack_rows writing every window's run straight into the pinned buffer, split over the staging pool by window ranges:
-        // range k packs back to back from where its first window would start in the dense layout (an 8-byte boundary for an even C), so no
-        // range waits for the count of the one before it and the runs cross PCIe as one transfer per range
-        struct Seg {
-            size_t off, bytes;
-            int64_t rows;
-        } seg[8];
-        int nseg = 0;
-        size_t tab_off = 0;
-        int64_t shipped = 0;
-        if (rows) {
-            std::vector<ExpandEntry> tab((size_t)batch);
-            if (pack) {
-                const size_t wbytes = (size_t)m->depth * row_bytes;
-                nseg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(StagePool::get().helpers() + 1, (int64_t)(xb / ((size_t)512 << 10))), batch));
-                StagePool::get().run(nseg, [&](int k) {
-                    const int64_t b0 = batch * k / nseg, b1 = batch * (k + 1) / nseg;
-                    size_t o = (size_t)b0 * wbytes;
-                    int64_t nr = 0;
-                    for (int64_t b = b0; b < b1; ++b) {
-                        const uint8_t *w = (const uint8_t *)x_host + (size_t)b * wbytes;
-                        int32_t first, count;
-                        occupied_run(w, m->depth, row_bytes, &first, &count);
-                        tab[(size_t)b] = ExpandEntry{(int64_t)o, first, count};
-                        memcpy((char *)sl.pin_x + o, w + (size_t)first * row_bytes, (size_t)count * row_bytes);
-                        o += (size_t)count * row_bytes, nr += count;
-                    }
-                    seg[k] = Seg{(size_t)b0 * wbytes, o - (size_t)b0 * wbytes, nr};
-                });
-                tab_off = nseg == 1 ? al(seg[0].bytes) : xb_al;
-            } else {
-                int64_t o = 0;
-                for (int64_t b = 0; b < batch; ++b) {
-                    const int32_t c = table_i32(in->row_count, b);
-                    tab[(size_t)b] = ExpandEntry{o, in->row_first ? table_i32(in->row_first, b) : (m->depth - c) / 2, c};
-                    o += (int64_t)c * (int64_t)row_bytes;
-                }
-                nseg = 1, seg[0] = Seg{0, xb, in->rows_total};
-                tab_off = xb_al;
-            }
-            for (int k = 0; k < nseg; ++k) shipped += seg[k].rows;
-            memcpy((char *)sl.pin_x + tab_off, tab.data(), (size_t)batch * sizeof(ExpandEntry));
-            xtot = tab_off + (size_t)batch * sizeof(ExpandEntry);
-        }
-        const bool prebuilt = narrow || laid_out || pack;  // the image is already in the pinned buffer
-        // the counts through the pinned buffer onto stream st, the starts and depths (already in the pinned buffer) behind them
-        auto stage = [&](hipStream_t st) -> int {
-            if (rows) {
-                if (pack) {
-                    for (int k = 0; k < nseg; ++k)
-                        if (seg[k].bytes) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + seg[k].off, (char *)sl.pin_x + seg[k].off, seg[k].bytes, hipMemcpyHostToDevice, st));
-                } else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
-                HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + tab_off, (char *)sl.pin_x + tab_off, xtot - tab_off, hipMemcpyHostToDevice, st));
-                return 0;
-            }
-            if (prebuilt) HIP_TRY(hipMemcpyAsync(sl.dev_x, sl.pin_x, xb, hipMemcpyHostToDevice, st));
-            else TRY(stage_h2d(sl.dev_x, sl.pin_x, x_host, xb, st));
-            if (xtot > xb) HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + xb_al, (char *)sl.pin_x + xb_al, xtot - xb_al, hipMemcpyHostToDevice, st));
-            return 0;
-        };
-        if (alone && xtot <= kKernelCopyMax && ytot <= kKernelCopyMax && nseg <= 1) {  // (the copy kernel moves ONE run: rows packed by several ranges take the transfers)
-            if (!prebuilt) StagePool::get().copy(sl.pin_x, x_host, xb);  // (plain memcpy below 1 MB, split over the helpers above)
-            hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, L.stream, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (xtot + 15) / 16,
-                               (const uint32_t *)nullptr, (uint32_t *)nullptr);
-            HIP_TRY(hipGetLastError());
-        } else if (in_lane) {
-            // a small batch in a lane brings its windows in on the lane's OWN stream: copy, kernels and the copy-out in order in one queue, no
-            // event between two streams -- the batches of the other lanes are what the copy runs under (c3_model.h, the streams)
-            TRY(stage(L.stream));
-        } else {
-            if (!m->h2d_stream) HIP_TRY(hipStreamCreateWithFlags(&m->h2d_stream, hipStreamNonBlocking));
-            TRY(stage(m->h2d_stream));
-            HIP_TRY(hipEventRecord(sl.ev_h2d, m->h2d_stream));
-            HIP_TRY(hipStreamWaitEvent(L.stream, sl.ev_h2d, 0));
-        }
-        sl.dev_starts = region ? (const int32_t *)((char *)sl.dev_x + xb_al) : nullptr;
-        sl.dev_depth = depth_host ? (const int32_t *)((char *)sl.dev_x + xb_al + sb_al) : nullptr;
-        sl.dev_rows = rows ? (const ExpandEntry *)((char *)sl.dev_x + tab_off) : nullptr;
-        sl.rows_shipped = shipped;
-        if (cand) {  // the selection, on the batch's stream in front of the forward pass; the slot keeps the compacted starts / depths for a re-run
-            char *d = (char *)sl.dev_x;
-            sl.dev_starts = (const int32_t *)(d + c_starts);
-            sl.dev_depth = depth_host ? (const int32_t *)(d + c_dep) : nullptr;
-            SelectParams sp;
-            sp.x = (const int32_t *)d, sp.chunks = (const SelectChunk *)(d + c_chk);
-            sp.pos = (const int64_t *)(d + c_pos), sp.depth_in = depth_host ? (const int32_t *)(d + c_din) : nullptr;
-            sp.status = (uint8_t *)sl.dev_y + y_status, sp.start_all = (int32_t *)(d + c_all), sp.starts = (int32_t *)(d + c_starts);
-            sp.depth = depth_host ? (int32_t *)(d + c_dep) : nullptr, sp.block_kept = (uint32_t *)(d + c_tiles);
-            sp.n_rows = (uint32_t *)((char *)sl.dev_y + y_count);
-            sp.n_cand = (int)batch, sp.n_chunks = (int)cand->chunks.size(), sp.C = m->C, sp.T = m->positions, sp.head_tail = cand->head_tail;
-            sp.img_cols = in->n_cols;
-            TRY(run_select(m, L.stream, sp));
-        }
-        const bool f16 = m->f16_ok;
-        TRY(forward_device(m, L.stream, sl.dev_x, x_dtype, batch, y_dev_out ? y_dev_out : sl.dev_y, sl.dev_starts, sl.dev_depth, sl.dev_rows));
-        if (y_dev_out && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
-            hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((batch * m->row + 255) / 256)), dim3(256), 0, L.stream, y_dev_out, batch * m->row, m->range_flag);
-        // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
-        // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
-        // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
-        hipLaunchKernelGGL(host_copy_kernel, dim3(y_dev_out ? 1 : rows_out_grid(ytot)), dim3(256), 0, L.stream, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                           y_dev_out ? 0 : (ytot + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(sl.ev_out, L.stream));
-        sl.used_f16 = f16;
-    }
-    if (batch == 0) sl.rows_shipped = 0;
-    if (!rows) sl.rows_shipped = -1;
-    sl.y_dev_out = y_dev_out;
-    sl.lane = m->lane_cur;
-    sl.y_host = y_host, sl.y_bytes = yb, sl.batch = batch, sl.x_dtype = x_dtype, sl.busy = true;
-    sl.tap_off = m->tap_call_off;
-    sl.cand = cand != nullptr, sl.cand_none = false;
-    if (cand) {
-        sl.status_host = cand->status_host, sl.n_rows_host = cand->n_rows_host, sl.tail_bytes = ytot - y_status;
-        sl.pin_depth = depth_host ? (const int32_t *)((char *)sl.pin_x + c_din) : nullptr, sl.n_chunks = (int64_t)cand->chunks.size();
-    }
-    return 0;
+    return predict_submit(m, ring_input(InKind::Sliced, x_host, x_dtype, batch, nullptr, nullptr, y_dev), slot);
 }
 
+// ------------------------------------------------------------------------------------------ the range guard
+// Safety net of the fp16x3 products: an activation beyond the fp16 range (|x| >= 65504; never seen) surfaces as inf / NaN
+// rows or as the range flag (sticky: an overflow in any earlier fp16x3 batch also lands here, which only costs a re-run).  This handle
+// continues on fp32 matrix instructions, and the batch runs again on stream s (tap_off: its first window in a c3_predict call of pieces)
+static int range_guard_rerun(c3_model *m, hipStream_t s, const void *x_dev, int x_dtype, int64_t batch, float *y_dev, int64_t tap_off = 0,
+                             const int32_t *starts = nullptr, const int32_t *depth = nullptr, const ExpandEntry *rows = nullptr) {
+    if (m->f16_ok)
+        fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
+    m->f16_ok = false, m->precision = "fp32-range-guard";
+    m->tap_call_off = tap_off;
+    const int rc = forward_device(m, s, x_dev, x_dtype, batch, y_dev, starts, depth, rows);
+    m->tap_call_off = 0;
+    return rc;
+}
 int c3_predict_wait(c3_model *m, int slot) {
-    if (!m) return fail("null model");
-    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
+    TRY(ring_ready(m, slot, false));
     HostSlot &sl = m->slot[slot];
     if (!sl.busy) return fail("slot %d has nothing in flight", slot);
     sl.busy = false;
+    const StagedBatch &p = sl.plan;
     // windows that travelled as occupied rows in the call this completes, and their rows (c3_model_describe)
     if (!m->rows_call) m->rows_windows = m->rows_shipped = 0;
     if (sl.rows_shipped >= 0) m->rows_windows += sl.batch, m->rows_shipped += sl.rows_shipped;
@@ -424,63 +487,41 @@ int c3_predict_wait(c3_model *m, int slot) {
         sl.cand = false;
         return 0;
     }
-    if (sl.y_bytes == 0) return 0;
+    if (p.y.bytes == 0) return 0;
     HIP_TRY(hipEventSynchronize(sl.ev_out));
-    if (sl.y_dev_out) {  // rows stayed on the device: the flag (range bit + the device-side scan for non-finite rows) is all there is to read
-        if (sl.used_f16 && *sl.pin_flag != 0) {
-            if (m->f16_ok)
-                fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
-            m->f16_ok = false, m->precision = "fp32-range-guard";
-            TRY(use_lane(m, sl.lane));
-            m->tap_call_off = sl.tap_off;
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out, sl.dev_starts, sl.dev_depth, sl.dev_rows);
-            m->tap_call_off = 0;
-            TRY(rc);
-            HIP_TRY(hipStreamSynchronize(lane(m).stream));
-        }
-        return 0;
-    }
-    if (sl.used_f16) {
-        // Safety net of the fp16x3 products, per batch: what matters is how THIS slot's rows were computed, not what the
-        // handle does now (another slot's wait may have switched it to fp32 while this batch was in flight).  An
-        // activation beyond the fp16 range (|x| >= 65504; never seen) surfaces as inf / NaN rows or as the
-        // range flag (sticky: an overflow in any earlier fp16x3 batch also lands here, which only costs a re-run).
+    // per batch: what matters is how THIS slot's rows were computed, not what the handle does now (another slot's wait may have switched it
+    // to fp32 while this batch was in flight).  Rows that stayed on the device were scanned there: the flag is all there is to read
+    bool bad = sl.used_f16 && *sl.pin_flag != 0;  // a conv stage produced a value near the fp16 range (kF16Range), or the device scan found a non-finite row
+    if (sl.used_f16 && !sl.y_dev_out) {
         const uint32_t *u = reinterpret_cast<const uint32_t *>(sl.pin_y);
-        bool bad = *sl.pin_flag != 0;  // a conv stage produced a value near the fp16 range (kF16Range): its consumers may have overflowed
-        for (size_t i = 0, n = sl.y_bytes / 4; i < n; ++i) bad |= (u[i] & 0x7f800000u) == 0x7f800000u;
-        if (bad) {
-            if (m->f16_ok)
-                fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
-            m->f16_ok = false, m->precision = "fp32-range-guard";
-            TRY(use_lane(m, sl.lane));
-            m->tap_call_off = sl.tap_off;
-            // (a region batch gathers again, a batch with depths rescales again, a rows batch expands again -- from what was staged: nothing has
-            // written dev_x)
-            const int rc = forward_device(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.dev_y, sl.dev_starts, sl.dev_depth, sl.dev_rows);
-            m->tap_call_off = 0;
-            TRY(rc);
-            HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, sl.y_bytes, hipMemcpyDeviceToHost, lane(m).stream));
-            HIP_TRY(hipStreamSynchronize(lane(m).stream));
-        }
+        for (size_t i = 0, n = p.y.bytes / 4; i < n; ++i) bad |= (u[i] & 0x7f800000u) == 0x7f800000u;
     }
+    if (bad) {  // in the batch's lane, from what was staged (a region batch gathers again, a batch with depths rescales again, a rows batch expands again: nothing has written dev_x)
+        TRY(use_lane(m, sl.lane));
+        TRY(range_guard_rerun(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sl.tap_off,
+                              sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
+        if (!sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
+        HIP_TRY(hipStreamSynchronize(lane(m).stream));
+    }
+    if (sl.y_dev_out) return 0;
     if (sl.cand) {  // rows [0, kept) are the result; the rest belong to the surplus windows of dropped candidates
-        const char *tail = (const char *)sl.pin_y + ((sl.y_bytes + 255) & ~(size_t)255);
-        const int64_t kept = (int64_t)*(const uint32_t *)(tail + sl.tail_bytes - 16);
+        const int64_t kept = (int64_t)*(const uint32_t *)((const char *)sl.pin_y + p.kept.off);
         if (kept < 0 || kept > sl.batch) return fail("internal: %lld of %lld candidates kept", (long long)kept, (long long)sl.batch);
-        memcpy(sl.status_host, tail, (size_t)sl.batch);
+        memcpy(sl.status_host, (const char *)sl.pin_y + p.status.off, (size_t)sl.batch);
         memcpy(sl.y_host, sl.pin_y, (size_t)kept * m->row * sizeof(float));
         *sl.n_rows_host = kept;
+        // the count of rescaled windows among the kept, from the candidates' depths as staged (c3_model_describe)
         int64_t deep = 0;
-        if (sl.pin_depth)
+        if (const int32_t *d = sl.pin<const int32_t>(p.depth_in))
             for (int64_t i = 0; i < sl.batch; ++i) {
                 const uint8_t st = sl.status_host[i];
-                deep += (st == kCandMain || st == kCandHead || st == kCandTail) && sl.pin_depth[i] > 0 && (double)sl.pin_depth[i] > 1.5 * (double)m->max_depth;
+                deep += (st == kCandMain || st == kCandHead || st == kCandTail) && d[i] > 0 && (double)d[i] > 1.5 * (double)m->max_depth;
             }
         m->cand_n = sl.batch, m->cand_kept = kept, m->cand_chunks = sl.n_chunks, m->rescaled = deep;
         sl.cand = false;
         return 0;
     }
-    memcpy(sl.y_host, sl.pin_y, sl.y_bytes);
+    memcpy(sl.y_host, sl.pin_y, p.y.bytes);
     return 0;
 }
 
@@ -498,10 +539,9 @@ static int64_t predict_chunk(const c3_model *m) {
 static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host) {
     if (!m) return fail("null model");
     const int64_t chunk = predict_chunk(m);
-    RingInput in;
-    in.depth = depth_host;
+    RingInput in = ring_input(InKind::Sliced, x_host, x_dtype, batch, y_host, depth_host);
     if (chunk <= 0 || batch < 2 * chunk) {
-        TRY(predict_submit(m, x_host, x_dtype, batch, y_host, 0, nullptr, depth_host ? &in : nullptr));
+        TRY(predict_submit(m, in, 0));
         return c3_predict_wait(m, 0);
     }
     m->rescaled = 0, in.piece = true;
@@ -537,10 +577,9 @@ static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_
         take = std::min(take, max_microbatch(m));
         if (n_sub - n_done == kRing) rc = c3_predict_wait(m, (int)(n_done++ % kRing));
         m->tap_call_off = off;
+        in.x = (const char *)x_host + off * wbytes, in.batch = take, in.y_host = y_host + off * m->row;
         if (depth_host) in.depth = depth_host + off;
-        if (rc == 0)
-            rc = predict_submit(m, (const char *)x_host + off * wbytes, x_dtype, take, y_host + off * m->row, (int)(n_sub % kRing), nullptr,
-                                depth_host ? &in : nullptr);
+        if (rc == 0) rc = predict_submit(m, in, (int)(n_sub % kRing));
         m->tap_call_off = 0;
         if (rc != 0) break;
         off += take;
@@ -593,9 +632,7 @@ int c3_predict_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch
 
 int c3_predict_submit_depth(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depth_host, float *y_host, int slot) {
     TRY(depth_args_ok(m, x_dtype, batch, depth_host, false));
-    RingInput in;
-    in.depth = depth_host;
-    return predict_submit(m, x_host, x_dtype, batch, y_host, slot, nullptr, &in);
+    return predict_submit(m, ring_input(InKind::Sliced, x_host, x_dtype, batch, y_host, depth_host), slot);
 }
 
 // ---- the region form of the pileup call on the ring ----
@@ -610,10 +647,9 @@ static int region_submit(c3_model *m, const char *who, const void *region_host, 
     for (int64_t i = 0; i < batch; ++i)
         if (starts_host[i] < 0 || (int64_t)starts_host[i] + m->positions > n_cols)
             return fail("window %lld starts at column %d: outside the %lld-column region", (long long)i, starts_host[i], (long long)n_cols);
-    RingInput in;
-    in.n_cols = n_cols, in.starts = starts_host, in.depth = depth_host;
-    in.narrow = x_dtype == C3_DTYPE_I64;
-    return predict_submit(m, region_host, in.narrow ? C3_DTYPE_I32 : x_dtype, batch, y_host, slot, nullptr, &in);
+    RingInput in = ring_input(InKind::Region, region_host, x_dtype == C3_DTYPE_I64 ? C3_DTYPE_I32 : x_dtype, batch, y_host, depth_host);
+    in.n_cols = n_cols, in.starts = starts_host, in.narrow = x_dtype == C3_DTYPE_I64;
+    return predict_submit(m, in, slot);
 }
 
 int c3_predict_submit_region(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int32_t *starts_host, int64_t batch,
@@ -641,15 +677,13 @@ int c3_predict_pileup_region_depth(c3_model *m, const void *region_host, int x_d
 // ---- full-alignment windows as their occupied rows (c3_expand.h) ----
 int c3_predict_submit_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, float *y_host,
                            int slot) {
-    if (!m) return fail("null model");
+    TRY(ring_ready(m, slot));
     if (m->kind != C3_KIND_FULL_ALIGNMENT)
         return fail("rows belong to full-alignment windows: a pileup model has no zero rows to restore (c3_predict_submit takes its windows)");
     if (batch < 0) return fail("negative batch");
     if (batch > 0 && (!rows_host || !row_count || !y_host)) return fail("null buffer: rows / row_count / y_host");
-    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
-    if (m->slot[slot].busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
-    RingInput in;
-    in.rows = true, in.row_first = row_first, in.row_count = row_count;
+    RingInput in = ring_input(InKind::Rows, rows_host, C3_DTYPE_I8, batch, y_host);
+    in.row_first = row_first, in.row_count = row_count;
     for (int64_t b = 0; b < batch; ++b) {
         const int32_t c = table_i32(row_count, b);
         if (c < 0) return fail("window %lld: negative row_count %d", (long long)b, c);
@@ -659,7 +693,7 @@ int c3_predict_submit_rows(c3_model *m, const void *rows_host, const int32_t *ro
             return fail("window %lld: rows [%d, %lld) reach beyond the depth of %d rows", (long long)b, first, (long long)first + c, m->depth);
         in.rows_total += c;
     }
-    return predict_submit(m, rows_host, C3_DTYPE_I8, batch, y_host, slot, nullptr, &in);
+    return predict_submit(m, in, slot);
 }
 
 int c3_predict_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, float *y_host) {
@@ -690,7 +724,7 @@ int64_t c3_pack_rows(int depth, int positions, int channels, const void *x_host,
 int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
                                  const int64_t *pos_host, const int32_t *depth_host, int64_t n_cand, int head_tail, float *y_host,
                                  uint8_t *status_host, int64_t *n_rows_host, int slot) {
-    if (!m) return fail("null model");
+    TRY(ring_ready(m, slot));
     if (m->kind != C3_KIND_PILEUP) return fail("candidate selection needs a pileup model: a full-alignment handle has no region matrix");
     if (n_cand < 0 || n_cols < 0) return fail("negative size");
     if (x_dtype == C3_DTYPE_I8)
@@ -700,13 +734,10 @@ int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dty
     if (!n_rows_host) return fail("null buffer: n_rows_host");
     if (n_cols > 0 && (!region_host || !major_host)) return fail("null buffer: region / major");
     if (n_cand > 0 && (!pos_host || !y_host || !status_host)) return fail("null buffer: positions / rows / status");
-    if (slot < 0 || slot >= kHostSlots) return fail("slot must be in [0, %d)", kHostSlots);
-    if (m->slot[slot].busy) return fail("slot %d still in flight: call c3_predict_wait first", slot);
-    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
     if (n_cand > INT32_MAX) return fail("too many candidates for one call (%lld)", (long long)n_cand);
     // the chunk table: one pass over major (8 bytes a column); the image column of a chunk's first follows from the layout
     CandInput ci;
-    ci.pos = pos_host, ci.head_tail = head_tail != 0, ci.n_cols = n_cols, ci.status_host = status_host, ci.n_rows_host = n_rows_host;
+    ci.pos = pos_host, ci.head_tail = head_tail != 0, ci.status_host = status_host, ci.n_rows_host = n_rows_host;
     const int64_t pad = ci.head_tail ? m->positions - 1 : 0;
     for (int64_t c = 0; c < n_cols; ++c) {
         if (c > 0 && major_host[c] <= major_host[c - 1])
@@ -721,15 +752,13 @@ int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dty
     const int64_t img_cols = n_cols + 2 * pad * (int64_t)ci.chunks.size();
     if (img_cols > INT32_MAX - m->positions) return fail("region too large: %lld columns on the device", (long long)img_cols);
     if (depth_host) TRY(depth_args_ok(m, x_dtype, n_cand, depth_host, true));
-    HostSlot &sl = m->slot[slot];
+    RingInput in = ring_input(InKind::Candidates, region_host, C3_DTYPE_I32, n_cand, y_host, depth_host);
+    in.n_cols = img_cols, in.narrow = x_dtype == C3_DTYPE_I64, in.cand = &ci;
     if (n_cand == 0 || img_cols < m->positions) {  // no candidate, or no window fits: nothing to launch, every status is "no window"
-        sl.cand = sl.cand_none = true, sl.status_host = status_host, sl.n_rows_host = n_rows_host, sl.n_chunks = (int64_t)ci.chunks.size();
-        sl.y_host = y_host, sl.y_bytes = 0, sl.batch = n_cand, sl.y_dev_out = nullptr, sl.busy = true;
+        record_batch(m, m->slot[slot], in, StagedBatch(), -1, false);
         return 0;
     }
-    RingInput in;
-    in.n_cols = img_cols, in.depth = depth_host, in.narrow = x_dtype == C3_DTYPE_I64, in.cand = &ci;
-    return predict_submit(m, region_host, C3_DTYPE_I32, n_cand, y_host, slot, nullptr, &in);
+    return predict_submit(m, in, slot);
 }
 
 int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host,
@@ -738,6 +767,16 @@ int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dty
     TRY(c3_predict_submit_candidates(m, region_host, x_dtype, n_cols, major_host, pos_host, depth_host, n_cand, head_tail, y_host, status_host,
                                      n_rows_host, 0));
     return c3_predict_wait(m, 0);
+}
+
+// the handle's scratch buffer of the two decoder entries below: grown, never shrunk
+static int ensure_decode_buf(c3_model *m, size_t bytes) {
+    if (m->decode_bytes >= bytes) return 0;
+    if (m->decode_dev) (void)hipFree(m->decode_dev);
+    m->decode_dev = nullptr, m->decode_bytes = 0;
+    HIP_TRY(hipMalloc(&m->decode_dev, bytes));
+    m->decode_bytes = bytes;
+    return 0;
 }
 
 int c3_outcome_maxima(c3_model *m, const float *y_host, int64_t batch, const uint8_t *ref21_host, float *maxp_host,
@@ -753,12 +792,7 @@ int c3_outcome_maxima(c3_model *m, const float *y_host, int64_t batch, const uin
     const size_t yb = (size_t)batch * m->nout * sizeof(float), rb = ((size_t)batch + 255) & ~(size_t)255;
     const size_t mb = (size_t)batch * kDecodeClasses * sizeof(float);
     const size_t total = yb + rb + 2 * mb + rb;
-    if (m->decode_bytes < total) {
-        if (m->decode_dev) (void)hipFree(m->decode_dev);
-        m->decode_dev = nullptr, m->decode_bytes = 0;
-        HIP_TRY(hipMalloc(&m->decode_dev, total));
-        m->decode_bytes = total;
-    }
+    TRY(ensure_decode_buf(m, total));
     char *base = (char *)m->decode_dev;
     float *y = (float *)base;
     uint8_t *ref = (uint8_t *)(base + yb);
@@ -784,12 +818,7 @@ int c3_decode_columns(c3_model *m, const float *y_host, int64_t batch, float *ro
     HIP_TRY(hipSetDevice(m->device));
     const int wide = m->nout + kDecodeCols;
     const size_t total = (size_t)batch * wide * sizeof(float);
-    if (m->decode_bytes < total) {
-        if (m->decode_dev) (void)hipFree(m->decode_dev);
-        m->decode_dev = nullptr, m->decode_bytes = 0;
-        HIP_TRY(hipMalloc(&m->decode_dev, total));
-        m->decode_bytes = total;
-    }
+    TRY(ensure_decode_buf(m, total));
     float *rows = (float *)m->decode_dev;
     {   // the rows widen on their way through the bounce buffer (the kernel fills the decoder columns behind each)
         BounceBuf &b = bounce_buf();

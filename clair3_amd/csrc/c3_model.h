@@ -5,10 +5,11 @@
 //   c3_model.h     this file
 //   c3_pack.h      c3_model_load: BatchNorm folding, gate re-ordering, matrix-instruction fragment layouts, fp16 pieces
 //   c3_forward.h   the launch sequences of the two forward passes (clair3/model.py:130-161 and :377-416)
-//   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait (staging, transfers, range guard), the region
-//                  entries, the entries that take per-window depths (c3_rescale.h: the pre-pass that rescales very deep windows) and the
-//                  candidate entries (c3_select.h: window selection from candidate positions in front of the forward pass), and the rows
-//                  entries of the full-alignment network (c3_expand.h: the pre-pass that restores the zero rows of a window)
+//   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait.  predict_submit is one sequence for every input
+//                  kind (sliced windows, a region with starts, candidates, occupied rows handed over or packed here): lane and shared-chip
+//                  forms, plan_batch (THE layout of a staged batch: StagedBatch below), ensure_slot, fill_<kind>, queue_input, launch_batch,
+//                  record_batch; c3_predict_wait and the range guard's one re-run (range_guard_rerun) read the slot's plan.  Behind them the
+//                  entries: per-window depths (c3_rescale.h), regions, candidates (c3_select.h), rows (c3_expand.h), the two decoder entries
 //   c3_comm.h      the gather of a sharded job on RCCL
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
@@ -107,6 +108,30 @@ struct ProfRec {
     double mfma_peak = 0.0;   // dense peak (TFLOP/s) of the matrix instruction the launch issues: 2500 (16-bit) or 157.3 (fp32)
 };
 
+// ---- one batch of the submit / wait ring as it is staged (c3_hostring.h plan_batch works every field out before anything is copied) ----
+struct Section { size_t off = 0, bytes = 0; };  // (a section the batch's kind does not use: bytes == 0)
+struct StagedBatch {
+    // the slot's input buffer (pin_x -> dev_x), in this order, every section from a multiple of 256 bytes
+    Section image;      // sliced windows | the region matrix (a candidate batch: the device image) | the occupied rows of full-alignment windows
+    Section cand_pos;   // candidates: their int64 positions
+    Section depth_in;   // candidates: their depths as handed over (the selection compacts them into `depth`)
+    Section chunks;     // candidates: the chunk table (SelectChunk) -- the last section a candidate batch stages
+    Section starts;     // window starts of a region batch (staged) / of the kept candidates (written by the selection kernels)
+    Section depth;      // per-window depths as the kernels read them: staged, or compacted by the selection (only when a window is deep)
+    Section start_all;  // candidates: every candidate's start
+    Section tiles;      // candidates: the compaction tiles' counts
+    Section rows_tab;   // a rows batch: one ExpandEntry per window.  A batch packed here (C3HIP_PACK_ROWS=1) by ONE range moves it, `tail`
+                        // and `staged` down behind the rows it found (fill_packed_rows) -- the only values settled after the plan
+    size_t tail = 0;    // [tail, staged): what is staged behind the image
+    size_t staged = 0;  // bytes of the input buffer that cross PCIe
+    size_t x_cap = 0;   // bytes the slot's input buffers must hold
+    // the slot's output buffer (dev_y -> pin_y)
+    Section y;          // the rows
+    Section status;     // candidates: one status byte each
+    Section kept;       // candidates: the count of kept candidates (16 bytes from a multiple of 16)
+    size_t y_total = 0;
+};
+
 struct HostSlot {
     void *pin_x = nullptr;
     float *pin_y = nullptr;
@@ -114,32 +139,26 @@ struct HostSlot {
     float *dev_y = nullptr;
     size_t cap_x = 0, cap_y = 0;
     hipEvent_t ev_h2d = nullptr, ev_out = nullptr;
-    float *y_host = nullptr;
-    float *y_dev_out = nullptr;  // c3_predict_submit_dev: the rows stay in the caller's device buffer
-    size_t y_bytes = 0;
-    int64_t batch = 0;  // what is in flight (for the fp32 re-run of c3_predict_wait)
     uint32_t *pin_flag = nullptr;  // pinned copy of the model's range_flag after this batch
-    int x_dtype = 0;
-    int64_t tap_off = 0;  // first window of this batch in the c3_predict call it is a piece of (debug taps)
+    // ---- the batch in flight (c3_hostring.h record_batch) ----
     bool busy = false;
+    // its layout.  Window starts, depths and the rows table stay on the device with the slot (behind the counts in dev_x): the range guard's
+    // re-run gathers, rescales and expands again from the ORIGINAL counts (the pre-passes never write dev_x)
+    StagedBatch plan;
+    int64_t batch = 0;
+    int x_dtype = 0, lane = 0;  // lane: the lane (Lane) the batch in flight runs in
+    float *y_host = nullptr, *y_dev_out = nullptr;  // y_dev_out (c3_predict_submit_dev): the rows stay in the caller's device buffer
+    int64_t tap_off = 0;  // first window of this batch in the c3_predict call it is a piece of (debug taps)
     bool used_f16 = false;  // the batch in flight was computed by the fp16x3 kernels (c3_predict_wait then checks its range)
-    int lane = 0;           // the lane (Lane) the batch in flight runs in
-    // a region batch / a batch with depths keeps its window starts and depths on the device with the slot (behind the counts in dev_x): the
-    // range guard's re-run gathers and rescales again from the ORIGINAL counts (c3_rescale.h never writes dev_x)
-    const int32_t *dev_starts = nullptr, *dev_depth = nullptr;
-    // a rows batch (c3_expand.h; c3_predict_submit_rows, or C3HIP_PACK_ROWS=1): dev_x holds the occupied rows, and behind them the table the
-    // pre-pass expands them by -- kept, never written, so that the range guard's re-run expands again
-    const ExpandEntry *dev_rows = nullptr;
     int64_t rows_shipped = -1;  // rows staged for the batch in flight (-1: a dense batch)
     // a candidate batch (c3_select.h; c3_predict_submit_candidates): the statuses and the count of kept candidates leave behind the rows
-    // (tail_bytes of dev_y / pin_y from y_bytes rounded up to 256 on: n_cand status bytes, then -- from the next multiple of 16 -- the count)
-    bool cand = false;
-    bool cand_none = false;        // nothing was launched: no candidate, or a region in which no window fits -- every status is "no window"
+    bool cand = false, cand_none = false;  // cand_none: nothing was launched: no candidate, or a region in which no window fits -- every status is "no window"
     uint8_t *status_host = nullptr;
     int64_t *n_rows_host = nullptr;
-    size_t tail_bytes = 0;
-    const int32_t *pin_depth = nullptr;  // the candidates' depths as staged (the count of rescaled windows among the kept, for c3_model_describe)
     int64_t n_chunks = 0;
+    // a section of the staged batch on the device / in the pinned input buffer (nullptr: the batch has none)
+    template <class T> T *dev(const Section &s) const { return s.bytes ? (T *)((char *)dev_x + s.off) : nullptr; }
+    template <class T> T *pin(const Section &s) const { return s.bytes ? (T *)((char *)pin_x + s.off) : nullptr; }
 };
 
 constexpr int kHostSlots = 4;  // batches in flight per handle through c3_predict_submit / _wait (C3_HOST_SLOTS)

@@ -244,9 +244,7 @@ int c3_predict_device_checked(c3_model *m, const void *x_dev, int x_dtype, int64
     HIP_TRY(hipMemcpyAsync(m->pin_flag, m->range_flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (*m->pin_flag) {
-        fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions\n");
-        m->f16_ok = false, m->precision = "fp32-range-guard";
-        TRY(forward_device(m, s, x_dev, x_dtype, batch, y_dev));
+        TRY(range_guard_rerun(m, s, x_dev, x_dtype, batch, y_dev));
         HIP_TRY(hipStreamSynchronize(s));
     }
     return 0;

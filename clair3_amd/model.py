@@ -212,14 +212,19 @@ class _HipModel:
             raise _lib.C3Error(f"depths must hold one entry per window: shape {d.shape} for {n} windows")
         return d
 
-    def predict_numpy(self, x, depths=None):
-        """depths: per-window read depths (predict.depths_from_alt_info); given, windows deeper than 1.5 x max_depth are rescaled on the
-        device the way the reference's in-process loops do before their model call (c3_predict_depth; pileup, int32 windows)."""
+    def _window_batch(self, x):
+        """(contiguous windows, their C ABI dtype), checked against the model's geometry: the head of every host-side entry"""
         x = np.ascontiguousarray(x)
         dt = _NP_DTYPE.get(x.dtype)
         if dt is None:
             raise _lib.C3Error(f"unsupported window dtype {x.dtype} (int8 / int32 expected)")
         self._check_shape(x.shape, dt)
+        return x, dt
+
+    def predict_numpy(self, x, depths=None):
+        """depths: per-window read depths (predict.depths_from_alt_info); given, windows deeper than 1.5 x max_depth are rescaled on the
+        device the way the reference's in-process loops do before their model call (c3_predict_depth; pileup, int32 windows)."""
+        x, dt = self._window_batch(x)
         y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
         if depths is None:
             _lib.check(_lib.lib().c3_predict(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data), "c3_predict")
@@ -230,11 +235,7 @@ class _HipModel:
 
     def submit(self, x, slot=0, depths=None):
         """Asynchronous half of predict_numpy (c3_predict_submit / c3_predict_submit_depth); returns a handle for wait()."""
-        x = np.ascontiguousarray(x)
-        dt = _NP_DTYPE.get(x.dtype)
-        if dt is None:
-            raise _lib.C3Error(f"unsupported window dtype {x.dtype} (int8 / int32 expected)")
-        self._check_shape(x.shape, dt)
+        x, dt = self._window_batch(x)
         y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
         if depths is None:
             _lib.check(_lib.lib().c3_predict_submit(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data, slot),
@@ -249,11 +250,7 @@ class _HipModel:
         """submit() with the rows left on the device: the forward pass writes them at device address ``y_dev_ptr``
         (len(x) * row_size floats; c3_predict_submit_dev) -- what a rank of a sharded job does with rows that go to the gather.
         wait() on the ticket returns None (it still runs the range guard)."""
-        x = np.ascontiguousarray(x)
-        dt = _NP_DTYPE.get(x.dtype)
-        if dt is None:
-            raise _lib.C3Error(f"unsupported window dtype {x.dtype} (int8 / int32 expected)")
-        self._check_shape(x.shape, dt)
+        x, dt = self._window_batch(x)
         _lib.check(_lib.lib().c3_predict_submit_dev(self._handle, x.ctypes.data, dt, x.shape[0], C.c_void_p(int(y_dev_ptr)), slot),
                    "c3_predict_submit_dev")
         return slot, None
@@ -354,13 +351,18 @@ class Clair3_P(_HipModel):
         _lib.check(_lib.lib().c3_model_set_max_depth(self._handle, int(n)), "c3_model_set_max_depth")
         return self
 
-    def _region_args(self, region, starts):
+    def _region(self, region, dtypes):
+        """(contiguous region matrix, its C ABI dtype); ``dtypes`` names what the entry takes in its refusal"""
         region = np.ascontiguousarray(region)
         # int64 / uint64: the size_t matrix of plp_data viewed in place (np.frombuffer(ffi.buffer(plp_data.matrix, ...)),
         # CreateTensorPileupFromCffi.py:140-146) -- no .copy(), no astype
         dt = _lib.DTYPE_I64 if region.dtype in (np.dtype(np.int64), np.dtype(np.uint64)) else _NP_DTYPE.get(region.dtype)
         if dt is None or region.ndim != 2 or region.shape[1] != self.input_channels:
-            raise _lib.C3Error(f"region must be (n_cols, {self.input_channels}) int8/int32/int64, got {region.dtype} {region.shape}")
+            raise _lib.C3Error(f"region must be (n_cols, {self.input_channels}) {dtypes}, got {region.dtype} {region.shape}")
+        return region, dt
+
+    def _region_args(self, region, starts):
+        region, dt = self._region(region, "int8/int32/int64")
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         return region, dt, starts, np.empty((len(starts), self.row_size), dtype=np.float32)
 
@@ -391,10 +393,7 @@ class Clair3_P(_HipModel):
         return slot, y
 
     def _candidate_args(self, region, major, positions, depths):
-        region = np.ascontiguousarray(region)
-        dt = _lib.DTYPE_I64 if region.dtype in (np.dtype(np.int64), np.dtype(np.uint64)) else _NP_DTYPE.get(region.dtype)
-        if dt is None or region.ndim != 2 or region.shape[1] != self.input_channels:
-            raise _lib.C3Error(f"region must be (n_cols, {self.input_channels}) int32/int64, got {region.dtype} {region.shape}")
+        region, dt = self._region(region, "int32/int64")
         major = np.ascontiguousarray(major, dtype=np.int64)
         if major.shape != (region.shape[0],):
             raise _lib.C3Error(f"major must hold one entry per column: shape {major.shape} for {region.shape[0]} columns")

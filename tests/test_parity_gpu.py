@@ -169,6 +169,10 @@ def test_async_submit_wait_and_device_paths_agree():
     yd = m(torch.from_numpy(xa).cuda())
     torch.cuda.synchronize()
     assert yd.is_cuda and np.array_equal(yd.cpu().numpy(), ya)
+    # a submit refused on the way (int32 counts are staged before the forward pass turns them down) leaves its slot free
+    with pytest.raises(_lib.C3Error, match="full-alignment windows must be int8"):
+        m.submit(xa.astype(np.int32), slot=1)
+    assert np.array_equal(m.wait(m.submit(xb, slot=1)), yb)
 
 
 @pytest.mark.parametrize("kind", [syn.FULL_ALIGNMENT, syn.PILEUP])
