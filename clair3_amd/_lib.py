@@ -26,7 +26,10 @@ EXPORTS = (
     "c3_model_set_max_depth", "c3_predict_depth", "c3_predict_submit_depth", "c3_predict_pileup_region_depth", "c3_predict_submit_region",
     "c3_predict_submit_candidates", "c3_predict_pileup_candidates",
     "c3_predict_submit_rows", "c3_predict_rows", "c3_pack_rows",
+    "c3_model_set_verify", "c3_model_verify_stats", "c3_model_verify_reset",
 )
+# policy of verify mode (C3_VERIFY_* in include/c3hip.h)
+VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
 
 
 class RowsConfig(C.Structure):
@@ -46,6 +49,15 @@ class TensorDesc(C.Structure):
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double), ("mfma_flops", C.c_double), ("mfma_peak_tflops", C.c_double)]
+
+
+class VerifyStats(C.Structure):
+    """c3_verify_stats (include/c3hip.h)"""
+    _fields_ = [("batches_submitted", C.c_int64), ("batches_checked", C.c_int64), ("batches_skipped", C.c_int64),
+                ("windows_checked", C.c_int64), ("worst_batch", C.c_int64), ("worst_row", C.c_int64), ("rows_over_tol", C.c_int64),
+                ("label_diffs", C.c_int64 * 4), ("near_ties", C.c_int64 * 4), ("escalations", C.c_int64),
+                ("max_abs_diff", C.c_float), ("head_max_abs_diff", C.c_float * 4), ("tol", C.c_float), ("near_tie", C.c_float),
+                ("every", C.c_int32), ("policy", C.c_int32)]
 
 
 class C3Error(RuntimeError):
@@ -140,6 +152,9 @@ def lib():
     L.c3_predict_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_pack_rows.restype = C.c_int64
     L.c3_pack_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.c3_model_set_verify.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]
+    L.c3_model_verify_stats.argtypes = [C.c_void_p, C.POINTER(VerifyStats)]
+    L.c3_model_verify_reset.argtypes = [C.c_void_p]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -198,7 +198,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             ps.mfma(2.0 * ((M + kS2BM - 1) / kS2BM * kS2BM) * (double)Cout * 9.0 * cin * 3, true);
             // more tiles than CUs: two 512-thread workgroups (66 KB of LDS, 128 registers a lane) per CU; otherwise one, with twice the registers
             const bool pair = sp.tiles > m->wg_slots / 2;
-            m->choice_s2[l == 3 ? 0 : 1] = pair ? "two-workgroups-per-cu" : "one-workgroup-per-cu";
+            m->choice.s2[l == 3 ? 0 : 1] = pair ? "two-workgroups-per-cu" : "one-workgroup-per-cu";
             int g = sp.tiles;
             const int slots = pair ? m->wg_slots : m->wg_slots / 2, unit = 8 * sp.tiles_n;
             if (g > slots) g = std::max(unit, slots / unit * unit);
@@ -234,7 +234,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             const double tiles_x = sppf ? (double)((n + wpt - 1) / wpt) : (double)tiles_m;  // pixel tiles the launch really runs
             const int c1_rows = l == 1 ? (kPlBM + 2 * ww[l] + 2 + 31) / 32 * 32 : kPlBM;
             ps.mfma(2.0 * tiles_x * kPlBM * (double)Cout * 9.0 * cin * 3 + (src8 ? 2.0 * tiles_m * c1_rows * 64.0 * (m->C == 8 ? 80.0 : 96.0) * 2 : 0.0), true);
-            m->choice_s1[(l / 3) * 2 + (l % 3 - 1)] = 'd';
+            m->choice.s1[(l / 3) * 2 + (l % 3 - 1)] = 'd';
             // F(2,3) along H (c3_conv3w.h) for the plain plane-to-plane layers: 12 instead of 18 groups of piece products per output
             // pair.  Not where conv1 is computed inside the kernel (res1a / res1b) or the pyramid pooling is its epilogue (res3b):
             // those stay on the direct kernel.  C3HIP_WINO: 0 none, 1 the 64- / 128-channel ones, 2 (default) every plain one -- same-box
@@ -267,7 +267,7 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                 }
                 HIP_TRY(hipGetLastError());
                 TRY(tap(m, s, l, L.act[l], n, true));
-                m->choice_s1[(l / 3) * 2 + (l % 3 - 1)] = 'w';
+                m->choice.s1[(l / 3) * 2 + (l % 3 - 1)] = 'w';
                 cin = Cout;
                 continue;
             }
@@ -376,10 +376,10 @@ static int run_fa_fp32(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, f
 
 static int run_fa(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float *y) {
     if (fa_planes_ok(m)) {
-        m->choice_fa = "planes-f16x3";
+        m->choice.fa = "planes-f16x3";
         return run_fa_planes(m, s, x, n, y);
     }
-    m->choice_fa = "fp32-mfma", m->choice_s2[0] = m->choice_s2[1] = "-";
+    m->choice.fa = "fp32-mfma", m->choice.s2[0] = m->choice.s2[1] = "-";
     return run_fa_fp32(m, s, x, n, y);
 }
 
@@ -411,7 +411,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
         if (l1_f16) {
             lp.whh = m->whh16[0];
             if (h1_planes) lp.hplanes = L.h1;
-            m->choice_lstm1 = half1 ? "fused-f16x3-half-tiles" : "fused-f16x3-full-tiles";
+            m->choice.lstm1 = half1 ? "fused-f16x3-half-tiles" : "fused-f16x3-full-tiles";
             bool launched = false;
             if constexpr (sizeof(T) == 1) {
                 if (half1) {
@@ -424,7 +424,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
                 else hipLaunchKernelGGL((lstm1_fused_kernel<T, true>), grid, dim3(512), 0, s, lp);
             }
         } else {
-            m->choice_lstm1 = "fused-fp32-mfma";
+            m->choice.lstm1 = "fused-fp32-mfma";
             hipLaunchKernelGGL(lstm1_fused_kernel<T>, grid, dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());
@@ -442,20 +442,20 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
             // beside other handles half as many, twice as long workgroups: 120 of them leave room for the 128 of another batch's
             // LSTM launch (three batches in flight 5.46 M -> 5.59 M windows/s; alone 4.9 M -> 4.3 M, hence the caller's hint)
             if (beside > 1) wp.lanes_per_xcd = std::max(1, wp.lanes_per_xcd / 2);
-            m->choice_proj2 = beside > 1 ? "weights-resident-half-grid" : "weights-resident";
+            m->choice.proj2 = beside > 1 ? "weights-resident-half-grid" : "weights-resident";
             hipLaunchKernelGGL(dense_planes_wres_kernel<0>, dim3(8 * wp.lanes_per_xcd * wp.tiles_n), dim3(kDnThreads), 0, s, wp);
             HIP_TRY(hipGetLastError());
         } else if (h1_planes) {  // batches below ~190 windows: fewer than two row tiles per lane
             DensePlanesParams dp;
             dp.a = L.h1, dp.w = m->proj2_pw, dp.bias = m->proj_b[1], dp.c = L.gx2, dp.post = m->proj2_post;
             dp.M = M, dp.N = 1280, dp.K = 256, dp.tiles_n = 1280 / kDnBN, dp.tiles = ((M + kDnBM - 1) / kDnBM) * dp.tiles_n;
-            m->choice_proj2 = "128x128-chunk-stream";
+            m->choice.proj2 = "128x128-chunk-stream";
             hipLaunchKernelGGL(dense_planes_pipe_kernel<0>, dim3(std::min(dp.tiles, m->wg_slots / 2)), dim3(kDnThreads), 0, s, dp);
             HIP_TRY(hipGetLastError());
         } else {
             DenseLoaderParams lp{L.h1, 256};
             EpilogueParams ep{L.gx2, m->proj_b[1], nullptr, 1280, 0};
-            m->choice_proj2 = "fp32-mfma";
+            m->choice.proj2 = "fp32-mfma";
             TRY((launch_gemm<DenseLoader<4>, EPI_BIAS, 128, 128>(s, lp, m->proj_w[1], 256, M, 1280, 8, 1, ep)));
         }
         TRY(tap(m, s, kTapGx2, L.gx2, n));
@@ -468,11 +468,11 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
         Lstm2Params lp{L.gx2, m->whh[1], L.h2, (int)n, Tn, 1280};
         if (l2_f16) {
             lp.whh = m->whh16[1];
-            m->choice_lstm2 = half2 ? "f16x3-half-tiles" : "f16x3-full-tiles";
+            m->choice.lstm2 = half2 ? "f16x3-half-tiles" : "f16x3-full-tiles";
             if (half2) hipLaunchKernelGGL((lstm_recurrent_kernel_v2<160, true, 4>), dim3((unsigned)((n + 7) / 8), 2), dim3(512), 0, s, lp);
             else hipLaunchKernelGGL((lstm_recurrent_kernel_v2<160, true>), dim3((unsigned)((n + 15) / 16), 2), dim3(512), 0, s, lp);
         } else {
-            m->choice_lstm2 = "fp32-mfma";
+            m->choice.lstm2 = "fp32-mfma";
             hipLaunchKernelGGL(lstm_recurrent_kernel_v2<160>, dim3((unsigned)((n + 15) / 16), 2), dim3(512), 0, s, lp);
         }
         HIP_TRY(hipGetLastError());

@@ -223,7 +223,7 @@ static const int32_t *deep_depths(c3_model *m, const RingInput &in) {
 
 // THE layout of a staged batch (c3_model.h StagedBatch), for every kind: nothing else computes an offset.  The kernels' alignment
 // assumptions hang on it: sections from multiples of 256 bytes, the 8-byte pieces of expand_rows_kernel, the 16-byte pieces of host_copy_kernel
-static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth) {
+static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth, bool verify = false) {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const bool cand = in.kind == InKind::Candidates, region = cand || in.kind == InKind::Region, rows = is_rows(in.kind);
     const size_t n = (size_t)in.batch, db = with_depth ? n * sizeof(int32_t) : 0;
@@ -247,6 +247,8 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
     p.status.off = al(p.y.bytes), p.status.bytes = cand ? n : 0;
     p.kept.off = p.status.off + ((n + 15) & ~(size_t)15), p.kept.bytes = cand ? 16 : 0;
     p.y_total = cand ? p.kept.off + p.kept.bytes : p.y.bytes;
+    // ... and a verified batch's record (c3_verify.h) behind them; rows that stay on the device: the record is all the slot's output buffer holds
+    if (verify) p.verify.off = in.y_dev ? 0 : al(p.y_total), p.verify.bytes = kVerifyRecordBytes, p.y_total = p.verify.off + p.verify.bytes;
     return p;
 }
 
@@ -336,7 +338,7 @@ static void fill_packed_rows(const c3_model *m, const HostSlot &sl, const RingIn
     if (nrun == 1) {  // the layout of these rows handed over
         RingInput found = in;
         found.kind = InKind::Rows, found.rows_total = rows[0];
-        p = plan_batch(m, found, false);
+        p = plan_batch(m, found, false, p.verify.bytes != 0);
     }
     memcpy((char *)sl.pin_x + p.rows_tab.off, tab.data(), p.rows_tab.bytes);
 }
@@ -372,6 +374,80 @@ static int queue_input(c3_model *m, const HostSlot &sl, const StagedBatch &p, co
     return 0;
 }
 
+// ---- verify mode (c3_verify.h): which batches, the second pass, what c3_predict_wait does with the record
+// The submits with batch > 0 are numbered; number k is selected when k % every == 0.  A selected batch that cannot be verified counts as skipped.
+// verify_select only LOOKS (true: this batch runs the second pass); verify_count numbers the submit once it is in flight, so that a submit
+// which failed on the way has moved no counter and checked + skipped stays the number of selected submits that flew
+static bool verify_select(const c3_model *m, int64_t batch, bool can, int64_t *ordinal) {
+    if (m->verify_every <= 0 || batch <= 0) return false;
+    *ordinal = m->vstats.batches_submitted;
+    if (*ordinal % m->verify_every != 0) return false;
+    // the second pass must not overwrite what keep mode, the taps or the profile record; a handle on the fp32 forms has nothing to compare
+    return can && m->f16_ok && !m->keep && !m->tap_mask && !m->prof;
+}
+static void verify_count(c3_model *m, int64_t batch, bool verified) {
+    if (m->verify_every <= 0 || batch <= 0) return;
+    if (m->vstats.batches_submitted++ % m->verify_every == 0 && !verified) ++m->vstats.batches_skipped;
+}
+// the slot's buffer of shadow rows, the compare kernel's partials behind them: allocated on first use, grown on demand (the slot is free: nothing reads it)
+static int ensure_shadow(HostSlot &sl, size_t row_bytes) {
+    const size_t part = (row_bytes + 255) & ~(size_t)255, bytes = part + (size_t)kVerifyMaxBlocks * sizeof(VerifyRecord);
+    if (bytes > sl.shadow_bytes) {
+        if (sl.shadow) (void)hipFree(sl.shadow);
+        sl.shadow = nullptr, sl.shadow_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&sl.shadow, bytes));
+        sl.shadow_bytes = bytes;
+    }
+    sl.shadow_part = part;
+    return 0;
+}
+// The batch again on the fp32 forms, same lane and stream, from the same staged input -- the call range_guard_rerun makes, without touching
+// `precision`: a region batch gathers again, depths rescale again, rows expand again, a candidate batch reuses its compacted starts (the
+// selection does NOT run again).  Then the compare kernels; the record lands in the slot's output buffer.  What c3_model_describe reports
+// of the last forward pass stays the product pass's
+static int shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p) {
+    hipStream_t s = lane(m).stream;
+    TRY(ensure_shadow(sl, p.y.bytes));
+    const c3_model::Choices reported = m->choice;
+    const bool f16 = m->f16_ok, planes = lane(m).last_planes;
+    m->f16_ok = false;
+    const int rc = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, sl.shadow, sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth),
+                                  sl.dev<const ExpandEntry>(p.rows_tab));
+    m->f16_ok = f16, lane(m).last_planes = planes, m->choice = reported;
+    TRY(rc);
+    CompareParams cp;
+    cp.a = in.y_dev ? in.y_dev : sl.dev_y, cp.b = sl.shadow;
+    cp.kept = in.kind == InKind::Candidates ? (const uint32_t *)((const char *)sl.dev_y + p.kept.off) : nullptr;
+    cp.part = (VerifyRecord *)((char *)sl.shadow + sl.shadow_part);
+    cp.stride = m->row, cp.nout = m->nout, cp.batch = (int)in.batch, cp.tol = m->verify_tol, cp.near_tie = m->verify_near_tie;
+    const int blocks = (int)std::min<int64_t>(kVerifyMaxBlocks, (in.batch + kVerifyThreads / 4 - 1) / (kVerifyThreads / 4));
+    hipLaunchKernelGGL(rows_compare_kernel, dim3((unsigned)blocks), dim3(kVerifyThreads), 0, s, cp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rows_compare_final_kernel, dim3(1), dim3(64), 0, s, (const VerifyRecord *)cp.part, blocks, cp.kept, (int)in.batch,
+                       (VerifyRecord *)((char *)sl.dev_y + p.verify.off));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// c3_predict_wait, a verified batch the range guard did not answer: the record joins the totals; true = the policy escalates this batch
+static bool verify_account(c3_model *m, const HostSlot &sl) {
+    const VerifyRecord &r = *(const VerifyRecord *)((const char *)sl.pin_y + sl.plan.verify.off);
+    c3_verify_stats &t = m->vstats;
+    ++t.batches_checked, t.windows_checked += r.n, t.rows_over_tol += r.rows_over;
+    if (t.worst_batch < 0 || r.max_abs > t.max_abs_diff) t.worst_batch = sl.verify_ordinal, t.worst_row = r.worst_row, t.max_abs_diff = r.max_abs;
+    int64_t labels = 0;
+    for (int k = 0; k < 4; ++k) {
+        t.head_max_abs_diff[k] = std::max(t.head_max_abs_diff[k], r.head_max[k]);
+        t.label_diffs[k] += r.label[k], t.near_ties[k] += r.tie[k], labels += r.label[k];
+    }
+    if (m->verify_policy != C3_VERIFY_ESCALATE || (r.rows_over == 0 && labels == 0)) return false;
+    ++t.escalations;
+    if (m->f16_ok)
+        fprintf(stderr, "libc3hip: verify mode: fp16x3 rows differ from the fp32 forms (max |d| = %.3g, %u rows beyond %.3g, %lld labels); this handle "
+                        "continues on fp32 matrix instructions\n", (double)r.max_abs, r.rows_over, (double)m->verify_tol, (long long)labels);
+    m->f16_ok = false, m->precision = "fp32-verify";
+    return true;
+}
+
 // ---- launch, on the active lane's stream: the selection in front of a candidate batch, the forward pass, the rows on their way out
 static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p) {
     hipStream_t s = lane(m).stream;
@@ -390,11 +466,12 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
                        sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
     if (in.y_dev && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, in.y_dev, in.batch * m->row, m->range_flag);
+    if (p.verify.bytes) TRY(shadow_pass(m, sl, in, p));
     // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
     // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
     hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                       in.y_dev ? 0 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+                       in.y_dev ? p.verify.bytes / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_out, s));
     sl.used_f16 = f16;
@@ -406,6 +483,7 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
     sl.plan = p, sl.batch = in.batch, sl.x_dtype = in.x_dtype, sl.y_host = in.y_host, sl.y_dev_out = in.y_dev;
     sl.lane = m->lane_cur, sl.tap_off = m->tap_call_off, sl.rows_shipped = rows_shipped;
     sl.cand = in.cand != nullptr, sl.cand_none = !launched;
+    sl.verified = p.verify.bytes != 0;
     if (in.cand) sl.status_host = in.cand->status_host, sl.n_rows_host = in.cand->n_rows_host, sl.n_chunks = (int64_t)in.cand->chunks.size();
     sl.busy = true;
 }
@@ -428,11 +506,12 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
     for (int k = 0; k < kHostSlots; ++k) alone &= !m->slot[k].busy;
     const LaneSharing shared_chip_forms(m, in.batch, in_lane && !alone);
     const int32_t *depth = deep_depths(m, in);
-    StagedBatch p = plan_batch(m, in, depth != nullptr);
+    const bool verify = verify_select(m, in.batch, true, &sl.verify_ordinal);
+    StagedBatch p = plan_batch(m, in, depth != nullptr, verify);
     Filled f;
     if (in.batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? 0 : p.y_total));  // (rows that stay on the device need no slot buffers)
+        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
         switch (in.kind) {
         case InKind::Sliced: fill_sliced(sl, in, p, depth, f); break;
         case InKind::Region: fill_region(m, sl, in, p, depth, f); break;
@@ -441,8 +520,17 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         case InKind::PackedHere: fill_packed_rows(m, sl, in, p, f); break;
         }
         TRY(queue_input(m, sl, p, f, alone, in_lane));
-        TRY(launch_batch(m, sl, in, p));
+        if (launch_batch(m, sl, in, p) != 0) {
+            // refused behind its input: the slot stays free, so the next submit may stage into it at once, in ANOTHER lane's stream -- the
+            // transfers queued above must have landed before that (the error message is the launch's)
+            const std::string why = g_err;
+            (void)hipStreamSynchronize(lane(m).stream);
+            if (m->h2d_stream) (void)hipStreamSynchronize(m->h2d_stream);
+            g_err = why;
+            return 1;
+        }
     }
+    verify_count(m, in.batch, verify);
     record_batch(m, sl, in, p, is_rows(in.kind) ? f.rows_shipped : -1);
     return 0;
 }
@@ -502,6 +590,15 @@ int c3_predict_wait(c3_model *m, int slot) {
                               sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
         if (!sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
         HIP_TRY(hipStreamSynchronize(lane(m).stream));
+    }
+    if (sl.verified) {  // the range guard keeps priority: a batch it answered counts as skipped
+        if (bad) ++m->vstats.batches_skipped;
+        else if (verify_account(m, sl)) {  // escalate: the batch is answered with its rows on the fp32 forms, decoder columns included
+            TRY(use_lane(m, sl.lane));
+            if (sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.y_dev_out, sl.shadow, p.y.bytes, hipMemcpyDeviceToDevice, lane(m).stream));
+            else HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.shadow, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
+            HIP_TRY(hipStreamSynchronize(lane(m).stream));
+        }
     }
     if (sl.y_dev_out) return 0;
     if (sl.cand) {  // rows [0, kept) are the result; the rest belong to the surplus windows of dropped candidates
@@ -755,6 +852,7 @@ int c3_predict_submit_candidates(c3_model *m, const void *region_host, int x_dty
     RingInput in = ring_input(InKind::Candidates, region_host, C3_DTYPE_I32, n_cand, y_host, depth_host);
     in.n_cols = img_cols, in.narrow = x_dtype == C3_DTYPE_I64, in.cand = &ci;
     if (n_cand == 0 || img_cols < m->positions) {  // no candidate, or no window fits: nothing to launch, every status is "no window"
+        verify_count(m, n_cand, false);  // (verify mode: numbered like every submit, skipped when selected)
         record_batch(m, m->slot[slot], in, StagedBatch(), -1, false);
         return 0;
     }
@@ -767,6 +865,39 @@ int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dty
     TRY(c3_predict_submit_candidates(m, region_host, x_dtype, n_cols, major_host, pos_host, depth_host, n_cand, head_tail, y_host, status_host,
                                      n_rows_host, 0));
     return c3_predict_wait(m, 0);
+}
+
+// ---- verify mode (c3_verify.h): the setting and the totals ----
+static void verify_zero(c3_model *m) {
+    m->vstats = c3_verify_stats{};
+    m->vstats.worst_batch = -1;
+}
+int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int policy) {
+    if (!m) return fail("null model");
+    if (every < 0) return fail("every must be >= 0 (0 = off), got %d", every);
+    if (!(tol > 0.f)) return fail("tol must be > 0, got %g", (double)tol);
+    if (!(near_tie >= 0.f)) return fail("near_tie must be >= 0, got %g", (double)near_tie);
+    if (policy != C3_VERIFY_REPORT && policy != C3_VERIFY_ESCALATE) return fail("policy must be C3_VERIFY_REPORT or C3_VERIFY_ESCALATE, got %d", policy);
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (every > 0 && !m->verify_seen) verify_zero(m);
+    m->verify_every = every, m->verify_tol = tol, m->verify_near_tie = near_tie, m->verify_policy = policy;
+    m->verify_seen |= every > 0;
+    return 0;
+}
+int c3_model_verify_stats(c3_model *m, c3_verify_stats *out) {
+    if (!m || !out) return fail("null argument");
+    *out = m->vstats;
+    if (!m->verify_seen) out->worst_batch = -1;
+    out->every = m->verify_every, out->policy = m->verify_policy, out->tol = m->verify_tol, out->near_tie = m->verify_near_tie;
+    return 0;
+}
+int c3_model_verify_reset(c3_model *m) {
+    if (!m) return fail("null model");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    verify_zero(m);
+    return 0;
 }
 
 // the handle's scratch buffer of the two decoder entries below: grown, never shrunk

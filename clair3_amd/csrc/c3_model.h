@@ -11,6 +11,9 @@
 //                  record_batch; c3_predict_wait and the range guard's one re-run (range_guard_rerun) read the slot's plan.  Behind them the
 //                  entries: per-window depths (c3_rescale.h), regions, candidates (c3_select.h), rows (c3_expand.h), the two decoder entries
 //   c3_comm.h      the gather of a sharded job on RCCL
+//   c3_verify.h    verify mode's two compare kernels and their record (included with the other kernels below): a selected batch of the ring
+//                  runs a second forward pass on the fp32 forms from the same staged input (c3_hostring.h shadow_pass) and the two sets of
+//                  rows are compared on the device
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
@@ -51,6 +54,7 @@
 #include "c3_conv3w.h"
 #include "c3_l4.h"
 #include "c3_dense.h"
+#include "c3_verify.h"
 
 using namespace c3;
 
@@ -129,6 +133,7 @@ struct StagedBatch {
     Section y;          // the rows
     Section status;     // candidates: one status byte each
     Section kept;       // candidates: the count of kept candidates (16 bytes from a multiple of 16)
+    Section verify;     // a verified batch (c3_verify.h): its VerifyRecord, behind the kept count (rows that stay on the device: the only section)
     size_t y_total = 0;
 };
 
@@ -156,6 +161,12 @@ struct HostSlot {
     uint8_t *status_host = nullptr;
     int64_t *n_rows_host = nullptr;
     int64_t n_chunks = 0;
+    // a verified batch (c3_verify.h): the rows of its second pass on the fp32 forms, the compare kernel's partials behind them.  The buffer
+    // belongs to the SLOT, not to the lane: two slots in flight in one lane would overwrite each other's rows before c3_predict_wait reads them
+    bool verified = false;
+    int64_t verify_ordinal = 0;  // which submit of the handle this batch was (c3_verify_stats.worst_batch)
+    float *shadow = nullptr;
+    size_t shadow_bytes = 0, shadow_part = 0;  // shadow_part: offset of the partials
     // a section of the staged batch on the device / in the pinned input buffer (nullptr: the batch has none)
     template <class T> T *dev(const Section &s) const { return s.bytes ? (T *)((char *)dev_x + s.off) : nullptr; }
     template <class T> T *pin(const Section &s) const { return s.bytes ? (T *)((char *)pin_x + s.off) : nullptr; }
@@ -241,7 +252,7 @@ struct c3_model {
     float auto_fp32_at = 4.0f;
     float lstm_wmax = 0.f;           // max |w| over W_hh of both LSTMs and W_ih of LSTM2 (what the decision looked at)
     float lstm_hh_norm = 0.f;        // max abs row sum of W_hh (reported, not decided on: ordinary LSTMs reach ~6)
-    const char *precision = "fp16x3";  // "fp16x3" | "fp32-forced" (C3HIP_FP32=1) | "fp32-auto" (this decision) | "fp32-range-guard"
+    const char *precision = "fp16x3";  // "fp16x3" | "fp32-forced" (C3HIP_FP32=1) | "fp32-auto" (this decision) | "fp32-range-guard" | "fp32-verify" (verify mode escalated)
 
     // ---- switches (README) ----
     bool spp_fused = true;    // PyramidPolling as the epilogue of res3b (c3_conv3.h SPPF; 12 x 5 windows); env C3HIP_SPP_FUSED
@@ -279,6 +290,13 @@ struct c3_model {
     int64_t rows_windows = 0, rows_shipped = 0;  // windows that travelled as rows in the last completed call, and their rows (c3_model_describe)
     bool rows_call = false;  // inside a c3_predict that runs its batch as pieces: the two counts add up over the pieces
 
+    // ---- verify mode (c3_model_set_verify, c3_verify.h): off = nothing allocated, nothing launched ----
+    int verify_every = 0;  // every n-th submit of the ring also runs on the fp32 forms and is compared; 0 = off
+    float verify_tol = 1e-4f, verify_near_tie = 1e-6f;
+    int verify_policy = C3_VERIFY_REPORT;
+    bool verify_seen = false;  // verify mode is or was on: c3_model_describe ends on verify=...
+    c3_verify_stats vstats = {};  // totals since the last load / reset (batches_submitted doubles as the selection counter)
+
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
 
@@ -301,10 +319,13 @@ struct c3_model {
 
     HostSlot slot[kHostSlots];
 
-    // which kernel forms the last forward pass took (c3_model_describe; bench.py reports it)
-    const char *choice_lstm1 = "-", *choice_proj2 = "-", *choice_lstm2 = "-", *choice_fa = "-";
-    const char *choice_s2[2] = {"-", "-"};  // conv3, conv5: one or two workgroups per CU (c3_conv3s2.h PAIR)
-    char choice_s1[8] = "------";           // the six stride-1 convolutions res1a .. res3b: d = direct, w = F(2,3) along H
+    // which kernel forms the last forward pass took (c3_model_describe; bench.py reports it).  ONE struct: verify mode's second pass
+    // (c3_hostring.h shadow_pass) puts it back as a whole, so whatever forward_device reports belongs in here
+    struct Choices {
+        const char *lstm1 = "-", *proj2 = "-", *lstm2 = "-", *fa = "-";
+        const char *s2[2] = {"-", "-"};  // conv3, conv5: one or two workgroups per CU (c3_conv3s2.h PAIR)
+        char s1[8] = "------";           // the six stride-1 convolutions res1a .. res3b: d = direct, w = F(2,3) along H
+    } choice;
 
     bool prof = false;
     std::vector<ProfRec> recs;

@@ -10,7 +10,7 @@
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.1 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.2 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -210,6 +210,7 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
     else if (m->kind == C3_KIND_FULL_ALIGNMENT) m->f16_ok = true, m->precision = "fp16x3";
     HIP_TRY(hipMemset(m->range_flag, 0, 256));
     HIP_TRY(hipDeviceSynchronize());  // (the handle's streams are non-blocking: the flag is zero before any of them runs again)
+    verify_zero(m);  // verify mode: the totals were about the weights before; the setting stays
     m->loaded = true;
     return 0;
 }
@@ -273,14 +274,24 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
     if (m->kind == C3_KIND_PILEUP)
         snprintf(buf, (size_t)n, "sharing=%d lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
                  "ring_lanes=%d lane_max_batch=%lld max_depth=%d rescaled=%lld candidates=%lld kept=%lld chunks=%lld", m->sharing,
-                 m->choice_lstm1, m->choice_proj2, m->choice_lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
+                 m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else
         snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
                  "precision=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
-                 m->choice_fa, m->choice_s1, m->choice_s2[0], m->choice_s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
+                 m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
                  m->precision, (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+    if (m->verify_seen) {  // verify mode is or was on (c3_verify.h): the setting and the totals behind everything else
+        const c3_verify_stats &t = m->vstats;
+        const size_t at = strlen(buf);
+        snprintf(buf + at, (size_t)n - at, " verify=every:%d,policy:%s,tol:%.3g,submitted:%lld,checked:%lld,skipped:%lld,windows:%lld,max_abs_diff:%.3g,"
+                 "rows_over_tol:%lld,label_diffs:%lld,near_ties:%lld,escalations:%lld", m->verify_every,
+                 m->verify_policy == C3_VERIFY_ESCALATE ? "escalate" : "report", (double)m->verify_tol, (long long)t.batches_submitted,
+                 (long long)t.batches_checked, (long long)t.batches_skipped, (long long)t.windows_checked, (double)t.max_abs_diff,
+                 (long long)t.rows_over_tol, (long long)(t.label_diffs[0] + t.label_diffs[1] + t.label_diffs[2] + t.label_diffs[3]),
+                 (long long)(t.near_ties[0] + t.near_ties[1] + t.near_ties[2] + t.near_ties[3]), (long long)t.escalations);
+    }
     return 0;
 }
 
@@ -324,6 +335,7 @@ int c3_model_destroy(c3_model *m) {
         if (sl.pin_flag) (void)hipHostFree(sl.pin_flag);
         if (sl.dev_x) (void)hipFree(sl.dev_x);
         if (sl.dev_y) (void)hipFree(sl.dev_y);
+        if (sl.shadow) (void)hipFree(sl.shadow);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
         if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
     }

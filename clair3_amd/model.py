@@ -52,6 +52,7 @@ class _HipModel:
         self._taps = ""
         self._geometry = None
         self._decode_cols = False
+        self._verify = None
         if device is not None:
             self.to(device)
 
@@ -75,6 +76,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_debug_tap(self._handle, self._taps.encode()), "c3_debug_tap")
         if self._decode_cols:
             _lib.check(_lib.lib().c3_model_set_decode_columns(self._handle, 1), "c3_model_set_decode_columns")
+        if self._verify is not None:
+            _lib.check(_lib.lib().c3_model_set_verify(self._handle, *self._verify), "c3_model_set_verify")
         if sd is not None:
             self._load(sd)
         return self
@@ -269,9 +272,59 @@ class _HipModel:
 
     def describe(self):
         """which kernel forms the last forward pass took (c3_model_describe)"""
-        buf = C.create_string_buffer(512)
-        _lib.check(_lib.lib().c3_model_describe(self._handle, buf, 512), "c3_model_describe")
+        buf = C.create_string_buffer(1024)
+        _lib.check(_lib.lib().c3_model_describe(self._handle, buf, 1024), "c3_model_describe")
         return buf.value.decode()
+
+    # ---- verify mode (c3_model_set_verify; DESIGN.md 4) ----
+    @staticmethod
+    def _verify_args(every, tol, near_tie, escalate):
+        """(every, tol, near_tie, policy) as the C ABI takes them; anything it would refuse is refused here with the same words"""
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)):
+            raise _lib.C3Error(f"every must be an integer >= 0 (0 = off), got {every!r}")
+        if every < 0 or every > 2 ** 31 - 1:
+            raise _lib.C3Error(f"every must be >= 0 (0 = off), got {every}")
+        try:
+            tol, near_tie = float(tol), float(near_tie)
+        except (TypeError, ValueError) as e:
+            raise _lib.C3Error(f"tol and near_tie must be numbers, got {tol!r}, {near_tie!r}") from e
+        if not np.float32(tol) > 0 or not np.isfinite(tol):
+            raise _lib.C3Error(f"tol must be > 0, got {tol}")
+        if not near_tie >= 0 or not np.isfinite(near_tie):
+            raise _lib.C3Error(f"near_tie must be >= 0, got {near_tie}")
+        return int(every), tol, near_tie, _lib.VERIFY_ESCALATE if escalate else _lib.VERIFY_REPORT
+
+    def verify(self, every=1, tol=1e-4, near_tie=1e-6, escalate=False):
+        """Verify mode: every ``every``-th batch of the submit / wait ring (predict_numpy, submit and everything built on them) also runs on the
+        fp32-MFMA forms from the same staged input and the two sets of rows are compared on the device (c3_model_set_verify).  ``tol`` and
+        ``near_tie`` default to the project's own gates (north_star's 1e-4, tests/util.py NEAR_TIE).  escalate=False: the rows stay the
+        fp16x3 ones, bit for bit; escalate=True: a batch that disagrees is answered with its fp32 rows and the handle continues on the
+        fp32 forms.  every=0 switches it off.  verify_stats() reads the totals."""
+        args = self._verify_args(every, tol, near_tie, escalate)
+        if self._handle is None:  # (a call that fails leaves nothing behind for a later .to(device) to apply)
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        _lib.check(_lib.lib().c3_model_set_verify(self._handle, *args), "c3_model_set_verify")
+        self._verify = args  # a handle created anew by .to(another device) takes the setting along
+        return self
+
+    def verify_stats(self):
+        """the totals of verify mode since the last load / verify_reset() as a dict (c3_model_verify_stats; include/c3hip.h names the fields)"""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        st = _lib.VerifyStats()
+        _lib.check(_lib.lib().c3_model_verify_stats(self._handle, C.byref(st)), "c3_model_verify_stats")
+        out = {}
+        for name, _ in _lib.VerifyStats._fields_:
+            v = getattr(st, name)
+            out[name] = list(v) if hasattr(v, "__len__") else v
+        out["policy"] = "escalate" if st.policy == _lib.VERIFY_ESCALATE else "report"
+        return out
+
+    def verify_reset(self):
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        _lib.check(_lib.lib().c3_model_verify_reset(self._handle), "c3_model_verify_reset")
+        return self
 
     def range_status(self):
         """(flag, on_fp32): flag != 0 when an fp16x3 batch of this handle produced an activation near the fp16 range

@@ -33,6 +33,75 @@ def _load_torch_checkpoint(model, checkpoint_path, device=None):
         state_dict = checkpoint
     model.load_state_dict(state_dict)
     _register_current(model)
+    verify_from_env(model)
+
+
+def parse_verify_env(value, tol=None):
+    """C3HIP_VERIFY=<n> | <n>,escalate (and C3HIP_VERIFY_TOL=<tol>) -> the keyword arguments of ``model.verify``; None when unset, empty or
+    0.  Anything else that is not such a setting raises: a job asked to verify must not run unverified because of a typo."""
+    if value is None or not value.strip():
+        return None
+    parts = [p.strip().lower() for p in value.split(",")]
+    if len(parts) > 2 or (len(parts) == 2 and parts[1] not in ("escalate", "report")):
+        raise _lib.C3Error(f"C3HIP_VERIFY must be <n> or <n>,escalate (every n-th batch; 0 = off), got {value!r}")
+    try:
+        every = int(parts[0])
+    except ValueError as e:
+        raise _lib.C3Error(f"C3HIP_VERIFY must be <n> or <n>,escalate (every n-th batch; 0 = off), got {value!r}") from e
+    if every < 0:
+        raise _lib.C3Error(f"C3HIP_VERIFY: n must be >= 0, got {every}")
+    kw = dict(every=every, escalate=len(parts) == 2 and parts[1] == "escalate")
+    if tol is not None and tol.strip():
+        try:
+            kw["tol"] = float(tol)
+        except ValueError as e:
+            raise _lib.C3Error(f"C3HIP_VERIFY_TOL must be a number > 0, got {tol!r}") from e
+        if not kw["tol"] > 0:
+            raise _lib.C3Error(f"C3HIP_VERIFY_TOL must be a number > 0, got {tol!r}")
+    return kw if every > 0 else None
+
+
+# models of this process that run in verify mode because the environment said so: their totals go to stderr when the process ends
+_VERIFIED = []
+
+
+def verify_from_env(model):
+    """Switch verify mode on where the model is built, as C3HIP_VERIFY / C3HIP_VERIFY_TOL say (README).  In a worker process one summary
+    line per such model goes to stderr at exit; stdout and the VCF stay untouched."""
+    import os
+    kw = parse_verify_env(os.environ.get("C3HIP_VERIFY"), os.environ.get("C3HIP_VERIFY_TOL"))
+    if kw is None:
+        return False
+    model.verify(**kw)
+    if not any(v is model for v in _VERIFIED):
+        import atexit
+        if not _VERIFIED:
+            atexit.register(_report_verified)
+        _VERIFIED.append(model)  # (held until the process ends: the loop's own reference is gone by then, and with it the handle's totals)
+    return True
+
+
+def verify_summary(model):
+    """the line a worker leaves on stderr: the handle's precision and the totals of verify mode (INTEGRATION.md says how to read it)"""
+    import re
+    st = model.verify_stats()
+    prec = re.search(r"precision=(\S+)", model.describe())
+    return ("[clair3_amd] verify: precision={} every={} policy={} tol={:g} batches submitted={} checked={} skipped={} windows={} "
+            "max_abs_diff={:.3g} per_head={} worst=(batch {}, row {}) rows_over_tol={} label_diffs={} near_ties={} escalations={}").format(
+        prec.group(1) if prec else "?", st["every"], st["policy"], st["tol"], st["batches_submitted"], st["batches_checked"],
+        st["batches_skipped"], st["windows_checked"], st["max_abs_diff"], "/".join(f"{v:.3g}" for v in st["head_max_abs_diff"]),
+        st["worst_batch"], st["worst_row"], st["rows_over_tol"], st["label_diffs"], st["near_ties"], st["escalations"])
+
+
+def _report_verified():
+    import sys
+    for model in _VERIFIED:
+        if model._handle is None:
+            continue
+        try:
+            print(verify_summary(model), file=sys.stderr)
+        except Exception as e:  # noqa: BLE001  (the process is ending: say it, do not raise)
+            print(f"[clair3_amd] verify: no summary ({e})", file=sys.stderr)
 
 
 # The model the worker process is calling variants with: the reference loop creates ONE model, loads it here, and only then
@@ -133,6 +202,8 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
     m.eval()
     if chkpnt_fn is not None:
         _load_torch_checkpoint(m, chkpnt_fn, device)
+    else:
+        verify_from_env(m)  # (C3HIP_VERIFY: with a checkpoint the loader has done it)
     return m
 
 

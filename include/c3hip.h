@@ -353,6 +353,52 @@ int c3_stream_wait(void *stream, int device, int timeout_ms);
  * kernels follow it (alone: 8-window LSTM tiles and 240 projection workgroups so that a 1024-window batch reaches every CU;
  * sharing: 16-window tiles and 120 workgroups, because the other batches fill the rest).  Rows are bit-identical either way. */
 int c3_model_set_sharing(c3_model *m, int handles);
+/* ---- verify mode: the fp16x3 rows of a job's own batches against the fp32 forms, compared on the device ----
+ * The product path stays on the fp16x3 kernels because of four decisions -- the per-channel weight scales, the channel equalisation at
+ * load, the 16000 range guard, the load-time |w| >= 4 rule -- that have only ever met synthetic weights ("parity on a
+ * TRAINED checkpoint is unpinned").  This is the instrument for a caller who has a real checkpoint: inside the job they run anyway, every
+ * `every`-th batch submitted to the submit / wait ring (c3_predict_submit and every entry built on it: the pieces of a blocking c3_predict,
+ * depths, regions, candidates, rows) also runs on the fp32-MFMA forms from the same staged input, and the two sets of rows are compared
+ * where they are.  The record comes back with the batch and adds up on the handle.
+ *   every       0 = off.  The submits of a handle with batch > 0 are numbered from 0 (from the last load / reset on); number k is selected
+ *               when k % every == 0.  A selected batch is SKIPPED (counted, not verified) when the handle is already on the fp32 forms,
+ *               when c3_debug_keep_activations, c3_debug_tap or c3_profile_enable is on (the second pass must not overwrite what they
+ *               record), when a candidate batch has nothing to launch, or when the range guard answered the batch (it keeps priority)
+ *   tol         > 0: a row counts in rows_over_tol when any of its probabilities differs by more than tol
+ *   near_tie    >= 0: an arg-max difference in a head whose fp32 top-2 gap is at most near_tie is excused (counted in near_ties)
+ *   policy      C3_VERIFY_REPORT: the caller gets the fp16x3 rows, bit for bit what a run without verify mode returns.
+ *               C3_VERIFY_ESCALATE: a batch with rows_over_tol > 0 or an arg-max difference outside near-ties is answered with its fp32
+ *               rows (decoder columns included; c3_predict_submit_dev: they replace the rows on the device), one line goes to stderr and
+ *               the handle continues on the fp32 forms (c3_model_describe: precision=fp32-verify).  Batches of other slots that are in
+ *               flight on fp16x3 and were not selected keep their rows: they are as unverified as any batch before them
+ * Compared per row and head (columns 0-21-24-57-90, the decoder columns are not): |a - b| in fp32, the arg-max, the fp32 row's top-2 gap;
+ * for a candidate batch only the rows of kept candidates.  With verify mode never enabled on a handle nothing is allocated or launched.
+ * c3_predict_device and c3_predict_device_checked are asynchronous entries on the CALLER's stream: they stay exactly as they are and are
+ * never verified.  Refused while a c3_predict_submit of the handle is pending.
+ *   c3_model_verify_stats   the totals since the last c3_model_load / c3_model_verify_reset (a reload resets them and keeps the setting)
+ *   c3_model_verify_reset   zero the totals (and the numbering of the submits)
+ * c3_model_describe ends on verify=... while verify mode is or was on for the handle. */
+#define C3_VERIFY_REPORT 0
+#define C3_VERIFY_ESCALATE 1
+typedef struct {
+    int64_t batches_submitted;  /* submits with batch > 0 while verify mode was on */
+    int64_t batches_checked;    /* ... compared */
+    int64_t batches_skipped;    /* ... selected but not compared (see above) */
+    int64_t windows_checked;    /* rows compared */
+    int64_t worst_batch;        /* number of the submit with the largest |d| (-1: none checked yet) ... */
+    int64_t worst_row;          /* ... and the lowest row inside it that reaches it */
+    int64_t rows_over_tol;
+    int64_t label_diffs[4];     /* per head: arg-max differences outside near-ties */
+    int64_t near_ties[4];       /* per head: arg-max differences excused as near-ties */
+    int64_t escalations;
+    float max_abs_diff;
+    float head_max_abs_diff[4];
+    float tol, near_tie;        /* the setting in force */
+    int32_t every, policy;
+} c3_verify_stats;
+int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int policy);
+int c3_model_verify_stats(c3_model *m, c3_verify_stats *out);
+int c3_model_verify_reset(c3_model *m);
 /* which kernel forms the handle's last forward pass took, as "key=value ..." text; bench.py reports it next to its rates */
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
