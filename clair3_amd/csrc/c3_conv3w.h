@@ -481,4 +481,332 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_wino_planes_kernel(Wino
     if (p.range_flag && !(omax < kF16Range)) atomicOr(p.range_flag, 1u);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The same convolution for launches with NO MORE TILES THAN CUs on a chip the handle has to itself (run_fa_planes, c3_forward.h).
+// There the merged kernel above is one 256-thread workgroup per CU: nothing runs under its loads, its transform, its barriers and
+// its epilogue, and the CU's second slot is empty.  This form fills the slot with the tile's own transform: 512 threads, one
+// workgroup per CU, exactly one tile per workgroup (no tile loop, no next-tile prefetch).
+//   waves 0-3  the matrix waves: the tap loops of the merged kernel (same 12 taps x 2 k-steps x 6 products per slab, same order,
+//              same weight ring), nothing else until the epilogue;
+//   waves 4-7  the transform waves: titem_issue / titem_finish of slab s + 1 into the OTHER of two V buffers while the matrix waves run
+//              slab s, and their residual pixels requested under the last slab.  A 512-thread workgroup puts waves w and w + 4 on
+//              one SIMD, so every SIMD holds one wave of either kind.
+// One lds_barrier per slab for all eight waves: "slab s has been read and slab s + 1 has been written".  The matrix waves stage the
+// output tile in the V buffer the last slab did NOT read (read last one slab earlier, a barrier ago: no barrier between the last matrix
+// instruction and the staging); after one more barrier all 512 threads run the store loop, four (pixel, 8-channel) items each.
+// Every value is computed by the merged kernel's instructions in the merged kernel's order: the output planes are bit-identical.
+constexpr int kWtThreads = 2 * kPlThreads;
+constexpr int kWtLds = 2 * kWLdsV + 512 + kWRows * 8;  // two V buffers, bias | post, one row table
+static_assert(kWtLds == 150144 && kWtLds <= 160 * 1024, "two V buffers + bias/post + the row table: 150 144 B of the CU's 160 KB");
+static_assert(4 * kWRows == kWtThreads, "the first slab: one (row, 8-channel group) transform item per thread");
+
+template <int C, bool RES, int ABL = 0>
+__global__ __launch_bounds__(kWtThreads, 2) void conv3x3_wino_tw_kernel(WinoConvParams p) {
+    constexpr int NS = C / 64;     // output column tiles
+    constexpr int NS32 = C / 32;   // input slabs
+    constexpr int PIXB = 4 * C;    // bytes per pixel
+    constexpr int NCH = 12 * NS32; // 8 KB weight chunks per tile
+    constexpr int T = kWRows;      // index of the zero row of every plane
+    __shared__ __attribute__((aligned(16))) char smem[kWtLds];
+    float *const bias_lds = reinterpret_cast<float *>(smem + 2 * kWLdsV);
+    float *const post_lds = bias_lds + 64;
+    int2 *const rinfo = reinterpret_cast<int2 *>(smem + 2 * kWLdsV + 512);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool mat = wave < 4;  // matrix wave (0-3) or transform wave (4-7)
+    const int wm = (wave >> 1) & 1, wn = wave & 1;
+    const int frow = lane & 31, kh = lane >> 5;
+    const int W = p.W, H = p.H;
+    const uint32_t rowB = (uint32_t)W * (uint32_t)PIXB;  // bytes between two image rows
+
+    const int tile = xcd_tile_index(blockIdx.x, p.tiles);
+    const int tn = tile % NS;
+    const int m0 = (tile / NS) * kWTM;
+
+    const __amdgpu_buffer_rsrc_t xrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, (uint32_t)((int64_t)p.M * PIXB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (uint32_t)((int64_t)p.M * PIXB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(RES ? p.res : p.out), 0, (uint32_t)((int64_t)p.M * PIXB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char *>(reinterpret_cast<const char *>(p.wf)) + (size_t)tn * NCH * 8192, 0, (uint32_t)(NCH * 8192), 0x00020000);
+    const uint32_t w_voff = (uint32_t)(wn * 4096 + lane * 16);
+
+    // the weight ring of the merged kernel: chunk cc (= slab * 12 + tap) in slot tap & 1, refilled with chunk cc + 2
+    pl_u32x4 wq[2][2][2];
+    auto w_issue = [&](int slot, int ks, int cc) __attribute__((always_inline)) {
+        if constexpr (ABL & 1) return;
+        const uint32_t so = (uint32_t)(cc * 8192 + ks * 2048);
+        wq[slot][ks][0] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, w_voff, so, 0));
+        wq[slot][ks][1] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, w_voff, so + 1024, 0));
+    };
+    auto mma = [](f32x16 c, pl_u32x4 w, pl_u32x4 x) __attribute__((always_inline)) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
+    };
+
+    // input transform of (V row, 8-channel group) item idx of slab s32, in two halves as in the merged kernel: the loads; and V0..V3 as
+    // fp16 pieces into the four planes of buffer `vbuf`
+    auto titem_issue = [&](int s32, int idx, pl_u32x4 (&rh)[4], pl_u32x4 (&rl)[4]) __attribute__((always_inline)) {
+        const uint32_t soff = (uint32_t)((s32 >> 1) * 256 + (s32 & 1) * 64);
+        const int r = idx >> 2, g = idx & 3;
+        const int2 ri = rinfo[r];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t off = ((ri.y >> k) & 1) ? (uint32_t)ri.x + (uint32_t)k * rowB + soff + (uint32_t)(g * 16) : kPlOob;
+            rh[k] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, off, 0, 0));
+            rl[k] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, off, 128, 0));
+        }
+    };
+    auto titem_finish = [&](char *vbuf, int idx, const pl_u32x4 (&rh)[4], const pl_u32x4 (&rl)[4]) __attribute__((always_inline)) {
+        const int r = idx >> 2, g = idx & 3;
+        char *dst = vbuf + r * kWRowB + g * 16;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {  // four channels at a time
+            f32x4 d[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                d[k][0] = mix_add<0>(rh[k][2 * half], rl[k][2 * half]), d[k][1] = mix_add<1>(rh[k][2 * half], rl[k][2 * half]);
+                d[k][2] = mix_add<0>(rh[k][2 * half + 1], rl[k][2 * half + 1]), d[k][3] = mix_add<1>(rh[k][2 * half + 1], rl[k][2 * half + 1]);
+            }
+            const f32x4 vv[4] = {d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]};
+#pragma unroll
+            for (int xi = 0; xi < 4; ++xi) {
+                u32x2 pc[2];
+                split2_f16_mix(vv[xi], pc);
+                *reinterpret_cast<u32x2 *>(dst + xi * kWPlaneB + half * 8) = pc[0];
+                *reinterpret_cast<u32x2 *>(dst + xi * kWPlaneB + 64 + half * 8) = pc[1];
+            }
+        }
+    };
+
+    // ABL 32 (tools/wino_probe.hip): shader clock of matrix wave 0 and transform wave 4 of workgroup 0 at phase boundaries
+    int tr_n = 0;
+    auto trace = [&](int tag) __attribute__((always_inline)) {
+        if constexpr (ABL & 32) {
+            if (blockIdx.x == 0 && (tid & 255) == 0 && tr_n < 250) {
+                long long *tb = p.trace + ((tid >> 8) * 256 + tr_n) * 2;
+                tb[0] = tag, tb[1] = (long long)__builtin_readcyclecounter();
+                ++tr_n;
+            }
+        }
+    };
+    trace(1);
+
+    // ---- prologue: the row table (c3_conv3w.h make_rowinfo of the merged kernel), the ring's first two chunks, bias and post, the zero
+    // rows of both buffers; then slab 0 by all eight waves, one item per thread
+    if (tid < kWRows) {
+        const int mp = m0 - 1 + tid;
+        int2 ri = make_int2(0, 0);
+        if ((unsigned)mp < (unsigned)p.Mp) {
+            const int hjw = p.Hj * W;
+            const int b = fast_div(mp, p.mg_hjw), rem = mp - b * hjw;
+            const int j = fast_div(rem, p.mg_w), w = rem - j * W;
+            ri.x = (int)((uint32_t)((b * H + 2 * j - 1) * W + w) * (uint32_t)PIXB);
+            int bits = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bits |= (unsigned)(2 * j - 1 + k) < (unsigned)H ? 1 << k : 0;
+            if (tid >= 1 && tid <= kWTM) {  // rows 0 and 127 are halo only: their own outputs belong to the neighbouring tiles
+                bits |= 0x100;
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) bits |= (unsigned)(w + kw - 1) < (unsigned)W ? 16 << kw : 0;
+                bits |= 2 * j + 1 < H ? 0x80 : 0;
+            }
+            ri.y = bits;
+        }
+        rinfo[tid] = ri;
+    }
+    if (mat) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) w_issue(0, ks, 0);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) w_issue(1, ks, 1);
+    }
+    if (tid < 64) {
+        bias_lds[tid] = p.bias[tn * 64 + tid], post_lds[tid] = p.post[tn * 64 + tid];
+        // (buffer tid >> 5, plane (tid >> 3) & 3, 16 bytes each: the 128 bytes of a zero row that are read)
+        *reinterpret_cast<pl_u32x4 *>(smem + (tid >> 5) * kWLdsV + ((tid >> 3) & 3) * kWPlaneB + T * kWRowB + (tid & 7) * 16) = pl_u32x4{0u, 0u, 0u, 0u};
+    }
+    lds_barrier();  // the row table is there
+    {
+        pl_u32x4 th[4], tl[4];
+        titem_issue(0, tid, th, tl);
+        titem_finish(smem, tid, th, tl);
+    }
+    trace(2);
+    lds_barrier();
+    trace(3);
+
+    const int lrow[2] = {wm * 64 + frow, wm * 64 + 32 + frow};  // this lane's V rows (tile-pixel m0 - 1 + lrow; its column taps: lrow + kw - 1)
+    const int cb0 = wn * 32 + 4 * kh;                            // first of this lane's output channels inside the column tile
+    // where this lane's two tile-pixels read their three column taps in buffer 0: V row lrow + kw - 1, or the zero row where the tap
+    // falls off the window or the tile
+    int asrc[2][3];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const uint32_t mk = (uint32_t)rinfo[lrow[i]].y >> 4;
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) asrc[i][kw] = (((mk >> kw) & 1u) ? lrow[i] + kw - 1 : T) * kWRowB + kh * 16;
+    }
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int xi = 0; xi < 4; ++xi)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[xi][i][e] = 0.f;
+
+    // the tap loop of slab s32 on V buffer s32 & 1 (matrix waves)
+    auto taps = [&](int s32) __attribute__((always_inline)) {
+        const char *const vb = smem + (s32 & 1) * kWLdsV;
+        const char *as[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) as[i][kw] = vb + asrc[i][kw];
+        pl_u32x4 xh[2][2], xl[2][2];  // operand registers of the tile-pixels: two stages (k-step 0 / 1 of a tap)
+        auto frags = [&](int tap, int ks, int st) __attribute__((always_inline)) {
+            const int xi = tap / 3, kw = tap % 3;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const char *src = as[i][kw] + xi * kWPlaneB + ks * 32;
+                xh[st][i] = *reinterpret_cast<const pl_u32x4 *>(src);
+                xl[st][i] = *reinterpret_cast<const pl_u32x4 *>(src + 64);
+            }
+        };
+        frags(0, 0, 0);
+#pragma unroll
+        for (int tap = 0; tap < 12; ++tap) {
+            const int xi = tap / 3, slot = tap & 1;
+            const int cc = s32 * 12 + tap;
+            int ccn = cc + 2;
+            if (ccn >= NCH) ccn -= NCH;  // (the last two refills of the tile are not used: in bounds, as in the merged kernel's last tile)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                if (ks == 0) frags(tap, 1, 1);
+                else if (tap != 11) frags(tap + 1, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (!(ABL & 8)) {
+                    acc[xi][0] = mma(acc[xi][0], wq[slot][ks][0], xl[ks][0]);
+                    acc[xi][1] = mma(acc[xi][1], wq[slot][ks][0], xl[ks][1]);
+                    acc[xi][0] = mma(acc[xi][0], wq[slot][ks][1], xh[ks][0]);
+                    acc[xi][1] = mma(acc[xi][1], wq[slot][ks][1], xh[ks][1]);
+                    acc[xi][0] = mma(acc[xi][0], wq[slot][ks][0], xh[ks][0]);
+                    acc[xi][1] = mma(acc[xi][1], wq[slot][ks][0], xh[ks][1]);
+                } else {
+                    acc[xi][0][ks] += __uint_as_float(wq[slot][ks][0][0] ^ xl[ks][0][1] ^ xh[ks][1][2] ^ wq[slot][ks][1][3]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                w_issue(slot, ks, ccn);
+            }
+        }
+    };
+
+#pragma unroll 1
+    for (int s32 = 0; s32 + 1 < NS32; ++s32) {
+        if (mat) {
+            taps(s32);
+        } else if constexpr (!(ABL & 2)) {  // slab s32 + 1 into the buffer slab s32 - 1 was read from
+            pl_u32x4 ta_h[4], ta_l[4], tb_h[4], tb_l[4];
+            char *const vnext = smem + ((s32 + 1) & 1) * kWLdsV;
+            titem_issue(s32 + 1, tid - kPlThreads, ta_h, ta_l);
+            titem_issue(s32 + 1, tid, tb_h, tb_l);
+            titem_finish(vnext, tid - kPlThreads, ta_h, ta_l);
+            titem_finish(vnext, tid, tb_h, tb_l);
+        }
+        trace(10 + s32);
+        lds_barrier();  // slab s32 has been read and slab s32 + 1 has been written
+        trace(20);
+    }
+
+    // ---- the last slab and the epilogue: output transform in registers, bias, the two output rows of every tile-pixel through LDS, then
+    // (output pixel, 8-channel) items idx = tid + 512 k, k = 0..3 -> staged row pr = idx >> 3 (output row of the pair = pr >> 7, V row =
+    // pr & 127), channel group g = idx & 7: residual, ReLU, split, two 16-byte stores.  The residual pixels are requested EARLY: by the
+    // transform waves under the last tap loop, by the matrix waves before they stage their accumulators
+    float omax = 0.f;
+    uint32_t ioff[4];
+    pl_u32x4 rh[4], rl[4];
+    auto item_request = [&](int k) __attribute__((always_inline)) {
+        const int idx = tid + kWtThreads * k;
+        const int pr = idx >> 3, g = idx & 7;
+        const int2 ri = rinfo[pr & (kWRows - 1)];
+        const bool ok = (ri.y >> ((pr >> 7) ? 7 : 8)) & 1;
+        ioff[k] = ok ? (uint32_t)ri.x + (uint32_t)(1 + (pr >> 7)) * rowB + (uint32_t)(tn * 256 + g * 16) : kPlOob;
+        if constexpr (RES) {
+            rh[k] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ioff[k], 0, 0));
+            rl[k] = __builtin_bit_cast(pl_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ioff[k], 128, 0));
+        }
+    };
+    char *const stage = smem + (NS32 & 1) * kWLdsV;  // the buffer the last slab does not read
+    if (mat) {
+        taps(NS32 - 1);
+        trace(10 + NS32 - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) item_request(k);
+        if constexpr (ABL & 4) {
+            float sacc = 0.f;
+#pragma unroll
+            for (int xi = 0; xi < 4; ++xi) sacc += acc[xi][0][0] + acc[xi][1][3];
+            if (sacc == 12345.f) p.range_flag[1] = 1u;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias_lds + cb0 + 8 * q);
+                    const f32x4 sv = *reinterpret_cast<const f32x4 *>(post_lds + cb0 + 8 * q);
+                    f32x4 y0, y1;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float a0 = acc[0][i][4 * q + e], a1 = acc[1][i][4 * q + e], a2 = acc[2][i][4 * q + e], a3 = acc[3][i][4 * q + e];
+                        y0[e] = __builtin_fmaf((a0 + a1) + a2, sv[e], bv[e]);
+                        y1[e] = __builtin_fmaf((a1 - a2) - a3, sv[e], bv[e]);
+                    }
+                    // (staged row = 128 * output row of the pair + V row: consecutive lanes 272 B apart, conflict-free 16-byte writes)
+                    *reinterpret_cast<f32x4 *>(stage + lrow[i] * kPlRowB + (cb0 + 8 * q) * 4) = y0;
+                    *reinterpret_cast<f32x4 *>(stage + (kWRows + lrow[i]) * kPlRowB + (cb0 + 8 * q) * 4) = y1;
+                }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) item_request(k);
+    }
+    trace(31);
+    lds_barrier();  // the output tile is staged
+    trace(32);
+    if constexpr (!(ABL & 4)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int idx = tid + kWtThreads * k;
+            const int pr = idx >> 3, g = idx & 7;
+            f32x4 a = *reinterpret_cast<const f32x4 *>(stage + pr * kPlRowB + g * 32);
+            f32x4 b = *reinterpret_cast<const f32x4 *>(stage + pr * kPlRowB + g * 32 + 16);
+            if constexpr (RES) {
+                const f16x8 h8 = __builtin_bit_cast(f16x8, rh[k]), l8 = __builtin_bit_cast(f16x8, rl[k]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a[e] += (float)h8[e] + (float)l8[e];
+                    b[e] += (float)h8[4 + e] + (float)l8[4 + e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a[e] = __int_as_float(max(__float_as_int(a[e]), 0));
+                b[e] = __int_as_float(max(__float_as_int(b[e]), 0));
+            }
+            if (ioff[k] != kPlOob)  // (rows 0 and 127 of the tile and rows beyond the tensor carry no output)
+                omax = fmaxf(omax, fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3]))));
+            u32x2 pa[2], pb[2];
+            split2_f16(a, pa);
+            split2_f16(b, pb);
+            const pl_u32x4 hi = {pa[0][0], pa[0][1], pb[0][0], pb[0][1]}, lo = {pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
+            __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, ioff[k], 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, ioff[k], 128, 0);
+        }
+    }
+    trace(33);
+    if (p.range_flag && !(omax < kF16Range)) atomicOr(p.range_flag, 1u);
+}
+
 }  // namespace c3

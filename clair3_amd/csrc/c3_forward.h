@@ -235,11 +235,13 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             const int c1_rows = l == 1 ? (kPlBM + 2 * ww[l] + 2 + 31) / 32 * 32 : kPlBM;
             ps.mfma(2.0 * tiles_x * kPlBM * (double)Cout * 9.0 * cin * 3 + (src8 ? 2.0 * tiles_m * c1_rows * 64.0 * (m->C == 8 ? 80.0 : 96.0) * 2 : 0.0), true);
             m->choice.s1[(l / 3) * 2 + (l % 3 - 1)] = 'd';
+            m->choice.wform[(l / 3) * 2 + (l % 3 - 1)] = '-';
             // F(2,3) along H (c3_conv3w.h) for the plain plane-to-plane layers: 12 instead of 18 groups of piece products per output
             // pair.  Not where conv1 is computed inside the kernel (res1a / res1b) or the pyramid pooling is its epilogue (res3b):
             // those stay on the direct kernel.  C3HIP_WINO: 0 none, 1 the 64- / 128-channel ones, 2 (default) every plain one -- same-box
-            // A/B of the whole step (profiles/r05_e_ab_wino_step*.txt): B = 256 707 k -> 729 k windows/s (res2a / res2b 48.3 / 50.3 -> 41.7 /
-            // 43.8 us; res3a unchanged: 244 tiles = one workgroup per CU), B = 1000 774 k -> 804 k (res3a 172 -> 148.5 us as well).
+            // A/B of the whole step in round 5 (profiles/r05_e_ab_wino_step*.txt): B = 256 707 k -> 729 k windows/s (res2a / res2b 48.3 / 50.3
+            // -> 41.7 / 43.8 us; res3a unchanged THEN: 244 tiles = one workgroup per CU, which is what the transform-waves form below is
+            // for), B = 1000 774 k -> 804 k (res3a 172 -> 148.5 us as well).
             const bool wino_layer = m->wino >= 2 || (m->wino == 1 && (Cout == 64 || Cout == 128));
             if (wino_layer && !src8 && !sppf && m->wconv_w[l]) {
                 WinoConvParams wp;
@@ -251,11 +253,33 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                 const int tiles_w = (wp.Mp + kWTM - 1) / kWTM;
                 wp.tiles = tiles_w * (Cout / 64);
                 ps.mfma(2.0 * tiles_w * kWRows * (double)Cout * 12.0 * cin * 3, true);
+                // Launches that leave the second workgroup slot of every CU empty take the transform-waves form (c3_conv3w.h): one
+                // 512-thread workgroup per tile, whose waves 4-7 transform the next slab under the tap loop of waves 0-3; rows are
+                // bit-identical.  It takes a whole CU's LDS, so not where the handle is TOLD or KNOWS that other batches need the CUs:
+                // `beside` is the caller's hint (c3_model_set_sharing: several handles feed the chip) or the ring's own finding that this
+                // batch and those in its other lanes together oversubscribe the CUs on half tiles (c3_hostring.h LaneSharing: beyond
+                // ~1000 windows in flight).  Smaller batches in three lanes (3 x 256 windows) keep beside == 1 and each takes the form.
+                // kWtMaxTiles: the tile count up to which it is taken, in CUs.  Same box, builds alternated (profiles/wino_transform_waves.txt):
+                // res3a at B = 256 (244 tiles) 45.0 -> 37.1 us, the step 744 k -> 764 k windows/s; with 2 (res2a / res2b, 440 tiles in two
+                // rounds) 42.1 / 40.1 -> 41.2 / 40.3 us and a step inside the run-to-run spread of 1: not taken.
+                constexpr int kWtMaxTiles = 1;
+                const int beside = std::max(m->sharing, m->lane_sharing);
+                const bool tw = wp.tiles <= kWtMaxTiles * (m->wg_slots / 2) && beside <= 1;
+                m->choice.wform[(l / 3) * 2 + (l % 3 - 1)] = tw ? 't' : 'p';
                 int gw = wp.tiles;
                 const int wslots = m->wg_slots, wunit = 8 * (Cout / 64);
                 if (gw > wslots) gw = std::max(wunit, wslots / wunit * wunit);
-                const dim3 wgrid(gw), wblock(kPlThreads);
-                if (Cout == 64) {
+                const dim3 wgrid(gw), wblock(tw ? kWtThreads : kPlThreads);
+                if (tw && Cout == 64) {
+                    if (res) hipLaunchKernelGGL((conv3x3_wino_tw_kernel<64, true>), wgrid, wblock, 0, s, wp);
+                    else hipLaunchKernelGGL((conv3x3_wino_tw_kernel<64, false>), wgrid, wblock, 0, s, wp);
+                } else if (tw && Cout == 128) {
+                    if (res) hipLaunchKernelGGL((conv3x3_wino_tw_kernel<128, true>), wgrid, wblock, 0, s, wp);
+                    else hipLaunchKernelGGL((conv3x3_wino_tw_kernel<128, false>), wgrid, wblock, 0, s, wp);
+                } else if (tw) {
+                    if (res) hipLaunchKernelGGL((conv3x3_wino_tw_kernel<256, true>), wgrid, wblock, 0, s, wp);
+                    else hipLaunchKernelGGL((conv3x3_wino_tw_kernel<256, false>), wgrid, wblock, 0, s, wp);
+                } else if (Cout == 64) {
                     if (res) hipLaunchKernelGGL((conv3x3_wino_planes_kernel<64, true>), wgrid, wblock, 0, s, wp);
                     else hipLaunchKernelGGL((conv3x3_wino_planes_kernel<64, false>), wgrid, wblock, 0, s, wp);
                 } else if (Cout == 128) {

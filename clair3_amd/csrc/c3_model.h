@@ -325,6 +325,7 @@ struct c3_model {
         const char *lstm1 = "-", *proj2 = "-", *lstm2 = "-", *fa = "-";
         const char *s2[2] = {"-", "-"};  // conv3, conv5: one or two workgroups per CU (c3_conv3s2.h PAIR)
         char s1[8] = "------";           // the six stride-1 convolutions res1a .. res3b: d = direct, w = F(2,3) along H
+        char wform[8] = "------";        // ... and the form of the F(2,3) ones (c3_conv3w.h): p = paired workgroups, t = transform waves
     } choice;
 
     bool prof = false;

@@ -277,11 +277,21 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
-    else
+    else {
+        // wino_form: the form of every F(2,3) layer of the last pass (c3_conv3w.h), res2a:paired/res2b:paired/res3a:transform-waves, "-" without
+        // one.  The row counters stay the last three fields, pack_rows the last one
+        static const char *const names[6] = {"res1a", "res1b", "res2a", "res2b", "res3a", "res3b"};
+        char wf[160] = "";
+        for (int i = 0; i < 6; ++i)
+            if (m->choice.s1[i] == 'w') {
+                const size_t at = strlen(wf);
+                snprintf(wf + at, sizeof(wf) - at, "%s%s:%s", at ? "/" : "", names[i], m->choice.wform[i] == 't' ? "transform-waves" : "paired");
+            }
         snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
-                 "precision=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
+                 "precision=%s wino_form=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
                  m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
-                 m->precision, (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+                 m->precision, wf[0] ? wf : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+    }
     if (m->verify_seen) {  // verify mode is or was on (c3_verify.h): the setting and the totals behind everything else
         const c3_verify_stats &t = m->vstats;
         const size_t at = strlen(buf);

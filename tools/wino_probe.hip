@@ -4,7 +4,8 @@
 // 1. correctness: both kernels on the same random planes / weights / residual; max |difference| between them and of each against
 //    an fp64 host evaluation of sampled outputs (small batches with ragged tails, then B = 256);
 // 2. time: direct whole, Winograd whole and with parts switched off (ABL bits: 1 no weight loads, 2 no transform after the first,
-//    4 no epilogue, 8 no matrix instructions, 16 transform loads not requested ahead), one and two workgroups per CU.
+//    4 no epilogue, 8 no matrix instructions, 16 transform loads not requested ahead), one and two workgroups per CU; the
+//    transform-waves form (conv3x3_wino_tw_kernel) whole, without its transform, without its epilogue, and its two roles' phase trace.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -43,6 +44,10 @@ static void put16(uint16_t *q, size_t dst, float v) {
 
 template <int C, bool RES, int ABL> static void launch_w(const WinoConvParams &wp, int grid) {
     hipLaunchKernelGGL((conv3x3_wino_planes_kernel<C, RES, ABL>), dim3(grid), dim3(kPlThreads), 0, 0, wp);
+}
+
+template <int C, bool RES, int ABL> static void launch_tw(const WinoConvParams &wp) {  // one workgroup per tile
+    hipLaunchKernelGGL((conv3x3_wino_tw_kernel<C, RES, ABL>), dim3(wp.tiles), dim3(kWtThreads), 0, 0, wp);
 }
 
 template <int C, bool RES, int ABL, int RT = 2, int WD = 4> static void launch_w16(const WinoConvParams &wp, int grid) {
@@ -179,6 +184,17 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
         for (size_t i = 0; i < a.size(); ++i) mixdiff += a[i] != b2[i];
         hipFree(yw2);
     }
+    size_t twdiff = 0;
+    {   // the transform-waves form (one 512-thread workgroup per tile, any number of rounds): the same planes bit for bit
+        void *yw5; CK(hipMalloc(&yw5, bytes)); CK(hipMemset(yw5, 0xff, bytes));
+        WinoConvParams w5 = wp; w5.out = yw5;
+        launch_tw<C, true, 0>(w5);
+        CK(hipGetLastError()); CK(hipDeviceSynchronize());
+        std::vector<uint32_t> a(bytes / 4), b2(bytes / 4);
+        CK(hipMemcpy(a.data(), yw, bytes, hipMemcpyDeviceToHost)); CK(hipMemcpy(b2.data(), yw5, bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < a.size(); ++i) twdiff += a[i] != b2[i];
+        hipFree(yw5);
+    }
     size_t w16diff = 0, s16diff = 0; double w16max = 0, s16max = 0;
     {   // the LDS-DMA / 16-channel-slab form: the same V values, the same products per accumulator in the same channel order
         void *yw3; CK(hipMalloc(&yw3, bytes)); CK(hipMemset(yw3, 0xff, bytes));
@@ -214,6 +230,7 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
     printf("  max|y| %.3f  max|wino - direct| %.3e (at pixel %zu ch %zu: direct %.6f wino %.6f)  NaN/unwritten in wino %zu\n", ymax, dmax, worst / C, worst % C,
            hd[worst], hw[worst], nan_w);
     printf("  vs fp64 host on %d sampled outputs: direct %.3e  wino %.3e;  words differing between the two transform forms: %zu\n", samples + 4, ed, ew, mixdiff);
+    printf("  words differing between the transform-waves form and the paired one: %zu\n", twdiff);
     printf("  wino16 (LDS-DMA, 16-channel slabs) against wino: %zu values differ, max |difference| %.3e\n", w16diff, w16max);
     printf("  wino16 with 64-row tiles against wino: %zu values differ, max |difference| %.3e\n", s16diff, s16max);
     if (timing && split_only) {
@@ -273,6 +290,24 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
         printf("  wino no loads/transform/epi  %6.1f us\n", time_it([&] { launch_w<C, true, 7>(wp, gw); }));
         printf("  wino no MFMA                 %6.1f us\n", time_it([&] { launch_w<C, true, 8>(wp, gw); }));
         printf("  wino loads not ahead         %6.1f us\n", time_it([&] { launch_w<C, true, 16>(wp, gw); }));
+        printf("  wino transform waves         %6.1f us (one 512-thread workgroup per tile: %d tiles on %d CUs)\n", time_it([&] { launch_tw<C, true, 0>(wp); }), wp.tiles, cus);
+        printf("  transform waves no transform %6.1f us\n", time_it([&] { launch_tw<C, true, 2>(wp); }));
+        printf("  transform waves no epilogue  %6.1f us\n", time_it([&] { launch_tw<C, true, 4>(wp); }));
+        {   // shader-clock trace of workgroup 0: matrix wave 0 and transform wave 4
+            long long *tb; CK(hipMalloc(&tb, 2 * 256 * 16)); CK(hipMemset(tb, 0, 2 * 256 * 16));
+            WinoConvParams wt = wp; wt.trace = tb;
+            launch_tw<C, true, 32>(wt); launch_tw<C, true, 32>(wt);
+            CK(hipDeviceSynchronize());
+            std::vector<long long> ht(2 * 256 * 2);
+            CK(hipMemcpy(ht.data(), tb, ht.size() * 8, hipMemcpyDeviceToHost));
+            for (int role = 0; role < 2; ++role) {
+                printf("  transform waves, trace of %s (tag:+cycles; 2 first slab transformed 3 barrier; 10+s slab s: taps done / slab s+1 written, 20 barrier; 31 staged / residual requested 32 barrier 33 stored):\n   ", role ? "transform wave 4" : "matrix wave 0");
+                for (int i = 1; i < 250 && ht[(role * 256 + i) * 2] != 0; ++i)
+                    printf(" %lld:+%lld", ht[(role * 256 + i) * 2], ht[(role * 256 + i) * 2 + 1] - ht[(role * 256 + i - 1) * 2 + 1]);
+                printf("\n");
+            }
+            hipFree(tb);
+        }
         WinoConvParams w6 = wp; w6.wf = wfw16;
         printf("  wino16 full                  %6.1f us\n", time_it([&] { launch_w16<C, true, 0>(w6, gw); }));
         printf("  wino16 no weight loads       %6.1f us\n", time_it([&] { launch_w16<C, true, 1>(w6, gw); }));
@@ -348,6 +383,13 @@ int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "split")) {  // round 6: what a split-K launch of the under-filled layers could take at most (no exchange)
         if (shape<256>("res3 split-K bound", 256, 12, 5, cus, true, true)) return 1;
         if (shape<128>("res2 split-K bound", 256, 23, 9, cus, true, true)) return 1;
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "tw")) {  // the transform-waves form: one round (res3a at B = 256, res2 at 149) and two (res2 at 256)
+        if (shape<256>("res3-small", 7, 12, 5, cus, false)) return 1;
+        if (shape<256>("res3", 256, 12, 5, cus, true)) return 1;
+        if (shape<128>("res2 B=149", 149, 23, 9, cus, true)) return 1;
+        if (shape<128>("res2", 256, 23, 9, cus, true)) return 1;
         return 0;
     }
     if (argc > 1 && !strcmp(argv[1], "big")) {  // the counter passes of tools/wino_pmc.sh: the two res2 batches only
