@@ -27,9 +27,12 @@ EXPORTS = (
     "c3_predict_submit_candidates", "c3_predict_pileup_candidates",
     "c3_predict_submit_rows", "c3_predict_rows", "c3_pack_rows",
     "c3_model_set_verify", "c3_model_verify_stats", "c3_model_verify_reset",
+    "c3_model_set_verify_layers", "c3_model_verify_layers",
 )
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
+# status of a layer of verify mode's layer records (C3_VERIFY_LAYER_* in include/c3hip.h)
+VERIFY_LAYER_STATUS = {0: "none", 1: "compared", 2: "fused"}
 
 
 class RowsConfig(C.Structure):
@@ -58,6 +61,13 @@ class VerifyStats(C.Structure):
                 ("label_diffs", C.c_int64 * 4), ("near_ties", C.c_int64 * 4), ("escalations", C.c_int64),
                 ("max_abs_diff", C.c_float), ("head_max_abs_diff", C.c_float * 4), ("tol", C.c_float), ("near_tie", C.c_float),
                 ("every", C.c_int32), ("policy", C.c_int32)]
+
+
+class VerifyLayer(C.Structure):
+    """c3_verify_layer (include/c3hip.h)"""
+    _fields_ = [("name", C.c_char * 16), ("status", C.c_int32), ("reserved", C.c_int32), ("batches", C.c_int64), ("windows", C.c_int64),
+                ("worst_batch", C.c_int64), ("worst_window", C.c_int64), ("worst_index", C.c_int64), ("max_abs_diff", C.c_float),
+                ("ref_max_abs", C.c_float), ("test_max_abs", C.c_float), ("reserved2", C.c_float)]
 
 
 class C3Error(RuntimeError):
@@ -155,6 +165,8 @@ def lib():
     L.c3_model_set_verify.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]
     L.c3_model_verify_stats.argtypes = [C.c_void_p, C.POINTER(VerifyStats)]
     L.c3_model_verify_reset.argtypes = [C.c_void_p]
+    L.c3_model_set_verify_layers.argtypes = [C.c_void_p, C.c_int]
+    L.c3_model_verify_layers.argtypes = [C.c_void_p, C.POINTER(VerifyLayer), C.c_int]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

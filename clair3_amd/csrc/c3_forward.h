@@ -20,8 +20,56 @@ static int64_t tap_window_floats(const c3_model *m, int id) {
         default: return (int64_t)m->positions * 320;
     }
 }
+// ---- layer records of a verified batch (c3_verify.h; c3_hostring.h sets layer_pass around its two forward passes) ----
+// The product pass (1) keeps the n windows of tensor `id` in the slot's buffer, at the part's windows of the batch; the fp32 pass (2) compares
+// what it just wrote at src with them, one launch per layer and part.  A tensor the product form did not produce is not compared
+static int layer_tap(c3_model *m, hipStream_t s, int id, const void *src, int64_t n, bool planes) {
+    HostSlot &sl = *m->layer_slot;
+    const int64_t pw = tap_window_floats(m, id), first = m->tap_base - m->tap_call_off;
+    if (pw % 8) return fail("internal: %s has %lld values per window, the compare kernel takes 8 at a time", kTapName[id], (long long)pw);
+    if (sl.layer_dropped) return 0;
+    if (m->layer_pass == 1) {
+        const size_t bytes = (size_t)(m->layer_batch * pw) * sizeof(float);
+        if (bytes > sl.layer_bytes[id]) {  // (the slot is free: nothing reads the smaller one)
+            if (sl.layer_buf[id]) (void)hipFree(sl.layer_buf[id]);
+            sl.layer_buf[id] = nullptr, sl.layer_bytes[id] = 0;
+            if (hipMalloc((void **)&sl.layer_buf[id], bytes) != hipSuccess) {
+                // no room for this batch's layer outputs: the prediction goes on, the batch brings no layer record (none of its layers counts)
+                (void)hipGetLastError();
+                sl.layer_buf[id] = nullptr, sl.layer_dropped = true, sl.layer_kept = 0;
+                return 0;
+            }
+            sl.layer_bytes[id] = bytes;
+        }
+        HIP_TRY(hipMemcpyAsync(sl.layer_buf[id] + first * pw, src, (size_t)(n * pw) * sizeof(float), hipMemcpyDeviceToDevice, s));
+        sl.layer_kept |= 1u << id;
+        if (planes) sl.layer_planes |= 1u << id;
+        return 0;
+    }
+    if (!(sl.layer_kept >> id & 1u)) return 0;
+    if (planes) return fail("internal: the fp32 forms write no planes");
+    const int blocks = (int)std::min<int64_t>(kLayerMaxBlocks, std::max<int64_t>(1, (n * (pw / 8) + kLayerThreads - 1) / kLayerThreads));
+    if (sl.layer_parts[id] + blocks > sl.layer_part_stride) return fail("internal: layer partials of %s", kTapName[id]);
+    LayerCompareParams cp;
+    cp.a = sl.layer_buf[id] + first * pw, cp.b = (const float *)src, cp.exp = nullptr, cp.cshift = 0;
+    cp.kept = m->layer_kept_count;
+    cp.part = sl.layer_part + (size_t)id * sl.layer_part_stride + sl.layer_parts[id];
+    cp.pw8 = (uint32_t)(pw / 8), cp.planes = (sl.layer_planes >> id & 1u) != 0;
+    cp.first = (uint32_t)first, cp.n = (uint32_t)n, cp.batch = (uint32_t)m->layer_batch;
+    int C = cp.planes ? (m->kind == C3_KIND_PILEUP ? 256 : kConvCout[id]) : 8;
+    if (m->kind == C3_KIND_FULL_ALIGNMENT && id <= kTapSpp && !m->act_exp[std::min(id, 8)].empty()) {
+        cp.exp = m->layer_exp + std::min(id, 8) * 256, C = (int)m->act_exp[std::min(id, 8)].size();
+    }
+    while ((8 << cp.cshift) < C) ++cp.cshift;
+    if ((8 << cp.cshift) != C || pw % C) return fail("internal: %s has %d channels", kTapName[id], C);
+    hipLaunchKernelGGL(layer_compare_kernel, dim3((unsigned)blocks), dim3(kLayerThreads), 0, s, cp);
+    HIP_TRY(hipGetLastError());
+    sl.layer_parts[id] += blocks;
+    return 0;
+}
 // the n windows of tensor `id` that the launch just enqueued on s wrote at src: behind it on s, into the tap buffer at the part's windows
 static int tap(c3_model *m, hipStream_t s, int id, const void *src, int64_t n, bool planes = false) {
+    if (m->layer_pass) return layer_tap(m, s, id, src, n, planes);  // (a verified batch: no user tap is set, c3_hostring.h verify_select)
     if (!(m->tap_mask >> id & 1u)) return 0;
     const int64_t pw = tap_window_floats(m, id);
     HIP_TRY(hipMemcpyAsync(m->tap_dev[id] + m->tap_base * pw, src, (size_t)(n * pw) * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -223,7 +223,7 @@ static const int32_t *deep_depths(c3_model *m, const RingInput &in) {
 
 // THE layout of a staged batch (c3_model.h StagedBatch), for every kind: nothing else computes an offset.  The kernels' alignment
 // assumptions hang on it: sections from multiples of 256 bytes, the 8-byte pieces of expand_rows_kernel, the 16-byte pieces of host_copy_kernel
-static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth, bool verify = false) {
+static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth, bool verify = false, bool layers = false) {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const bool cand = in.kind == InKind::Candidates, region = cand || in.kind == InKind::Region, rows = is_rows(in.kind);
     const size_t n = (size_t)in.batch, db = with_depth ? n * sizeof(int32_t) : 0;
@@ -249,6 +249,8 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
     p.y_total = cand ? p.kept.off + p.kept.bytes : p.y.bytes;
     // ... and a verified batch's record (c3_verify.h) behind them; rows that stay on the device: the record is all the slot's output buffer holds
     if (verify) p.verify.off = in.y_dev ? 0 : al(p.y_total), p.verify.bytes = kVerifyRecordBytes, p.y_total = p.verify.off + p.verify.bytes;
+    // ... and its layer records (c3_model_set_verify_layers) behind that
+    if (verify && layers) p.layers.off = p.y_total, p.layers.bytes = kLayerRecordsBytes, p.y_total = p.layers.off + p.layers.bytes;
     return p;
 }
 
@@ -338,7 +340,7 @@ static void fill_packed_rows(const c3_model *m, const HostSlot &sl, const RingIn
     if (nrun == 1) {  // the layout of these rows handed over
         RingInput found = in;
         found.kind = InKind::Rows, found.rows_total = rows[0];
-        p = plan_batch(m, found, false, p.verify.bytes != 0);
+        p = plan_batch(m, found, false, p.verify.bytes != 0, p.layers.bytes != 0);
     }
     memcpy((char *)sl.pin_x + p.rows_tab.off, tab.data(), p.rows_tab.bytes);
 }
@@ -401,6 +403,36 @@ static int ensure_shadow(HostSlot &sl, size_t row_bytes) {
     sl.shadow_part = part;
     return 0;
 }
+// ---- layer records (c3_model_set_verify_layers): the layers in network order as tap ids; returns how many
+static int verify_layer_ids(const c3_model *m, int ids[kLayerMaxLayers]) {
+    if (m->kind == C3_KIND_PILEUP) return ids[0] = kTapLstm1, ids[1] = kTapGx2, ids[2] = kTapLstm2, ids[3] = kTapL4, 4;
+    for (int k = 0; k <= kTapL4; ++k) ids[k] = k;
+    return kTapL4 + 1;
+}
+// what a batch with layer records needs before its first launch: the slot's partials (one launch per layer and micro-batch: a batch is
+// cut into at most ceil(batch / max_microbatch) of them, c3_model.h ensure_workspace), the channel exponents on the device, a clean count
+static int ensure_layers(c3_model *m, HostSlot &sl, int64_t batch) {
+    const int stride = (int)((batch + max_microbatch(m) - 1) / max_microbatch(m)) * kLayerMaxBlocks;
+    if (stride > sl.layer_part_stride) {
+        if (sl.layer_part) (void)hipFree(sl.layer_part);
+        sl.layer_part = nullptr, sl.layer_part_stride = 0;
+        HIP_TRY(hipMalloc((void **)&sl.layer_part, (size_t)kTapCount * stride * sizeof(LayerRecord)));
+        sl.layer_part_stride = stride;
+    }
+    if (!m->layer_exp_ok && m->kind == C3_KIND_FULL_ALIGNMENT) {
+        std::vector<int> e(9 * 256, 0);
+        for (int l = 0; l < 9; ++l) {
+            if (m->act_exp[l].size() > 256) return fail("internal: %zu channel exponents in layer %d", m->act_exp[l].size(), l);
+            std::copy(m->act_exp[l].begin(), m->act_exp[l].end(), e.begin() + l * 256);
+        }
+        if (!m->layer_exp) HIP_TRY(hipMalloc((void **)&m->layer_exp, e.size() * sizeof(int)));
+        TRY(h2d_staged(m->layer_exp, e.data(), e.size() * sizeof(int)));
+        m->layer_exp_ok = true;
+    }
+    sl.layer_kept = sl.layer_planes = 0, sl.layer_dropped = false;
+    for (int &n : sl.layer_parts) n = 0;
+    return 0;
+}
 // The batch again on the fp32 forms, same lane and stream, from the same staged input -- the call range_guard_rerun makes, without touching
 // `precision`: a region batch gathers again, depths rescale again, rows expand again, a candidate batch reuses its compacted starts (the
 // selection does NOT run again).  Then the compare kernels; the record lands in the slot's output buffer.  What c3_model_describe reports
@@ -411,10 +443,22 @@ static int shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, const Sta
     const c3_model::Choices reported = m->choice;
     const bool f16 = m->f16_ok, planes = lane(m).last_planes;
     m->f16_ok = false;
+    if (p.layers.bytes) m->layer_pass = 2;  // every layer's compare launch goes behind the launch that wrote it (c3_forward.h layer_tap)
     const int rc = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, sl.shadow, sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth),
                                   sl.dev<const ExpandEntry>(p.rows_tab));
-    m->f16_ok = f16, lane(m).last_planes = planes, m->choice = reported;
+    m->f16_ok = f16, lane(m).last_planes = planes, m->choice = reported, m->layer_pass = 0;
     TRY(rc);
+    if (p.layers.bytes) {  // one wave per layer: the partials of its launches -> its record
+        LayerFinalParams fp;
+        int ids[kLayerMaxLayers];
+        const int nl = verify_layer_ids(m, ids);
+        fp.part = sl.layer_part, fp.kept = m->layer_kept_count, fp.out = (LayerRecord *)((char *)sl.dev_y + p.layers.off);
+        fp.batch = (int)in.batch;
+        for (int k = 0; k < kLayerMaxLayers; ++k) fp.part_at[k] = fp.n_parts[k] = 0;
+        for (int k = 0; k < nl; ++k) fp.part_at[k] = ids[k] * sl.layer_part_stride, fp.n_parts[k] = sl.layer_parts[ids[k]];  // (partials by tap id, records in network order)
+        hipLaunchKernelGGL(layer_compare_final_kernel, dim3((unsigned)nl), dim3(64), 0, s, fp);
+        HIP_TRY(hipGetLastError());
+    }
     CompareParams cp;
     cp.a = in.y_dev ? in.y_dev : sl.dev_y, cp.b = sl.shadow;
     cp.kept = in.kind == InKind::Candidates ? (const uint32_t *)((const char *)sl.dev_y + p.kept.off) : nullptr;
@@ -448,6 +492,26 @@ static bool verify_account(c3_model *m, const HostSlot &sl) {
     return true;
 }
 
+// ... and its layer records, when it brought some, join the layers' totals (the rule of worst_batch above, per layer)
+static void verify_layers_account(c3_model *m, const HostSlot &sl) {
+    if (!sl.plan.layers.bytes) return;
+    const LayerRecord *r = (const LayerRecord *)((const char *)sl.pin_y + sl.plan.layers.off);
+    int ids[kLayerMaxLayers];
+    const int nl = verify_layer_ids(m, ids);
+    bool any = false;
+    for (int k = 0; k < nl; ++k) any |= r[k].compared != 0;
+    if (!any) return;  // (the slot had no room for the layer outputs: c3_forward.h layer_tap)
+    ++m->vlayer_batches;
+    for (int k = 0; k < nl; ++k) {
+        if (!r[k].compared) continue;
+        c3_verify_layer &t = m->vlayer[k];
+        ++t.batches, t.windows += r[k].windows;
+        if (t.worst_batch < 0 || r[k].max_abs > t.max_abs_diff)
+            t.worst_batch = sl.verify_ordinal, t.worst_window = r[k].window, t.worst_index = r[k].index, t.max_abs_diff = r[k].max_abs;
+        t.ref_max_abs = std::max(t.ref_max_abs, r[k].ref_max), t.test_max_abs = std::max(t.test_max_abs, r[k].test_max);
+    }
+}
+
 // ---- launch, on the active lane's stream: the selection in front of a candidate batch, the forward pass, the rows on their way out
 static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p) {
     hipStream_t s = lane(m).stream;
@@ -462,8 +526,15 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
         TRY(run_select(m, s, sp));
     }
     const bool f16 = m->f16_ok;
-    TRY(forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, sl.dev<const int32_t>(p.starts),
-                       sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
+    if (p.layers.bytes) {  // layer records: the product pass keeps its layer outputs in the slot (c3_forward.h layer_tap)
+        TRY(ensure_layers(m, sl, in.batch));
+        m->layer_slot = &sl, m->layer_batch = in.batch, m->layer_pass = 1;
+        m->layer_kept_count = in.kind == InKind::Candidates ? (const uint32_t *)((const char *)sl.dev_y + p.kept.off) : nullptr;
+    }
+    const int rc_product = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, sl.dev<const int32_t>(p.starts),
+                                          sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab));
+    m->layer_pass = 0;
+    TRY(rc_product);
     if (in.y_dev && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, in.y_dev, in.batch * m->row, m->range_flag);
     if (p.verify.bytes) TRY(shadow_pass(m, sl, in, p));
@@ -471,7 +542,7 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
     // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
     hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                       in.y_dev ? p.verify.bytes / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+                       in.y_dev ? (p.verify.bytes + p.layers.bytes) / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_out, s));
     sl.used_f16 = f16;
@@ -507,11 +578,11 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
     const LaneSharing shared_chip_forms(m, in.batch, in_lane && !alone);
     const int32_t *depth = deep_depths(m, in);
     const bool verify = verify_select(m, in.batch, true, &sl.verify_ordinal);
-    StagedBatch p = plan_batch(m, in, depth != nullptr, verify);
+    StagedBatch p = plan_batch(m, in, depth != nullptr, verify, m->verify_layers);
     Filled f;
     if (in.batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
+        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes + p.layers.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
         switch (in.kind) {
         case InKind::Sliced: fill_sliced(sl, in, p, depth, f); break;
         case InKind::Region: fill_region(m, sl, in, p, depth, f); break;
@@ -592,6 +663,7 @@ int c3_predict_wait(c3_model *m, int slot) {
         HIP_TRY(hipStreamSynchronize(lane(m).stream));
     }
     if (sl.verified) {  // the range guard keeps priority: a batch it answered counts as skipped
+        if (!bad) verify_layers_account(m, sl);
         if (bad) ++m->vstats.batches_skipped;
         else if (verify_account(m, sl)) {  // escalate: the batch is answered with its rows on the fp32 forms, decoder columns included
             TRY(use_lane(m, sl.lane));
@@ -868,9 +940,14 @@ int c3_predict_pileup_candidates(c3_model *m, const void *region_host, int x_dty
 }
 
 // ---- verify mode (c3_verify.h): the setting and the totals ----
+static void verify_layers_zero(c3_model *m) {
+    for (c3_verify_layer &t : m->vlayer) t = c3_verify_layer{}, t.worst_batch = -1;
+    m->vlayer_batches = 0;
+}
 static void verify_zero(c3_model *m) {
     m->vstats = c3_verify_stats{};
     m->vstats.worst_batch = -1;
+    verify_layers_zero(m);
 }
 int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int policy) {
     if (!m) return fail("null model");
@@ -898,6 +975,31 @@ int c3_model_verify_reset(c3_model *m) {
         if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
     verify_zero(m);
     return 0;
+}
+
+// layer records (c3_verify.h): the switch, and the layers' totals in network order
+int c3_model_set_verify_layers(c3_model *m, int enable) {
+    if (!m) return fail("null model");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (enable && !m->verify_layers_seen) verify_layers_zero(m);
+    m->verify_layers = enable != 0, m->verify_layers_seen |= enable != 0;
+    return 0;
+}
+int c3_model_verify_layers(c3_model *m, c3_verify_layer *out, int max_entries) {
+    if (!m || (!out && max_entries > 0)) {
+        fail("null argument");
+        return -1;
+    }
+    if (!m->verify_layers_seen) return 0;
+    int ids[kLayerMaxLayers];
+    const int nl = verify_layer_ids(m, ids);
+    for (int k = 0; k < nl && k < max_entries; ++k) {
+        out[k] = m->vlayer[k];
+        snprintf(out[k].name, sizeof(out[k].name), "%s", kTapName[ids[k]]);
+        out[k].status = out[k].batches > 0 ? C3_VERIFY_LAYER_COMPARED : m->vlayer_batches > 0 ? C3_VERIFY_LAYER_FUSED : C3_VERIFY_LAYER_NONE;
+    }
+    return nl;
 }
 
 // the handle's scratch buffer of the two decoder entries below: grown, never shrunk

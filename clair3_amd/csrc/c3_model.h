@@ -13,7 +13,7 @@
 //   c3_comm.h      the gather of a sharded job on RCCL
 //   c3_verify.h    verify mode's two compare kernels and their record (included with the other kernels below): a selected batch of the ring
 //                  runs a second forward pass on the fp32 forms from the same staged input (c3_hostring.h shadow_pass) and the two sets of
-//                  rows are compared on the device
+//                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
@@ -134,6 +134,7 @@ struct StagedBatch {
     Section status;     // candidates: one status byte each
     Section kept;       // candidates: the count of kept candidates (16 bytes from a multiple of 16)
     Section verify;     // a verified batch (c3_verify.h): its VerifyRecord, behind the kept count (rows that stay on the device: the only section)
+    Section layers;     // ... with layer records (c3_model_set_verify_layers): one LayerRecord per layer in network order, behind the verify record
     size_t y_total = 0;
 };
 
@@ -167,6 +168,15 @@ struct HostSlot {
     int64_t verify_ordinal = 0;  // which submit of the handle this batch was (c3_verify_stats.worst_batch)
     float *shadow = nullptr;
     size_t shadow_bytes = 0, shadow_part = 0;  // shadow_part: offset of the partials
+    // ... with layer records: the product pass's layer outputs of the whole batch (copied behind the producing launches like a tap's, never
+    // into a user's tap buffers) and the layer compare kernel's partials.  The slot's like the shadow rows, allocated on first use
+    float *layer_buf[kTapCount] = {};
+    size_t layer_bytes[kTapCount] = {};
+    LayerRecord *layer_part = nullptr;
+    int layer_part_stride = 0;               // partials per layer the buffer holds
+    uint32_t layer_kept = 0, layer_planes = 0;  // of the batch in flight: tensors the product pass produced / as planes
+    bool layer_dropped = false;               // ... a buffer for them could not be allocated: the batch brings no layer record
+    int layer_parts[kTapCount] = {};          // ... and the partials written per tensor so far
     // a section of the staged batch on the device / in the pinned input buffer (nullptr: the batch has none)
     template <class T> T *dev(const Section &s) const { return s.bytes ? (T *)((char *)dev_x + s.off) : nullptr; }
     template <class T> T *pin(const Section &s) const { return s.bytes ? (T *)((char *)pin_x + s.off) : nullptr; }
@@ -296,6 +306,17 @@ struct c3_model {
     int verify_policy = C3_VERIFY_REPORT;
     bool verify_seen = false;  // verify mode is or was on: c3_model_describe ends on verify=...
     c3_verify_stats vstats = {};  // totals since the last load / reset (batches_submitted doubles as the selection counter)
+    // ... layer records (c3_model_set_verify_layers): off = nothing allocated, nothing launched, a verified batch laid out as without it
+    bool verify_layers = false;
+    bool verify_layers_seen = false;         // is or was on: c3_model_verify_layers lists the layers
+    c3_verify_layer vlayer[kLayerMaxLayers] = {};  // totals per layer in network order since the last load / reset
+    int64_t vlayer_batches = 0;              // batches that brought layer records
+    int *layer_exp = nullptr;                // device [9][256]: act_exp as the compare kernel reads it; uploaded on first use after a load
+    bool layer_exp_ok = false;
+    int layer_pass = 0;                      // forward_device is enqueuing 1: the product pass, 2: the fp32 pass of ...
+    HostSlot *layer_slot = nullptr;          // ... this slot's batch with layer records
+    int64_t layer_batch = 0;                 // ... of this many windows
+    const uint32_t *layer_kept_count = nullptr;  // ... a candidate batch: the device word with its kept count
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;

@@ -211,6 +211,7 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
     HIP_TRY(hipMemset(m->range_flag, 0, 256));
     HIP_TRY(hipDeviceSynchronize());  // (the handle's streams are non-blocking: the flag is zero before any of them runs again)
     verify_zero(m);  // verify mode: the totals were about the weights before; the setting stays
+    m->layer_exp_ok = false;  // (layer records: the channel exponents are these weights')
     m->loaded = true;
     return 0;
 }
@@ -301,6 +302,7 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  (long long)t.batches_checked, (long long)t.batches_skipped, (long long)t.windows_checked, (double)t.max_abs_diff,
                  (long long)t.rows_over_tol, (long long)(t.label_diffs[0] + t.label_diffs[1] + t.label_diffs[2] + t.label_diffs[3]),
                  (long long)(t.near_ties[0] + t.near_ties[1] + t.near_ties[2] + t.near_ties[3]), (long long)t.escalations);
+        if (m->verify_layers) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), ",layers:1");
     }
     return 0;
 }
@@ -329,6 +331,7 @@ int c3_model_destroy(c3_model *m) {
     for (float *p : m->tap_dev)
         if (p) (void)hipFree(p);
     if (m->range_flag) (void)hipFree(m->range_flag);
+    if (m->layer_exp) (void)hipFree(m->layer_exp);
     if (m->pin_flag) (void)hipHostFree(m->pin_flag);
     for (int l = 0; l < 9; ++l) {
         if (m->conv_w[l]) (void)hipFree(m->conv_w[l]);
@@ -346,6 +349,9 @@ int c3_model_destroy(c3_model *m) {
         if (sl.dev_x) (void)hipFree(sl.dev_x);
         if (sl.dev_y) (void)hipFree(sl.dev_y);
         if (sl.shadow) (void)hipFree(sl.shadow);
+        if (sl.layer_part) (void)hipFree(sl.layer_part);
+        for (float *p : sl.layer_buf)
+            if (p) (void)hipFree(p);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
         if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
     }

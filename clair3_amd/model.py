@@ -53,6 +53,7 @@ class _HipModel:
         self._geometry = None
         self._decode_cols = False
         self._verify = None
+        self._verify_layers = False
         if device is not None:
             self.to(device)
 
@@ -78,6 +79,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_decode_columns(self._handle, 1), "c3_model_set_decode_columns")
         if self._verify is not None:
             _lib.check(_lib.lib().c3_model_set_verify(self._handle, *self._verify), "c3_model_set_verify")
+        if self._verify_layers:
+            _lib.check(_lib.lib().c3_model_set_verify_layers(self._handle, 1), "c3_model_set_verify_layers")
         if sd is not None:
             self._load(sd)
         return self
@@ -294,17 +297,22 @@ class _HipModel:
             raise _lib.C3Error(f"near_tie must be >= 0, got {near_tie}")
         return int(every), tol, near_tie, _lib.VERIFY_ESCALATE if escalate else _lib.VERIFY_REPORT
 
-    def verify(self, every=1, tol=1e-4, near_tie=1e-6, escalate=False):
+    def verify(self, every=1, tol=1e-4, near_tie=1e-6, escalate=False, layers=False):
         """Verify mode: every ``every``-th batch of the submit / wait ring (predict_numpy, submit and everything built on them) also runs on the
         fp32-MFMA forms from the same staged input and the two sets of rows are compared on the device (c3_model_set_verify).  ``tol`` and
         ``near_tie`` default to the project's own gates (north_star's 1e-4, tests/util.py NEAR_TIE).  escalate=False: the rows stay the
         fp16x3 ones, bit for bit; escalate=True: a batch that disagrees is answered with its fp32 rows and the handle continues on the
-        fp32 forms.  every=0 switches it off.  verify_stats() reads the totals."""
+        fp32 forms.  every=0 switches it off.  verify_stats() reads the totals.  layers=True: every compared batch also compares the
+        two forms layer by layer on the device (c3_model_set_verify_layers); verify_layers() reads that table."""
         args = self._verify_args(every, tol, near_tie, escalate)
+        if not isinstance(layers, (bool, np.bool_)):
+            raise _lib.C3Error(f"layers must be True or False, got {layers!r}")
         if self._handle is None:  # (a call that fails leaves nothing behind for a later .to(device) to apply)
             raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
         _lib.check(_lib.lib().c3_model_set_verify(self._handle, *args), "c3_model_set_verify")
+        _lib.check(_lib.lib().c3_model_set_verify_layers(self._handle, int(layers)), "c3_model_set_verify_layers")
         self._verify = args  # a handle created anew by .to(another device) takes the setting along
+        self._verify_layers = bool(layers)
         return self
 
     def verify_stats(self):
@@ -318,6 +326,24 @@ class _HipModel:
             v = getattr(st, name)
             out[name] = list(v) if hasattr(v, "__len__") else v
         out["policy"] = "escalate" if st.policy == _lib.VERIFY_ESCALATE else "report"
+        return out
+
+    def verify_layers(self):
+        """the layer records of verify(layers=True) since the last load / verify_reset(): one dict per layer in network order
+        (c3_model_verify_layers; include/c3hip.h names the fields), each with ``rel`` = max_abs_diff / max(1, ref_max_abs) -- the measure of
+        the suite's layer gate.  Empty when layers was never switched on."""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        buf = (_lib.VerifyLayer * 16)()
+        n = _lib.lib().c3_model_verify_layers(self._handle, buf, 16)
+        if n < 0:
+            raise _lib.C3Error(f"c3_model_verify_layers: {_lib.last_error()}")
+        out = []
+        for e in buf[:n]:
+            d = {name: getattr(e, name) for name, _ in _lib.VerifyLayer._fields_ if not name.startswith("reserved")}
+            d["name"], d["status"] = e.name.decode(), _lib.VERIFY_LAYER_STATUS.get(e.status, "?")
+            d["rel"] = float(np.float32(e.max_abs_diff) / max(np.float32(1), np.float32(e.ref_max_abs)))
+            out.append(d)
         return out
 
     def verify_reset(self):

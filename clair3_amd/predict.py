@@ -72,6 +72,8 @@ def verify_from_env(model):
     kw = parse_verify_env(os.environ.get("C3HIP_VERIFY"), os.environ.get("C3HIP_VERIFY_TOL"))
     if kw is None:
         return False
+    if os.environ.get("C3HIP_VERIFY_LAYERS", "").strip().lower() not in ("", "0", "false", "no", "off"):
+        kw["layers"] = True  # (only when set: without it the call is what it was; _report_verified follows the handle, not the environment)
     model.verify(**kw)
     if not any(v is model for v in _VERIFIED):
         import atexit
@@ -93,6 +95,26 @@ def verify_summary(model):
         st["worst_batch"], st["worst_row"], st["rows_over_tol"], st["label_diffs"], st["near_ties"], st["escalations"])
 
 
+# the suite's layer gate (tests/test_caller_inputs_gpu.py LAYER_TOL): a layer whose rel = max_abs_diff / max(1, ref_max_abs) exceeds it is marked
+LAYER_TOL = 2e-5
+
+
+def verify_layer_lines(layers):
+    """the lines a worker leaves behind its summary line under C3HIP_VERIFY_LAYERS=1, one per layer of ``model.verify_layers()`` in network
+    order (INTEGRATION.md 8 says how to read them).  A layer beyond LAYER_TOL ends on " <<"."""
+    lines = []
+    for e in layers:
+        if e["status"] != "compared":
+            lines.append("[clair3_amd] verify layer {:<10s} {}".format(e["name"], "fused (not materialised by the product form)" if e["status"] == "fused"
+                                                                   else "no batch compared"))
+            continue
+        lines.append("[clair3_amd] verify layer {:<10s} batches={} windows={} max_abs_diff={:.3g} ref_max_abs={:.3g} test_max_abs={:.3g} rel={:.3g} "
+                     "worst=(batch {}, window {}, index {}){}".format(
+                         e["name"], e["batches"], e["windows"], e["max_abs_diff"], e["ref_max_abs"], e["test_max_abs"], e["rel"],
+                         e["worst_batch"], e["worst_window"], e["worst_index"], " <<" if not e["rel"] <= LAYER_TOL else ""))
+    return lines
+
+
 def _report_verified():
     import sys
     for model in _VERIFIED:
@@ -100,6 +122,9 @@ def _report_verified():
             continue
         try:
             print(verify_summary(model), file=sys.stderr)
+            if getattr(model, "_verify_layers", False):
+                for line in verify_layer_lines(model.verify_layers()):
+                    print(line, file=sys.stderr)
         except Exception as e:  # noqa: BLE001  (the process is ending: say it, do not raise)
             print(f"[clair3_amd] verify: no summary ({e})", file=sys.stderr)
 

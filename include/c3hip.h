@@ -399,6 +399,40 @@ typedef struct {
 int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int policy);
 int c3_model_verify_stats(c3_model *m, c3_verify_stats *out);
 int c3_model_verify_reset(c3_model *m);
+/* ---- layer records of verify mode: WHERE the two forms differ ----
+ * With c3_model_set_verify_layers(m, 1) every batch that verify mode selects and compares also compares, per layer, the output a of the
+ * product (fp16x3) form with the output b of the fp32 form -- both from the same staged input, both in the checkpoint's units (the values
+ * c3_debug_tap_fetch returns), on the device, for all windows of the batch (a candidate batch: the kept ones).  The product pass keeps its
+ * layer outputs with the tap mechanism's copies into buffers of the slot, so the kernel forms, c3_model_describe and the rows stay what
+ * they are; a batch that verify mode skips brings no layer record.  It has no effect while every == 0; with it never enabled nothing is
+ * allocated or launched and verify mode is what it is without it.  Refused while a c3_predict_submit of the handle is pending.
+ * Layers, in network order, under the tap names: full alignment act0 .. act8, spp, l4_out; pileup lstm1_out, gx2, lstm2_out, l4_out.  A
+ * layer the product form does not materialise (default forms: act0 inside res1a, act8 inside res3b) is not compared: status FUSED.
+ *   c3_model_verify_layers   fills up to max_entries entries and returns the number of layers (0: never enabled on this handle; < 0: error).
+ *                            Totals since the last c3_model_load / c3_model_verify_reset (both zero them and keep the setting)
+ * Per layer: |a - b| in fp32 (a value that is not finite counts as +inf); worst_*: the first batch that reached a strictly larger
+ * max_abs_diff, the lowest (window, index) in it that reaches it -- index: the flat index inside the window in the order of
+ * c3_debug_tap_fetch (NHWC for act*, (bin, c) for spp, (t, feature) for the pileup tensors).
+ * c3_model_describe appends ,layers:1 to its verify=... text while the switch is on. */
+#define C3_VERIFY_LAYER_NONE 0     /* no batch with layer records yet */
+#define C3_VERIFY_LAYER_COMPARED 1
+#define C3_VERIFY_LAYER_FUSED 2    /* the product form computes it inside a fused kernel: not compared */
+typedef struct {
+    char name[16];
+    int32_t status;         /* C3_VERIFY_LAYER_* */
+    int32_t reserved;
+    int64_t batches;        /* batches in which the layer was compared */
+    int64_t windows;        /* ... and their windows */
+    int64_t worst_batch;    /* number of the submit (as c3_verify_stats.worst_batch; -1: none yet) ... */
+    int64_t worst_window;   /* ... the window inside it ... */
+    int64_t worst_index;    /* ... and the flat index inside that window */
+    float max_abs_diff;     /* max |a - b| */
+    float ref_max_abs;      /* max |b| */
+    float test_max_abs;     /* max |a| */
+    float reserved2;
+} c3_verify_layer;
+int c3_model_set_verify_layers(c3_model *m, int enable);
+int c3_model_verify_layers(c3_model *m, c3_verify_layer *out, int max_entries);
 /* which kernel forms the handle's last forward pass took, as "key=value ..." text; bench.py reports it next to its rates */
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
