@@ -28,6 +28,7 @@ EXPORTS = (
     "c3_predict_submit_rows", "c3_predict_rows", "c3_pack_rows",
     "c3_model_set_verify", "c3_model_verify_stats", "c3_model_verify_reset",
     "c3_model_set_verify_layers", "c3_model_verify_layers",
+    "c3_model_set_layer_precision", "c3_model_layer_precision", "c3_layer_precision_check",
 )
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
@@ -166,6 +167,9 @@ def lib():
     L.c3_model_verify_stats.argtypes = [C.c_void_p, C.POINTER(VerifyStats)]
     L.c3_model_verify_reset.argtypes = [C.c_void_p]
     L.c3_model_set_verify_layers.argtypes = [C.c_void_p, C.c_int]
+    L.c3_model_set_layer_precision.argtypes = [C.c_void_p, C.c_char_p]
+    L.c3_model_layer_precision.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.c3_layer_precision_check.argtypes = [C.c_int, C.c_char_p]
     L.c3_model_verify_layers.argtypes = [C.c_void_p, C.POINTER(VerifyLayer), C.c_int]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]

@@ -1,6 +1,6 @@
 // c3_forward.h -- the launch sequences of the two forward passes (clair3/model.py:130-161 Clair3_P, :377-416 Clair3_F) on a
-// stream, device pointers in and out.  Per layer: the product (fp16x3 on the 16-bit matrix instructions) while m->f16_ok, else
-// its one fp32-MFMA form.
+// stream, device pointers in and out.  Per layer: the product (fp16x3 on the 16-bit matrix instructions) while layer_f16(m, layer)
+// (c3_model.h: the handle is on fp16x3 and the precision plan does not name the layer), else its one fp32-MFMA form.
 #pragma once
 #include "c3_model.h"
 
@@ -100,6 +100,15 @@ static int tap_prepare(c3_model *m, int64_t batch) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ the precision plan's boundary forms
+// The fp32 forms that read or write plane activations between product layers (c3_model.h layer_f16) are defined in c3_mixed.h, which
+// c3_model.hip includes LAST: their kernels are then instantiated behind every kernel of the handle without a plan, whose code keeps the
+// place in the code object it has without them (clair3_amd/build.py on what moving a hot kernel costs).
+static int fa_conv_fp32_planes(c3_model *m, hipStream_t s, ProfScope &ps, int l, const int8_t *x, int64_t n, int cin, const int *hh, const int *ww);
+static int lstm1_fp32_planes(hipStream_t s, const LstmFusedParams<int8_t> &lp, int64_t n);  // (plain overloads: a template would be instantiated where it is used)
+static int lstm1_fp32_planes(hipStream_t s, const LstmFusedParams<int32_t> &lp, int64_t n);
+static int proj2_fp32_from_planes(c3_model *m, hipStream_t s, int M);
+
 // ------------------------------------------------------------------------------------------ FC tail (both networks)
 // L4 as a split-K contraction -> splitk_reduce_selu_kernel -> fc_tail_mfma_kernel (c3_tail.h); the decoder columns behind it
 static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int64_t n, float *y, const char *tag_l4,
@@ -108,7 +117,7 @@ static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int
     const int FC = m->FC, K4 = m->K4;
     const int nk_total = K4 / kBK;
     const int S = l4_splits(m);
-    const bool l4_f16 = m->f16_ok && m->l4_wf;
+    const bool l4_f16 = layer_f16(m, kLayerL4) && m->l4_wf;
     {
         ProfScope ps(m, s, tag_l4, 2.0 * n * FC * K4, 4.0 * (n * K4 + (double)FC * K4 + (double)S * n * FC));
         if (l4_f16) {  // partials carry the features' powers of two (l4_pre)
@@ -191,6 +200,8 @@ static int div_magic(int d, int64_t n, uint32_t *magic) {
 // the plane pipeline needs every layer packed for it and images no wider than the halo tile is sized for
 static bool fa_planes_ok(const c3_model *m) {
     if (!m->f16_ok) return false;
+    const uint32_t all = layer_mask_all(C3_KIND_FULL_ALIGNMENT);
+    if (((m->fp32_plan | m->fp32_auto) & all) == all) return false;  // a plan of every layer IS the fp32 form (run_fa_fp32)
     int hh[10], ww[10];
     fa_geometry(m, hh, ww);
     for (int l = 1; l < 9; ++l)
@@ -205,12 +216,16 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
     int hh[10], ww[10];
     fa_geometry(m, hh, ww);
     int cin = m->C;
-    const bool sppf_ok = m->spp_fused && !m->keep && hh[9] == 12 && ww[9] == 5 && 14 * 256 == m->K4;
+    // the precision plan (c3_model.h layer_f16): a named convolution runs as an fp32 implicit GEMM that reads planes and writes planes
+    // (c3_gemm.h ConvPlanesLoader, EPI_BIAS_*_PLANES), so its neighbours keep their product kernels and act[] its meaning.  conv1 lives
+    // inside res1a / res1b and the pooling inside res3b: a plan that names one of those runs the unfused arrangement
+    const uint32_t plan = m->fp32_plan | m->fp32_auto;
+    const bool sppf_ok = m->spp_fused && !m->keep && hh[9] == 12 && ww[9] == 5 && 14 * 256 == m->K4 && !(plan & (1u << 8));
     for (int l = 0; l < 9; ++l) {
         const int Cout = kConvCout[l];
         const int M = (int)(n * hh[l + 1] * ww[l + 1]);
         // conv1 inside the first residual block (c3_conv3.h SRC8; 8-channel windows, or 9 with the dwell channel)
-        const bool fuse1 = m->conv1_fused && (m->C == 8 || m->C == 9) && m->conv1_wfrag16 && !m->keep && ww[1] <= kPlMaxW && ww[0] >= 3;
+        const bool fuse1 = m->conv1_fused && (m->C == 8 || m->C == 9) && m->conv1_wfrag16 && !m->keep && ww[1] <= kPlMaxW && ww[0] >= 3 && !(plan & 7u);
         if (l == 0 && fuse1) {  // no launch, no conv1 planes: res1a computes its input rows, res1b its residual, from the windows
             tap_skip(m, 0);
             cin = Cout;
@@ -221,7 +236,9 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
         if (fuse1 && l == 1) flops += 2.0 * M * 64.0 * 9.0 * m->C, bytes += 1.0 * n * hh[0] * ww[0] * m->C - 4.0 * M * 64;  // conv1's algorithmic work rides here
         if (fuse1 && l == 2) bytes += 1.0 * n * hh[0] * ww[0] * m->C - 4.0 * M * 64;  // residual from the windows, not from conv1 planes
         ProfScope ps(m, s, kFaLayerTag[l], flops, bytes);
-        if (l == 0 && cin == 8) {
+        if (plan >> l & 1u) {  // the fp32 form between planes (c3_mixed.h)
+            TRY(fa_conv_fp32_planes(m, s, ps, l, x, n, cin, hh, ww));
+        } else if (l == 0 && cin == 8) {
             ps.mfma(2.0 * ((M + 31) / 32 * 32) * 64.0 * 80.0 * 2, true);
             Conv1F16Params cp;
             cp.x = x, cp.wfrag = reinterpret_cast<const uint32_t *>(m->conv1_wfrag16), cp.bias = m->conv_b[0], cp.out = L.act[0];
@@ -465,9 +482,13 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
     const int M = (int)(n * Tn);
     // int8 windows feed the fp16 projection fragments (counts are exact in fp16); int32 windows keep an fp32 projection inside
     // the fp16x3 recurrence kernel
-    const bool l1_f16 = m->f16_ok && m->whh16[0] && (sizeof(T) != 1 || m->l1_wih16);
+    const bool l1_f16 = layer_f16(m, kLayerLstm1) && m->whh16[0] && (sizeof(T) != 1 || m->l1_wih16);
     const int beside = std::max(m->sharing, m->lane_sharing);  // other batches on the chip: the caller's handles, or this handle's other lanes (c3_model.h)
-    const bool h1_planes = l1_f16 && m->proj2_pw;  // h1 leaves LSTM1 as fp16 piece planes for c3_dense.h
+    // h1 leaves LSTM1 as fp16 piece planes for c3_dense.h.  Under a precision plan (c3_model.h layer_f16) the product LSTM1 keeps writing
+    // them whatever reads them -- an fp32 projection then reads planes (c3_gemm.h DensePlanesLoader), so that LSTM1 runs the very kernel and
+    // tile shape it runs without a plan -- and an fp32 LSTM1 in front of the product projection writes them too (c3_lstm_fused.h OPT bit 4)
+    const bool p2_f16 = layer_f16(m, kLayerProj2) && m->proj2_pw;
+    const bool h1_planes = l1_f16 ? m->proj2_pw != nullptr : p2_f16 && ((m->fp32_plan | m->fp32_auto) & kLayerLstm1);
     L.last_planes = h1_planes;
     {
         ProfScope ps(m, s, "p.lstm1", 2.0 * M * 1024.0 * m->C + 2.0 * M * 2.0 * 512.0 * 128.0, sizeof(T) * (double)M * m->C + 4.0 * M * 256.0);
@@ -495,6 +516,10 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
                 if (h1_planes) hipLaunchKernelGGL((lstm1_fused_kernel<T, true, 3>), grid, dim3(512), 0, s, lp);
                 else hipLaunchKernelGGL((lstm1_fused_kernel<T, true>), grid, dim3(512), 0, s, lp);
             }
+        } else if (h1_planes) {
+            lp.hplanes = L.h1;
+            m->choice.lstm1 = "fused-fp32-mfma-planes";
+            TRY(lstm1_fp32_planes(s, lp, n));
         } else {
             m->choice.lstm1 = "fused-fp32-mfma";
             hipLaunchKernelGGL(lstm1_fused_kernel<T>, grid, dim3(512), 0, s, lp);
@@ -504,8 +529,11 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
     }
     {
         ProfScope ps(m, s, "p.proj2", 2.0 * M * 1280.0 * 256.0, 4.0 * M * (256.0 + 1280.0));
-        ps.mfma(2.0 * ((M + 127) / 128 * 128) * 1280.0 * 256.0 * (h1_planes ? 3 : 1), h1_planes);
-        if (h1_planes && m->proj2_pwr && (M + kWrBM - 1) / kWrBM >= 2 * 8 * std::max(1, m->wg_slots / 16 / (1280 / kWrBN))) {
+        ps.mfma(2.0 * ((M + 127) / 128 * 128) * 1280.0 * 256.0 * (h1_planes && p2_f16 ? 3 : 1), h1_planes && p2_f16);
+        if (!p2_f16 && h1_planes) {  // the fp32 form behind a product LSTM1
+            m->choice.proj2 = "fp32-mfma";
+            TRY(proj2_fp32_from_planes(m, s, M));
+        } else if (h1_planes && m->proj2_pwr && (M + kWrBM - 1) / kWrBM >= 2 * 8 * std::max(1, m->wg_slots / 16 / (1280 / kWrBN))) {
             // weights resident in registers (c3_dense.h): 8 XCDs x lanes x 5 column tiles of workgroups, each walking the row tiles of its lane
             DenseWresParams wp;
             wp.a = L.h1, wp.w = m->proj2_pwr, wp.bias = m->proj_b[1], wp.c = L.gx2, wp.post_scale = m->proj2_post_scale;
@@ -534,7 +562,7 @@ static int run_pileup_t(c3_model *m, hipStream_t s, const T *x, int64_t n, float
     }
     {
         ProfScope ps(m, s, "p.lstm2", 2.0 * M * 2.0 * 640.0 * 160.0, 4.0 * M * (1280.0 + 320.0));
-        const bool l2_f16 = m->f16_ok && m->whh16[1];
+        const bool l2_f16 = layer_f16(m, kLayerLstm2) && m->whh16[1];
         const bool half2 = l2_f16 && m->half_tiles && beside <= 1 && 2 * ((n + 15) / 16) <= m->wg_slots / 4;
         ps.mfma((double)(half2 ? (n + 7) / 8 * 16 : (n + 15) / 16 * 16) * Tn * 2 * 2.0 * 640 * 160 * (l2_f16 ? 3 : 1), l2_f16);
         Lstm2Params lp{L.gx2, m->whh[1], L.h2, (int)n, Tn, 1280};

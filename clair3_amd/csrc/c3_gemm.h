@@ -48,6 +48,12 @@ __device__ __forceinline__ void split2_f16(const f32x4 x, u32x2 (&piece)[2]) {
     }
 }
 
+// four values of a plane activation from their hi and lo pieces (8 bytes each): (float)hi + (float)lo
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 planes_value(const u32x2 hi, const u32x2 lo) {
+    return __builtin_convertvector(__builtin_bit_cast(f16x4, hi), f32x4) + __builtin_convertvector(__builtin_bit_cast(f16x4, lo), f32x4);
+}
+
 // Outputs at or above this magnitude make the host re-run the batch on fp32 matrix instructions: a consumer may add up
 // to four of them (Winograd input transform) before splitting the sum into fp16 pieces (max 65504).
 constexpr float kF16Range = 16000.f;
@@ -148,6 +154,53 @@ struct ConvLoader {
     }
 };
 
+// The same convolution over PLANE activations (c3_conv3.h: per pixel Cin / 64 slabs of 256 bytes, 64 hi fp16 pieces then 64 lo pieces): the
+// fp32 form of a layer whose neighbours stay on their product kernels (c3_model_set_layer_precision).  ConvLoader's address logic (tap
+// mask, zero page); a lane's four channels are 8 bytes of the hi and 8 bytes of the lo plane of the pixel's slab, finish() adds the pieces.
+template <int R>
+struct ConvPlanesLoader {
+    typedef ConvLoaderParams Params;  // x: the planes (a pixel takes the bytes of its Cin floats)
+    struct Raw {
+        u32x2 hi, lo;
+    };
+    const char *x, *zeros;
+    int64_t off[R];  // byte offset of pixel (b, ih0, iw0) + this lane's 8 bytes inside a 32-channel half slab
+    uint32_t mask[R];
+    int Win, Cin, cpt_shift, cpt_mask;
+    __device__ __forceinline__ void init(const Params &p, int m0, int lr, int lc, int M) {
+        x = reinterpret_cast<const char *>(p.x), zeros = reinterpret_cast<const char *>(p.zeros), Win = p.Win, Cin = p.Cin;
+        cpt_mask = p.chunks_per_tap - 1, cpt_shift = 31 - __builtin_clz(p.chunks_per_tap);  // power of two
+        const int hw = p.Ho * p.Wo;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            int m = m0 + lr + 32 * i;
+            if (m >= M) m = M - 1;
+            const int b = m / hw, rem = m - b * hw;
+            const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
+            const int ih0 = oh * p.stride - 1, iw0 = ow * p.stride - 1;
+            off[i] = (((int64_t)b * p.Hin + ih0) * p.Win + iw0) * p.Cin * 4 + lc * 8;
+            mask[i] = tap_mask9(ih0, iw0, p.Hin, p.Win);
+        }
+    }
+    __device__ __forceinline__ void issue(Raw (&raw)[R], int kc) const {
+        const int tap = kc >> cpt_shift, cc = kc & cpt_mask;
+        const int kh = tap / 3, kw = tap - kh * 3;
+        // chunk cc = channels 32 cc .. 32 cc + 31: slab cc >> 1, its hi pieces from byte 64 (cc & 1) of the slab
+        const int64_t koff = (int64_t)(kh * Win + kw) * Cin * 4 + (cc >> 1) * 256 + (cc & 1) * 64;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const bool ok = (mask[i] >> tap) & 1u;
+            const char *q = ok ? x + off[i] + koff : zeros;
+            raw[i].hi = *reinterpret_cast<const u32x2 *>(q);
+            raw[i].lo = *reinterpret_cast<const u32x2 *>(q + 128);
+        }
+    }
+    __device__ __forceinline__ void finish(const Raw (&raw)[R], f32x4 (&out)[R]) const {
+#pragma unroll
+        for (int i = 0; i < R; ++i) out[i] = planes_value(raw[i].hi, raw[i].lo);
+    }
+};
+
 // conv1 of Clair3_F straight from the int8 window (B, H, W, C), stride 2, pad 1, 3*C <= 32.
 // K is padded to 3 chunks (one per kh) of 32 slots: slot j = kw*C + c for j < 3C (weights are zero beyond);
 // the three input pixels (kw = 0..2) of one kh are 3C consecutive bytes starting at pixel (ih, iw0).
@@ -242,14 +295,47 @@ struct DenseLoader {
     }
 };
 
+// Rows of PLANE activations as A (c3_conv3.h layout: per row K / 64 slabs of 256 bytes, 64 hi fp16 pieces then 64 lo pieces), K % 64 == 0,
+// no split-K: the fp32 form of a dense layer behind a product layer that keeps writing planes (the LSTM2 projection of a precision plan)
+template <int R>
+struct DensePlanesLoader {
+    typedef DenseLoaderParams Params;  // a: the planes, lda: K (a row takes the bytes of its K floats)
+    struct Raw {
+        u32x2 hi, lo;
+    };
+    const char *row[R];
+    __device__ __forceinline__ void init(const Params &p, int m0, int lr, int lc, int M) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            int m = m0 + lr + 32 * i;
+            if (m >= M) m = M - 1;
+            row[i] = reinterpret_cast<const char *>(p.a) + (int64_t)m * p.lda * 4 + lc * 8;
+        }
+    }
+    __device__ __forceinline__ void issue(Raw (&raw)[R], int kc) const {  // chunk kc = values 32 kc .. 32 kc + 31: slab kc >> 1, half kc & 1
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const char *q = row[i] + (kc >> 1) * 256 + (kc & 1) * 64;
+            raw[i].hi = *reinterpret_cast<const u32x2 *>(q);
+            raw[i].lo = *reinterpret_cast<const u32x2 *>(q + 128);
+        }
+    }
+    __device__ __forceinline__ void finish(const Raw (&raw)[R], f32x4 (&out)[R]) const {
+#pragma unroll
+        for (int i = 0; i < R; ++i) out[i] = planes_value(raw[i].hi, raw[i].lo);
+    }
+};
+
 // ------------------------------------------------------------------------------------------ epilogues
 enum { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_BIAS_RES_RELU = 2, EPI_PARTIAL = 3,
-       EPI_BIAS_RELU_PLANES = 4 };  // bias + ReLU, output written as plane activations (c3_conv3.h) with ldc = N channels
+       EPI_BIAS_RELU_PLANES = 4,   // bias + ReLU, output written as plane activations (c3_conv3.h) with ldc = N channels
+       EPI_BIAS_RES_RELU_PLANES = 5 };  // bias + residual read from planes + ReLU, output as planes (the fp32 form between product layers)
+constexpr bool epi_planes(int epi) { return epi == EPI_BIAS_RELU_PLANES || epi == EPI_BIAS_RES_RELU_PLANES; }
 
 struct EpilogueParams {
     float *c;            // [M][ldc]   (EPI_PARTIAL: [split][M][ldc])
     const float *bias;   // [N]
-    const float *res;    // residual, same layout as c (EPI_BIAS_RES_RELU)
+    const float *res;    // residual, same layout as c (EPI_BIAS_RES_RELU, EPI_BIAS_RES_RELU_PLANES)
     int64_t ldc;
     int64_t split_stride;  // M*ldc for EPI_PARTIAL
     uint32_t *range_flag = nullptr;  // SPLIT: set to 1 when an output reaches kF16Range (the consumers split it into fp16 pieces)
@@ -486,7 +572,7 @@ __global__ __launch_bounds__(kThreads) void gemm_mfma_kernel(typename Loader::Pa
     float *cbase = ep.c + (EPI == EPI_PARTIAL ? (int64_t)split * ep.split_stride : 0);
     const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(cbase, 0, (uint32_t)((int64_t)gp.M * ep.ldc * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(EPI == EPI_BIAS_RES_RELU ? ep.res : ep.c), 0, (uint32_t)((int64_t)gp.M * ep.ldc * 4), 0x00020000);
+        const_cast<float *>(EPI == EPI_BIAS_RES_RELU || EPI == EPI_BIAS_RES_RELU_PLANES ? ep.res : ep.c), 0, (uint32_t)((int64_t)gp.M * ep.ldc * 4), 0x00020000);
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     float omax = 0.f;
     if constexpr (SPLIT == 2 && BM == 128 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU_PLANES)) {
@@ -568,12 +654,19 @@ __global__ __launch_bounds__(kThreads) void gemm_mfma_kernel(typename Loader::Pa
                     for (int e = 0; e < 4; ++e) val[e] = __builtin_fmaf(val[e], sv[e], bv[e]);  // 1: the plain add
                 }
                 if (EPI == EPI_BIAS_RES_RELU) val += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off + 32 * q, 0, 0));
-                if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RES_RELU || EPI == EPI_BIAS_RELU_PLANES) {
+                if constexpr (EPI == EPI_BIAS_RES_RELU_PLANES) {  // the residual's two pieces at the plane offset the store below takes
+                    const int n = nb + 8 * q;
+                    const uint32_t po = m < gp.M ? (uint32_t)((int64_t)m * ep.ldc * 4) + (uint32_t)((n >> 6) * 256 + (n & 63) * 2) : 0xffffff00u;
+                    const u32x2 rh = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rrsrc, po, 0, 0));
+                    const u32x2 rl = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rrsrc, po + 128, 0, 0));
+                    val += planes_value(rh, rl);
+                }
+                if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RES_RELU || epi_planes(EPI)) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) val[e] = __int_as_float(max(__float_as_int(val[e]), 0));
                 }
-                if constexpr (SPLIT != 0 && EPI != EPI_PARTIAL) omax = fmaxf(omax, fmaxf(fmaxf(fabsf(val[0]), fabsf(val[1])), fmaxf(fabsf(val[2]), fabsf(val[3]))));
-                if constexpr (EPI == EPI_BIAS_RELU_PLANES) {
+                if constexpr ((SPLIT != 0 && EPI != EPI_PARTIAL) || epi_planes(EPI)) omax = fmaxf(omax, fmaxf(fmaxf(fabsf(val[0]), fabsf(val[1])), fmaxf(fabsf(val[2]), fabsf(val[3]))));
+                if constexpr (epi_planes(EPI)) {
                     // channel n of pixel m: slab n >> 6, hi piece at 2 (n & 63), lo piece 128 bytes further; `off` is the pixel
                     // row (4 ldc bytes) + 4 nb, so the plane offset of column nb + 8 q is (off - 4 nb) + ...
                     const int n = nb + 8 * q;
@@ -587,7 +680,7 @@ __global__ __launch_bounds__(kThreads) void gemm_mfma_kernel(typename Loader::Pa
             }
         }
     }
-    if constexpr (SPLIT != 0 && EPI != EPI_PARTIAL)
+    if constexpr ((SPLIT != 0 && EPI != EPI_PARTIAL) || epi_planes(EPI))
         if (ep.range_flag && !(omax < kF16Range)) atomicOr(ep.range_flag, 1u);  // also taken for NaN
 }
 

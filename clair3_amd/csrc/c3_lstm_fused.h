@@ -49,6 +49,9 @@ constexpr int kFusedKS = 5;  // k-steps of 4 covering C <= 20 input channels
 //            of 1024 windows becomes 256 workgroups instead of 128: the recurrences are latency-bound chains and half of the
 //            chip was idle.  The host picks it when the full tiles would leave CUs empty.
 // OPT bit 3: phase trace (debug).
+// OPT bit 4: the fp32 form (F16 = false) writes h as plane activations too -- the same split and slab layout as the F16 form, so that an
+//            fp32 LSTM1 can feed the product form of the LSTM2 projection (c3_model_set_layer_precision).  Two 2-byte stores per value in
+//            place of the one 4-byte store; the caller guarantees hplanes != nullptr.
 template <typename TX, bool F16 = false, int OPT = 0>
 __global__ __launch_bounds__(512) void lstm1_fused_kernel(LstmFusedParams<TX> p) {
     constexpr int H = 128, NW = 8, NQ = 8, LDH = H + 4;
@@ -161,6 +164,7 @@ __global__ __launch_bounds__(512) void lstm1_fused_kernel(LstmFusedParams<TX> p)
         }
     };
     constexpr bool TRACE = (OPT & 8) != 0;
+    constexpr bool PLANES32 = !F16 && (OPT & 16);
     auto stamp = [&](int step, int k) __attribute__((always_inline)) {
         if constexpr (TRACE) {
             __builtin_amdgcn_sched_barrier(0);
@@ -177,12 +181,15 @@ __global__ __launch_bounds__(512) void lstm1_fused_kernel(LstmFusedParams<TX> p)
     // hipcc then waits for the step's four count loads with vmcnt(3..0) -- which, loads and stores sharing one in-order
     // counter, also waits for the 16-byte store issued just before them: a full HBM write round trip on every step.
     const bool planes = (F16 && (OPT & 2)) ? true : (F16 && p.hplanes != nullptr);  // same bytes per (window, step): 2H x 4
-    const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(planes ? p.hplanes : (void *)p.hout, 0,
+    const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(planes || PLANES32 ? p.hplanes : (void *)p.hout, 0,
                                                                             (uint32_t)((int64_t)p.B * p.T * 2 * H * 4), 0x00020000);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
         const int b = row_window(4 * s + v);
         ho[v] = b < p.B ? (uint32_t)((((int64_t)b * p.T) * (2 * H) + h_col) * 4) : 0x80000000u;
+        // PLANES32: the hi piece of unit h_col in the window's plane row instead (slab h_col >> 6, the lo piece 128 bytes further)
+        if constexpr (PLANES32)
+            ho[v] = b < p.B ? (uint32_t)(((int64_t)b * p.T) * (2 * H) * 4 + (h_col >> 6) * 256 + (h_col & 63) * 2) : 0x80000000u;
     }
     // planes: the step's h tile (16 windows x H units, two pieces) already sits in LDS in plane order; one step later -- behind
     // the barrier that publishes it -- every thread copies ONE 16-byte piece of it to global memory: thread (piece, window,
@@ -293,6 +300,14 @@ __global__ __launch_bounds__(512) void lstm1_fused_kernel(LstmFusedParams<TX> p)
                     if (planes) continue;  // copied out of LDS one step later (copy_planes)
                 } else {
                     hbuf[cur ^ 1][4 * s + v + e][wave * 16 + col] = h[e];
+                    if constexpr (PLANES32) {
+                        const _Float16 h0 = (_Float16)h[e];
+                        const _Float16 h1 = (_Float16)(h[e] - (float)h0);
+                        const uint32_t po = ho[v + e] + (uint32_t)(t * 2 * H * 4);
+                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h0), prsrc, po, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h1), prsrc, po + 128, 0, 0);
+                        continue;
+                    }
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(h[e]), hrsrc, ho[v + e] + (uint32_t)(t * 2 * H * 4), 0, 0);
             }

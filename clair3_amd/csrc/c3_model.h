@@ -5,6 +5,7 @@
 //   c3_model.h     this file
 //   c3_pack.h      c3_model_load: BatchNorm folding, gate re-ordering, matrix-instruction fragment layouts, fp16 pieces
 //   c3_forward.h   the launch sequences of the two forward passes (clair3/model.py:130-161 and :377-416)
+//   c3_mixed.h     the boundary forms of a per-layer precision plan: fp32 forms that read / write plane activations between product layers
 //   c3_hostring.h  the host <-> device ring behind c3_predict / c3_predict_submit / _wait.  predict_submit is one sequence for every input
 //                  kind (sliced windows, a region with starts, candidates, occupied rows handed over or packed here): lane and shared-chip
 //                  forms, plan_batch (THE layout of a staged batch: StagedBatch below), ensure_slot, fill_<kind>, queue_input, launch_batch,
@@ -98,6 +99,34 @@ static const char *kFaLayerTag[9] = {"fa.conv1", "fa.res1a", "fa.res1b", "fa.con
 enum { kTapSpp = 9, kTapL4 = 10, kTapLstm1 = 11, kTapGx2 = 12, kTapLstm2 = 13, kTapCount = 14 };
 static const char *kTapName[kTapCount] = {"act0", "act1", "act2", "act3", "act4", "act5", "act6", "act7", "act8",
                                           "spp",  "l4_out", "lstm1_out", "gx2", "lstm2_out"};
+
+// ---- the per-layer precision plan (c3_model_set_layer_precision): one bit per named layer; a layer takes its product form iff
+// layer_f16(m, bit).  Full alignment: bit l = convolution l, kLayerL4 behind them; pileup: its three layers behind that
+enum { kLayerL4 = 1u << 9, kLayerLstm1 = 1u << 10, kLayerProj2 = 1u << 11, kLayerLstm2 = 1u << 12 };
+struct LayerName { const char *name; uint32_t bit; };
+// the names of a kind in network order (the kFaLayerTag / ProfScope tags without their prefix); the FC tail is fp32 in both forms and has none
+static const LayerName kPileupLayers[] = {{"lstm1", kLayerLstm1}, {"proj2", kLayerProj2}, {"lstm2", kLayerLstm2}, {"l4", kLayerL4}};
+static const LayerName kFaLayers[] = {{"conv1", 1u << 0}, {"res1a", 1u << 1}, {"res1b", 1u << 2}, {"conv3", 1u << 3}, {"res2a", 1u << 4}, {"res2b", 1u << 5},
+                                      {"conv5", 1u << 6}, {"res3a", 1u << 7}, {"res3b", 1u << 8}, {"l4", kLayerL4}};
+static int layer_names(int kind, const LayerName **out) {
+    if (kind == C3_KIND_PILEUP) return *out = kPileupLayers, (int)(sizeof(kPileupLayers) / sizeof(LayerName));
+    if (kind == C3_KIND_FULL_ALIGNMENT) return *out = kFaLayers, (int)(sizeof(kFaLayers) / sizeof(LayerName));
+    return *out = nullptr, 0;
+}
+static uint32_t layer_mask_all(int kind) {
+    const LayerName *t;
+    uint32_t all = 0;
+    for (int i = 0, n = layer_names(kind, &t); i < n; ++i) all |= t[i].bit;
+    return all;
+}
+// "conv3,res2a" of a mask, network order ("" = none)
+static std::string layer_mask_text(int kind, uint32_t mask) {
+    const LayerName *t;
+    std::string out;
+    for (int i = 0, n = layer_names(kind, &t); i < n; ++i)
+        if (mask & t[i].bit) out += (out.empty() ? "" : ","), out += t[i].name;
+    return out;
+}
 
 struct DevBuf {
     void *p = nullptr;
@@ -253,6 +282,12 @@ struct c3_model {
     uint32_t *range_flag = nullptr;  // device word set by the fp16x3 kernels when an activation nears the fp16 range (c3_gemm.h kF16Range)
     uint32_t *pin_flag = nullptr;    // pinned copy of range_flag for c3_predict_device_checked
     bool f16_ok = true;              // cleared when a batch came back out of range / non-finite (or by C3HIP_FP32=1): every layer then runs its fp32-MFMA form
+    // The per-layer plan: layers that run their fp32-MFMA form while the rest of the handle stays on fp16x3 (0 = none: nothing changes).
+    // plan: what the caller named (c3_model_set_layer_precision, C3HIP_FP32_LAYERS; survives a load); auto: what the load-time rule below
+    // escalated INSTEAD of the whole handle (C3HIP_AUTO_FP32_LAYERS; decided again by every load)
+    uint32_t fp32_plan = 0, fp32_auto = 0;
+    uint32_t auto_layers = 0;        // C3HIP_AUTO_FP32_LAYERS: the layers the load-time rule escalates (0 = unset: the whole handle)
+    std::string precision_text;      // storage of precision = "fp32-auto(<layers>)"
     // Precision escalation decided at c3_model_load (pileup only, c3_pack.h lstm_sensitivity): a recurrence whose weights hold an entry of
     // magnitude >= auto_fp32_at amplifies the 2^-22 of the fp16 piece pairs over its 33 steps beyond north_star's 1e-4 on rare windows
     // (tests/diag/sensitive_window.py), so such a handle STARTS on the fp32 matrix instructions.  C3HIP_FP32 set (0 or 1) is an explicit
@@ -354,6 +389,9 @@ struct c3_model {
 };
 
 static int conv_out(int n, int s) { return (n - 1) / s + 1; }
+
+// THE predicate of the plan: layer `bit` takes its product (fp16x3) form
+static bool layer_f16(const c3_model *m, uint32_t bit) { return m->f16_ok && !((m->fp32_plan | m->fp32_auto) & bit); }
 
 // the active lane: the workspace and the kernel stream of the forward pass being enqueued
 static Lane &lane(c3_model *m) { return m->lanes[m->lane_cur]; }

@@ -7,6 +7,7 @@
 #include "c3_comm.h"
 #include "c3_debug.h"
 #include "c3_rows.h"
+#include "c3_mixed.h"  // (last: c3_forward.h says why)
 
 extern "C" {
 
@@ -41,6 +42,67 @@ int c3_device_pci_bus_id(int device, char *buf, int buf_bytes) {
     if (!buf || buf_bytes < 16) return fail("c3_device_pci_bus_id: buffer of at least 16 bytes needed");
     HIP_TRY(hipDeviceGetPCIBusId(buf, buf_bytes, device));
     for (char *c = buf; *c; ++c) *c = (char)tolower((unsigned char)*c);  // sysfs spells the address in lower case
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the per-layer precision plan (c3_model.h layer_f16): "lstm2,l4" -> mask.  Plain host code; `what` names the source in the error
+static int parse_layer_names(int kind, const char *names, uint32_t *mask, const char *what) {
+    const LayerName *mine, *other;
+    const int n_mine = layer_names(kind, &mine);
+    if (!n_mine) return fail("%s: unknown model kind %d", what, kind);
+    if (!names) return fail("%s: null layer names", what);
+    const int other_kind = kind == C3_KIND_PILEUP ? C3_KIND_FULL_ALIGNMENT : C3_KIND_PILEUP;
+    const int n_other = layer_names(other_kind, &other);
+    const std::string valid = layer_mask_text(kind, layer_mask_all(kind));
+    uint32_t out = 0;
+    if (!strcmp(names, "all")) return *mask = layer_mask_all(kind), 0;
+    for (const char *p = names; *p;) {
+        const char *e = strchr(p, ',');
+        const std::string entry = e ? std::string(p, e) : std::string(p);
+        if (entry.empty()) return fail("%s: empty entry in \"%s\" (expected names out of %s, \"all\" or \"\")", what, names, valid.c_str());
+        uint32_t bit = 0;
+        for (int i = 0; i < n_mine; ++i)
+            if (entry == mine[i].name) bit = mine[i].bit;
+        if (!bit) {
+            for (int i = 0; i < n_other; ++i)
+                if (entry == other[i].name)
+                    return fail("%s: \"%s\" is a layer of the %s network; this one has %s", what, entry.c_str(),
+                                other_kind == C3_KIND_PILEUP ? "pileup" : "full-alignment", valid.c_str());
+            return fail("%s: unknown layer \"%s\" (expected names out of %s, \"all\" or \"\")", what, entry.c_str(), valid.c_str());
+        }
+        out |= bit;
+        if (!e) break;
+        p = e + 1;
+        if (!*p) return fail("%s: empty entry in \"%s\" (expected names out of %s, \"all\" or \"\")", what, names, valid.c_str());
+    }
+    *mask = out;
+    return 0;
+}
+
+extern "C" {
+
+int c3_layer_precision_check(int kind, const char *names) {
+    uint32_t mask = 0;
+    return parse_layer_names(kind, names, &mask, "c3_layer_precision_check");
+}
+
+int c3_model_set_layer_precision(c3_model *m, const char *names) {
+    if (!m) return fail("null model");
+    uint32_t mask = 0;
+    TRY(parse_layer_names(m->kind, names, &mask, "c3_model_set_layer_precision"));
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    m->fp32_plan = mask;
+    return 0;
+}
+
+int c3_model_layer_precision(c3_model *m, char *buf, int buf_bytes) {
+    if (!m || !buf || buf_bytes <= 0) return fail("null argument");
+    const std::string text = layer_mask_text(m->kind, m->fp32_plan | m->fp32_auto);
+    if ((int)text.size() >= buf_bytes) return fail("c3_model_layer_precision: buffer of %d bytes needed", (int)text.size() + 1);
+    memcpy(buf, text.c_str(), text.size() + 1);
     return 0;
 }
 
@@ -92,6 +154,19 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
         if (!m->f16_ok) m->precision = "fp32-forced";
     }
     if (const char *e = getenv("C3HIP_AUTO_FP32")) m->auto_fp32_at = (float)atof(e);
+    // the per-layer plan (c3_model.h): an invalid value fails the creation -- a precision request is never dropped silently
+    if (const char *e = getenv("C3HIP_FP32_LAYERS")) {
+        if (parse_layer_names(kind, e, &m->fp32_plan, "C3HIP_FP32_LAYERS")) {
+            c3_model_destroy(m);
+            return nullptr;
+        }
+    }
+    if (const char *e = getenv("C3HIP_AUTO_FP32_LAYERS")) {  // what the load-time rule escalates instead of the whole handle
+        if (parse_layer_names(kind, e, &m->auto_layers, "C3HIP_AUTO_FP32_LAYERS")) {
+            c3_model_destroy(m);
+            return nullptr;
+        }
+    }
     if (const char *e = getenv("C3HIP_CONV1_FUSED")) m->conv1_fused = atoi(e) != 0;
     if (const char *e = getenv("C3HIP_WINO")) m->wino = atoi(e);
     if (const char *e = getenv("C3HIP_SPP_FUSED")) m->spp_fused = atoi(e) != 0;
@@ -180,10 +255,21 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
         // precision escalation without a user switch (c3_model.h): decided once per load, from the weights alone
         if (!m->precision_forced) {
             const bool up = m->auto_fp32_at > 0.f && m->lstm_wmax >= m->auto_fp32_at;
-            if (up)
-                fprintf(stderr, "libc3hip: LSTM weights reach |w| = %.3g (>= %.3g): this pileup handle runs on the fp32 matrix instructions "
-                                "(C3HIP_FP32=0 keeps the fp16x3 kernels)\n", (double)m->lstm_wmax, (double)m->auto_fp32_at);
-            m->f16_ok = !up, m->precision = up ? "fp32-auto" : "fp16x3";
+            // C3HIP_AUTO_FP32_LAYERS: the rule escalates those layers and the handle stays on fp16x3 beside them
+            const bool part = up && m->auto_layers && m->auto_layers != layer_mask_all(m->kind);
+            m->fp32_auto = part ? m->auto_layers : 0;
+            if (part) {
+                m->precision_text = "fp32-auto(" + layer_mask_text(m->kind, m->fp32_auto) + ")";
+                fprintf(stderr, "libc3hip: LSTM weights reach |w| = %.3g (>= %.3g): this pileup handle runs %s on the fp32 matrix instructions "
+                                "(C3HIP_AUTO_FP32_LAYERS; C3HIP_FP32=0 keeps the fp16x3 kernels)\n", (double)m->lstm_wmax, (double)m->auto_fp32_at,
+                        layer_mask_text(m->kind, m->fp32_auto).c_str());
+                m->f16_ok = true, m->precision = m->precision_text.c_str();
+            } else {
+                if (up)
+                    fprintf(stderr, "libc3hip: LSTM weights reach |w| = %.3g (>= %.3g): this pileup handle runs on the fp32 matrix instructions "
+                                    "(C3HIP_FP32=0 keeps the fp16x3 kernels)\n", (double)m->lstm_wmax, (double)m->auto_fp32_at);
+                m->f16_ok = !up, m->precision = up ? "fp32-auto" : "fp16x3";
+            }
         }
     } else {
         int cin = m->C;
@@ -292,6 +378,10 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  "precision=%s wino_form=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
                  m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
                  m->precision, wf[0] ? wf : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+    }
+    if (m->fp32_plan | m->fp32_auto) {  // only while a precision plan is in force (c3_model.h layer_f16)
+        const size_t at = strlen(buf);
+        snprintf(buf + at, (size_t)n - at, " fp32_layers=%s", layer_mask_text(m->kind, m->fp32_plan | m->fp32_auto).c_str());
     }
     if (m->verify_seen) {  // verify mode is or was on (c3_verify.h): the setting and the totals behind everything else
         const c3_verify_stats &t = m->vstats;

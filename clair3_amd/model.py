@@ -54,6 +54,7 @@ class _HipModel:
         self._decode_cols = False
         self._verify = None
         self._verify_layers = False
+        self._layer_precision = None
         if device is not None:
             self.to(device)
 
@@ -81,6 +82,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_verify(self._handle, *self._verify), "c3_model_set_verify")
         if self._verify_layers:
             _lib.check(_lib.lib().c3_model_set_verify_layers(self._handle, 1), "c3_model_set_verify_layers")
+        if self._layer_precision is not None:
+            _lib.check(_lib.lib().c3_model_set_layer_precision(self._handle, self._layer_precision.encode()), "c3_model_set_layer_precision")
         if sd is not None:
             self._load(sd)
         return self
@@ -350,6 +353,41 @@ class _HipModel:
         if self._handle is None:
             raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
         _lib.check(_lib.lib().c3_model_verify_reset(self._handle), "c3_model_verify_reset")
+        return self
+
+    # ---- per-layer precision (c3_model_set_layer_precision) ----
+    @staticmethod
+    def _layer_names(names):
+        """the plan as the C ABI takes it: a string as it is, an iterable of names joined by commas"""
+        if isinstance(names, bytes):
+            names = names.decode()
+        if isinstance(names, str):
+            return names
+        try:
+            names = list(names)
+        except TypeError as e:
+            raise _lib.C3Error(f"layer names must be a string or an iterable of strings, got {names!r}") from e
+        for n in names:
+            if not isinstance(n, str) or not n or "," in n:
+                raise _lib.C3Error(f"layer names must be non-empty strings without commas, got {n!r}")
+        return ",".join(names)
+
+    def layer_precision(self, names=None):
+        """The per-layer precision plan: the layers ``names`` (a string "lstm2,l4" or an iterable of names; "" = none, "all" = every layer)
+        run their fp32-MFMA forms, every other layer its fp16x3 form (c3_model_set_layer_precision; include/c3hip.h lists the names of
+        both networks).  Without an argument: the plan in force as a tuple of names in network order."""
+        if names is None:
+            if self._handle is None:
+                raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+            buf = C.create_string_buffer(256)
+            _lib.check(_lib.lib().c3_model_layer_precision(self._handle, buf, 256), "c3_model_layer_precision")
+            return tuple(n for n in buf.value.decode().split(",") if n)
+        text = self._layer_names(names)
+        _lib.check(_lib.lib().c3_layer_precision_check(self.KIND, text.encode()), "c3_layer_precision_check")
+        if self._handle is None:  # (a call that fails leaves nothing behind for a later .to(device) to apply)
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        _lib.check(_lib.lib().c3_model_set_layer_precision(self._handle, text.encode()), "c3_model_set_layer_precision")
+        self._layer_precision = text  # a handle created anew by .to(another device) takes the plan along
         return self
 
     def range_status(self):

@@ -434,6 +434,27 @@ typedef struct {
 int c3_model_set_verify_layers(c3_model *m, int enable);
 int c3_model_verify_layers(c3_model *m, c3_verify_layer *out, int max_entries);
 /* which kernel forms the handle's last forward pass took, as "key=value ..." text; bench.py reports it next to its rates */
+/* ---- per-layer precision: named layers on their fp32-MFMA forms, the rest of the handle on fp16x3 ----
+ * Precision used to be a property of the whole handle: C3HIP_FP32=1, the range guard and the load-time rule move EVERY layer off the 16-bit
+ * matrix instructions.  A plan names the layers that run their fp32 form; every other layer keeps its product kernel, and activations
+ * cross the boundary in the layout the neighbour reads (plane activations stay planes: c3_gemm.h ConvPlanesLoader, c3_lstm_fused.h).
+ *   names       comma separated layer names, "" = none (the default), "all" = every layer (the handle then runs exactly what C3HIP_FP32=1 runs).
+ *               pileup: lstm1, proj2, lstm2, l4        full alignment: conv1, res1a, res1b, conv3, res2a, res2b, conv5, res3a, res3b, l4
+ *               (the FC tail is fp32 in both forms and has no name; naming a layer twice is accepted)
+ * An unknown name, a name of the other network and an empty entry between commas are errors that name the entry and leave the plan as it
+ * was; so is a call while a c3_predict_submit of the handle is pending.  The plan belongs to the handle: it survives c3_model_load and
+ * applies to every entry and lane, the device-resident ones included.  A full-alignment plan that names conv1, res1a or res1b runs conv1 as
+ * its own launch (as C3HIP_CONV1_FUSED=0), one that names res3b the pooling (as C3HIP_SPP_FUSED=0).  The range guard is unchanged (a raised
+ * flag moves the whole handle to fp32 for good); verify mode compares the plan's rows and layer outputs with the all-fp32 forms.
+ * env C3HIP_FP32_LAYERS=<names>: the plan a handle starts with (an invalid value makes c3_model_create fail with that message);
+ * env C3HIP_AUTO_FP32_LAYERS=<names>: what the load-time rule escalates INSTEAD of the whole handle (c3_model_describe:
+ * precision=fp32-auto(<names>), on_fp32=0).  C3HIP_FP32=1 wins over both; with C3HIP_FP32=0 an explicit plan still applies.
+ *   c3_model_layer_precision   the plan in force, network order ("" = none)
+ *   c3_layer_precision_check   plain host code, no device: 0, or != 0 with c3_last_error() naming the bad entry
+ * c3_model_describe gains fp32_layers=<names> only while a plan is in force. */
+int c3_model_set_layer_precision(c3_model *m, const char *names);
+int c3_model_layer_precision(c3_model *m, char *buf, int buf_bytes);
+int c3_layer_precision_check(int kind, const char *names);
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
 int c3_model_synchronize(c3_model *m);
