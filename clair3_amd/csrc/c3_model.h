@@ -16,6 +16,7 @@
 //                  runs a second forward pass on the fp32 forms from the same staged input (c3_hostring.h shadow_pass) and the two sets of
 //                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
+//   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
 // one fp32-MFMA form that the range guard falls back to (and that C3HIP_FP32=1 selects from the start).
@@ -233,6 +234,7 @@ struct Lane {
     int8_t *xe = nullptr;   // dense int8 windows of a micro-batch that came as occupied rows (c3_expand.h); allocated on first use
     int64_t xe_cap = 0;     // windows it holds
 };
+constexpr int kCalChannels = 896;  // the channels of the six groups of c3_pack.h FaChannelExps: 2 x (64 + 128 + 256)
 constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
 
 struct c3_model {
@@ -352,6 +354,22 @@ struct c3_model {
     HostSlot *layer_slot = nullptr;          // ... this slot's batch with layer records
     int64_t layer_batch = 0;                 // ... of this many windows
     const uint32_t *layer_kept_count = nullptr;  // ... a candidate batch: the device word with its kept count
+
+    // ---- calibration (c3_calibrate.h; full alignment): off = nothing allocated, nothing launched, a load packs what it packs without it ----
+    int census_pass = 0;              // forward_device is enqueuing a census pass: tap() takes the channels' maxima instead of copying
+    uint32_t *census_dev = nullptr;   // device [9][256]: bit patterns of max |x| per convolution and channel, in the units of the current load
+    float census[9][256] = {};        // the same in the checkpoint's units, accumulated over calls until c3_model_calibrate_reset
+    int64_t census_windows = 0;
+    bool lowering_set = false;        // c3_model_set_channel_lowering: the next loads pack k = k0 - lowering (survives a load, like the plan)
+    uint8_t lowering[kCalChannels] = {};
+    int lowering_cap = 0;             // ... and where that lowering came from, recorded WITH it (c3_model_describe): the cap and the windows of
+    int64_t lowering_windows = 0;     //     the solve that made it (c3_model_set_calibration_origin for one made elsewhere; 0 = not known)
+    bool solved = false;              // the handle's last c3_model_calibration_solve: its result, cap and the census windows it saw
+    uint8_t solved_lowering[kCalChannels] = {};
+    int solved_cap = 0;
+    int64_t solved_windows = 0;
+    bool chan_ok = false;             // a load has filled ...
+    int8_t chan_k0[kCalChannels] = {}, chan_k[kCalChannels] = {};  // ... the exponents fa_channel_exps gave it / it runs with
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;

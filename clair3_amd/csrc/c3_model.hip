@@ -7,11 +7,12 @@
 #include "c3_comm.h"
 #include "c3_debug.h"
 #include "c3_rows.h"
-#include "c3_mixed.h"  // (last: c3_forward.h says why)
+#include "c3_mixed.h"  // (behind every kernel of the handle without a plan: c3_forward.h says why)
+#include "c3_calibrate.h"  // (last, for the same reason)
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.2 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.3 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -276,6 +277,7 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
         if (3 * cin > 32) return fail("full-alignment input_channels %d not supported (3*C must be <= 32)", cin);
         FaChannelExps ex;
         TRY(fa_channel_exps(tm, ex));
+        TRY(apply_channel_lowering(m, ex));  // (c3_calibrate.h: records k0; changes ex only while a lowering is set)
         for (int l = 0; l < 9; ++l) {
             TRY(pack_conv(m, tm, l, cin, ex));
             m->act_exp[l] = *ex.out_of(l);
@@ -383,6 +385,11 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
         const size_t at = strlen(buf);
         snprintf(buf + at, (size_t)n - at, " fp32_layers=%s", layer_mask_text(m->kind, m->fp32_plan | m->fp32_auto).c_str());
     }
+    if (m->lowering_set) {  // only while a lowering is set (c3_calibrate.h)
+        const size_t at = strlen(buf);
+        snprintf(buf + at, (size_t)n - at, " calibration=cap:%d,windows:%lld,lowered:%d", m->lowering_cap, (long long)m->lowering_windows,
+                 (int)std::count_if(m->lowering, m->lowering + kCalChannels, [](uint8_t v) { return v != 0; }));
+    }
     if (m->verify_seen) {  // verify mode is or was on (c3_verify.h): the setting and the totals behind everything else
         const c3_verify_stats &t = m->vstats;
         const size_t at = strlen(buf);
@@ -422,6 +429,7 @@ int c3_model_destroy(c3_model *m) {
         if (p) (void)hipFree(p);
     if (m->range_flag) (void)hipFree(m->range_flag);
     if (m->layer_exp) (void)hipFree(m->layer_exp);
+    if (m->census_dev) (void)hipFree(m->census_dev);
     if (m->pin_flag) (void)hipHostFree(m->pin_flag);
     for (int l = 0; l < 9; ++l) {
         if (m->conv_w[l]) (void)hipFree(m->conv_w[l]);

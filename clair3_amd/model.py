@@ -55,6 +55,9 @@ class _HipModel:
         self._verify = None
         self._verify_layers = False
         self._layer_precision = None
+        self._lowering = None   # calibration (set_calibration): the channel lowering a handle created anew takes along ...
+        self._cal_meta = None   # ... and (cap_log2, windows) of the calibration it came from, for save_calibration
+        self._calibration_file = None  # C3HIP_CALIBRATION of a model built without a checkpoint (predict.calibration_from_env): applied by the first load
         if device is not None:
             self.to(device)
 
@@ -84,6 +87,10 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_verify_layers(self._handle, 1), "c3_model_set_verify_layers")
         if self._layer_precision is not None:
             _lib.check(_lib.lib().c3_model_set_layer_precision(self._handle, self._layer_precision.encode()), "c3_model_set_layer_precision")
+        if self._lowering is not None:
+            _lib.check(_lib.lib().c3_model_set_channel_lowering(self._handle, self._lowering.ctypes.data), "c3_model_set_channel_lowering")
+            if self._cal_meta is not None:
+                _lib.check(_lib.lib().c3_model_set_calibration_origin(self._handle, *self._cal_meta), "c3_model_set_calibration_origin")
         if sd is not None:
             self._load(sd)
         return self
@@ -103,6 +110,8 @@ class _HipModel:
         self._geometry = (int(depth), int(positions))
         if self._handle is not None:
             _lib.check(_lib.lib().c3_model_set_geometry(self._handle, *self._geometry), "c3_model_set_geometry")
+            if self.KIND == _lib.KIND_FULL_ALIGNMENT:  # (a census counts windows of ONE geometry: the layers' shapes follow it)
+                _lib.check(_lib.lib().c3_model_calibrate_reset(self._handle), "c3_model_calibrate_reset")
             if self._pending_sd is not None:
                 self._load(self._pending_sd)
         return self
@@ -138,7 +147,12 @@ class _HipModel:
         if self._handle is None:
             self.to(0)
         else:
+            if self.KIND == _lib.KIND_FULL_ALIGNMENT:  # (the census was about the checkpoint before; a lowering stays, as the precision plan does)
+                _lib.check(_lib.lib().c3_model_calibrate_reset(self._handle), "c3_model_calibrate_reset")
             self._load(sd)
+        if self._calibration_file is not None:
+            path, self._calibration_file = self._calibration_file, None
+            self.load_calibration(path)
         return self
 
     def _load(self, sd):
@@ -388,6 +402,94 @@ class _HipModel:
             raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
         _lib.check(_lib.lib().c3_model_set_layer_precision(self._handle, text.encode()), "c3_model_set_layer_precision")
         self._layer_precision = text  # a handle created anew by .to(another device) takes the plan along
+        return self
+
+    # ---- calibration of the channel exponents from observed activations (c3_model_calibrate; full alignment; DESIGN.md 1 Range) ----
+    def _need_handle(self):
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+
+    def calibrate(self, x, cap_log2=10, apply=True):
+        """Measure the activations of the windows ``x`` on the fp32 forms (added to the handle's census), work out by how many powers of two
+        every channel's exponent has to come down for them to stay below 2^cap_log2 (c3_model_calibration_solve; include/c3hip.h states the
+        rule) and, with apply=True, set that lowering and load the held state dict again with it.  Exact rescaling: the rows stay the
+        checkpoint's.  Returns a summary (clair3_amd/calibrate.py summary): per group the channels lowered, the group shift and the largest scaled activation
+        before and after.  INTEGRATION.md 8 says when and on what sample."""
+        from . import calibrate as cal
+        self._need_handle()
+        if isinstance(cap_log2, bool) or not isinstance(cap_log2, (int, np.integer)) or not 4 <= cap_log2 <= 13:
+            raise _lib.C3Error(f"cap_log2 must be an integer in [4, 13], got {cap_log2!r}")
+        x, dt = self._window_batch(x)
+        _lib.check(_lib.lib().c3_model_calibrate(self._handle, x.ctypes.data, dt, x.shape[0], None), "c3_model_calibrate")
+        lowering = np.zeros(cal.CHANNELS, dtype=np.uint8)
+        _lib.check(_lib.lib().c3_model_calibration_solve(self._handle, int(cap_log2), lowering.ctypes.data), "c3_model_calibration_solve")
+        state = self.calibration()
+        if apply:
+            self.set_calibration(lowering, reload=True, cap_log2=int(cap_log2), windows=state["windows"])
+        out = cal.summary(state["census"], state["k0"], lowering)
+        out.update(cap_log2=int(cap_log2), windows=state["windows"], applied=bool(apply), lowering=lowering)
+        return out
+
+    def calibration(self):
+        """the handle's calibration state as a dict: ``census`` (9, 256) max |x| per convolution and channel in the checkpoint's units and
+        the ``windows`` it counts (c3_model_calibration_census), ``k0`` / ``k`` (896) the channel exponents of the last load as the load-time
+        rule gave them / as the handle runs them (c3_model_channel_exps), ``lowering`` (896, or None while none is set)"""
+        self._need_handle()
+        census, windows = np.zeros((9, 256), dtype=np.float32), C.c_int64(0)
+        _lib.check(_lib.lib().c3_model_calibration_census(self._handle, census.ctypes.data, C.byref(windows)), "c3_model_calibration_census")
+        k0, k = np.zeros(896, dtype=np.int8), np.zeros(896, dtype=np.int8)
+        _lib.check(_lib.lib().c3_model_channel_exps(self._handle, k0.ctypes.data, k.ctypes.data), "c3_model_channel_exps")
+        return dict(census=census, windows=int(windows.value), k0=k0, k=k, lowering=None if self._lowering is None else self._lowering.copy())
+
+    def set_calibration(self, lowering, reload=False, cap_log2=0, windows=0):
+        """Set the channel lowering (896 entries, stage0 | inner0 | stage1 | inner1 | stage2 | inner2; None = none).  It takes effect at the
+        next load -- load_state_dict, or here with reload=True from the state dict the object holds -- and stays with the model from then on
+        (c3_model_set_channel_lowering).  ``cap_log2`` and ``windows`` say where it came from (c3_model_set_calibration_origin: what describe()
+        and save_calibration report with it; 0 = not known)."""
+        from . import calibrate as cal
+        self._need_handle()
+        if lowering is not None:
+            lowering = cal.as_lowering(lowering)
+        _lib.check(_lib.lib().c3_model_set_channel_lowering(self._handle, None if lowering is None else lowering.ctypes.data),
+                   "c3_model_set_channel_lowering")
+        if lowering is not None:
+            _lib.check(_lib.lib().c3_model_set_calibration_origin(self._handle, int(cap_log2), int(windows)), "c3_model_set_calibration_origin")
+        self._lowering, self._cal_meta = lowering, None if lowering is None else (int(cap_log2), int(windows))
+        if reload and self._pending_sd is not None:
+            self._load(self._pending_sd)
+        return self
+
+    def calibration_reset(self):
+        """zero the census and its window count (c3_model_calibrate_reset); a lowering that is set stays"""
+        self._need_handle()
+        _lib.check(_lib.lib().c3_model_calibrate_reset(self._handle), "c3_model_calibrate_reset")
+        return self
+
+    def save_calibration(self, path):
+        """the lowering in force as a calibration file (clair3_amd/calibrate.py names the format): what C3HIP_CALIBRATION=<file> hands to
+        every worker process of a job"""
+        from . import calibrate as cal
+        if self._lowering is None:
+            raise _lib.C3Error("no calibration is set: calibrate() first")
+        cap, windows = self._cal_meta or (0, 0)
+        depth = (self._geometry or (89, 33))[0]
+        cal.write_file(path, channels=self.input_channels, depth=depth, cap_log2=cap, windows=windows, k0=self.calibration()["k0"],
+                       lowering=self._lowering)
+        return self
+
+    def load_calibration(self, path):
+        """Apply a calibration file: checked against this model (input channels, depth, and ``k0`` -- the channel exponents of the checkpoint
+        it was made for -- against the loaded checkpoint's), set, and the held state dict loaded again with it.  Anything that does not fit raises."""
+        from . import calibrate as cal
+        self._need_handle()
+        k0 = self.calibration()["k0"]  # (a pileup handle, or one without weights, is refused here with the library's words)
+        f = cal.read_file(path)
+        depth = (self._geometry or (89, 33))[0]
+        if f["channels"] != self.input_channels or f["depth"] != depth:
+            raise _lib.C3Error(f"{path}: made for windows of {f['channels']} channels and depth {f['depth']}, this model has {self.input_channels} and {depth}")
+        if not np.array_equal(f["k0"], k0):
+            raise _lib.C3Error(f"{path}: made for another checkpoint (its channel exponents k0 differ from the loaded checkpoint's)")
+        self.set_calibration(f["lowering"], reload=True, cap_log2=f["cap_log2"], windows=f["windows"])
         return self
 
     def range_status(self):

@@ -9,9 +9,9 @@ from . import _lib
 from .model import Clair3_F, Clair3_P, _device_index
 
 
-def _load_torch_checkpoint(model, checkpoint_path, device=None):
-    """clair3/CallVariantsFromCffi.py:19-28: append '.pt' when missing, deserialise, accept a bare state_dict or {"state_dict": ...},
-    strict load.  The file is read by clair3_amd/ptfile.py (numpy only: a worker process that never needs torch never imports it,
+def _read_checkpoint(checkpoint_path):
+    """the state dict of a checkpoint file, as _load_torch_checkpoint reads it: '.pt' appended when missing, a bare state_dict or
+    {"state_dict": ...}.  The file is read by clair3_amd/ptfile.py (numpy only: a worker process that never needs torch never imports it,
     clair3_amd/lazy_torch.py); what that reader does not handle -- the legacy non-zip format, exotic dtypes, pickled modules -- goes to
     torch.load(map_location='cpu') as before (C3HIP_PTFILE=0: always)."""
     import os
@@ -28,12 +28,34 @@ def _load_torch_checkpoint(model, checkpoint_path, device=None):
         import torch
         checkpoint = torch.load(checkpoint_path, map_location="cpu")
     if isinstance(checkpoint, dict) and "state_dict" in checkpoint:
-        state_dict = checkpoint["state_dict"]
-    else:
-        state_dict = checkpoint
-    model.load_state_dict(state_dict)
+        return checkpoint["state_dict"]
+    return checkpoint
+
+
+def _load_torch_checkpoint(model, checkpoint_path, device=None):
+    """clair3/CallVariantsFromCffi.py:19-28: append '.pt' when missing, deserialise, accept a bare state_dict or {"state_dict": ...},
+    strict load; then what the environment asks of a model where it is built (C3HIP_CALIBRATION, C3HIP_VERIFY)."""
+    model.load_state_dict(_read_checkpoint(checkpoint_path))
     _register_current(model)
+    calibration_from_env(model)
     verify_from_env(model)
+
+
+def calibration_from_env(model):
+    """C3HIP_CALIBRATION=<file>: a full-alignment model takes the calibration file (clair3_amd/calibrate.py) where it is built, so that every
+    worker process of a job runs the same channel exponents; a pileup model ignores it.  A file that is missing, invalid or made for another
+    checkpoint raises: a job asked to run calibrated must not run uncalibrated because of a typo."""
+    import os
+    path = os.environ.get("C3HIP_CALIBRATION")
+    if not path or not path.strip() or getattr(model, "KIND", None) != _lib.KIND_FULL_ALIGNMENT:
+        return False
+    if model._pending_sd is None:  # built without a checkpoint: the file is checked now and applied by the model's first load_state_dict
+        from . import calibrate as cal
+        cal.read_file(path.strip())
+        model._calibration_file = path.strip()
+        return True
+    model.load_calibration(path.strip())
+    return True
 
 
 def parse_verify_env(value, tol=None):
@@ -227,8 +249,9 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
     m.eval()
     if chkpnt_fn is not None:
         _load_torch_checkpoint(m, chkpnt_fn, device)
-    else:
-        verify_from_env(m)  # (C3HIP_VERIFY: with a checkpoint the loader has done it)
+    else:  # (with a checkpoint the loader has done both)
+        calibration_from_env(m)
+        verify_from_env(m)
     return m
 
 

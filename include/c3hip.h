@@ -455,6 +455,49 @@ int c3_model_verify_layers(c3_model *m, c3_verify_layer *out, int max_entries);
 int c3_model_set_layer_precision(c3_model *m, const char *names);
 int c3_model_layer_precision(c3_model *m, char *buf, int buf_bytes);
 int c3_layer_precision_check(int kind, const char *names);
+/* ---- full alignment: channel exponents calibrated from observed activations (DESIGN.md 1 Range) ----
+ * The reference keeps its activations in fp32 (clair3/model.py:377-416, torch conv2d + BatchNorm2d in eval mode) and has no range to mind.
+ * Here they live as fp16 piece pairs: c3_model_load gives every channel an exact power of two 2^k0 from its BatchNorm's gamma and beta, and
+ * the range guard (see c3_predict) moves a handle whose activations reach 16000 all the same to the fp32 matrix instructions for good.
+ * Calibration measures instead: a sample of the job's own windows runs on the fp32 forms, a census takes max |x| of every convolution's
+ * output channels, and a rule turns it into a LOWERING per channel -- by how many powers of two its exponent comes down, k = k0 - lowering.
+ * Exact rescaling, as at load time: the rows are those of the checkpoint as given.  Opt-in; a handle without a lowering packs and runs what
+ * it did before these entries existed.
+ *   channels    896 = 2 x (64 + 128 + 256), the groups in the order stage0, inner0, stage1, inner1, stage2, inner2: stage s = the outputs
+ *               of convolutions 3 s and 3 s + 2 (one exponent for both: the residual add), inner s = the output of convolution 3 s + 1
+ *   c3_model_calibrate             runs the windows on the fp32 forms in the handle's first lane, blocking, and adds them to the census;
+ *                                  y_host (may be NULL) receives their rows, [batch][c3_model_row_size].  It leaves the handle's precision, range
+ *                                  flag, verify totals and what c3_model_describe reports of the last predict call as they are
+ *   c3_model_calibrate_reset       zeroes the census and its window count (the census outlives c3_model_load: reset it with a new checkpoint)
+ *   c3_model_calibration_census    absmax_out[9][256]: max |x| per convolution and channel in the CHECKPOINT's units (the same whatever
+ *                                  exponents the handle ran with), entries beyond a layer's channels 0; windows_out: windows counted.  Either may be NULL
+ *   c3_model_calibration_solve     the rule on the census and the k0 of the last load, group by group: for a stage the larger of its two layers
+ *   c3_calibration_rule            the rule for ONE group of n channels, plain host code, no device: with s[c] = scaled_max[c] = f * 2^e, f in
+ *                                  [0.5, 1): d[c] = max(0, e - cap_log2) (0 for s[c] = 0); d_group = the lower median of d over the channels
+ *                                  with s[c] > 0 (0 without one); lowering[c] = max(d[c], d_group) for EVERY channel -- a channel the sample
+ *                                  left silent follows its group.  cap_log2 in [4, 13]; 10 leaves 16000 / 2^10 = 15.6 x for windows the sample
+ *                                  did not contain and is 50 x above what ordinary checkpoints reach.  A value that is not finite is an error
+ *                                  that names the channel (c3_model_calibration_solve: the layer and the channel).  The solve additionally keeps
+ *                                  k0 - lowering >= -40, the clamp of the load-time rule
+ *   c3_model_set_channel_lowering  lowering[896], NULL = none.  Takes effect at the next c3_model_load; belongs to the handle like the precision
+ *                                  plan: it survives loads and applies to every entry and lane
+ *   c3_model_channel_exps          k0_out[896] / k_out[896] of the last load (either may be NULL): k0 identifies the checkpoint a lowering was made for
+ * All but c3_calibration_rule: full-alignment handles only (the gates of the pileup network's LSTMs are not homogeneous) and refused while a
+ * c3_predict_submit of the handle is pending.  The range guard, verify mode (which compares the calibrated product rows with the fp32 forms on
+ * the same packed weights) and the precision plan are unchanged.  c3_model_describe gains calibration=cap:<n>,windows:<n>,lowered:<channels>
+ * only while a lowering is set.  cap and windows describe the lowering in force and are recorded with it: c3_model_set_channel_lowering takes
+ * them from the handle's last solve where the lowering is that solve's result, else 0 (not known), and
+ *   c3_model_set_calibration_origin   states them for a lowering made elsewhere (cap_log2 in [0, 13], windows >= 0; what a calibration file carries).
+ * What the census pass does leave behind: the first lane's workspace holds ITS activations, so c3_debug_fetch after c3_model_calibrate returns
+ * those (fp32 forms) and not the last predict call's; tap buffers (c3_debug_tap) and a profile being taken (c3_profile_enable) are not touched. */
+int c3_model_calibrate(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host);
+int c3_model_calibrate_reset(c3_model *m);
+int c3_model_calibration_census(c3_model *m, float *absmax_out, int64_t *windows_out);
+int c3_model_calibration_solve(c3_model *m, int cap_log2, uint8_t *lowering_out);
+int c3_model_set_channel_lowering(c3_model *m, const uint8_t *lowering);
+int c3_model_set_calibration_origin(c3_model *m, int cap_log2, int64_t windows);
+int c3_model_channel_exps(c3_model *m, int8_t *k0_out, int8_t *k_out);
+int c3_calibration_rule(const float *scaled_max, int n, int cap_log2, uint8_t *lowering_out);
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
 int c3_model_synchronize(c3_model *m);
