@@ -31,6 +31,7 @@ EXPORTS = (
     "c3_model_set_layer_precision", "c3_model_layer_precision", "c3_layer_precision_check",
     "c3_model_calibrate", "c3_model_calibrate_reset", "c3_model_calibration_census", "c3_model_calibration_solve",
     "c3_model_set_channel_lowering", "c3_model_set_calibration_origin", "c3_model_channel_exps", "c3_calibration_rule",
+    "c3_model_set_exact", "c3_predict_exact", "c3_exact_fetch",
 )
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
@@ -181,6 +182,9 @@ def lib():
     L.c3_model_set_calibration_origin.argtypes = [C.c_void_p, C.c_int, C.c_int64]
     L.c3_model_channel_exps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_calibration_rule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.c3_model_set_exact.argtypes = [C.c_void_p, C.c_int]
+    L.c3_predict_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+    L.c3_exact_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -17,6 +17,7 @@
 //                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries
+//   c3_exact.h     the exact form: both networks in fp64 on the device, its kernels, workspace and entries (c3_predict_exact, c3_exact_fetch)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
 // one fp32-MFMA form that the range guard falls back to (and that C3HIP_FP32=1 selects from the start).
@@ -234,6 +235,23 @@ struct Lane {
     int8_t *xe = nullptr;   // dense int8 windows of a micro-batch that came as occupied rows (c3_expand.h); allocated on first use
     int64_t xe_cap = 0;     // windows it holds
 };
+// ---- the exact form (c3_exact.h): never enabled = nothing allocated, uploaded or launched ----
+struct ExactState {
+    bool want = false;    // c3_model_set_exact: the next loads also place the double weights
+    bool loaded = false;  // the last load did
+    std::vector<void *> weights;  // every device allocation of the double weights (c3_pack.h pack_exact)
+    double *wih[2] = {}, *pb[2] = {}, *whh[2] = {};  // pileup: W_ih [2 * 4H][in], b_ih + b_hh [2 * 4H] in PyTorch row order; W_hh as exact_lstm_kernel fragments
+    double *cw[9] = {}, *cb[9] = {};                 // full alignment: [Cout][tap][Cin] and [Cout], BatchNorm folded in double
+    double *l4w = nullptr, *l4b = nullptr, *w5 = nullptr, *b5 = nullptr, *wh = nullptr, *bh = nullptr;  // L4 [FC][K4]; L5_k stacked [nb * 128][FC]; heads stacked [nout][128]
+    // the workspace of a pass (c3_exact.h states the sizes): the staged windows, every layer output, the rows
+    std::vector<void *> ws;
+    int64_t cap = 0;            // windows a pass can hold
+    size_t x_window_bytes = 0;  // ... of up to this many bytes each
+    void *x = nullptr;
+    double *act[9] = {}, *spp = nullptr, *gx1 = nullptr, *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
+    double *l4 = nullptr, *l5 = nullptr, *logit = nullptr, *y = nullptr;
+    int64_t last_n = 0;  // windows of the last pass of the last call (c3_exact_fetch)
+};
 constexpr int kCalChannels = 896;  // the channels of the six groups of c3_pack.h FaChannelExps: 2 x (64 + 128 + 256)
 constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
 
@@ -370,6 +388,8 @@ struct c3_model {
     int64_t solved_windows = 0;
     bool chan_ok = false;             // a load has filled ...
     int8_t chan_k0[kCalChannels] = {}, chan_k[kCalChannels] = {};  // ... the exponents fa_channel_exps gave it / it runs with
+
+    ExactState exact;
 
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
@@ -597,6 +617,18 @@ static void free_workspace(Lane &L) {
 }
 static void free_all_workspaces(c3_model *m) {  // every lane's (geometry change, destruction)
     for (Lane &L : m->lanes) free_workspace(L);
+}
+
+static void exact_free_workspace(c3_model *m) {  // (geometry change, growth, destruction)
+    ExactState &E = m->exact;
+    for (void *p : E.ws) (void)hipFree(p);
+    E.ws.clear();
+    E.cap = 0, E.x_window_bytes = 0, E.last_n = 0;
+}
+static void exact_free_weights(c3_model *m) {
+    for (void *p : m->exact.weights) (void)hipFree(p);
+    m->exact.weights.clear();
+    m->exact.loaded = false, m->exact.last_n = 0;
 }
 
 static int64_t max_microbatch(const c3_model *m) { return m->kind == C3_KIND_PILEUP ? 16384 : 2048; }

@@ -9,10 +9,11 @@
 #include "c3_rows.h"
 #include "c3_mixed.h"  // (behind every kernel of the handle without a plan: c3_forward.h says why)
 #include "c3_calibrate.h"  // (last, for the same reason)
+#include "c3_exact.h"  // (behind every other kernel: the exact form is an instrument and moves none of them)
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.3 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.4 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -205,6 +206,7 @@ int c3_model_set_geometry(c3_model *m, int depth, int positions) {
     if (m->K4 % kBK) return fail("unsupported geometry: L4 fan-in %d is not a multiple of %d", m->K4, kBK);
     HIP_TRY(hipDeviceSynchronize());
     free_all_workspaces(m);
+    exact_free_workspace(m);
     m->loaded = false;
     return 0;
 }
@@ -292,6 +294,8 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
         // strict like load_state_dict: report the first unexpected key
         return fail("Unexpected key(s) in state_dict: %zu tensors given, %zu expected", tm.size(), expected);
     }
+    exact_free_weights(m);  // the exact form (c3_exact.h): the double weights travel with a load only while c3_model_set_exact is on
+    if (m->exact.want) TRY(pack_exact(m, tm));
     // new weights, new start: what the range guard decided (f16_ok and the sticky device flag) was about the weights before.  The
     // handle goes back to what C3HIP_FP32 chose, else to the load-time decision above (pileup) or to fp16x3 (full alignment).
     if (m->precision_forced) m->f16_ok = m->forced_f16, m->precision = m->forced_f16 ? "fp16x3" : "fp32-forced";
@@ -401,6 +405,7 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  (long long)(t.near_ties[0] + t.near_ties[1] + t.near_ties[2] + t.near_ties[3]), (long long)t.escalations);
         if (m->verify_layers) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), ",layers:1");
     }
+    if (m->exact.want) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " exact=1");  // only while the exact form is enabled (c3_exact.h)
     return 0;
 }
 
@@ -416,6 +421,8 @@ int c3_model_destroy(c3_model *m) {
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
     free_all_workspaces(m);
+    exact_free_workspace(m);
+    exact_free_weights(m);
     for (const Lane &L : m->lanes)
         if (L.stream) (void)hipStreamDestroy(L.stream);
     float *ws[] = {m->proj_w[0], m->proj_w[1], m->proj_b[0], m->proj_b[1], m->whh[0], m->whh[1], m->whh16[0], m->whh16[1],

@@ -615,3 +615,97 @@ static int pack_conv(c3_model *m, const TensorMap &tm, int l, int Cin, const FaC
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------------------ the exact form (c3_exact.h)
+static int upload_f64(c3_model *m, double **dst, const std::vector<double> &src) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, std::max<size_t>(src.size() * sizeof(double), 256)));
+    m->exact.weights.push_back(p);
+    TRY(h2d_staged(p, src.data(), src.size() * sizeof(double)));
+    *dst = (double *)p;
+    return 0;
+}
+
+// The checkpoint's fp32 values widened to double, in the layouts of c3_exact.h: no exponent, no scale, no lowering.  BatchNorm2d(eval,
+// eps = 1e-3; clair3/model.py:191,195-197) is folded in double -- scale = gamma / sqrt(var + eps), w' = w * scale, b' = (b - mean) * scale + beta --
+// and stays double: within 1e-15 relative of applying it as its own step.  The /100 of the input (model.py:378) is NOT folded: the loader divides.
+static int pack_exact(c3_model *m, const TensorMap &tm) {
+    ExactState &E = m->exact;
+    const float *w, *b;
+    if (m->kind == C3_KIND_PILEUP) {
+        for (int layer = 0; layer < 2; ++layer) {
+            const int H = layer ? 160 : 128, in = layer ? 256 : m->C, NU = H / 16, NK = H / 4;
+            const std::string base = layer ? "LSTM2" : "LSTM1";
+            std::vector<double> wi((size_t)2 * 4 * H * in), pb((size_t)2 * 4 * H), wf((size_t)2 * 4 * H * H);
+            for (int dir = 0; dir < 2; ++dir) {
+                const std::string sfx = dir ? "_reverse" : "";
+                const float *wih, *whh, *bih, *bhh;
+                TRY(want(tm, base + ".weight_ih_l0" + sfx, {4 * H, in}, &wih));
+                TRY(want(tm, base + ".weight_hh_l0" + sfx, {4 * H, H}, &whh));
+                TRY(want(tm, base + ".bias_ih_l0" + sfx, {4 * H}, &bih));
+                TRY(want(tm, base + ".bias_hh_l0" + sfx, {4 * H}, &bhh));
+                for (int r = 0; r < 4 * H; ++r) {
+                    pb[(size_t)dir * 4 * H + r] = (double)bih[r] + (double)bhh[r];
+                    for (int k = 0; k < in; ++k) wi[((size_t)dir * 4 * H + r) * in + k] = (double)wih[(size_t)r * in + k];
+                }
+                // exact_lstm_kernel: [dir][unit block u][gate][k-step][lane] = W_hh[gate * H + 16 u + (lane & 15)][4 ks + (lane >> 4)]
+                for (int u = 0; u < NU; ++u)
+                    for (int g = 0; g < 4; ++g)
+                        for (int ks = 0; ks < NK; ++ks)
+                            for (int lane = 0; lane < 64; ++lane)
+                                wf[((((size_t)dir * NU + u) * 4 + g) * NK + ks) * 64 + lane] =
+                                    (double)whh[(size_t)(g * H + 16 * u + (lane & 15)) * H + 4 * ks + (lane >> 4)];
+            }
+            TRY(upload_f64(m, &E.wih[layer], wi));
+            TRY(upload_f64(m, &E.pb[layer], pb));
+            TRY(upload_f64(m, &E.whh[layer], wf));
+        }
+    } else {
+        int Cin = m->C;
+        for (int l = 0; l < 9; ++l) {
+            const int Cout = kConvCout[l];
+            const float *g, *beta, *mean, *var;
+            const std::string cv = kConvName[l], bn = kBnName[l];
+            TRY(want(tm, cv + ".weight", {Cout, Cin, 3, 3}, &w));
+            TRY(want(tm, cv + ".bias", {Cout}, &b));
+            TRY(want(tm, bn + ".weight", {Cout}, &g));
+            TRY(want(tm, bn + ".bias", {Cout}, &beta));
+            TRY(want(tm, bn + ".running_mean", {Cout}, &mean));
+            TRY(want(tm, bn + ".running_var", {Cout}, &var));
+            std::vector<double> pw((size_t)Cout * 9 * Cin), pbias(Cout);
+            for (int co = 0; co < Cout; ++co) {
+                const double scale = (double)g[co] / std::sqrt((double)var[co] + 1e-3);
+                pbias[co] = ((double)b[co] - (double)mean[co]) * scale + (double)beta[co];
+                for (int ci = 0; ci < Cin; ++ci)
+                    for (int tap = 0; tap < 9; ++tap)
+                        pw[((size_t)co * 9 + tap) * Cin + ci] = (double)w[((size_t)co * Cin + ci) * 9 + tap] * scale;
+            }
+            TRY(upload_f64(m, &E.cw[l], pw));
+            TRY(upload_f64(m, &E.cb[l], pbias));
+            Cin = Cout;
+        }
+    }
+    const int FC = m->FC, K4 = m->K4, nb = m->nb;
+    TRY(want(tm, "L4.weight", {FC, K4}, &w));
+    TRY(want(tm, "L4.bias", {FC}, &b));
+    TRY(upload_f64(m, &E.l4w, std::vector<double>(w, w + (size_t)FC * K4)));
+    TRY(upload_f64(m, &E.l4b, std::vector<double>(b, b + FC)));
+    std::vector<double> w5((size_t)nb * 128 * FC), b5((size_t)nb * 128), wh((size_t)m->nout * 128), bh((size_t)m->nout);
+    for (int br = 0, off = 0; br < nb; off += kHeadN[br], ++br) {
+        const std::string l5 = "L5_" + std::to_string(br + 1), hd = kHeadName[br];
+        TRY(want(tm, l5 + ".weight", {128, FC}, &w));
+        TRY(want(tm, l5 + ".bias", {128}, &b));
+        std::copy(w, w + (size_t)128 * FC, w5.begin() + (size_t)br * 128 * FC);
+        std::copy(b, b + 128, b5.begin() + (size_t)br * 128);
+        TRY(want(tm, hd + ".weight", {kHeadN[br], 128}, &w));
+        TRY(want(tm, hd + ".bias", {kHeadN[br]}, &b));
+        std::copy(w, w + (size_t)kHeadN[br] * 128, wh.begin() + (size_t)off * 128);
+        std::copy(b, b + kHeadN[br], bh.begin() + off);
+    }
+    TRY(upload_f64(m, &E.w5, w5));
+    TRY(upload_f64(m, &E.b5, b5));
+    TRY(upload_f64(m, &E.wh, wh));
+    TRY(upload_f64(m, &E.bh, bh));
+    E.loaded = true;
+    return 0;
+}

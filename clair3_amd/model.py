@@ -57,6 +57,7 @@ class _HipModel:
         self._layer_precision = None
         self._lowering = None   # calibration (set_calibration): the channel lowering a handle created anew takes along ...
         self._cal_meta = None   # ... and (cap_log2, windows) of the calibration it came from, for save_calibration
+        self._exact = False     # the exact form (exact()): a handle created anew takes the setting along
         self._calibration_file = None  # C3HIP_CALIBRATION of a model built without a checkpoint (predict.calibration_from_env): applied by the first load
         if device is not None:
             self.to(device)
@@ -91,6 +92,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_channel_lowering(self._handle, self._lowering.ctypes.data), "c3_model_set_channel_lowering")
             if self._cal_meta is not None:
                 _lib.check(_lib.lib().c3_model_set_calibration_origin(self._handle, *self._cal_meta), "c3_model_set_calibration_origin")
+        if self._exact:
+            _lib.check(_lib.lib().c3_model_set_exact(self._handle, 1), "c3_model_set_exact")
         if sd is not None:
             self._load(sd)
         return self
@@ -491,6 +494,37 @@ class _HipModel:
             raise _lib.C3Error(f"{path}: made for another checkpoint (its channel exponents k0 differ from the loaded checkpoint's)")
         self.set_calibration(f["lowering"], reload=True, cap_log2=f["cap_log2"], windows=f["windows"])
         return self
+
+    # ---- the exact form: the network in fp64 from end to end on the device (c3_predict_exact) ----
+    def exact(self, enable=True):
+        """Enable the exact form: the double weights are placed on the device by a load, so the state dict the object holds is loaded again
+        (c3_model_set_exact takes effect at the next c3_model_load); without one the next load_state_dict does it.  predict_exact() and
+        exact_fetch() need it; nothing else changes: rows, precision, describe() apart from its last field `` exact=1``."""
+        if not isinstance(enable, (bool, np.bool_)):
+            raise _lib.C3Error(f"enable must be True or False, got {enable!r}")
+        self._need_handle()
+        _lib.check(_lib.lib().c3_model_set_exact(self._handle, int(enable)), "c3_model_set_exact")
+        self._exact = bool(enable)
+        if self._pending_sd is not None:
+            self._load(self._pending_sd)
+        return self
+
+    def predict_exact(self, x):
+        """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;
+        blocking; windows only).  Whatever precision, plan or calibration the handle runs does not enter."""
+        self._need_handle()
+        x, dt = self._window_batch(x)
+        y = np.empty((x.shape[0], self.output_size), dtype=np.float64)
+        _lib.check(_lib.lib().c3_predict_exact(self._handle, x.ctypes.data, dt, x.shape[0], y.ctypes.data), "c3_predict_exact")
+        return y
+
+    def exact_fetch(self, name, first, shape):
+        """windows first .. first + shape[0] of a layer output of the LAST PASS of the last predict_exact call as float64 (c3_exact_fetch);
+        names and layouts are tap_fetch's"""
+        self._need_handle()
+        out = np.empty(shape, dtype=np.float64)
+        _lib.check(_lib.lib().c3_exact_fetch(self._handle, name.encode(), int(first), int(shape[0]), out.ctypes.data, out.size), "c3_exact_fetch")
+        return out
 
     def range_status(self):
         """(flag, on_fp32): flag != 0 when an fp16x3 batch of this handle produced an activation near the fp16 range

@@ -39,6 +39,20 @@ def _load_torch_checkpoint(model, checkpoint_path, device=None):
     _register_current(model)
     calibration_from_env(model)
     verify_from_env(model)
+    exact_from_env(model)
+
+
+def exact_from_env(model):
+    """C3HIP_EXACT=1: the model takes the exact form along where it is built (model.exact(): the double weights travel with its loads);
+    unset, empty or 0: the model is left alone.  Anything else raises."""
+    import os
+    value = (os.environ.get("C3HIP_EXACT") or "").strip()
+    if value in ("", "0"):
+        return False
+    if value != "1":
+        raise _lib.C3Error(f"C3HIP_EXACT must be 0 or 1, got {value!r}")
+    model.exact(True)
+    return True
 
 
 def calibration_from_env(model):
@@ -252,6 +266,7 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
     else:  # (with a checkpoint the loader has done both)
         calibration_from_env(m)
         verify_from_env(m)
+        exact_from_env(m)
     return m
 
 

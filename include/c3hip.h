@@ -498,6 +498,32 @@ int c3_model_set_channel_lowering(c3_model *m, const uint8_t *lowering);
 int c3_model_set_calibration_origin(c3_model *m, int cap_log2, int64_t windows);
 int c3_model_channel_exps(c3_model *m, int8_t *k0_out, int8_t *k_out);
 int c3_calibration_rule(const float *scaled_max, int n, int cap_log2, uint8_t *lowering_out);
+
+/* ---- the exact form: both networks in fp64 from end to end on the device (csrc/c3_exact.h) ----
+ * The arithmetic of oracle/c3_oracle.c at the speed of the chip: the checkpoint's fp32 weights widened to double, every product, sum,
+ * activation and intermediate tensor double (v_mfma_f64_16x16x4_f64; exp, tanh, expm1 the double-precision library functions);
+ * BatchNorm with eps 1e-3 and running statistics (clair3/model.py:191,195-197), folded in double; the full-alignment input x / 100
+ * (model.py:378); LSTM gate order i, f, g, o with both biases (model.py:132-133); SELU before the soft-max (model.py:142-150).  No channel
+ * exponent, no weight scale, no calibration lowering: the precision plan and the handle's fp32 / range-guard state do not enter.
+ * An instrument for measuring the other forms against the exact row (python -m clair3_amd.audit), not a path of a pipeline.
+ *   c3_model_set_exact   takes effect at the next c3_model_load (like c3_model_set_channel_lowering): that load also places the double
+ *                        weights on the device.  Refused while a c3_predict_submit is pending.  While it was never enabled nothing is
+ *                        allocated, uploaded or launched and c3_model_describe is unchanged; while enabled describe ends on " exact=1"
+ *   c3_predict_exact     blocking; y_host[batch][c3_model_output_size()] doubles, no decoder columns.  Windows only (x_dtype: pileup
+ *                        C3_DTYPE_I8 | C3_DTYPE_I32, full alignment C3_DTYPE_I8, in the geometry of c3_model_set_geometry): regions,
+ *                        candidates, depths and rows are materialised by the caller.  The call is cut into passes of at most
+ *                        C3HIP_EXACT_CHUNK windows (default 256 full alignment, 1024 pileup) in a workspace of its own (2.2 MB per
+ *                        full-alignment window, 0.8 MB per pileup window); a window's row is bit-identical whatever batch or pass it
+ *                        travels in.  It runs on the first lane's stream with the device synchronised before and behind, and leaves what
+ *                        c3_model_calibrate leaves: precision, range flag, verify totals, taps, a profile being taken and what
+ *                        c3_model_describe reports of the last predict call.  batch == 0 launches nothing.  Errors (exact not enabled at
+ *                        the last load, a pending submit, a dtype the kind does not take, null buffers) leave the handle usable
+ *   c3_exact_fetch       windows [first, first + windows) of the LAST PASS of the last c3_predict_exact call; names and layouts those of
+ *                        c3_debug_tap_fetch (full-aln "act0".."act8", "spp", "l4_out"; pileup "lstm1_out", "gx2", "lstm2_out", "l4_out").
+ *                        Every tensor exists: nothing is fused here */
+int c3_model_set_exact(c3_model *m, int enable);
+int c3_predict_exact(c3_model *m, const void *x_host, int x_dtype, int64_t batch, double *y_host);
+int c3_exact_fetch(c3_model *m, const char *name, int64_t first, int64_t windows, double *host_out, int64_t n_doubles);
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
 int c3_model_synchronize(c3_model *m);
