@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv1_i8_f16_kernel(Conv1F16Params p) 
     auto store_piece = [&](uint32_t o0, int j) __attribute__((always_inline)) {
         const int idx = lane + 64 * j;  // piece idx & 15 of pixel idx >> 4
         const c1_u32x4 d = *reinterpret_cast<const c1_u32x4 *>(st + (idx >> 4) * 272 + (idx & 15) * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, o0 + (uint32_t)(idx * 16), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, o0 + (uint32_t)(idx * 16), 0, C3_PLANE_STORE_AUX);
     };
     auto store_one = [&](const f32x16 (&r)[2], uint32_t o0, int idx) __attribute__((always_inline)) {
         if constexpr (PLANES) {

@@ -75,12 +75,13 @@ struct PlaneConvParams {
     int skew = 0;                    // units of 1024 cycles the second workgroup of a CU (the later half of the grid) starts later (probe knob)
 };
 
+// Every store of plane activations carries C3_PLANE_STORE_AUX (c3_gemm.h: write-through, so that the end of a launch has nothing to flush).
 // split four fp32 values into their fp16 pieces and store them behind `off` (hi plane) / `off + 128` (lo plane)
 __device__ __forceinline__ void store_planes4(const __amdgpu_buffer_rsrc_t rsrc, uint32_t off, const f32x4 v) {
     u32x2 pc[2];
     split2_f16(v, pc);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_u32x2, pc[0]), rsrc, off, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_u32x2, pc[1]), rsrc, off + 128, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_u32x2, pc[0]), rsrc, off, 0, C3_PLANE_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_u32x2, pc[1]), rsrc, off + 128, 0, C3_PLANE_STORE_AUX);
 }
 
 // four consecutive channels of a plane activation back as fp32 (hi + lo is exact in fp32)
@@ -540,8 +541,8 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
             split2_f16(a, pa);
             split2_f16(b, pb);
             const pl_u32x4 hi = {pa[0][0], pa[0][1], pb[0][0], pb[0][1]}, lo = {pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
-            __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, off, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, off + 128, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, off, 0, C3_PLANE_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, off + 128, 0, C3_PLANE_STORE_AUX);
         }
         if constexpr (SPPF) {
             // thread (channel c = tid & 63, window w = (tid >> 6) & 1 of the tile, level half = tid >> 7): half 0 takes the nine
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
                 float *dst = p.spp + ((int64_t)wb * 14 + (half ? 9 : 0)) * C + tn * 64 + sc;
 #pragma unroll
                 for (int k = 0; k < 9; ++k)
-                    if (k < (half ? 5 : 9)) dst[(int64_t)k * C] = mx[k];
+                    if (k < (half ? 5 : 9)) store_handoff_f32(dst + (int64_t)k * C, mx[k]);
             }
         }
         }

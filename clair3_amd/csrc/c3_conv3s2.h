@@ -256,8 +256,8 @@ __global__ __launch_bounds__(kS2Threads, PAIR ? 4 : 2) void conv3x3_s2_planes_ke
                 split2_f16(b, pb);
                 const pl_u32x4 hi = {pa[0][0], pa[0][1], pb[0][0], pb[0][1]}, lo = {pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
                 const uint32_t off = m < p.M ? (uint32_t)m * (uint32_t)(p.N * 4) + (uint32_t)((tn * 2 + half) * 256 + c8 * 16) : kPlOob;
-                __builtin_amdgcn_raw_buffer_store_b128(hi, crsrc, off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(lo, crsrc, off + 128, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(hi, crsrc, off, 0, C3_PLANE_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(lo, crsrc, off + 128, 0, C3_PLANE_STORE_AUX);
             }
             lds_barrier();  // the staged half has been read: the next half / the DMA of the chunk after next may overwrite the stage
         }

@@ -449,8 +449,8 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_wino_planes_kernel(Wino
                 split2_f16(a, pa);
                 split2_f16(b, pb);
                 const pl_u32x4 hi = {pa[0][0], pa[0][1], pb[0][0], pb[0][1]}, lo = {pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
-                __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, ioff[k], 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, ioff[k], 128, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, ioff[k], 0, C3_PLANE_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, ioff[k], 128, C3_PLANE_STORE_AUX);
             }
         }
         trace(33);
@@ -801,8 +801,8 @@ __global__ __launch_bounds__(kWtThreads, 2) void conv3x3_wino_tw_kernel(WinoConv
             split2_f16(a, pa);
             split2_f16(b, pb);
             const pl_u32x4 hi = {pa[0][0], pa[0][1], pb[0][0], pb[0][1]}, lo = {pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
-            __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, ioff[k], 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, ioff[k], 128, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(hi, orsrc, ioff[k], 0, C3_PLANE_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, orsrc, ioff[k], 128, C3_PLANE_STORE_AUX);
         }
     }
     trace(33);

@@ -33,6 +33,32 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int st_u32x2 __attribute__((__vector_size__(8)));  // the data operand type of __builtin_amdgcn_raw_buffer_store_b64
 
+// The cache policy (aux operand of the buffer stores) of what a launch of the product forward pass hands to the NEXT launch: plane activations
+// (c3_conv3.h), the pooled tensor, the split-K sum of L4.  16 = sc1, write-through; 0 = the default policy; the stored bits are the same.
+// The eight XCDs' L2s are write-back: with default stores a convolution ends with its latest output dirty in them, and the release at the
+// end of the dispatch writes it back while every CU idles (MI355X_MICROARCH.md, table row "boundary": + B / 6 TB/s behind B dirty bytes;
+// row "publish-large": write-through wins for an epilogue's tens of KB per workgroup).  Write-through, the same bytes travel to the fabric
+// under the launch's matrix work, and the next launch reads them on other XCDs through the Infinity Cache either way.  Measured
+// (profiles/plane_stores_write_through.txt): tools/boundary_probe.hip, a 35 us launch + dependent reader: + 2.3 - 2.5 us behind 27 - 50 MB of
+// default stores, flat with sc1; in the B = 256 step every plane-writing convolution 0.9 - 1.9 us shorter begin to begin, the step + 2 %.
+// Decided per site: the L4 partials stay on the default policy (c3_l4.h says what they lost).  Never nt: "nt is not write-through" (same
+// guide), and gx2 lost 19 % with it (profiles/r05_c_ab_gx2_nontemporal_not_kept.txt).
+// A macro only so that a scratch build with -DC3_PLANE_STORE_AUX=0 (clair3_amd/build.py build(extra=...), selected with C3HIP_LIB) can be
+// compared on the same box; c3_model_describe names the build (plane_stores=).  Defined here, not in c3_conv3.h, because c3_conv1.h and
+// c3_tail.h are compiled in front of that header.
+#ifndef C3_PLANE_STORE_AUX
+#define C3_PLANE_STORE_AUX 16  // sc1: write-through
+#endif
+static_assert(C3_PLANE_STORE_AUX == 16 || C3_PLANE_STORE_AUX == 0, "C3_PLANE_STORE_AUX: 16 (sc1, write-through) or 0 (default policy)");
+// the same policy for a 4-byte value stored through a pointer (pooled tensor, split-K sum): a relaxed agent-scope store is global_store ... sc1
+__device__ __forceinline__ void store_handoff_f32(float *dst, float v) {
+#if C3_PLANE_STORE_AUX == 16
+    __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *dst = v;
+#endif
+}
+
 // SPLIT (fp16x3): x = h0 + h1 with two fp16 pieces (11 mantissa bits each, round to nearest, subnormals kept --
 // v_mfma_f32_32x32x16_f16 honours subnormal inputs, tools/f16_denorm_probe.hip); x*w from x0w0 + x0w1 + x1w0, dropping
 // x1w1 < 2^-22 of the product.  Same operand bytes as fp32 (two 16-bit pieces), 2.5 vector instructions per split

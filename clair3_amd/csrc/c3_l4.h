@@ -179,6 +179,9 @@ __global__ __launch_bounds__(kL4Threads, 2) void l4_stream_kernel(L4Params p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const pl_u32x4 v = {__float_as_uint(acc[4 * q]), __float_as_uint(acc[4 * q + 1]), __float_as_uint(acc[4 * q + 2]), __float_as_uint(acc[4 * q + 3])};
+        // default policy, NOT C3_PLANE_STORE_AUX (c3_gemm.h): the partials are all stored at the very end of a 7 us launch, where nothing is
+        // left for a write-through store to travel under, and the sum reads them back at once.  Write-through here: the launch 6.8 - 6.9 ->
+        // 7.6 us begin to begin in the full-alignment step, 17.6 -> 19.6 us in the pileup step (profiles/plane_stores_write_through.txt)
         __builtin_amdgcn_raw_buffer_store_b128(v, prsrc, poff, 32 * q, 0);
     }
 }

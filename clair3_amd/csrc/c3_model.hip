@@ -364,10 +364,13 @@ int c3_model_set_sharing(c3_model *m, int handles) {
 
 int c3_model_describe(c3_model *m, char *buf, int n) {
     if (!m || !buf || n <= 0) return fail("null argument");
+    // plane_stores: the build's C3_PLANE_STORE_AUX (c3_gemm.h), so that the log of a same-box comparison names the build.  Second field, not
+    // last: the suite looks at the last field of both strings (chunks / pack_rows, ",layers:1")
+    static const char *const stores = C3_PLANE_STORE_AUX == 16 ? "write-through" : "default";
     if (m->kind == C3_KIND_PILEUP)
-        snprintf(buf, (size_t)n, "sharing=%d lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
+        snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
                  "ring_lanes=%d lane_max_batch=%lld max_depth=%d rescaled=%lld candidates=%lld kept=%lld chunks=%lld", m->sharing,
-                 m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
+                 stores, m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else {
@@ -380,9 +383,9 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                 const size_t at = strlen(wf);
                 snprintf(wf + at, sizeof(wf) - at, "%s%s:%s", at ? "/" : "", names[i], m->choice.wform[i] == 't' ? "transform-waves" : "paired");
             }
-        snprintf(buf, (size_t)n, "sharing=%d conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
+        snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
                  "precision=%s wino_form=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
-                 m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
+                 stores, m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
                  m->precision, wf[0] ? wf : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
     }
     if (m->fp32_plan | m->fp32_auto) {  // only while a precision plan is in force (c3_model.h layer_f16)

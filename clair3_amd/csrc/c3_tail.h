@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_selu_kernel(ReduceParams p)
         for (int u = 0; u < 8; ++u)
             if (s + u < p.S) v += t[u];
     }
-    p.out[i] = selu_f(p.post ? v * p.post[k] : v);
+    store_handoff_f32(p.out + i, selu_f(p.post ? v * p.post[k] : v));
 }
 
 struct Tail2Params {
