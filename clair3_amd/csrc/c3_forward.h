@@ -110,9 +110,11 @@ static int fa_conv_fp32_planes(c3_model *m, hipStream_t s, ProfScope &ps, int l,
 static int lstm1_fp32_planes(hipStream_t s, const LstmFusedParams<int8_t> &lp, int64_t n);  // (plain overloads: a template would be instantiated where it is used)
 static int lstm1_fp32_planes(hipStream_t s, const LstmFusedParams<int32_t> &lp, int64_t n);
 static int proj2_fp32_from_planes(c3_model *m, hipStream_t s, int M);
+static int fa_tail_sum_launch(hipStream_t s, int W, const Tail2Params &tp);  // (fc_tail_sum_kernel<W>, c3_tail.h: defined there for its place alone)
 
 // ------------------------------------------------------------------------------------------ FC tail (both networks)
-// L4 as a split-K contraction -> splitk_reduce_selu_kernel -> fc_tail_mfma_kernel (c3_tail.h); the decoder columns behind it
+// L4 as a split-K contraction -> splitk_reduce_selu_kernel -> fc_tail_mfma_kernel, or the latter two as one launch (c3_tail.h); the decoder
+// columns behind it
 static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int64_t n, float *y, const char *tag_l4,
                     const char *tag_tail) {
     Lane &L = lane(m);
@@ -135,11 +137,24 @@ static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int
         }
     }
     {
+        // full alignment's product form: the sum inside fc_tail_sum_kernel<W> (c3_tail.h).  auto: the smallest W whose grid has no more
+        // workgroups than the device has CUs -- every CU streams its share of the partials once --, up to fa_tail_max_batch windows and
+        // while no other batch shares the chip; otherwise workgroups would queue behind each other, and the three launches stay.  A window's
+        // bits are the same in every form, so the choice may follow the batch size
+        int W = 0;
+        if (m->kind == C3_KIND_FULL_ALIGNMENT && FC == 256 && l4_f16 && S <= kTailSumMaxS && m->fa_tail >= 0) {
+            W = m->fa_tail;
+            if (!W && n <= m->fa_tail_max_batch && m->sharing == 1 && !m->lane_beside)  // (alone on the chip: c3_model.h fa_tail)
+                for (const int w : {4, 8, 16})
+                    if (!W && (n + w - 1) / w * m->nb <= m->wg_slots / 2) W = w;
+        }
+        if (m->kind == C3_KIND_FULL_ALIGNMENT) m->choice.fa_tail = W == 4 ? "fused-w4" : W == 8 ? "fused-w8" : W == 16 ? "fused-w16" : "split";
+        const int64_t rows = W ? (n + W - 1) / W * 16 : (n + 15) / 16 * 16;  // tile rows the matrix instructions work on
         const double fl = 2.0 * n * (FC * 128.0 * m->nb + 128.0 * m->nout);
         ProfScope ps(m, s, tag_tail, fl, 4.0 * ((double)S * n * FC + n * m->nout));
-        ps.mfma(2.0 * ((n + 15) / 16 * 16) * m->nb * (FC * 128.0 + 128.0 * 48.0), false);
+        ps.mfma(2.0 * rows * m->nb * (FC * 128.0 + 128.0 * 48.0), false);
         Tail2Params tp{L.l4dbg, m->w5f, m->b5, m->whf, m->bh48, y, (int)n, m->nb, m->row};
-        if (m->tail_fused) {  // the split-K sum inside the tail kernel: two launches behind the last convolution / recurrence, not three
+        if (m->tail_fused || W) {  // the split-K sum inside the tail kernel: two launches behind the last convolution / recurrence, not three
             tp.part = L.part, tp.S = S, tp.bias4 = m->l4_b, tp.l4out = L.l4dbg;
             if (l4_f16) tp.pre = m->l4_pre, tp.post = m->l4_post;
         } else {
@@ -149,7 +164,9 @@ static int run_tail(c3_model *m, hipStream_t s, const float *a, int64_t lda, int
             HIP_TRY(hipGetLastError());
         }
         const dim3 grid((unsigned)((n + 15) / 16), m->nb);
-        if (FC == 256)
+        if (W) {
+            TRY(fa_tail_sum_launch(s, W, tp));
+        } else if (FC == 256)
             hipLaunchKernelGGL(fc_tail_mfma_kernel<256>, grid, dim3(256), 0, s, tp);
         else
             hipLaunchKernelGGL(fc_tail_mfma_kernel<128>, grid, dim3(256), 0, s, tp);

@@ -208,8 +208,9 @@ struct LaneSharing {
         std::sort(other, other + no, std::greater<int64_t>());
         for (int k = 0; k < no && k < m->ring_lanes - 1; ++k) beside_windows += other[k];
         m->lane_sharing = (beside_windows > 0 && 2 * ((batch + beside_windows + 7) / 8) > m->wg_slots / 2) ? m->ring_lanes : 1;
+        m->lane_beside = beside_windows > 0;
     }
-    ~LaneSharing() { m->lane_sharing = 1; }
+    ~LaneSharing() { m->lane_sharing = 1, m->lane_beside = false; }
 };
 
 // the depths the batch stages; counts the windows the rule rescales (depth > 0 and depth > 1.5 x max_depth) for c3_model_describe.  A batch

@@ -5,6 +5,7 @@
 //   pileup           the fp32 LSTM1 in front of the product projection (c3_lstm_fused.h OPT bit 4: h1 leaves as planes), the fp32
 //                    projection behind the product LSTM1 (c3_gemm.h DensePlanesLoader)
 // Declared in c3_forward.h; c3_model.hip includes this file last, so that these kernels are instantiated behind all the others.
+// For that reason alone the launch of full alignment's fc_tail_sum_kernel (c3_tail.h, run_tail's two-launch chain) is defined here as well.
 #pragma once
 #include "c3_forward.h"
 
@@ -44,4 +45,19 @@ static int proj2_fp32_from_planes(c3_model *m, hipStream_t s, int M) {
     DenseLoaderParams lp{L.h1, 256};
     EpilogueParams ep{L.gx2, m->proj_b[1], nullptr, 1280, 0};
     return launch_gemm<DensePlanesLoader<4>, EPI_BIAS, 128, 128>(s, lp, m->proj_w[1], 256, M, 1280, 8, 1, ep);
+}
+
+// ---- run_tail's launch of fc_tail_sum_kernel<W> (c3_tail.h): here, so that its three instantiations follow every kernel the library had
+// before them and none of those moves in the code object
+static int fa_tail_sum_launch(hipStream_t s, int W, const Tail2Params &tp) {
+    const dim3 grid((unsigned)((tp.B + W - 1) / W), (unsigned)tp.NB);
+    if (W == 4)
+        hipLaunchKernelGGL(fc_tail_sum_kernel<4>, grid, dim3(512), 0, s, tp);
+    else if (W == 8)
+        hipLaunchKernelGGL(fc_tail_sum_kernel<8>, grid, dim3(512), 0, s, tp);
+    else if (W == 16)
+        hipLaunchKernelGGL(fc_tail_sum_kernel<16>, grid, dim3(512), 0, s, tp);
+    else
+        return fail("internal: no fc_tail_sum_kernel<%d>", W);
+    return 0;
 }

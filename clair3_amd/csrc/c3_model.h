@@ -333,6 +333,7 @@ struct c3_model {
     // CUs between them -- a half-tile launch alone owns every CU: 144 KB of LDS per workgroup, and the second lane's batch waits), the
     // LSTM2 projection half its grid (profiles/r06_n_ab_lane_sharing.txt).  Set around forward_device by the ring; 1 everywhere else.
     int lane_sharing = 1;
+    bool lane_beside = false;   // ... and whether any batch is in flight in another lane at all (run_tail's choice of full alignment's FC chain)
     unsigned lane_next = 0;     // the lane of the ring's next small batch (round robin over the submits)
     // As few streams as the work needs.  The runtime gives a process FOUR hardware queues (GPU_MAX_HW_QUEUES) and places every stream on the
     // least-used one; two streams on one queue run in submission order, and a wait between streams on two queues costs tens of microseconds.
@@ -343,7 +344,20 @@ struct c3_model {
     // exists only from the first batch on that stages outside a lane: three lanes + the null stream are the four queues.  (The FC chain on a
     // stream of its own gained 1.5 - 2 % in one placement of the streams and lost in another: profiles/r06_h_ab_tail_stream.txt, r06_o_*.)
     bool tail_fused = false;  // the split-K sum of L4 inside fc_tail_mfma_kernel (c3_tail.h) instead of its own launch: on for the pileup network (+0.7 %:
-                              // 15 partials of 128 features), off for full alignment (-1 %: four branch workgroups re-read 28 partials of 256)
+                              // 15 partials of 128 features), off for full alignment (-1 %: four branch workgroups re-read 28 partials of 256
+                              // on a 64-workgroup grid), which takes fa_tail's kernel below instead
+    // Full alignment has a two-launch chain of its own (c3_tail.h fc_tail_sum_kernel<W>: W windows per workgroup, every partial of an item in
+    // flight at once).  env C3HIP_FA_TAIL = auto | split | w4 | w8 | w16: 0 = auto (run_tail: the smallest W whose grid has no more workgroups
+    // than the device has CUs, the three launches beyond fa_tail_max_batch windows and beside other batches), -1 = split (the three
+    // launches), 4 / 8 / 16 = that W whatever the batch.  The fp32 forms and the pileup network do not look at it.
+    // Beside other batches -- the caller's sharing hint, or a batch in flight in another lane of the ring -- auto stays on the three launches:
+    // a 512-thread workgroup with 229 registers per lane starts only on a CU that holds nothing else, and behind the convolution
+    // workgroups of the neighbours it waits for one (three batches in flight, B = 256: 867 k -> 854 k windows/s with the fused form)
+    int fa_tail = 0;
+    // 512: with four branches that is the last batch W = 8 covers with one workgroup per CU.  Measured (profiles/fa_tail_two_launches.txt,
+    // forms alternating in one process): the chain's two launches 3.4 us shorter at 256 windows (w4) and 2.9 us at 512 (w8), but W = 16 no
+    // better than the three launches at 512 and 6.6 us longer at 1000, where its workgroups sum two items one after the other
+    int64_t fa_tail_max_batch = 512;
     int wg_slots = 512;       // co-resident 256-thread / 64 KiB-LDS workgroups on the device (2 per CU)
 
     // the reference's rescaling of very deep pileup windows (c3_rescale.h; the *_depth entries and c3_predict_submit_region)
@@ -420,6 +434,7 @@ struct c3_model {
         const char *s2[2] = {"-", "-"};  // conv3, conv5: one or two workgroups per CU (c3_conv3s2.h PAIR)
         char s1[8] = "------";           // the six stride-1 convolutions res1a .. res3b: d = direct, w = F(2,3) along H
         char wform[8] = "------";        // ... and the form of the F(2,3) ones (c3_conv3w.h): p = paired workgroups, t = transform waves
+        const char *fa_tail = "-";       // full alignment's FC chain (run_tail): split | fused-w4 | fused-w8 | fused-w16
     } choice;
 
     bool prof = false;

@@ -173,6 +173,16 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
     if (const char *e = getenv("C3HIP_WINO")) m->wino = atoi(e);
     if (const char *e = getenv("C3HIP_SPP_FUSED")) m->spp_fused = atoi(e) != 0;
     m->tail_fused = kind == C3_KIND_PILEUP;  // (profiles/r04_e_ab_tail_pileup.txt, r04_e_ab_tail_fa.txt)
+    if (const char *e = getenv("C3HIP_FA_TAIL")) {  // a form switch (c3_model.h fa_tail); a value that names no form fails the creation
+        static const struct { const char *name; int v; } forms[] = {{"auto", 0}, {"split", -1}, {"w4", 4}, {"w8", 8}, {"w16", 16}};
+        const auto *f = std::find_if(std::begin(forms), std::end(forms), [e](const auto &x) { return !strcmp(x.name, e); });
+        if (f == std::end(forms)) {
+            fail("C3HIP_FA_TAIL=%s: expected auto, split, w4, w8 or w16", e);
+            c3_model_destroy(m);
+            return nullptr;
+        }
+        m->fa_tail = f->v;
+    }
     if (const char *e = getenv("C3HIP_HALF_TILES")) m->half_tiles = atoi(e) != 0;
     if (const char *e = getenv("C3HIP_PACK_ROWS")) m->pack_rows = kind == C3_KIND_FULL_ALIGNMENT && atoi(e) != 0;  // (c3_expand.h; default off)
     // two lanes for the ring (c3_model.h Lane): the kind's default follows the same-box A/B of profiles/r06_i_ab_ring_lanes.txt
@@ -375,7 +385,7 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else {
         // wino_form: the form of every F(2,3) layer of the last pass (c3_conv3w.h), res2a:paired/res2b:paired/res3a:transform-waves, "-" without
-        // one.  The row counters stay the last three fields, pack_rows the last one
+        // one; fa_tail: the FC chain of the last pass (c3_forward.h run_tail).  The row counters stay the last three fields, pack_rows the last one
         static const char *const names[6] = {"res1a", "res1b", "res2a", "res2b", "res3a", "res3b"};
         char wf[160] = "";
         for (int i = 0; i < 6; ++i)
@@ -384,9 +394,9 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                 snprintf(wf + at, sizeof(wf) - at, "%s%s:%s", at ? "/" : "", names[i], m->choice.wform[i] == 't' ? "transform-waves" : "paired");
             }
         snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
-                 "precision=%s wino_form=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
+                 "precision=%s wino_form=%s fa_tail=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
                  stores, m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
-                 m->precision, wf[0] ? wf : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+                 m->precision, wf[0] ? wf : "-", m->choice.fa_tail, (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
     }
     if (m->fp32_plan | m->fp32_auto) {  // only while a precision plan is in force (c3_model.h layer_f16)
         const size_t at = strlen(buf);
