@@ -32,9 +32,12 @@ EXPORTS = (
     "c3_model_calibrate", "c3_model_calibrate_reset", "c3_model_calibration_census", "c3_model_calibration_solve",
     "c3_model_set_channel_lowering", "c3_model_set_calibration_origin", "c3_model_channel_exps", "c3_calibration_rule",
     "c3_model_set_exact", "c3_predict_exact", "c3_exact_fetch",
+    "c3_model_set_range_policy", "c3_range_policy_check", "c3_model_range_stats",
 )
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
+# policy of the range guard (C3_RANGE_* in include/c3hip.h)
+RANGE_STICKY, RANGE_RECALIBRATE = 0, 1
 # status of a layer of verify mode's layer records (C3_VERIFY_LAYER_* in include/c3hip.h)
 VERIFY_LAYER_STATUS = {0: "none", 1: "compared", 2: "fused"}
 
@@ -72,6 +75,13 @@ class VerifyLayer(C.Structure):
     _fields_ = [("name", C.c_char * 16), ("status", C.c_int32), ("reserved", C.c_int32), ("batches", C.c_int64), ("windows", C.c_int64),
                 ("worst_batch", C.c_int64), ("worst_window", C.c_int64), ("worst_index", C.c_int64), ("max_abs_diff", C.c_float),
                 ("ref_max_abs", C.c_float), ("test_max_abs", C.c_float), ("reserved2", C.c_float)]
+
+
+class RangeStats(C.Structure):
+    """c3_range_stats (include/c3hip.h)"""
+    _fields_ = [("trips", C.c_int64), ("recalibrations", C.c_int64), ("reruns", C.c_int64), ("census_windows", C.c_int64),
+                ("channels_lowered", C.c_int32), ("cap_log2", C.c_int32), ("policy", C.c_int32), ("max_recalibrations", C.c_int32),
+                ("fell_back", C.c_int32), ("reason", C.c_char * 96)]
 
 
 class C3Error(RuntimeError):
@@ -185,6 +195,9 @@ def lib():
     L.c3_model_set_exact.argtypes = [C.c_void_p, C.c_int]
     L.c3_predict_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
     L.c3_exact_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    L.c3_model_set_range_policy.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.c3_range_policy_check.argtypes = [C.c_char_p]
+    L.c3_model_range_stats.argtypes = [C.c_void_p, C.POINTER(RangeStats)]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

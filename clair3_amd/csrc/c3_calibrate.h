@@ -7,6 +7,8 @@
 //   rule     per channel group of FaChannelExps: how many powers of two a channel's exponent has to come DOWN for what was seen to stay
 //            below 2^cap, and a group shift (the lower median of those) for the channels the sample happened not to excite.  Never up
 //   load     c3_model_load packs with k = k0 - lowering wherever it used k0: exact powers of two, the rows of the checkpoint as given
+//   online   the range guard's own fp32 re-run is such a pass over exactly the windows that tripped it: under the policy C3_RANGE_RECALIBRATE
+//            (c3_model_set_range_policy; the end of this file) a trip takes the census, solves, packs again and the handle stays on fp16x3
 // c3_model.hip includes this file behind c3_mixed.h: its kernel is instantiated behind every other one (c3_forward.h says why).
 #pragma once
 #include "c3_forward.h"
@@ -81,6 +83,43 @@ static int apply_channel_lowering(c3_model *m, FaChannelExps &ex) {
     return 0;
 }
 
+// The packing part of a full-alignment c3_model_load -- and ALL a repack of the range guard's recalibration runs (fa_repack below): the
+// exponents of the checkpoint, the lowering in force, the nine convolutions, the FC tail
+static int fa_pack_weights(c3_model *m, const TensorMap &tm) {
+    int cin = m->C;
+    if (3 * cin > 32) return fail("full-alignment input_channels %d not supported (3*C must be <= 32)", cin);
+    FaChannelExps ex;
+    TRY(fa_channel_exps(tm, ex));
+    TRY(apply_channel_lowering(m, ex));  // (records k0; changes ex only while a lowering is set)
+    for (int l = 0; l < 9; ++l) {
+        TRY(pack_conv(m, tm, l, cin, ex));
+        m->act_exp[l] = *ex.out_of(l);
+        cin = kConvCout[l];
+    }
+    return pack_tail(m, tm, &ex.stage[2]);
+}
+// c3_model_load under the RECALIBRATE policy: the float32 tensors as given, for the repacks to come
+static void keep_tensors(c3_model *m, const TensorMap &tm) {
+    m->kept.clear();
+    m->kept.reserve(tm.size());
+    for (const auto &kv : tm) {
+        size_t n = 1;
+        for (int64_t d : kv.second.shape) n *= (size_t)d;
+        m->kept.push_back(KeptTensor{kv.first, kv.second.shape, std::vector<float>(kv.second.d, kv.second.d + n)});
+    }
+}
+// The weights packed again from the kept tensors with the lowering now in force: the bytes of c3_model_set_channel_lowering followed by
+// c3_model_load, and nothing else a load does -- verify mode's totals, the precision plan, taps, a profile, the exact form's weights and
+// what C3HIP_FP32 decided stay.  The caller has made sure that nothing runs on the weights
+static int fa_repack(c3_model *m) {
+    if (m->kept.empty()) return fail("internal: a repack without the tensors of the last load");
+    TensorMap tm;
+    for (const KeptTensor &t : m->kept) tm[t.name] = TensorView{t.data.data(), t.shape};
+    TRY(fa_pack_weights(m, tm));
+    m->layer_exp_ok = false;  // (layer records: the channel exponents changed)
+    return 0;
+}
+
 // The rule for one group.  e[c]: binary exponent of the scaled maximum s[c] = f * 2^e[c], f in [0.5, 1) (frexp); live[c]: s[c] > 0
 static void calibration_rule(const int *e, const uint8_t *live, int n, int cap_log2, uint8_t *lowering_out) {
     std::vector<int> d(n, 0), seen;
@@ -91,6 +130,13 @@ static void calibration_rule(const int *e, const uint8_t *live, int n, int cap_l
     for (int c = 0; c < n; ++c) lowering_out[c] = (uint8_t)std::min(255, std::max(d[c], d_group));
 }
 
+// a pass's device census (the units of the current load) joins the handle's, in the checkpoint's units: exact, and it commutes with the maximum
+static void census_merge(c3_model *m, const std::vector<float> &dev, int64_t batch) {
+    for (int l = 0; l < 9; ++l)
+        for (int c = 0; c < kConvCout[l]; ++c) m->census[l][c] = std::max(m->census[l][c], std::ldexp(dev[l * 256 + c], -m->act_exp[l][c]));
+    m->census_windows += batch;
+}
+static int calibration_solve(c3_model *m, int cap_log2, uint8_t *lowering_out);
 static int calibration_handle(c3_model *m, const char *who) {
     if (!m) return fail("null model");
     if (m->kind != C3_KIND_FULL_ALIGNMENT)
@@ -167,9 +213,7 @@ int c3_model_calibrate(c3_model *m, const void *x_host, int x_dtype, int64_t bat
     if (x_dev) (void)hipFree(x_dev);
     if (y_dev) (void)hipFree(y_dev);
     if (rc) return g_err = why, rc;
-    for (int l = 0; l < 9; ++l)
-        for (int c = 0; c < kConvCout[l]; ++c) m->census[l][c] = std::max(m->census[l][c], std::ldexp(dev[l * 256 + c], -m->act_exp[l][c]));
-    m->census_windows += batch;
+    census_merge(m, dev, batch);
     return 0;
 }
 
@@ -182,6 +226,13 @@ int c3_model_calibration_census(c3_model *m, float *absmax_out, int64_t *windows
 
 int c3_model_calibration_solve(c3_model *m, int cap_log2, uint8_t *lowering_out) {
     TRY(calibration_handle(m, "c3_model_calibration_solve"));
+    return calibration_solve(m, cap_log2, lowering_out);
+}
+
+}  // extern "C"
+
+// (the range guard's recalibration solves inside c3_predict_wait, with other slots of the ring still waiting to be read)
+static int calibration_solve(c3_model *m, int cap_log2, uint8_t *lowering_out) {
     if (!lowering_out) return fail("null argument");
     if (cap_log2 < 4 || cap_log2 > 13) return fail("cap_log2 must be in [4, 13], got %d", cap_log2);
     if (!m->loaded || !m->chan_ok) return fail("model has no weights: call c3_model_load first");
@@ -208,6 +259,8 @@ int c3_model_calibration_solve(c3_model *m, int cap_log2, uint8_t *lowering_out)
     return 0;
 }
 
+extern "C" {
+
 int c3_model_set_channel_lowering(c3_model *m, const uint8_t *lowering) {
     TRY(calibration_handle(m, "c3_model_set_channel_lowering"));
     m->lowering_set = lowering != nullptr;
@@ -232,6 +285,126 @@ int c3_model_channel_exps(c3_model *m, int8_t *k0_out, int8_t *k_out) {
     if (!m->loaded || !m->chan_ok) return fail("model has no weights: call c3_model_load first");
     if (k0_out) memcpy(k0_out, m->chan_k0, kCalChannels);
     if (k_out) memcpy(k_out, m->chan_k, kCalChannels);
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the range guard's recalibration
+// The policy C3_RANGE_RECALIBRATE (include/c3hip.h c3_model_set_range_policy).  The sticky guard answers a trip with an fp32 pass over the
+// windows that tripped it; that pass is the best sample there is, so here it also takes the census, the rule runs on it, the weights are
+// packed again with the new lowering and the handle stays on the fp16x3 kernels.  No kernel of its own: the fp32 forms, the census kernel
+// and the load's packing as they are.
+static int parse_range_policy(const char *text, int *policy, int *max_recal, const char *what) {
+    static const char *const expected = "expected sticky, recalibrate or recalibrate:<n> with n >= 0";
+    if (!text) return fail("%s: null text (%s)", what, expected);
+    if (!strcmp(text, "sticky")) return *policy = C3_RANGE_STICKY, *max_recal = 0, 0;
+    if (!strcmp(text, "recalibrate")) return *policy = C3_RANGE_RECALIBRATE, *max_recal = 4, 0;
+    if (!strncmp(text, "recalibrate:", 12)) {
+        const char *p = text + 12;
+        long n = 0;
+        int digits = 0;
+        for (; *p >= '0' && *p <= '9' && digits < 7; ++p, ++digits) n = 10 * n + (*p - '0');
+        if (digits > 0 && !*p) return *policy = C3_RANGE_RECALIBRATE, *max_recal = (int)n, 0;
+    }
+    return fail("%s=%s: %s", what, text, expected);
+}
+
+// what the sticky guard prints, and why this handle is back on its behaviour
+static void range_guard_fall_back(c3_model *m, const char *why) {
+    fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; this handle continues on fp32 matrix instructions (range guard: %s)\n", why);
+    m->f16_ok = false, m->precision = "fp32-range-guard";
+    m->rstats.fell_back = 1;
+    snprintf(m->rstats.reason, sizeof(m->rstats.reason), "%s", why);
+}
+
+extern "C" {  // (declared in c3_hostring.h beside range_guard_rerun, inside its extern "C" block)
+
+// A trip under the policy (c3_hostring.h c3_predict_wait, c3_model.hip c3_predict_device_checked; the arguments of range_guard_rerun, the
+// batch's lane active).  On return y_dev holds the rows of the fp32 forms -- bit for bit the sticky guard's -- and the handle either runs the
+// fp16x3 kernels on weights packed with the new lowering or has fallen back to the sticky behaviour
+static int range_guard_recalibrate(c3_model *m, hipStream_t s, const void *x_dev, int x_dtype, int64_t batch, float *y_dev, int64_t tap_off,
+                                   const int32_t *starts, const int32_t *depth, const ExpandEntry *rows) {
+    ++m->rstats.trips;
+    // nothing may run on the weights while they are packed again: every lane's work, the transfers included.  The rows and flag copies of the
+    // other slots in flight have landed in their pinned buffers by then; their own c3_predict_wait deals with them
+    for (const Lane &L : m->lanes)
+        if (L.stream) HIP_TRY(hipStreamSynchronize(L.stream));
+    if (m->h2d_stream) HIP_TRY(hipStreamSynchronize(m->h2d_stream));
+    if (m->rstats.recalibrations >= m->range_max_recal) {
+        range_guard_fall_back(m, "allowance of recalibrations used up");
+        return range_guard_rerun(m, s, x_dev, x_dtype, batch, y_dev, tap_off, starts, depth, rows);
+    }
+    // the fp32 pass of range_guard_rerun, with the census behind every convolution (census_pass 2: a user's taps are served as well)
+    if (!m->census_dev) HIP_TRY(hipMalloc((void **)&m->census_dev, 9 * 256 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(m->census_dev, 0, 9 * 256 * sizeof(uint32_t), s));
+    const c3_model::Choices reported = m->choice;
+    m->f16_ok = false, m->census_pass = 2, m->tap_call_off = tap_off;
+    int rc = forward_device(m, s, x_dev, x_dtype, batch, y_dev, starts, depth, rows);
+    m->f16_ok = true, m->census_pass = 0, m->tap_call_off = 0;
+    TRY(rc);
+    std::vector<float> dev(9 * 256, 0.f);
+    TRY(d2h_staged(dev.data(), m->census_dev, dev.size() * sizeof(float), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    census_merge(m, dev, batch);  // (in the units of the packing that just ran)
+    bool finite = true;
+    for (int l = 0; l < 9; ++l)
+        for (int c = 0; c < kConvCout[l]; ++c) finite &= std::isfinite(m->census[l][c]);
+    if (!finite) return range_guard_fall_back(m, "census not finite"), 0;
+    // the rule at the cap of the lowering in force, else 2^10; never up
+    const int cap = m->lowering_set && m->lowering_cap >= 4 && m->lowering_cap <= 13 ? m->lowering_cap : 10;
+    uint8_t solved[kCalChannels];
+    TRY(calibration_solve(m, cap, solved));
+    int moved = 0;
+    for (int c = 0; c < kCalChannels; ++c) {
+        const uint8_t old = m->lowering_set ? m->lowering[c] : 0;
+        solved[c] = std::max(solved[c], old), moved += solved[c] != old;
+    }
+    if (!moved) return range_guard_fall_back(m, "the census asks for no further lowering"), 0;
+    memcpy(m->lowering, solved, kCalChannels);
+    m->lowering_set = true, m->lowering_cap = cap, m->lowering_windows = m->census_windows;
+    if (fa_repack(m) != 0) {  // (half-packed weights answer nothing)
+        m->loaded = false;
+        return 1;
+    }
+    HIP_TRY(hipMemsetAsync(m->range_flag, 0, 256, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    m->choice = reported;  // what c3_model_describe says of the last pass stays the product pass's: that is what the handle runs
+    ++m->pack_epoch, ++m->rstats.recalibrations;
+    m->rstats.channels_lowered = moved, m->rstats.cap_log2 = cap;
+    fprintf(stderr, "libc3hip: activations beyond the range of the fp16x3 kernels; recalibrated from this batch (%d channels lowered, census of %lld "
+                    "windows); this handle stays on the fp16x3 kernels\n", moved, (long long)m->census_windows);
+    return 0;
+}
+
+int c3_range_policy_check(const char *text) {
+    int policy = 0, max_recal = 0;
+    return parse_range_policy(text, &policy, &max_recal, "c3_range_policy_check");
+}
+
+int c3_model_set_range_policy(c3_model *m, int policy, int max_recalibrations) {
+    if (!m) return fail("null model");
+    if (policy != C3_RANGE_STICKY && policy != C3_RANGE_RECALIBRATE) return fail("c3_model_set_range_policy: unknown policy %d", policy);
+    if (max_recalibrations < 0) return fail("c3_model_set_range_policy: max_recalibrations must be >= 0, got %d", max_recalibrations);
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (policy == C3_RANGE_RECALIBRATE) {
+        if (m->kind != C3_KIND_FULL_ALIGNMENT)
+            return fail("c3_model_set_range_policy: recalibration is for full-alignment handles (the pileup network's LSTM layers have no ReLU "
+                        "homogeneity to rescale a channel through)");
+        if (m->loaded && m->kept.empty())
+            return fail("c3_model_set_range_policy: this handle holds no copy of the tensors it was loaded from: set it before c3_model_load");
+    }
+    m->range_policy = policy, m->range_max_recal = policy == C3_RANGE_RECALIBRATE ? max_recalibrations : 0;
+    if (policy == C3_RANGE_STICKY) std::vector<KeptTensor>().swap(m->kept);
+    return 0;
+}
+
+int c3_model_range_stats(c3_model *m, c3_range_stats *out) {
+    if (!m) return fail("null model");
+    if (!out) return fail("null argument");
+    *out = m->rstats;
+    out->census_windows = m->census_windows, out->policy = m->range_policy, out->max_recalibrations = m->range_max_recal;
     return 0;
 }
 

@@ -70,7 +70,11 @@ static int layer_tap(c3_model *m, hipStream_t s, int id, const void *src, int64_
 // the n windows of tensor `id` that the launch just enqueued on s wrote at src: behind it on s, into the tap buffer at the part's windows
 static int census_tap(c3_model *m, hipStream_t s, int id, const float *src, int64_t n);  // (c3_calibrate.h, included last like c3_mixed.h below)
 static int tap(c3_model *m, hipStream_t s, int id, const void *src, int64_t n, bool planes = false) {
-    if (m->census_pass) return planes ? fail("internal: a census pass runs the fp32 forms") : census_tap(m, s, id, (const float *)src, n);
+    if (m->census_pass) {  // 1: c3_model_calibrate, the tap buffers stay as they are; 2: the range guard's recalibrating re-run, which serves a user's taps like its sticky one
+        if (planes) return fail("internal: a census pass runs the fp32 forms");
+        TRY(census_tap(m, s, id, (const float *)src, n));
+        if (m->census_pass == 1) return 0;
+    }
     if (m->layer_pass) return layer_tap(m, s, id, src, n, planes);  // (a verified batch: no user tap is set, c3_hostring.h verify_select)
     if (!(m->tap_mask >> id & 1u)) return 0;
     const int64_t pw = tap_window_floats(m, id);

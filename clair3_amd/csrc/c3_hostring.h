@@ -557,6 +557,7 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
     sl.cand = in.cand != nullptr, sl.cand_none = !launched;
     sl.verified = p.verify.bytes != 0;
     if (in.cand) sl.status_host = in.cand->status_host, sl.n_rows_host = in.cand->n_rows_host, sl.n_chunks = (int64_t)in.cand->chunks.size();
+    sl.pack_epoch = m->pack_epoch;
     sl.busy = true;
 }
 
@@ -631,6 +632,45 @@ static int range_guard_rerun(c3_model *m, hipStream_t s, const void *x_dev, int 
     m->tap_call_off = 0;
     return rc;
 }
+// ---- the policy C3_RANGE_RECALIBRATE (c3_calibrate.h, included behind this file): a trip recalibrates instead
+static int range_guard_recalibrate(c3_model *m, hipStream_t s, const void *x_dev, int x_dtype, int64_t batch, float *y_dev, int64_t tap_off = 0,
+                                   const int32_t *starts = nullptr, const int32_t *depth = nullptr, const ExpandEntry *rows = nullptr);
+static bool range_recalibrates(const c3_model *m) {
+    // (kept: a load that failed half way left none -- the weights on the device are then not the ones a repack would pack from)
+    return m->range_policy == C3_RANGE_RECALIBRATE && m->range_max_recal > 0 && !m->rstats.fell_back && m->f16_ok && !m->kept.empty();
+}
+// what c3_predict_wait reads of a batch the fp16x3 kernels computed: its copy of the range flag, and its rows where they came to this host
+static bool slot_out_of_range(const HostSlot &sl) {
+    bool bad = *sl.pin_flag != 0;  // a conv stage produced a value near the fp16 range (kF16Range), or the device scan found a non-finite row
+    if (!sl.y_dev_out) {
+        const uint32_t *u = reinterpret_cast<const uint32_t *>(sl.pin_y);
+        for (size_t i = 0, n = sl.plan.y.bytes / 4; i < n; ++i) bad |= (u[i] & 0x7f800000u) == 0x7f800000u;
+    }
+    return bad;
+}
+// A batch that was in flight across a recalibration (its packing is older than the handle's) and came back with its flag copy raised -- the
+// flag word is sticky, so that is every such batch -- or with a non-finite row: again on the PRODUCT forms with the weights as they are packed
+// now, in its lane, from what was staged; then it is read like a fresh batch (*bad: it tripped again)
+static int range_guard_stale_rerun(c3_model *m, HostSlot &sl, bool *bad) {
+    const StagedBatch &p = sl.plan;
+    TRY(use_lane(m, sl.lane));
+    hipStream_t s = lane(m).stream;
+    float *y = sl.y_dev_out ? sl.y_dev_out : sl.dev_y;
+    m->tap_call_off = sl.tap_off;
+    const int rc = forward_device(m, s, sl.dev_x, sl.x_dtype, sl.batch, y, sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth),
+                                  sl.dev<const ExpandEntry>(p.rows_tab));
+    m->tap_call_off = 0;
+    TRY(rc);
+    if (sl.y_dev_out) {
+        hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((sl.batch * m->row + 255) / 256)), dim3(256), 0, s, y, sl.batch * m->row, m->range_flag);
+        HIP_TRY(hipGetLastError());
+    } else HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sl.pin_flag, m->range_flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    sl.pack_epoch = m->pack_epoch, ++m->rstats.reruns;
+    *bad = slot_out_of_range(sl);
+    return 0;
+}
 int c3_predict_wait(c3_model *m, int slot) {
     TRY(ring_ready(m, slot, false));
     HostSlot &sl = m->slot[slot];
@@ -651,21 +691,20 @@ int c3_predict_wait(c3_model *m, int slot) {
     HIP_TRY(hipEventSynchronize(sl.ev_out));
     // per batch: what matters is how THIS slot's rows were computed, not what the handle does now (another slot's wait may have switched it
     // to fp32 while this batch was in flight).  Rows that stayed on the device were scanned there: the flag is all there is to read
-    bool bad = sl.used_f16 && *sl.pin_flag != 0;  // a conv stage produced a value near the fp16 range (kF16Range), or the device scan found a non-finite row
-    if (sl.used_f16 && !sl.y_dev_out) {
-        const uint32_t *u = reinterpret_cast<const uint32_t *>(sl.pin_y);
-        for (size_t i = 0, n = p.y.bytes / 4; i < n; ++i) bad |= (u[i] & 0x7f800000u) == 0x7f800000u;
-    }
+    const bool guarded = sl.used_f16 && slot_out_of_range(sl);
+    bool bad = guarded;
+    if (bad && range_recalibrates(m) && sl.pack_epoch != m->pack_epoch) TRY(range_guard_stale_rerun(m, sl, &bad));
     if (bad) {  // in the batch's lane, from what was staged (a region batch gathers again, a batch with depths rescales again, a rows batch expands again: nothing has written dev_x)
         TRY(use_lane(m, sl.lane));
-        TRY(range_guard_rerun(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sl.tap_off,
-                              sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
+        const auto rerun = range_recalibrates(m) ? range_guard_recalibrate : range_guard_rerun;
+        TRY(rerun(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sl.tap_off,
+                  sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
         if (!sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
         HIP_TRY(hipStreamSynchronize(lane(m).stream));
     }
     if (sl.verified) {  // the range guard keeps priority: a batch it answered counts as skipped
-        if (!bad) verify_layers_account(m, sl);
-        if (bad) ++m->vstats.batches_skipped;
+        if (!guarded) verify_layers_account(m, sl);
+        if (guarded) ++m->vstats.batches_skipped;
         else if (verify_account(m, sl)) {  // escalate: the batch is answered with its rows on the fp32 forms, decoder columns included
             TRY(use_lane(m, sl.lane));
             if (sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.y_dev_out, sl.shadow, p.y.bytes, hipMemcpyDeviceToDevice, lane(m).stream));

@@ -16,7 +16,9 @@
 //                  runs a second forward pass on the fp32 forms from the same staged input (c3_hostring.h shadow_pass) and the two sets of
 //                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
-//   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries
+//   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries;
+//                  the packing part of a full-alignment load (fa_pack_weights) and, on it, the range guard's policy C3_RANGE_RECALIBRATE: a trip
+//                  takes the census during its fp32 re-run, solves, packs again and stays on the product forms (range_guard_recalibrate)
 //   c3_exact.h     the exact form: both networks in fp64 on the device, its kernels, workspace and entries (c3_predict_exact, c3_exact_fetch)
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
@@ -187,6 +189,7 @@ struct HostSlot {
     float *y_host = nullptr, *y_dev_out = nullptr;  // y_dev_out (c3_predict_submit_dev): the rows stay in the caller's device buffer
     int64_t tap_off = 0;  // first window of this batch in the c3_predict call it is a piece of (debug taps)
     bool used_f16 = false;  // the batch in flight was computed by the fp16x3 kernels (c3_predict_wait then checks its range)
+    uint64_t pack_epoch = 0;  // ... with the weights of this packing (c3_model pack_epoch: the range guard's recalibration moves it on)
     int64_t rows_shipped = -1;  // rows staged for the batch in flight (-1: a dense batch)
     // a candidate batch (c3_select.h; c3_predict_submit_candidates): the statuses and the count of kept candidates leave behind the rows
     bool cand = false, cand_none = false;  // cand_none: nothing was launched: no candidate, or a region in which no window fits -- every status is "no window"
@@ -251,6 +254,12 @@ struct ExactState {
     double *act[9] = {}, *spp = nullptr, *gx1 = nullptr, *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
     double *l4 = nullptr, *l5 = nullptr, *logit = nullptr, *y = nullptr;
     int64_t last_n = 0;  // windows of the last pass of the last call (c3_exact_fetch)
+};
+// a tensor of the last c3_model_load as the handle keeps it while the range-guard policy is RECALIBRATE
+struct KeptTensor {
+    std::string name;
+    std::vector<int64_t> shape;
+    std::vector<float> data;
 };
 constexpr int kCalChannels = 896;  // the channels of the six groups of c3_pack.h FaChannelExps: 2 x (64 + 128 + 256)
 constexpr int kMaxLanes = 3;  // = the batches a worker keeps in flight (ring of three slots)
@@ -402,6 +411,13 @@ struct c3_model {
     int64_t solved_windows = 0;
     bool chan_ok = false;             // a load has filled ...
     int8_t chan_k0[kCalChannels] = {}, chan_k[kCalChannels] = {};  // ... the exponents fa_channel_exps gave it / it runs with
+
+    // ---- the range-guard policy (c3_model_set_range_policy; c3_calibrate.h range_guard_recalibrate): sticky = nothing kept, nothing counted ----
+    int range_policy = C3_RANGE_STICKY;
+    int range_max_recal = 0;
+    c3_range_stats rstats = {};       // totals since the last load (census_windows, policy and max_recalibrations are filled in when read)
+    uint64_t pack_epoch = 0;          // how often the weights of this load were packed again
+    std::vector<KeptTensor> kept;     // RECALIBRATE: the float32 tensors of the last load, what a repack packs from
 
     ExactState exact;
 

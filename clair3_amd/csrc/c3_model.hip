@@ -183,6 +183,14 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
         }
         m->fa_tail = f->v;
     }
+    if (const char *e = getenv("C3HIP_RANGE_GUARD")) {  // the range-guard policy a full-alignment handle starts with; a value that names none fails the creation
+        int policy = 0, max_recal = 0;
+        if (parse_range_policy(e, &policy, &max_recal, "C3HIP_RANGE_GUARD")) {
+            c3_model_destroy(m);
+            return nullptr;
+        }
+        if (kind == C3_KIND_FULL_ALIGNMENT) m->range_policy = policy, m->range_max_recal = max_recal;
+    }
     if (const char *e = getenv("C3HIP_HALF_TILES")) m->half_tiles = atoi(e) != 0;
     if (const char *e = getenv("C3HIP_PACK_ROWS")) m->pack_rows = kind == C3_KIND_FULL_ALIGNMENT && atoi(e) != 0;  // (c3_expand.h; default off)
     // two lanes for the ring (c3_model.h Lane): the kind's default follows the same-box A/B of profiles/r06_i_ab_ring_lanes.txt
@@ -245,6 +253,7 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
         if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());  // (the device-resident entries may still run the weights before on a caller's stream)
+    m->kept.clear();  // (the range-guard policy: the tensors of the load before; kept again at the end of a load that succeeds)
     TensorMap tm;
     for (int i = 0; i < n_tensors; ++i) {
         const c3_tensor_desc &t = tensors[i];
@@ -285,18 +294,8 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
             }
         }
     } else {
-        int cin = m->C;
-        if (3 * cin > 32) return fail("full-alignment input_channels %d not supported (3*C must be <= 32)", cin);
-        FaChannelExps ex;
-        TRY(fa_channel_exps(tm, ex));
-        TRY(apply_channel_lowering(m, ex));  // (c3_calibrate.h: records k0; changes ex only while a lowering is set)
-        for (int l = 0; l < 9; ++l) {
-            TRY(pack_conv(m, tm, l, cin, ex));
-            m->act_exp[l] = *ex.out_of(l);
-            cin = kConvCout[l];
-        }
+        TRY(fa_pack_weights(m, tm));  // (c3_calibrate.h: what a repack of the range guard's recalibration runs as well)
         expected = 54;
-        TRY(pack_tail(m, tm, &ex.stage[2]));
     }
     if (m->kind == C3_KIND_PILEUP) TRY(pack_tail(m, tm));
     expected += 2 + 4 * (size_t)m->nb;
@@ -314,6 +313,9 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
     HIP_TRY(hipDeviceSynchronize());  // (the handle's streams are non-blocking: the flag is zero before any of them runs again)
     verify_zero(m);  // verify mode: the totals were about the weights before; the setting stays
     m->layer_exp_ok = false;  // (layer records: the channel exponents are these weights')
+    // the range-guard policy (c3_calibrate.h): the setting stays, the totals start again, and under RECALIBRATE the tensors are kept for its repacks
+    m->rstats = c3_range_stats{}, m->pack_epoch = 0;
+    if (m->range_policy == C3_RANGE_RECALIBRATE) keep_tensors(m, tm);
     m->loaded = true;
     return 0;
 }
@@ -348,7 +350,7 @@ int c3_predict_device_checked(c3_model *m, const void *x_dev, int x_dtype, int64
     HIP_TRY(hipMemcpyAsync(m->pin_flag, m->range_flag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (*m->pin_flag) {
-        TRY(range_guard_rerun(m, s, x_dev, x_dtype, batch, y_dev));
+        TRY((range_recalibrates(m) ? range_guard_recalibrate : range_guard_rerun)(m, s, x_dev, x_dtype, batch, y_dev, 0, nullptr, nullptr, nullptr));
         HIP_TRY(hipStreamSynchronize(s));
     }
     return 0;
@@ -406,6 +408,10 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
         const size_t at = strlen(buf);
         snprintf(buf + at, (size_t)n - at, " calibration=cap:%d,windows:%lld,lowered:%d", m->lowering_cap, (long long)m->lowering_windows,
                  (int)std::count_if(m->lowering, m->lowering + kCalChannels, [](uint8_t v) { return v != 0; }));
+    }
+    if (m->range_policy != C3_RANGE_STICKY) {  // only while a range-guard policy other than sticky is set (c3_calibrate.h)
+        const size_t at = strlen(buf);
+        snprintf(buf + at, (size_t)n - at, " range_guard=recalibrate,recalibrations:%lld%s", (long long)m->rstats.recalibrations, m->rstats.fell_back ? ",fell_back" : "");
     }
     if (m->verify_seen) {  // verify mode is or was on (c3_verify.h): the setting and the totals behind everything else
         const c3_verify_stats &t = m->vstats;

@@ -58,6 +58,8 @@ class _HipModel:
         self._lowering = None   # calibration (set_calibration): the channel lowering a handle created anew takes along ...
         self._cal_meta = None   # ... and (cap_log2, windows) of the calibration it came from, for save_calibration
         self._exact = False     # the exact form (exact()): a handle created anew takes the setting along
+        self._range_policy = None  # the range-guard policy (range_policy): (policy, max_recalibrations) a handle created anew takes along
+        self._recal_seen = 0       # recalibrations of the handle whose lowering self._lowering already mirrors (_sync_recalibration)
         self._calibration_file = None  # C3HIP_CALIBRATION of a model built without a checkpoint (predict.calibration_from_env): applied by the first load
         if device is not None:
             self.to(device)
@@ -67,9 +69,16 @@ class _HipModel:
         idx = _device_index(device)
         if self._handle is not None and idx == self._device:
             return self
+        return self._create(idx)
+
+    def _create(self, idx):
+        """a fresh handle on device ``idx`` with every setting the object carries, loaded from the state dict it holds"""
+        if self._handle is not None:
+            self._sync_recalibration()  # (what the old handle learned online travels as the lowering)
         sd = self._pending_sd
         self._destroy()
         self._device = idx
+        self._recal_seen = 0
         h = _lib.lib().c3_model_create(self.KIND, self.input_channels, int(self.add_indel_length), idx)
         if not h:
             raise _lib.C3Error(f"c3_model_create: {_lib.last_error()}")
@@ -94,6 +103,8 @@ class _HipModel:
                 _lib.check(_lib.lib().c3_model_set_calibration_origin(self._handle, *self._cal_meta), "c3_model_set_calibration_origin")
         if self._exact:
             _lib.check(_lib.lib().c3_model_set_exact(self._handle, 1), "c3_model_set_exact")
+        if self._range_policy is not None:  # (before the load: under "recalibrate" it keeps the tensors)
+            _lib.check(_lib.lib().c3_model_set_range_policy(self._handle, *self._range_policy), "c3_model_set_range_policy")
         if sd is not None:
             self._load(sd)
         return self
@@ -159,6 +170,7 @@ class _HipModel:
         return self
 
     def _load(self, sd):
+        self._sync_recalibration()  # (a load starts the handle's count of recalibrations again; the lowering they left stays with it)
         n = len(sd)
         descs = (_lib.TensorDesc * n)()
         keep = []
@@ -174,6 +186,7 @@ class _HipModel:
         rc = _lib.lib().c3_model_load(self._handle, descs, n)
         if rc != 0:
             raise _lib.C3Error(f"Error(s) in loading state_dict for {type(self).__name__}: {_lib.last_error()}")
+        self._recal_seen = 0
 
     # ---- the forward pass ----
     def __call__(self, x):
@@ -438,6 +451,7 @@ class _HipModel:
         the ``windows`` it counts (c3_model_calibration_census), ``k0`` / ``k`` (896) the channel exponents of the last load as the load-time
         rule gave them / as the handle runs them (c3_model_channel_exps), ``lowering`` (896, or None while none is set)"""
         self._need_handle()
+        self._sync_recalibration()
         census, windows = np.zeros((9, 256), dtype=np.float32), C.c_int64(0)
         _lib.check(_lib.lib().c3_model_calibration_census(self._handle, census.ctypes.data, C.byref(windows)), "c3_model_calibration_census")
         k0, k = np.zeros(896, dtype=np.int8), np.zeros(896, dtype=np.int8)
@@ -451,6 +465,7 @@ class _HipModel:
         and save_calibration report with it; 0 = not known)."""
         from . import calibrate as cal
         self._need_handle()
+        self._sync_recalibration()  # (what the handle learned online is on record before this call replaces it)
         if lowering is not None:
             lowering = cal.as_lowering(lowering)
         _lib.check(_lib.lib().c3_model_set_channel_lowering(self._handle, None if lowering is None else lowering.ctypes.data),
@@ -462,6 +477,66 @@ class _HipModel:
             self._load(self._pending_sd)
         return self
 
+    # ---- the range-guard policy: recalibrate on a trip and stay on the fp16x3 kernels (c3_model_set_range_policy; DESIGN.md 1 Range) ----
+    _RANGE_POLICIES = {"sticky": _lib.RANGE_STICKY, "recalibrate": _lib.RANGE_RECALIBRATE}
+
+    def range_policy(self, policy=None, max_recalibrations=4):
+        """What the range guard does when a batch comes back beyond the fp16 range.  "sticky" (the default): the batch runs again on the
+        fp32 forms and the handle stays there.  "recalibrate": that re-run also takes the census of calibrate(), the channel exponents come
+        down by the rule, the weights are packed again and the handle stays on the fp16x3 kernels -- at most ``max_recalibrations`` times
+        between two loads, after which (or when the census is not finite, or asks for nothing) it behaves as sticky.  Full alignment only.
+        The library keeps the float32 tensors of its loads while the policy is "recalibrate", so a handle that already has weights is
+        created anew and loaded from the state dict the object holds.  Without an argument: (policy, max_recalibrations) in force."""
+        self._need_handle()
+        if policy is None:
+            st = self.range_stats()
+            return st["policy"], st["max_recalibrations"]
+        if policy not in self._RANGE_POLICIES:
+            raise _lib.C3Error(f"policy must be 'sticky' or 'recalibrate', got {policy!r}")
+        if isinstance(max_recalibrations, bool) or not isinstance(max_recalibrations, (int, np.integer)) or not 0 <= max_recalibrations < 2 ** 31:
+            raise _lib.C3Error(f"max_recalibrations must be an integer >= 0, got {max_recalibrations!r}")
+        args = (self._RANGE_POLICIES[policy], int(max_recalibrations))
+        # a loaded handle that kept no tensors cannot start to recalibrate (the library says so): it is created anew and loads from the held state dict
+        anew = (args[0] == _lib.RANGE_RECALIBRATE and self._pending_sd is not None and self.range_stats()["policy"] != "recalibrate")
+        if anew and self.KIND != _lib.KIND_FULL_ALIGNMENT:
+            anew = False  # (refused below with the library's words)
+        if anew:
+            old, self._range_policy = self._range_policy, args
+            try:
+                self._create(self._device)
+            except _lib.C3Error:
+                self._range_policy = old
+                raise
+            return self
+        _lib.check(_lib.lib().c3_model_set_range_policy(self._handle, *args), "c3_model_set_range_policy")
+        self._range_policy = args
+        return self
+
+    def range_stats(self):
+        """the totals of the range-guard policy since the last load as a dict (c3_model_range_stats; include/c3hip.h names the fields);
+        ``fell_back``: the reason as text, "" while the handle has not fallen back to the sticky behaviour"""
+        self._need_handle()
+        st = _lib.RangeStats()
+        _lib.check(_lib.lib().c3_model_range_stats(self._handle, C.byref(st)), "c3_model_range_stats")
+        out = {name: getattr(st, name) for name, _ in _lib.RangeStats._fields_ if name not in ("reason", "fell_back", "policy")}
+        out["policy"] = "recalibrate" if st.policy == _lib.RANGE_RECALIBRATE else "sticky"
+        out["fell_back"] = st.reason.decode() if st.fell_back else ""
+        return out
+
+    def _sync_recalibration(self):
+        """after an online recalibration the lowering in force is the handle's, not the one this object set: mirror it (k0 - k of the last
+        packing) with its origin, so that calibration(), save_calibration() and a handle created anew carry what was learned"""
+        if self._handle is None or self.KIND != _lib.KIND_FULL_ALIGNMENT:
+            return
+        st = _lib.RangeStats()
+        if _lib.lib().c3_model_range_stats(self._handle, C.byref(st)) != 0 or st.recalibrations == self._recal_seen:
+            return
+        k0, k = np.zeros(896, dtype=np.int8), np.zeros(896, dtype=np.int8)
+        _lib.check(_lib.lib().c3_model_channel_exps(self._handle, k0.ctypes.data, k.ctypes.data), "c3_model_channel_exps")
+        self._lowering = (k0.astype(np.int16) - k.astype(np.int16)).astype(np.uint8)
+        self._cal_meta = (int(st.cap_log2), int(st.census_windows))
+        self._recal_seen = int(st.recalibrations)
+
     def calibration_reset(self):
         """zero the census and its window count (c3_model_calibrate_reset); a lowering that is set stays"""
         self._need_handle()
@@ -472,6 +547,7 @@ class _HipModel:
         """the lowering in force as a calibration file (clair3_amd/calibrate.py names the format): what C3HIP_CALIBRATION=<file> hands to
         every worker process of a job"""
         from . import calibrate as cal
+        self._sync_recalibration()
         if self._lowering is None:
             raise _lib.C3Error("no calibration is set: calibrate() first")
         cap, windows = self._cal_meta or (0, 0)

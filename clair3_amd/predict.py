@@ -40,6 +40,7 @@ def _load_torch_checkpoint(model, checkpoint_path, device=None):
     calibration_from_env(model)
     verify_from_env(model)
     exact_from_env(model)
+    range_guard_from_env(model)
 
 
 def exact_from_env(model):
@@ -165,6 +166,50 @@ def _report_verified():
             print(f"[clair3_amd] verify: no summary ({e})", file=sys.stderr)
 
 
+# full-alignment models of this process built under C3HIP_RANGE_GUARD: what their range guard did goes to stderr when the process ends
+_GUARDED = []
+
+
+def range_guard_from_env(model):
+    """C3HIP_RANGE_GUARD=sticky | recalibrate | recalibrate:<n> is read by the library where the handle is created (README); here the
+    model is only noted, so that a worker process whose handle tripped leaves one line on stderr at exit.  stdout and the VCF stay untouched."""
+    import os
+    value = os.environ.get("C3HIP_RANGE_GUARD")
+    if not value or getattr(model, "KIND", None) != _lib.KIND_FULL_ALIGNMENT or any(g is model for g in _GUARDED):
+        return False
+    import atexit
+    if not _GUARDED:
+        atexit.register(_report_guarded)
+    _GUARDED.append(model)  # (held until the process ends, like _VERIFIED)
+    return True
+
+
+def range_guard_summary(model):
+    """the line a worker leaves on stderr when its range guard tripped (INTEGRATION.md 8 says how to read it); None without a trip"""
+    import re
+    st = model.range_stats()
+    if st["trips"] == 0:
+        return None
+    prec = re.search(r"precision=(\S+)", model.describe())
+    return ("[clair3_amd] range guard: policy={}:{} precision={} trips={} recalibrations={} reruns={} channels_lowered={} cap_log2={} "
+            "census_windows={} fell_back={}").format(
+        st["policy"], st["max_recalibrations"], prec.group(1) if prec else "?", st["trips"], st["recalibrations"], st["reruns"],
+        st["channels_lowered"], st["cap_log2"], st["census_windows"], repr(st["fell_back"]) if st["fell_back"] else "no")
+
+
+def _report_guarded():
+    import sys
+    for model in _GUARDED:
+        if model._handle is None:
+            continue
+        try:
+            line = range_guard_summary(model)
+            if line:
+                print(line, file=sys.stderr)
+        except Exception as e:  # noqa: BLE001  (the process is ending: say it, do not raise)
+            print(f"[clair3_amd] range guard: no summary ({e})", file=sys.stderr)
+
+
 # The model the worker process is calling variants with: the reference loop creates ONE model, loads it here, and only then
 # creates its batch generator (clair3/CallVariantsFromCffi.py:246-273), so the rebound generator (callvar.install: the
 # transport of clair3_amd/worker.py behind tensor_generator_for_chunk) can find the handle it should run ahead on.
@@ -267,6 +312,7 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
         calibration_from_env(m)
         verify_from_env(m)
         exact_from_env(m)
+        range_guard_from_env(m)
     return m
 
 

@@ -498,6 +498,50 @@ int c3_model_set_channel_lowering(c3_model *m, const uint8_t *lowering);
 int c3_model_set_calibration_origin(c3_model *m, int cap_log2, int64_t windows);
 int c3_model_channel_exps(c3_model *m, int8_t *k0_out, int8_t *k_out);
 int c3_calibration_rule(const float *scaled_max, int n, int cap_log2, uint8_t *lowering_out);
+/* ---- the range-guard policy: recalibrate on a trip and stay on the fp16x3 kernels (full alignment; DESIGN.md 1 Range) ----
+ * The range guard (see c3_predict) answers a trip by running the batch again on the fp32 forms -- and, by default, leaves the handle there
+ * for the rest of its life.  That re-run is an fp32 pass over exactly the windows that tripped: under C3_RANGE_RECALIBRATE the guard takes
+ * the census of c3_model_calibrate during it, solves (c3_model_calibration_solve at the cap of the lowering in force, else 10; the new
+ * lowering is the element-wise maximum of the old and the solved one: never up), packs the weights again from a private host copy of the
+ * float32 tensors of the last load and continues on the fp16x3 kernels.  The rows that answer the batch are those of the fp32 re-run, bit
+ * for bit what the sticky guard returns.  Opt-in: with no policy set nothing changes.
+ *   c3_model_set_range_policy   policy C3_RANGE_STICKY (the default) or C3_RANGE_RECALIBRATE; max_recalibrations >= 0 bounds how often the
+ *                               handle may recalibrate between two loads (0 behaves as sticky).  Refused while a c3_predict_submit is
+ *                               pending; RECALIBRATE is refused on a pileup handle (LSTM layers have no ReLU homogeneity to rescale
+ *                               through) and on a loaded handle that holds no copy of its tensors: set it before c3_model_load.  While the
+ *                               policy is RECALIBRATE c3_model_load keeps that copy (about 12 MB for this network), freed with the handle
+ *                               or when the policy goes back to sticky
+ *   c3_range_policy_check       plain host code, no device: 0 for "sticky", "recalibrate" and "recalibrate:<n>" (n = max_recalibrations,
+ *                               default 4), else != 0 with c3_last_error() saying what is expected
+ *   c3_model_range_stats        the totals since the last c3_model_load
+ * Where it applies: c3_predict_wait -- and so the blocking c3_predict* entries -- and c3_predict_device_checked; c3_predict_device is
+ * unchanged.  Before the weights are packed again the guard waits for the device work of every other batch in flight; such a batch, should
+ * its own flag copy be raised (the flag word is sticky) or a row of it not be finite, runs again on the fp16x3 kernels with the new weights
+ * when its c3_predict_wait comes and is then checked like a fresh batch.  The handle falls back to the sticky behaviour for this and all
+ * later batches when the solve lowers nothing further, when the census is not finite or when the allowance is used up; stderr then carries
+ * the sticky guard's sentence and the reason.  A repack does not touch the precision plan, verify mode's totals, taps, a profile or the
+ * exact form's weights.  Verify mode: the guard keeps priority.  A lowering set before (c3_model_set_channel_lowering, a calibration file)
+ * is where the handle starts from.  After a recalibration the lowering in force is k0 - k of c3_model_channel_exps, its origin cap_log2 and
+ * census_windows below.
+ * env C3HIP_RANGE_GUARD=<text of c3_range_policy_check>: the policy a full-alignment handle starts with (an invalid value makes
+ * c3_model_create fail with that message; a pileup handle ignores it).
+ * c3_model_describe gains range_guard=recalibrate,recalibrations:<n>[,fell_back] only while a policy other than sticky is set. */
+#define C3_RANGE_STICKY 0
+#define C3_RANGE_RECALIBRATE 1
+typedef struct {
+    int64_t trips;             /* batches that came back out of range while the policy was RECALIBRATE */
+    int64_t recalibrations;    /* ... answered by packing the weights again */
+    int64_t reruns;            /* batches in flight across a recalibration that ran again on the new weights */
+    int64_t census_windows;    /* windows in the handle's census (c3_model_calibration_census) */
+    int32_t channels_lowered;  /* channels whose exponent the last recalibration moved */
+    int32_t cap_log2;          /* the cap of the last recalibration's solve */
+    int32_t policy, max_recalibrations;  /* the setting in force */
+    int32_t fell_back;         /* != 0: the handle went back to the sticky behaviour ... */
+    char reason[96];           /* ... and why ("" otherwise) */
+} c3_range_stats;
+int c3_model_set_range_policy(c3_model *m, int policy, int max_recalibrations);
+int c3_range_policy_check(const char *text);
+int c3_model_range_stats(c3_model *m, c3_range_stats *out);
 
 /* ---- the exact form: both networks in fp64 from end to end on the device (csrc/c3_exact.h) ----
  * The arithmetic of oracle/c3_oracle.c at the speed of the chip: the checkpoint's fp32 weights widened to double, every product, sum,
