@@ -73,7 +73,38 @@ struct PlaneConvParams {
     int Hin = 0, Win = 0;
     uint32_t mg_hw = 0, mg_w = 0;    // fast_div magics of H * W and W (c3_gemm.h)
     int skew = 0;                    // units of 1024 cycles the second workgroup of a CU (the later half of the grid) starts later (probe knob)
+    uint32_t prio[2] = {0u, 0u};     // wave priority masks (wave_prio_masks below) of the workgroups with blockIdx.x < cus / >= cus; 0: no s_setprio at all
+    int cus = 0;                     // the device's CUs
+    long long *trace = nullptr;      // ABL bit 128 (tools/conv_probe.hip): start / end stamp of every workgroup
 };
+
+// ---- wave priority between the two workgroups of a CU (profiles/wave_priority.txt).  Both run the same code on the
+// same amount of work, one wave of each on every SIMD, and the issue arbiter picks by priority, then by AGE: at equal priority the older
+// workgroup gets every contested slot for the whole launch and the younger one finishes alone, at the rate of a lone workgroup.  Priority
+// outranks age, so a scheme hands the slots over for part of the work.  The work of a workgroup is a sequence of steps -- the slabs of a tile
+// (here and c3_conv3w.h; one slab per tile in the 64-channel block, so there a step is a tile of the walk) or the chunks of a tile (c3_conv3s2.h) -- and a scheme is one 32-bit mask per workgroup: bit i
+// (i < 30) is the priority the workgroup's waves take at the start of step i, bit 31 says that the kernel sets priorities at all, bit 30
+// (512-thread forms with a CU to themselves) that waves 4-7, the second wave of every SIMD, run at priority 1 throughout.  The kernel
+// takes prio[1] where blockIdx.x >= cus -- the second workgroup a CU receives, presumed the younger one (tools/census_probe.hip; placement
+// is no contract: a wrong guess leaves the age order in place and changes no result) -- and prio[0] elsewhere.  The masks come from the
+// kernel arguments and blockIdx, so every branch around an s_setprio is a scalar one (the instruction ignores EXEC).
+constexpr uint32_t kPrioOn = 1u << 31, kPrioUpper = 1u << 30;
+constexpr int kPrioNone = 0, kPrioYoungHalf = 1, kPrioAlternate = 2, kPrioUpperWaves = 4;
+// host: the masks of a scheme for workgroups of n steps
+//   kPrioYoungHalf   the younger workgroup at priority 1 for the first half of its steps, at 0 for the rest; the older one untouched
+//   kPrioAlternate   both alternate per step, in opposite phase
+//   kPrioUpperWaves  bit 30 alone
+inline void wave_prio_masks(int scheme, int n, uint32_t (&m)[2]) {
+    m[0] = m[1] = 0u;
+    n = n < 30 ? n : 30;
+    if (scheme == kPrioYoungHalf) m[1] = kPrioOn | ((1u << ((n + 1) / 2)) - 1u);
+    if (scheme == kPrioAlternate) m[0] = kPrioOn | 0x2aaaaaaau, m[1] = kPrioOn | 0x15555555u;
+    if (scheme == kPrioUpperWaves) m[0] = m[1] = kPrioUpper;
+}
+__device__ __forceinline__ void wave_prio_set(uint32_t bit) {
+    if (bit & 1u) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
 
 // Every store of plane activations carries C3_PLANE_STORE_AUX (c3_gemm.h: write-through, so that the end of a launch has nothing to flush).
 // split four fp32 values into their fp16 pieces and store them behind `off` (hi plane) / `off + 128` (lo plane)
@@ -94,7 +125,9 @@ __device__ __forceinline__ f32x4 load_planes4(const __amdgpu_buffer_rsrc_t rsrc,
 
 // ABL: ablation switches of tools/conv_probe.hip (0 in the product): 1 no weight loads, 2 no halo loads after the first tile,
 // 4 no epilogue, 8 no matrix instructions, 64 shader-clock trace of two
-// workgroups (wave 0) at phase boundaries into p.res ([2][256] x {tag, clock}).
+// workgroups (wave 0) at phase boundaries into p.res ([2][256] x {tag, clock}), 128 start / end stamps of every workgroup on the
+// device-wide 100 MHz counter into p.trace, 256 the priority scheme per weight chunk instead of per slab
+// (both workgroups alternate, bit 0 of the mask is the phase).
 // SRC8 (C = 64 only; the first residual block behind the 8-channel conv1): conv1's output never exists in HBM.
 //   1  the INPUT halo rows are computed here from the int8 windows (conv1 + BatchNorm + ReLU, split into the two fp16 pieces,
 //      written straight into the LDS halo tile): 165 rows x 64 channels = 6 groups of 32 pixels over the 4 waves, 20 matrix
@@ -330,6 +363,10 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
         }
     };
     trace(1);
+    if constexpr (ABL & 128) {
+        if (tid == 0) p.trace[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
+    }
+    uint32_t pmask = p.prio[blockIdx.x >= (unsigned)p.cus ? 1 : 0];  // wave priority (wave_prio_masks above): a step is a slab of a tile of this workgroup's walk
     // ---- prologue: zero row, first halo slab, the first chunk of the weight ring
     // (the long-latency requests go out first -- halo rows / window taps and the weight ring -- and only then the small tables that
     // are copied into LDS: a copy waits for its load, and every request behind that wait would start a memory latency late)
@@ -425,12 +462,16 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
         frags(0, 0);
 
 #pragma unroll 1
-        for (int slab = 0; slab < NS; ++slab)
+        for (int slab = 0; slab < NS; ++slab) {
+        if constexpr (!(ABL & 256))
+            if (pmask & kPrioOn) wave_prio_set(pmask), pmask = (pmask >> 1) | kPrioOn;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int cc = slab * 9 + tap;
             const bool last = cc == NCH - 1;
             const int ccn = last ? 0 : cc + 1;  // the ring refills with the next chunk of this workgroup's (cyclic) stream
+            if constexpr (ABL & 256)
+                if (pmask & kPrioOn) wave_prio_set(pmask ^ (uint32_t)cc);
             constexpr int kHaloTap = 8;
             if (tap == kHaloTap) {
                 if constexpr (NS > 1 && !(ABL & 2)) {
@@ -471,6 +512,7 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
                 frags(0, 0);
             }
             trace(10 + tap);
+        }
         }
 
         // ---- epilogue (c3_conv3.h): the tile crosses LDS once, (pixel, 8-channel) items, residual, ReLU, split, two stores
@@ -583,6 +625,10 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_planes_kernel(PlaneConv
         lds_barrier();
         trace(33);
         v = vn, m0 = m0n;
+    }
+    if constexpr (ABL & 128) {
+        __builtin_amdgcn_s_waitcnt(0);  // (the tile's stores have been issued and acknowledged)
+        if (tid == 0) p.trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
     }
     if (p.range_flag && !(omax < kF16Range)) atomicOr(p.range_flag, 1u);
 }

@@ -46,10 +46,14 @@ struct S2ConvParams {
     int tiles_n, tiles;  // N / 128, ceil(M / 128) * tiles_n
     int Hin, Win, Cin, Ho, Wo;
     uint32_t mg_hw, mg_w;  // fast_div magics of Ho * Wo and Wo
+    uint32_t prio[2] = {0u, 0u};    // ABL bit 64 (tools/dense_probe.hip): wave priority masks (c3_conv3.h wave_prio_masks) of the workgroups with
+    int cus = 0;                    //   blockIdx.x < cus / >= cus, and the device's CUs
+    long long *trace = nullptr;     // ABL bit 32 (tools/dense_probe.hip): start / end stamp of every workgroup
 };
 
 // ABL (tools/dense_probe.hip only; 0 in the product): 1 no DMA requests inside the chunk loop, 2 no weight loads, 4 no matrix
-// instructions, 8 no fragment reads, 16 no epilogue
+// instructions, 8 no fragment reads, 16 no epilogue, 32 start / end stamps of every workgroup on the device-wide 100 MHz counter into p.trace, 64 the wave priority schemes of c3_conv3.h (a step is a
+// chunk of a tile; neither form keeps one in the product -- profiles/wave_priority.txt -- so the product issues no s_setprio here)
 // PAIR: two workgroups per CU (128 registers a lane: ONE set of fragment registers, the reads of k-step ks + 1 issued behind the matrix
 // instructions of k-step ks and landing under the other waves' matrix work) -- for a layer with more tiles than CUs (conv3: 414),
 // whose second round would leave 40 % of the chip idle and whose epilogues then hide under the neighbour's matrix work; otherwise
@@ -69,6 +73,15 @@ __global__ __launch_bounds__(kS2Threads, PAIR ? 4 : 2) void conv3x3_s2_planes_ke
 
     int v = blockIdx.x;
     if (v >= p.tiles) return;
+    if constexpr (ABL & 32) {
+        if (tid == 0) p.trace[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
+    }
+    // wave priority (ABL bit 64; c3_conv3.h wave_prio_masks): a step is a chunk of a tile (NK of them: 9 or 18)
+    uint32_t pmask = 0u;
+    if constexpr (ABL & 64) {
+        pmask = p.prio[blockIdx.x >= (unsigned)p.cus ? 1 : 0];
+        if ((pmask & kPrioUpper) && wave >= 4) __builtin_amdgcn_s_setprio(1);
+    }
     const int tile0 = xcd_tile_index(v, p.tiles);
     const int tn = tile0 % p.tiles_n;  // the grid is a multiple of 8 tiles_n (or the tile count): every tile of this workgroup has this tn
     int m0 = (tile0 / p.tiles_n) * kS2BM;
@@ -155,6 +168,8 @@ __global__ __launch_bounds__(kS2Threads, PAIR ? 4 : 2) void conv3x3_s2_planes_ke
     float omax = 0.f;
     f32x16 acc[2];
     auto chunk = [&](int kc, bool first) __attribute__((always_inline)) {
+        if constexpr (ABL & 64)
+            if (pmask & kPrioOn) wave_prio_set(pmask >> kc);
         const bool req = advance();  // the next chunk is requested during this one, into the other stage
         const int nstage = (g + 1) & 1;
         const int ccn = kc + 1 == NK ? 0 : kc + 1;  // the weight stream of this wave is cyclic: the same column tile for every tile
@@ -273,6 +288,10 @@ __global__ __launch_bounds__(kS2Threads, PAIR ? 4 : 2) void conv3x3_s2_planes_ke
         v += G;
         if (v >= p.tiles) break;
         m0 = (xcd_tile_index(v, p.tiles) / p.tiles_n) * kS2BM;
+    }
+    if constexpr (ABL & 32) {
+        __builtin_amdgcn_s_waitcnt(0);  // (the tile's stores have been issued and acknowledged)
+        if (tid == 0) p.trace[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
     }
     if (p.range_flag && !(omax < kF16Range)) atomicOr(p.range_flag, 1u);  // also taken for NaN
 }

@@ -55,6 +55,8 @@ struct WinoConvParams {
     int tiles;            // ceil(Mp / 126) * (C / 64)
     uint32_t mg_hjw = 0, mg_w = 0;  // fast_div magics of Hj * W and W
     long long *trace = nullptr;     // ABL bit 32 (tools/wino_probe.hip): [2 workgroups][256] x {tag, shader clock}
+    uint32_t prio[2] = {0u, 0u};    // wave priority masks (c3_conv3.h wave_prio_masks) of the workgroups with blockIdx.x < cus / >= cus; 0: no s_setprio at all
+    int cus = 0;                    // the device's CUs
 };
 
 // One mixed-precision instruction instead of two conversions and an add: (float)h16 + (float)l16 -- exact (the two fp16 pieces of an
@@ -248,6 +250,7 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_wino_planes_kernel(Wino
     const int cb0 = wn * 32 + 4 * kh;                            // first of this lane's output channels inside the column tile
     float omax = 0.f;
     pl_u32x4 ta_h[4], ta_l[4], tb_h[4], tb_l[4];                 // the two transform items in flight
+    const uint32_t pmask = p.prio[blockIdx.x >= (unsigned)p.cus ? 1 : 0];  // wave priority (c3_conv3.h wave_prio_masks): a step is a slab of a tile
 
     // ---- prologue
     int cur = 0;
@@ -306,11 +309,15 @@ __global__ __launch_bounds__(kPlThreads, 2) void conv3x3_wino_planes_kernel(Wino
 #pragma unroll 1
         for (int s32 = 0; s32 < NSL; ++s32) {
             const bool last_slab = s32 + 1 == NSL;
+            if constexpr (!(ABL & 256))
+                if (pmask & kPrioOn) wave_prio_set(pmask >> s32);
             frags(0, 0, 0);
 #pragma unroll
             for (int tap = 0; tap < 12; ++tap) {
                 const int xi = tap / 3, slot = tap & 1;
                 const int cc = s32 * 12 + tap;
+                if constexpr (ABL & 256)
+                    if (pmask & kPrioOn) wave_prio_set(pmask ^ (uint32_t)tap);
                 int ccn = cc + 2;  // the ring refills with the chunk two ahead of this workgroup's cyclic stream
                 if (ccn >= NCH) ccn -= NCH;
 #pragma unroll
@@ -592,6 +599,10 @@ __global__ __launch_bounds__(kWtThreads, 2) void conv3x3_wino_tw_kernel(WinoConv
         }
     };
     trace(1);
+    // ABL 256 (tools/wino_probe.hip): waves 4-7, the second wave of every SIMD, at priority 1 (c3_conv3.h kPrioUpper).  Not in the product: the
+    // launch gets longer (profiles/wave_priority.txt) -- they are the transform waves, and a tile's critical path is the matrix waves' tap loop
+    if constexpr (ABL & 256)
+        if ((p.prio[0] & kPrioUpper) && wave >= 4) __builtin_amdgcn_s_setprio(1);
 
     // ---- prologue: the row table (c3_conv3w.h make_rowinfo of the merged kernel), the ring's first two chunks, bias and post, the zero
     // rows of both buffers; then slab 0 by all eight waves, one item per thread

@@ -232,10 +232,26 @@ static bool fa_planes_ok(const c3_model *m) {
     return m->C == 8 ? m->conv1_wfrag16 != nullptr : m->conv1_w16 != nullptr;
 }
 
+// The wave priority scheme of every kernel form that puts two workgroups on a CU (c3_conv3.h wave_prio_masks), chosen on the B = 256 step
+// from the workgroup stamps of the probes and kept where the step's own launch got shorter by more than its run-to-run spread
+// (profiles/wave_priority.txt); kPrioNone issues no s_setprio at all.
+//   direct       conv3x3_planes_kernel (res1b, res3b, and whatever C3HIP_WINO leaves on it; steps = slabs of the tiles of a workgroup's walk):
+//                res1b 43.4 -> 41.6 us, res3b with the pooling epilogue 44.2 -> 43.5
+//   direct halo  ... with conv1 of the halo rows inside (res1a): 45.7 -> 45.3 us, inside the spread of the parent's runs -- not kept
+//   wino paired  conv3x3_wino_planes_kernel (steps = slabs of a tile): res2a 36.5 -> 35.5 us, res2b 38.5 -> 37.4
+// The stride-2 pair form (conv3 26.2 -> 25.9 us: inside the spread) and the two 512-thread forms that have a CU to themselves (waves 4-7 at
+// priority 1: longer, or no different) keep none; their kernels carry the hook under a probe-only ABL bit.
+constexpr int kPrioDirect = kPrioYoungHalf, kPrioDirectHalo = kPrioNone, kPrioWinoPaired = kPrioYoungHalf;
+
 // activations as fp16 piece planes (c3_conv3.h), 8 convolution launches: conv1 inside res1a / res1b, the stride-2 convolutions
 // on the chunk stream of c3_dense.h, the pyramid pooling as the epilogue of res3b
 static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n, float *y) {
     Lane &L = lane(m);
+    // wave priority only while the handle has the chip to itself (the rule of the transform-waves form below): beside other handles or
+    // lanes the second workgroup of a CU is somebody else's
+    const bool prio_ok = m->wave_prio && std::max(m->sharing, m->lane_sharing) <= 1;
+    const int cus = m->wg_slots / 2;
+    m->choice.prio = 0;
     int hh[10], ww[10];
     fa_geometry(m, hh, ww);
     int cin = m->C;
@@ -358,6 +374,10 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
                 const int wslots = m->wg_slots, wunit = 8 * (Cout / 64);
                 if (gw > wslots) gw = std::max(wunit, wslots / wunit * wunit);
                 const dim3 wgrid(gw), wblock(tw ? kWtThreads : kPlThreads);
+                if (const int scheme = prio_ok && !tw && gw > cus ? kPrioWinoPaired : kPrioNone) {
+                    wave_prio_masks(scheme, cin / 32, wp.prio), wp.cus = cus;
+                    m->choice.prio |= 1u << l;
+                }
                 if (tw && Cout == 64) {
                     if (res) hipLaunchKernelGGL((conv3x3_wino_tw_kernel<64, true>), wgrid, wblock, 0, s, wp);
                     else hipLaunchKernelGGL((conv3x3_wino_tw_kernel<64, false>), wgrid, wblock, 0, s, wp);
@@ -389,6 +409,10 @@ static int run_fa_planes(c3_model *m, hipStream_t s, const int8_t *x, int64_t n,
             const int slots = m->wg_slots, unit = 8 * (Cout / 64);
             if (g > slots) g = std::max(unit, slots / unit * unit);
             const dim3 grid(g), block(kPlThreads);
+            if (const int scheme = !(prio_ok && g > cus) ? kPrioNone : src8 && l == 1 ? kPrioDirectHalo : kPrioDirect) {
+                wave_prio_masks(scheme, (cp.tiles + g - 1) / g * (Cout / 64), cp.prio), cp.cus = cus;
+                m->choice.prio |= 1u << l;
+            }
             if (Cout == 64 && src8 && m->C == 9) {
                 if (res) hipLaunchKernelGGL((conv3x3_planes_kernel<64, true, 0, 2, false, 9>), grid, block, 0, s, cp);
                 else hipLaunchKernelGGL((conv3x3_planes_kernel<64, false, 0, 1, false, 9>), grid, block, 0, s, cp);

@@ -367,6 +367,10 @@ struct c3_model {
     // forms alternating in one process): the chain's two launches 3.4 us shorter at 256 windows (w4) and 2.9 us at 512 (w8), but W = 16 no
     // better than the three launches at 512 and 6.6 us longer at 1000, where its workgroups sum two items one after the other
     int64_t fa_tail_max_batch = 512;
+    // Wave priority between the two workgroups of a CU (c3_conv3.h wave_prio_masks; DESIGN.md 3.8-10, profiles/wave_priority.txt): the schemes
+    // run_fa_planes gives the convolution kernels, and only while the handle has the chip to itself -- beside other handles or lanes a
+    // workgroup's CU mate is somebody else's.  env C3HIP_WAVE_PRIO = 0 | 1, read when the handle is created; rows do not depend on it
+    bool wave_prio = true;
     int wg_slots = 512;       // co-resident 256-thread / 64 KiB-LDS workgroups on the device (2 per CU)
 
     // the reference's rescaling of very deep pileup windows (c3_rescale.h; the *_depth entries and c3_predict_submit_region)
@@ -451,6 +455,7 @@ struct c3_model {
         char s1[8] = "------";           // the six stride-1 convolutions res1a .. res3b: d = direct, w = F(2,3) along H
         char wform[8] = "------";        // ... and the form of the F(2,3) ones (c3_conv3w.h): p = paired workgroups, t = transform waves
         const char *fa_tail = "-";       // full alignment's FC chain (run_tail): split | fused-w4 | fused-w8 | fused-w16
+        uint32_t prio = 0;               // bit l: convolution l of the full-alignment pass ran a wave priority scheme (c3_conv3.h wave_prio_masks)
     } choice;
 
     bool prof = false;

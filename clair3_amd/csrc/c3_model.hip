@@ -183,6 +183,7 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
         }
         m->fa_tail = f->v;
     }
+    if (const char *e = getenv("C3HIP_WAVE_PRIO")) m->wave_prio = atoi(e) != 0;  // (c3_model.h wave_prio)
     if (const char *e = getenv("C3HIP_RANGE_GUARD")) {  // the range-guard policy a full-alignment handle starts with; a value that names none fails the creation
         int policy = 0, max_recal = 0;
         if (parse_range_policy(e, &policy, &max_recal, "C3HIP_RANGE_GUARD")) {
@@ -395,10 +396,17 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
                 const size_t at = strlen(wf);
                 snprintf(wf + at, sizeof(wf) - at, "%s%s:%s", at ? "/" : "", names[i], m->choice.wform[i] == 't' ? "transform-waves" : "paired");
             }
+        // wave_prio: the convolutions of the last pass that ran a wave priority scheme (c3_forward.h run_fa_planes), conv3/res2a/res2b, "-" for none
+        char wp[96] = "";
+        for (int l = 1; l < 9; ++l)
+            if (m->choice.prio >> l & 1u) {
+                const size_t at = strlen(wp);
+                snprintf(wp + at, sizeof(wp) - at, "%s%s", at ? "/" : "", kFaLayerTag[l] + 3);  // ("fa.res2a" -> "res2a")
+            }
         snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
-                 "precision=%s wino_form=%s fa_tail=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
+                 "precision=%s wino_form=%s fa_tail=%s wave_prio=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
                  stores, m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
-                 m->precision, wf[0] ? wf : "-", m->choice.fa_tail, (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+                 m->precision, wf[0] ? wf : "-", m->choice.fa_tail, wp[0] ? wp : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
     }
     if (m->fp32_plan | m->fp32_auto) {  // only while a precision plan is in force (c3_model.h layer_f16)
         const size_t at = strlen(buf);

@@ -4,11 +4,14 @@
 // bits: 1 no weight loads, 2 no halo loads after the first tile, 4 no epilogue, 8 no matrix instructions), at one and two
 // workgroups per CU, with the second workgroup of a CU started later (skew), and prints a shader-clock trace of workgroups 0 and
 // 256 (the two that share a CU: tools/census_probe.hip).  Numbers only -- correctness is the parity tests' job.
+//   conv_probe prio   the wave priority schemes (c3_conv3.h wave_prio_step) on res1 (1530 tiles on 512 workgroups) and on res3b with the
+//                     pooling epilogue (512 tiles): start / end stamps of every workgroup and the launch time per scheme, alternating
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 #include "../clair3_amd/csrc/c3_conv3.h"
+#include "stamp_report.h"
 using namespace c3;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
@@ -22,7 +25,10 @@ static float time_it(K launch, int reps = 20) {
 template <int C, int ABL> static float run(const PlaneConvParams &cp, int grid) {
     return time_it([&] { hipLaunchKernelGGL((conv3x3_planes_kernel<C, true, ABL>), dim3(grid), dim3(kPlThreads), 0, 0, cp); });
 }
-template <int C> static int shape(const char *name, int B, int H, int W, int cus) {
+template <int C, bool SPPF, int ABL> static void launch_p(const PlaneConvParams &cp, int grid) {
+    hipLaunchKernelGGL((conv3x3_planes_kernel<C, true, ABL, 0, SPPF>), dim3(grid), dim3(kPlThreads), 0, 0, cp);
+}
+template <int C, bool SPPF = false> static int shape(const char *name, int B, int H, int W, int cus, bool prio = false) {
     constexpr int NS = C / 64;
     const size_t bytes = (size_t)B * H * W * C * 4;
     void *x, *y, *r, *wf; float *bias, *post; uint32_t *flag;
@@ -59,6 +65,50 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
     const int unit = 8 * NS;
     auto grid_for = [&](int s) { return cp.tiles <= s ? cp.tiles : s / unit * unit; };
     const int g = grid_for(2 * cus);
+    if (prio) {
+        float *spp = nullptr;
+        if constexpr (SPPF) {  // (c3_forward.h run_fa_planes: two whole windows per tile, the pooled bins instead of planes)
+            CK(hipMalloc((void **)&spp, (size_t)B * 14 * C * 4));
+            cp.spp = spp, cp.tiles = (B + 1) / 2 * NS;
+        }
+        const int gp = grid_for(2 * cus);
+        long long *tb; CK(hipMalloc(&tb, (size_t)2 * gp * 8));
+        cp.trace = tb, cp.cus = cus;
+        printf("== %s%s: M = %d, %d tiles on %d workgroups, %d CUs; schemes: 0 none, 1 younger workgroup at priority 1 for the first half of its slabs, "
+               "2 both alternate per slab, 3 both alternate per weight chunk\n", name, SPPF ? " with the pooling epilogue" : "", cp.M, cp.tiles, gp, cus);
+        const int steps = (cp.tiles + gp - 1) / gp * NS;  // slabs of the tiles of a workgroup's walk
+        auto set_scheme = [&](int scheme) {  // 3: per chunk (ABL bit 256: bit 0 of the mask is the phase)
+            if (scheme < 3) wave_prio_masks(scheme, steps, cp.prio);
+            else cp.prio[0] = kPrioOn, cp.prio[1] = kPrioOn | 1u;
+        };
+        for (int scheme = 0; scheme < 4; ++scheme) {
+            set_scheme(scheme);
+            CK(hipMemset(tb, 0, (size_t)2 * gp * 8));
+            std::vector<long long> ht((size_t)2 * gp);
+            printf("  scheme %d, first start to last end of six launches (us):", scheme);
+            for (int k = 0; k < 6; ++k) {  // (the last launch is the one reported in full)
+                if (scheme < 3) launch_p<C, SPPF, 128>(cp, gp);
+                else launch_p<C, SPPF, 128 | 256>(cp, gp);
+                CK(hipDeviceSynchronize());
+                CK(hipMemcpy(ht.data(), tb, ht.size() * 8, hipMemcpyDeviceToHost));
+                printf(" %.2f", stamp_span(ht, gp));
+            }
+            printf("\n");
+            char what[32]; snprintf(what, sizeof what, "scheme %d, one launch:", scheme);
+            stamp_report(what, ht, gp, cus);
+        }
+        for (int rep = 0; rep < 5; ++rep) {
+            printf("  launch time, 200 launches back to back (us), schemes 0 1 2 3:");
+            for (int scheme = 0; scheme < 4; ++scheme) {
+                set_scheme(scheme);
+                printf(" %6.2f", scheme < 3 ? time_it([&] { launch_p<C, SPPF, 0>(cp, gp); }, 200) : time_it([&] { launch_p<C, SPPF, 256>(cp, gp); }, 200));
+            }
+            printf("\n");
+        }
+        hipFree(tb); hipFree(spp);
+        hipFree(x); hipFree(y); hipFree(r); hipFree(wf); hipFree(bias); hipFree(post); hipFree(flag);
+        return 0;
+    }
     const double mf = 2.0 * tiles_m * kPlBM * (double)C * 9.0 * C * 3;
     printf("== %s: M = %d, %d tiles of %d pixels, grid %d; executed matrix work %.1f GFLOP = %.1f us at 2500 TF; in+out+res %.0f MB\n", name, cp.M, cp.tiles, kPlBM, g,
            mf / 1e9, mf / 2500e6, 3 * bytes / 1e6);
@@ -94,9 +144,14 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
     hipFree(x); hipFree(y); hipFree(r); hipFree(wf); hipFree(bias); hipFree(post); hipFree(flag);
     return 0;
 }
-int main() {
+int main(int argc, char **argv) {
     hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
+    if (argc > 1 && !strcmp(argv[1], "prio")) {
+        if (shape<64>("res1", 256, 45, 17, cus, true)) return 1;
+        if (shape<256, true>("res3b", 256, 12, 5, cus, true)) return 1;
+        return 0;
+    }
     if (shape<64>("res1", 256, 45, 17, cus)) return 1;
     if (shape<128>("res2", 256, 23, 9, cus)) return 1;
     if (shape<256>("res3", 256, 12, 5, cus)) return 1;

@@ -1,6 +1,9 @@
 // dense_probe.hip -- where the time of dense_planes_pipe_kernel goes on the LSTM2 projection shape (M = 33 * 1024, N = 1280,
 // K = 256): both kernels of c3_dense.h with parts switched off (ABL bits).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fno-gpu-flush-denormals-to-zero -w -I clair3_amd/csrc tools/dense_probe.hip -o tools/bin/dense_probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fno-gpu-flush-denormals-to-zero -w -I clair3_amd/csrc -I tools tools/dense_probe.hip -o tools/bin/dense_probe
+//   dense_probe prio   the wave priority schemes (c3_conv3.h wave_prio_masks) on the stride-2 convolutions of a B = 256 step: conv3 in the
+//                      pair form (414 tiles), start / end stamps of every workgroup and the launch time per scheme; conv5 (one workgroup
+//                      per CU) with waves 4-7 at priority 1
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <stdint.h>
@@ -13,6 +16,7 @@ static int fail(const char *, ...) { return -1; }
 #include "c3_dense.h"
 #include "c3_conv3s2.h"
 #include "c3_conv3s2q.h"
+#include "stamp_report.h"
 using namespace c3;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 
@@ -30,7 +34,82 @@ static float time_us(F launch, int reps) {
     return 1e3f * ms / reps;
 }
 
+static int s2_prio() {
+    hipDeviceProp_t prop;
+    CK(hipGetDeviceProperties(&prop, 0));
+    const int cus = prop.multiProcessorCount, Bc = 256;
+    const int shapes[2][6] = {{45, 17, 64, 23, 9, 128}, {23, 9, 128, 12, 5, 256}};
+    uint32_t s = 12345u;
+    auto rnd = [&]() { s = s * 1664525u + 1013904223u; return s; };
+    for (int si = 0; si < 2; ++si) {
+        const int Hin = shapes[si][0], Win = shapes[si][1], Cin = shapes[si][2], Ho = shapes[si][3], Wo = shapes[si][4], Co = shapes[si][5];
+        const int Mc = Bc * Ho * Wo, Kc = 9 * Cin;
+        const size_t abytes = (size_t)Bc * Hin * Win * Cin * 4, wbytes = (size_t)Co * Kc * 4, cbytes = (size_t)Mc * Co * 4;
+        std::vector<uint16_t> ha(abytes / 2), hw(wbytes / 2);  // fp16 values in roughly (-1, 1), hi and lo pieces alike (power realism)
+        for (auto &x : ha) { const uint32_t r = rnd(); x = (uint16_t)(((r >> 31) << 15) | ((8 + (r >> 8) % 7) << 10) | (r & 0x3ff)); }
+        for (auto &x : hw) { const uint32_t r = rnd(); x = (uint16_t)(((r >> 31) << 15) | ((6 + (r >> 8) % 7) << 10) | (r & 0x3ff)); }
+        void *ca, *cw, *cc;
+        float *dz;
+        CK(hipMalloc(&ca, abytes));
+        CK(hipMalloc(&cw, wbytes));
+        CK(hipMalloc(&cc, cbytes));
+        CK(hipMalloc((void **)&dz, Co * 4));
+        CK(hipMemcpy(ca, ha.data(), abytes, hipMemcpyHostToDevice));
+        CK(hipMemcpy(cw, hw.data(), wbytes, hipMemcpyHostToDevice));
+        CK(hipMemset(dz, 0, Co * 4));
+        auto magic = [](int d) { return d <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) / (uint64_t)d) + 1); };
+        S2ConvParams sp;
+        sp.a = ca, sp.wf = cw, sp.bias = dz, sp.post = dz, sp.c = cc, sp.range_flag = nullptr;
+        sp.M = Mc, sp.N = Co, sp.NK = Kc / 64, sp.tiles_n = Co / kS2BN, sp.tiles = (Mc + kS2BM - 1) / kS2BM * sp.tiles_n;
+        sp.Hin = Hin, sp.Win = Win, sp.Cin = Cin, sp.Ho = Ho, sp.Wo = Wo, sp.mg_hw = magic(Ho * Wo), sp.mg_w = magic(Wo);
+        sp.cus = cus;
+        const bool pair = sp.tiles > cus;  // (c3_forward.h run_fa_planes)
+        const int unit = 8 * sp.tiles_n, slots = pair ? 2 * cus : cus;
+        const int g = sp.tiles > slots ? slots / unit * unit : sp.tiles;
+        long long *tb;
+        CK(hipMalloc(&tb, (size_t)2 * g * 8));
+        sp.trace = tb;
+        printf("== stride-2 convolution %dx%dx%d -> %dx%dx%d, B = %d: %d tiles of %d chunks on %d workgroups (%s), %d CUs\n", Hin, Win, Cin, Ho, Wo, Co, Bc, sp.tiles,
+               sp.NK, g, pair ? "two per CU" : "one per CU", cus);
+        printf("   schemes: 0 none, %s\n", pair ? "1 younger workgroup at priority 1 for the first half of its chunks, 2 both alternate per chunk" : "4 waves 4-7 at priority 1");
+        const int schemes[2][3] = {{0, kPrioUpperWaves, -1}, {0, kPrioYoungHalf, kPrioAlternate}};
+        auto launch = [&](bool stamps) {
+            if (pair && stamps) hipLaunchKernelGGL((conv3x3_s2_planes_kernel<32 | 64, true>), dim3(g), dim3(kS2Threads), 0, 0, sp);
+            else if (pair) hipLaunchKernelGGL((conv3x3_s2_planes_kernel<64, true>), dim3(g), dim3(kS2Threads), 0, 0, sp);
+            else if (stamps) hipLaunchKernelGGL((conv3x3_s2_planes_kernel<32 | 64, false>), dim3(g), dim3(kS2Threads), 0, 0, sp);
+            else hipLaunchKernelGGL((conv3x3_s2_planes_kernel<64, false>), dim3(g), dim3(kS2Threads), 0, 0, sp);
+        };
+        for (int k = 0; k < 3 && schemes[pair][k] >= 0; ++k) {
+            wave_prio_masks(schemes[pair][k], sp.NK, sp.prio);
+            CK(hipMemset(tb, 0, (size_t)2 * g * 8));
+            std::vector<long long> ht((size_t)2 * g);
+            printf("  scheme %d, first start to last end of six launches (us):", schemes[pair][k]);
+            for (int i = 0; i < 6; ++i) {  // (the last launch is the one reported in full)
+                launch(true);
+                CK(hipDeviceSynchronize());
+                CK(hipMemcpy(ht.data(), tb, ht.size() * 8, hipMemcpyDeviceToHost));
+                printf(" %.2f", stamp_span(ht, g));
+            }
+            printf("\n");
+            char what[32];
+            snprintf(what, sizeof what, "scheme %d, one launch:", schemes[pair][k]);
+            stamp_report(what, ht, g, cus);
+        }
+        for (int rep = 0; rep < 5; ++rep) {
+            printf("  launch time, 200 launches back to back (us), schemes in that order:");
+            for (int k = 0; k < 3 && schemes[pair][k] >= 0; ++k) {
+                wave_prio_masks(schemes[pair][k], sp.NK, sp.prio);
+                printf(" %6.2f", time_us([&] { launch(false); }, 200));
+            }
+            printf("\n");
+        }
+        (void)hipFree(ca), (void)hipFree(cw), (void)hipFree(cc), (void)hipFree(dz), (void)hipFree(tb);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "prio")) return s2_prio();
     const int B = argc > 1 ? atoi(argv[1]) : 1024;
     const int M = 33 * B, N = 1280, K = 256;
     std::vector<uint16_t> ha((size_t)M * K * 2), hw((size_t)N * K * 2);

@@ -1,11 +1,13 @@
 // tools/wino_probe.hip -- conv3x3_wino_planes_kernel (Winograd F(2,3) along H, c3_conv3w.h) against conv3x3_planes_kernel (direct,
 // c3_conv3.h) on the residual-block shapes of a full-alignment batch (run on the GPU box):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fno-gpu-flush-denormals-to-zero -I clair3_amd/csrc tools/wino_probe.hip -o /tmp/wino_probe && /tmp/wino_probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -fno-gpu-flush-denormals-to-zero -I clair3_amd/csrc -I tools tools/wino_probe.hip -o /tmp/wino_probe && /tmp/wino_probe
 // 1. correctness: both kernels on the same random planes / weights / residual; max |difference| between them and of each against
 //    an fp64 host evaluation of sampled outputs (small batches with ragged tails, then B = 256);
 // 2. time: direct whole, Winograd whole and with parts switched off (ABL bits: 1 no weight loads, 2 no transform after the first,
 //    4 no epilogue, 8 no matrix instructions, 16 transform loads not requested ahead), one and two workgroups per CU; the
 //    transform-waves form (conv3x3_wino_tw_kernel) whole, without its transform, without its epilogue, and its two roles' phase trace.
+// 3. `wino_probe prio`: the wave priority schemes (c3_conv3.h wave_prio_masks) on res2 at B = 256 (440 tiles, one per workgroup): start /
+//    end stamps of every workgroup and the launch time per scheme; the transform-waves form on res3a with waves 4-7 at priority 1.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -14,6 +16,7 @@
 #include <random>
 #include <vector>
 #include "c3_conv3w16.h"
+#include "stamp_report.h"
 using namespace c3;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
@@ -54,7 +57,7 @@ template <int C, bool RES, int ABL, int RT = 2, int WD = 4> static void launch_w
     hipLaunchKernelGGL((conv3x3_wino16_planes_kernel<C, RES, ABL, RT, WD>), dim3(grid), dim3(kPlThreads), 0, 0, wp);
 }
 
-template <int C> static int shape(const char *name, int B, int H, int W, int cus, bool timing, bool split_only = false) {
+template <int C> static int shape(const char *name, int B, int H, int W, int cus, bool timing, bool split_only = false, bool prio_only = false) {
     constexpr int NS = C / 64, NS32 = C / 32;
     const int M = B * H * W, Hj = (H + 1) / 2, Mp = B * Hj * W;
     const size_t bytes = (size_t)M * C * 4;
@@ -233,7 +236,60 @@ template <int C> static int shape(const char *name, int B, int H, int W, int cus
     printf("  words differing between the transform-waves form and the paired one: %zu\n", twdiff);
     printf("  wino16 (LDS-DMA, 16-channel slabs) against wino: %zu values differ, max |difference| %.3e\n", w16diff, w16max);
     printf("  wino16 with 64-row tiles against wino: %zu values differ, max |difference| %.3e\n", s16diff, s16max);
-    if (timing && split_only) {
+    if (timing && prio_only) {
+        WinoConvParams wq = wp;
+        wq.cus = cus;
+        if (wp.tiles > cus) {  // the paired form; schemes: 0 none, 1 younger workgroup first half of its slabs, 2 alternate per slab, 3 alternate per weight chunk (ABL bit 256)
+            long long *tb; CK(hipMalloc(&tb, (size_t)2 * gw * 8));
+            void *yq; CK(hipMalloc(&yq, bytes));
+            wq.trace = tb, wq.out = yq;
+            auto set_scheme = [&](int scheme) {
+                if (scheme < 3) wave_prio_masks(scheme, NS32, wq.prio);
+                else wq.prio[0] = kPrioOn, wq.prio[1] = kPrioOn | 1u;
+            };
+            std::vector<uint32_t> a(bytes / 4), b2(bytes / 4);
+            CK(hipMemcpy(a.data(), yw, bytes, hipMemcpyDeviceToHost));
+            printf("  paired form, %d tiles of %d slabs on %d workgroups, %d CUs; schemes: 0 none, 1 younger workgroup at priority 1 for the first half of its slabs, "
+                   "2 both alternate per slab, 3 both alternate per weight chunk\n", wp.tiles, NS32, gw, cus);
+            for (int scheme = 0; scheme < 4; ++scheme) {
+                set_scheme(scheme);
+                CK(hipMemset(tb, 0, (size_t)2 * gw * 8)); CK(hipMemset(yq, 0xff, bytes));
+                std::vector<long long> ht((size_t)2 * gw);
+                printf("  scheme %d, first start to last end of six launches (us):", scheme);
+                for (int k = 0; k < 6; ++k) {  // (the last launch is the one reported in full)
+                    if (scheme < 3) launch_w<C, true, 128>(wq, gw);
+                    else launch_w<C, true, 128 | 256>(wq, gw);
+                    CK(hipDeviceSynchronize());
+                    CK(hipMemcpy(ht.data(), tb, ht.size() * 8, hipMemcpyDeviceToHost));
+                    printf(" %.2f", stamp_span(ht, gw));
+                }
+                printf("\n");
+                CK(hipMemcpy(b2.data(), yq, bytes, hipMemcpyDeviceToHost));
+                size_t nd = 0;
+                for (size_t i = 0; i < a.size(); ++i) nd += a[i] != b2[i];
+                char what[48]; snprintf(what, sizeof what, "scheme %d (%zu words differ):", scheme, nd);
+                stamp_report(what, ht, gw, cus);
+            }
+            for (int rep = 0; rep < 5; ++rep) {
+                printf("  launch time, 200 launches back to back (us), schemes 0 1 2 3:");
+                for (int scheme = 0; scheme < 4; ++scheme) {
+                    set_scheme(scheme);
+                    printf(" %6.2f", scheme < 3 ? time_it([&] { launch_w<C, true, 0>(wq, gw); }, 200) : time_it([&] { launch_w<C, true, 256>(wq, gw); }, 200));
+                }
+                printf("\n");
+            }
+            hipFree(tb); hipFree(yq);
+        } else {  // the transform-waves form, a CU to itself: waves 4-7 (the transform waves) at priority 1
+            for (int rep = 0; rep < 5; ++rep) {
+                printf("  transform waves, %d tiles; 200 launches back to back (us), waves 4-7 at priority 0 / 1:", wp.tiles);
+                for (int scheme : {0, kPrioUpperWaves}) {
+                    wave_prio_masks(scheme, NS32, wq.prio);
+                    printf(" %6.2f", time_it([&] { launch_tw<C, true, 256>(wq); }, 200));
+                }
+                printf("\n");
+            }
+        }
+    } else if (timing && split_only) {
         {   // when do the workgroups of ONE launch start and finish (100 MHz device-wide counter: 10 ns ticks)?  A
             // consumer tile of the next layer needs its three producer tiles: it cannot start before they have finished.
             long long *tb; CK(hipMalloc(&tb, (size_t)2 * 1024 * 8)); CK(hipMemset(tb, 0, (size_t)2 * 1024 * 8));
@@ -383,6 +439,11 @@ int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "split")) {  // round 6: what a split-K launch of the under-filled layers could take at most (no exchange)
         if (shape<256>("res3 split-K bound", 256, 12, 5, cus, true, true)) return 1;
         if (shape<128>("res2 split-K bound", 256, 23, 9, cus, true, true)) return 1;
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "prio")) {
+        if (shape<128>("res2 wave priority", 256, 23, 9, cus, true, false, true)) return 1;
+        if (shape<256>("res3a wave priority", 256, 12, 5, cus, true, false, true)) return 1;
         return 0;
     }
     if (argc > 1 && !strcmp(argv[1], "tw")) {  // the transform-waves form: one round (res3a at B = 256, res2 at 149) and two (res2 at 256)
