@@ -33,7 +33,9 @@ EXPORTS = (
     "c3_model_set_channel_lowering", "c3_model_set_calibration_origin", "c3_model_channel_exps", "c3_calibration_rule",
     "c3_model_set_exact", "c3_predict_exact", "c3_exact_fetch",
     "c3_model_set_range_policy", "c3_range_policy_check", "c3_model_range_stats",
+    "c3_predict_submit_parts", "c3_predict_parts",
 )
+MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
 # policy of the range guard (C3_RANGE_* in include/c3hip.h)
@@ -174,6 +176,8 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     L.c3_predict_submit_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
     L.c3_predict_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.c3_predict_submit_parts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]
+    L.c3_predict_parts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.c3_pack_rows.restype = C.c_int64
     L.c3_pack_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_model_set_verify.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]

@@ -194,13 +194,67 @@ def _make_batch_generator(original):
 PREFETCH_DEPTH = int(os.environ.get("C3HIP_PREFETCH_DEPTH", "2"))
 
 
-def install(worker=True, gpu_wrapper=True, decoder=False, lazy_torch=None):
+# ---- serve mode (clair3_amd/serve.py): the worker WITHOUT --use_gpu sends its batches to one GPU process ----
+# The reference's counterpart is its --use_triton_gpu branch (clair3/CallVariantsFromCffi.py:201-214,287-294).  Opt-in: install(server=PATH) or
+# C3HIP_SERVER=PATH.  The branch is known when the loop calls _select_device (:217 with True, :221 with False), before it builds its model
+# (:230-243): from a call with False on, the rebound class names construct client.RemoteModel objects, the rebound loader compares the
+# checkpoint's sha256 with the server's and the rebound _torch_predict is the remote call.  With --use_gpu every name does what it does
+# without the opt-in.
+SERVER = None           # the socket path while the opt-in is installed
+_REMOTE_BRANCH = False  # the loop took the branch without --use_gpu
+
+
+def _select_device_serving(use_gpu):
+    global _REMOTE_BRANCH
+    _REMOTE_BRANCH = SERVER is not None and not use_gpu
+    return _select_device_for_cffi_worker(use_gpu)
+
+
+def _model_factory(hip_class, name):
+    def factory(*args, **kwargs):
+        if not _REMOTE_BRANCH:
+            return hip_class(*args, **kwargs)
+        from . import client
+        if args:
+            raise client.ServerError(f"{hip_class.__name__}: keyword arguments expected, as the reference's worker passes them")
+        return client.RemoteModel(SERVER, name, add_indel_length=kwargs.get("add_indel_length", False),
+                                  input_channels=kwargs.get("input_channels"), decoder=bool(predict.DECODER_COLUMNS))
+
+    factory.__name__ = factory.__qualname__ = hip_class.__name__
+    factory._c3hip_class, factory._c3hip_server_name = hip_class, name
+    return factory
+
+
+def _is_remote(model):
+    from . import client
+    return isinstance(model, client.RemoteModel)
+
+
+def _load_checkpoint_serving(model, checkpoint_path, device=None):
+    if _is_remote(model):
+        return model.check_checkpoint(checkpoint_path)
+    return predict._load_torch_checkpoint(model, checkpoint_path, device)
+
+
+def _predict_serving(model, device, X):
+    if _is_remote(model):
+        return model.predict_numpy(X)
+    return predict._hip_predict(model, device, X)
+
+
+def install(worker=True, gpu_wrapper=True, decoder=False, lazy_torch=None, server=None):
     """Patch the imported (or importable) reference modules in place.  Returns the list of rebound names.
+    server=PATH (or C3HIP_SERVER=PATH): serve mode, see above -- the same names, bound to objects that send a worker WITHOUT --use_gpu to the
+    server behind PATH; decoder=True then needs a server started with --decoder (checked at its hello).
     decoder=True additionally makes the rows of either network carry the decoder columns of libc3hip and
     rebinds clair3.CallVariants.possible_outcome_probabilites_from / batch_output to read them
     (clair3_amd/decode.py): same VCF text, ~6x the decode rate per host core on rows with the indel-length heads, ~2x on
     the 24-probability rows of the pileup network.  lazy_torch (default: C3HIP_LAZY_TORCH, on): see below."""
+    global SERVER
     done = []
+    SERVER = server or os.environ.get("C3HIP_SERVER", "").strip() or None
+    serving = SERVER is not None and worker
+    P, F = (_model_factory(Clair3_P, "pileup"), _model_factory(Clair3_F, "alignment")) if serving else (Clair3_P, Clair3_F)
     # ``import torch`` is 1.2 - 1.9 s of a worker process that, with these names rebound, never uses it (lazy_torch.py): when the package
     # has not been imported yet, a stand-in takes its place that imports it on first real use, and clair3.model -- whose classes are
     # replaced anyway, and whose import needs torch.nn -- is stood in for the same way
@@ -213,19 +267,19 @@ def install(worker=True, gpu_wrapper=True, decoder=False, lazy_torch=None):
         def load_reference_models():
             sys.modules.pop("clair3.model", None)
             real = importlib.import_module("clair3.model")
-            real.Clair3_P, real.Clair3_F = Clair3_P, Clair3_F
+            real.Clair3_P, real.Clair3_F = P, F
             return real
-        clair3.model = sys.modules["clair3.model"] = _lazy.standin_module("clair3.model", {"Clair3_P": Clair3_P, "Clair3_F": Clair3_F},
+        clair3.model = sys.modules["clair3.model"] = _lazy.standin_module("clair3.model", {"Clair3_P": P, "Clair3_F": F},
                                                                           load_reference_models)
     else:
         import clair3.model as ref_model
-        ref_model.Clair3_P, ref_model.Clair3_F = Clair3_P, Clair3_F
+        ref_model.Clair3_P, ref_model.Clair3_F = P, F
     done += ["clair3.model.Clair3_P", "clair3.model.Clair3_F"]
     if worker:
         import clair3.CallVariantsFromCffi as w
-        w._torch_predict = predict._hip_predict
-        w._load_torch_checkpoint = predict._load_torch_checkpoint
-        w._select_device = _select_device_for_cffi_worker
+        w._torch_predict = _predict_serving if serving else predict._hip_predict
+        w._load_torch_checkpoint = _load_checkpoint_serving if serving else predict._load_torch_checkpoint
+        w._select_device = _select_device_serving if serving else _select_device_for_cffi_worker
         w._limit_gpu_memory = _limit_gpu_memory
         if not hasattr(w.tensor_generator_for_chunk, "_c3hip_original"):
             w.tensor_generator_for_chunk = _make_batch_generator(w.tensor_generator_for_chunk)

@@ -151,6 +151,8 @@ enum class InKind {
     Rows,        // full alignment: x holds the occupied rows of the windows back to back, row_count[b] of them for window b from dense row
                  // row_first[b] on (nullptr: centred, (depth - row_count[b]) / 2); checked by the caller, which also adds the counts up
     PackedHere,  // C3HIP_PACK_ROWS=1: sliced int8 full-alignment windows, packed into their occupied rows while they are staged (c3_expand.h)
+    Parts,       // the windows themselves, in n_parts host buffers of counts[i] windows each: laid behind each other in the image section, so
+                 // the batch the device sees is the plain batch of their concatenation; rows leave to y_parts[i] (c3_predict_submit_parts)
 };
 // candidate positions instead of window starts (c3_predict_submit_candidates): what the host knows of the region before it is staged
 struct CandInput {
@@ -175,6 +177,10 @@ struct RingInput {
     const CandInput *cand = nullptr;                            // Candidates
     const int32_t *row_first = nullptr, *row_count = nullptr;  // Rows
     int64_t rows_total = 0;
+    const void *const *parts = nullptr;  // Parts
+    const int64_t *counts = nullptr;
+    float *const *y_parts = nullptr;
+    int n_parts = 0;
 };
 static RingInput ring_input(InKind kind, const void *x, int x_dtype, int64_t batch, float *y_host, const int32_t *depth = nullptr, float *y_dev = nullptr) {
     RingInput in;
@@ -278,6 +284,25 @@ static void fill_region_image(const c3_model *m, const HostSlot &sl, const RingI
 static void fill_sliced(const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
     if (depth) memcpy(sl.pin<char>(p.depth), depth, p.depth.bytes);
     f.src = in.x;
+}
+// parts: each caller buffer gets the one copy every caller buffer gets, part i behind part i - 1 in the image section
+static void fill_parts(const HostSlot &sl, const RingInput &in, const StagedBatch &p, size_t window_bytes, Filled &f) {
+    size_t off = p.image.off;
+    for (int i = 0; i < in.n_parts; ++i) {
+        const size_t n = (size_t)in.counts[i] * window_bytes;
+        if (n) StagePool::get().copy((char *)sl.pin_x + off, in.parts[i], n);
+        off += n;
+    }
+    f.prebuilt(p.image.bytes);
+}
+// ... and c3_predict_wait's way back: the rows of part i, in batch order, to where its caller wants them
+static void scatter_parts(const HostSlot &sl, size_t row_bytes) {
+    const char *src = (const char *)sl.pin_y + sl.plan.y.off;
+    for (int i = 0; i < sl.n_parts; ++i) {
+        const size_t n = (size_t)sl.part_count[i] * row_bytes;
+        if (n) memcpy(sl.part_y[i], src, n);
+        src += n;
+    }
 }
 static void fill_region(const c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
     memcpy(sl.pin<char>(p.starts), in.starts, p.starts.bytes);
@@ -557,6 +582,8 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
     sl.cand = in.cand != nullptr, sl.cand_none = !launched;
     sl.verified = p.verify.bytes != 0;
     if (in.cand) sl.status_host = in.cand->status_host, sl.n_rows_host = in.cand->n_rows_host, sl.n_chunks = (int64_t)in.cand->chunks.size();
+    sl.n_parts = in.kind == InKind::Parts ? in.n_parts : 0;
+    for (int i = 0; i < sl.n_parts; ++i) sl.part_count[i] = in.counts[i], sl.part_y[i] = in.y_parts[i];
     sl.pack_epoch = m->pack_epoch;
     sl.busy = true;
 }
@@ -564,7 +591,7 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
 static int predict_submit(c3_model *m, RingInput in, int slot) {
     TRY(ring_ready(m, slot));
     if (in.batch < 0) return fail("negative batch");
-    if (in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev))) return fail("null buffer");
+    if (in.kind != InKind::Parts && in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev))) return fail("null buffer");  // (parts: checked one by one at the entry)
     HIP_TRY(hipSetDevice(m->device));
     if (in.kind == InKind::Sliced && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && in.x_dtype == C3_DTYPE_I8) in.kind = InKind::PackedHere;
     HostSlot &sl = m->slot[slot];
@@ -591,6 +618,7 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         case InKind::Candidates: fill_candidates(m, sl, in, p, depth, f); break;
         case InKind::Rows: fill_rows(m, sl, in, p, f); break;
         case InKind::PackedHere: fill_packed_rows(m, sl, in, p, f); break;
+        case InKind::Parts: fill_parts(sl, in, p, (size_t)c3_model_window_bytes(m, in.x_dtype), f); break;
         }
         TRY(queue_input(m, sl, p, f, alone, in_lane));
         if (launch_batch(m, sl, in, p) != 0) {
@@ -730,7 +758,8 @@ int c3_predict_wait(c3_model *m, int slot) {
         sl.cand = false;
         return 0;
     }
-    memcpy(sl.y_host, sl.pin_y, p.y.bytes);
+    if (sl.n_parts) scatter_parts(sl, (size_t)m->row * sizeof(float));  // (whoever wrote pin_y: the product pass, the range guard's re-run, verify mode's escalation)
+    else memcpy(sl.y_host, sl.pin_y, p.y.bytes);
     return 0;
 }
 
@@ -807,6 +836,27 @@ static int predict_blocking(c3_model *m, const void *x_host, int x_dtype, int64_
 
 int c3_predict(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_host) {
     return predict_blocking(m, x_host, x_dtype, batch, nullptr, y_host);
+}
+
+// ---- one batch staged from several host buffers (the server of clair3_amd/serve.py: requests of several clients in one forward pass) ----
+int c3_predict_submit_parts(c3_model *m, const void *const *parts, const int64_t *counts, int n_parts, int x_dtype, float *const *y_parts, int slot) {
+    TRY(ring_ready(m, slot));
+    if (n_parts < 1 || n_parts > kMaxParts) return fail("n_parts must be in [1, %d], got %d", kMaxParts, n_parts);
+    if (!parts || !counts || !y_parts) return fail("null table: parts / counts / y_parts");
+    if (x_dtype != C3_DTYPE_I8 && !(x_dtype == C3_DTYPE_I32 && m->kind == C3_KIND_PILEUP))
+        return fail("windows must be int8%s (got dtype %d)", m->kind == C3_KIND_PILEUP ? " or int32" : "", x_dtype);
+    RingInput in = ring_input(InKind::Parts, nullptr, x_dtype, 0, nullptr);
+    for (int i = 0; i < n_parts; ++i) {
+        if (counts[i] < 0) return fail("part %d: negative count %lld", i, (long long)counts[i]);
+        if (counts[i] > 0 && (!parts[i] || !y_parts[i])) return fail("part %d: null buffer", i);
+        in.batch += counts[i];
+    }
+    in.parts = parts, in.counts = counts, in.y_parts = y_parts, in.n_parts = n_parts;
+    return predict_submit(m, in, slot);
+}
+int c3_predict_parts(c3_model *m, const void *const *parts, const int64_t *counts, int n_parts, int x_dtype, float *const *y_parts) {
+    TRY(c3_predict_submit_parts(m, parts, counts, n_parts, x_dtype, y_parts, 0));
+    return c3_predict_wait(m, 0);
 }
 
 // ---- depths: the reference's CPU-branch meaning of a pileup window (c3_rescale.h) ----

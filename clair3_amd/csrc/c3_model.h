@@ -171,6 +171,8 @@ struct StagedBatch {
     size_t y_total = 0;
 };
 
+constexpr int kMaxParts = 64;  // host buffers one staged batch may be assembled from (C3_MAX_PARTS)
+
 struct HostSlot {
     void *pin_x = nullptr;
     float *pin_y = nullptr;
@@ -196,6 +198,11 @@ struct HostSlot {
     uint8_t *status_host = nullptr;
     int64_t *n_rows_host = nullptr;
     int64_t n_chunks = 0;
+    // a batch of parts (c3_predict_submit_parts): rows [sum(part_count[0 .. i)), + part_count[i]) of the batch belong at part_y[i].  The caller's
+    // tables are copied here: they may be reused as soon as submit returns
+    int n_parts = 0;  // 0: a batch from one buffer, its rows go to y_host
+    int64_t part_count[kMaxParts] = {};
+    float *part_y[kMaxParts] = {};
     // a verified batch (c3_verify.h): the rows of its second pass on the fp32 forms, the compare kernel's partials behind them.  The buffer
     // belongs to the SLOT, not to the lane: two slots in flight in one lane would overwrite each other's rows before c3_predict_wait reads them
     bool verified = false;

@@ -294,6 +294,46 @@ class _HipModel:
                    "c3_predict_submit_dev")
         return slot, None
 
+    def _parts_args(self, arrays):
+        """(windows, pointer table, counts, rows, pointer table, dtype) of a batch of parts as the C ABI takes them.  An entry is an array of
+        windows, or a pair (windows, rows) whose rows -- float32 (n, row_size), C-contiguous -- the caller owns: a server hands the mapped
+        regions of its clients' segments over that way, and nothing is copied on either side of the library"""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        arrays = list(arrays)
+        n = len(arrays)
+        if not 1 <= n <= _lib.MAX_PARTS:
+            raise _lib.C3Error(f"a batch takes 1 to {_lib.MAX_PARTS} parts, got {n}")
+        xs, ys, dt = [], [], None
+        for i, a in enumerate(arrays):
+            x, y = a if isinstance(a, tuple) else (a, None)
+            x, d = self._window_batch(x)
+            if dt is not None and d != dt:
+                raise _lib.C3Error(f"part {i}: dtype {x.dtype} differs from the parts before it (one dtype per batch)")
+            dt = d
+            if y is None:
+                y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
+            elif y.dtype != np.float32 or y.shape != (x.shape[0], self.row_size) or not y.flags.c_contiguous or not y.flags.writeable:
+                raise _lib.C3Error(f"part {i}: rows must be writeable C-contiguous float32 {(x.shape[0], self.row_size)}, got {y.dtype} {y.shape}")
+            xs.append(x), ys.append(y)
+        xp = (C.c_void_p * n)(*[x.ctypes.data for x in xs])
+        yp = (C.c_void_p * n)(*[y.ctypes.data for y in ys])
+        counts = (C.c_int64 * n)(*[x.shape[0] for x in xs])
+        return xs, xp, counts, ys, yp, dt
+
+    def predict_parts(self, arrays):
+        """One forward pass over the windows of several arrays (c3_predict_parts): the list of their rows, each bit-identical to predict_numpy
+        on that array alone.  An array of 0 windows is legal."""
+        xs, xp, counts, ys, yp, dt = self._parts_args(arrays)
+        _lib.check(_lib.lib().c3_predict_parts(self._handle, xp, counts, len(xs), dt, yp), "c3_predict_parts")
+        return ys
+
+    def submit_parts(self, arrays, slot=0):
+        """Asynchronous half of predict_parts (c3_predict_submit_parts); wait() on the ticket returns the list of rows."""
+        xs, xp, counts, ys, yp, dt = self._parts_args(arrays)
+        _lib.check(_lib.lib().c3_predict_submit_parts(self._handle, xp, counts, len(xs), dt, yp, slot), "c3_predict_submit_parts")
+        return slot, ys
+
     def wait(self, ticket):
         slot, y = ticket
         _lib.check(_lib.lib().c3_predict_wait(self._handle, slot), "c3_predict_wait")

@@ -142,6 +142,25 @@ int c3_predict_wait(c3_model *m, int slot);
  * disk (clair3/CallVariantsFromCffiGPU.py:138-199); here they meet on rank 0 over xGMI and cross PCIe once, there.
  * c3_predict_wait(slot) runs the range guard (flag + a device-side scan for non-finite rows) and re-runs on fp32 if needed. */
 int c3_predict_submit_dev(c3_model *m, const void *x_host, int x_dtype, int64_t batch, float *y_dev, int slot);
+/* ---- one batch staged from SEVERAL host buffers (clair3_amd/serve.py: one GPU process answering the reference's CPU workers) ----
+ * The reference's authors let the per-chunk CPU workers of `parallel ... CallVariantsFromCffi` send their batches to one GPU process
+ * (--use_triton_gpu, clair3/CallVariantsFromCffi.py:201-214,287-294: models `pileup` INT32 and `alignment` INT8).  A server that coalesces the
+ * requests of several clients needs one forward pass over windows that sit in several buffers:
+ *   parts[i]    counts[i] windows (C-contiguous, c3_model_window_bytes(x_dtype) each); y_parts[i]: where their counts[i] rows of
+ *               c3_model_row_size() floats go (decoder columns included).  1 <= n_parts <= C3_MAX_PARTS; counts[i] == 0 is legal (its
+ *               pointers are not read); all parts share x_dtype.  Windows only: pileup C3_DTYPE_I8 | C3_DTYPE_I32, full alignment
+ *               C3_DTYPE_I8 -- depths, regions, candidates and rows keep their own entries
+ *   meaning     part i is staged behind part i - 1 (the one copy every caller buffer gets), and from there on the batch IS the plain batch
+ *               of sum(counts) windows c3_predict_submit takes: same lanes, range guard (its re-run works from the staged image; either
+ *               policy), verify mode.  Rows are bit-identical to c3_predict on the concatenation, and so to c3_predict on each part alone
+ *   errors      before anything is queued, the slot left free: n_parts outside [1, C3_MAX_PARTS], null tables, a negative count, a null
+ *               buffer of a part with windows, a dtype the kind does not take, a busy slot
+ * parts, counts, y_parts and every parts[i] may be reused as soon as submit returns; c3_predict_wait(slot) writes every y_parts[i].
+ * c3_predict_parts = submit + wait on slot 0. */
+#define C3_MAX_PARTS 64
+int c3_predict_submit_parts(c3_model *m, const void *const *parts, const int64_t *counts, int n_parts, int x_dtype, float *const *y_parts,
+                            int slot);
+int c3_predict_parts(c3_model *m, const void *const *parts, const int64_t *counts, int n_parts, int x_dtype, float *const *y_parts);
 /* There is deliberately NO entry that page-locks caller memory.  Rounds 3-5 exported c3_host_register /
  * c3_host_unregister / c3_model_set_lock_sources (hipHostRegister on a whole np.load'ed tensor file or on libclair3's
  * fa_data.matrix buffer, preprocess/CreateTensorFullAlignmentFromCffi.py:136-168).  On ROCm 7.2 a process that registers and
