@@ -34,6 +34,7 @@ EXPORTS = (
     "c3_model_set_exact", "c3_predict_exact", "c3_exact_fetch",
     "c3_model_set_range_policy", "c3_range_policy_check", "c3_model_range_stats",
     "c3_predict_submit_parts", "c3_predict_parts",
+    "c3_model_set_score", "c3_score_submit", "c3_score_wait", "c3_score", "c3_score_rows",
 )
 MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
@@ -84,6 +85,12 @@ class RangeStats(C.Structure):
     _fields_ = [("trips", C.c_int64), ("recalibrations", C.c_int64), ("reruns", C.c_int64), ("census_windows", C.c_int64),
                 ("channels_lowered", C.c_int32), ("cap_log2", C.c_int32), ("policy", C.c_int32), ("max_recalibrations", C.c_int32),
                 ("fell_back", C.c_int32), ("reason", C.c_char * 96)]
+
+
+class ScoreResult(C.Structure):
+    """c3_score_result (include/c3hip.h)"""
+    _fields_ = [("windows", C.c_int64), ("tasks", C.c_int32), ("reserved", C.c_int32), ("loss_sum", C.c_double * 4),
+                ("correct", C.c_int64 * 4), ("nonfinite", C.c_int64)]
 
 
 class C3Error(RuntimeError):
@@ -202,6 +209,11 @@ def lib():
     L.c3_model_set_range_policy.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.c3_range_policy_check.argtypes = [C.c_char_p]
     L.c3_model_range_stats.argtypes = [C.c_void_p, C.POINTER(RangeStats)]
+    L.c3_model_set_score.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    L.c3_score_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.c3_score_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(ScoreResult)]
+    L.c3_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ScoreResult)]
+    L.c3_score_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.POINTER(ScoreResult), C.c_void_p]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

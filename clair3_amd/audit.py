@@ -9,6 +9,10 @@ against the EXACT rows: ``windows``, ``max_abs_err`` overall and per head (``hea
 ``worst_window``, ``rows_over_tol``, the arg-max differences per head outside near-ties (``label_diffs``; a near-tie is an exact top-2 gap
 <= near_tie), the excused ones (``near_ties``), and ``seconds`` / ``windows_per_s`` of the form's pass.  ``precision`` is what the handle
 reports behind the pass (a form that met the range guard continues on fp32 and says so here), ``fp32_layers`` the plan in force.
+With ``--label_fn L.npy`` (labels (N, 24|90) in the row's column layout, one-hot or soft) every line also carries what the form costs in
+the unit the checkpoint was trained in: ``loss`` (the reference's validation loss, clair3/Train.py:87-107 and :236-240: the sum over the
+tasks of the mean focal loss), ``task_loss`` and ``accuracy`` per task and ``nonfinite`` -- the forms' float32 rows scored on the device
+(score mode, c3_score_rows), the exact form's double rows by the same rule in numpy (synthetic.focal_scores).
 """
 import json
 import sys
@@ -70,6 +74,8 @@ def parse_args(argv=None):
     ap.add_argument("--plans", default="", help="per-layer precision plans to audit besides none and all: plans separated by ';', layers by ','")
     ap.add_argument("--tol", type=float, default=1e-4, help="a row is over tol when one probability is further from the exact one (default 1e-4)")
     ap.add_argument("--near_tie", type=float, default=1e-6, help="an arg-max difference is excused when the exact top-2 gap is at most this (default 1e-6)")
+    ap.add_argument("--label_fn", default=None, help="labels of the windows (.npy, (N, 24|90)): every line also carries loss and accuracy")
+    ap.add_argument("--gamma", type=float, default=2.0, help="the focal loss's gamma (default 2, the reference's)")
     ap.add_argument("--max_windows", type=int, default=None, help="use the first n windows (default: all)")
     ap.add_argument("--platform", default="ont")
     ap.add_argument("--enable_dwell_time", action="store_true")
@@ -85,7 +91,19 @@ def parse_args(argv=None):
     return args
 
 
-def audit(model, x, plans=(), tol=1e-4, near_tie=1e-6, rows_out=None):
+def score_fields(model, y, labels, gamma=2.0):
+    """loss, task_loss, accuracy and nonfinite of a form's rows: float32 rows on the device, double rows by the numpy rule"""
+    from . import synthetic as syn
+    if np.asarray(y).dtype == np.float64:
+        r = syn.focal_scores(y, labels, gamma=gamma)
+        task = r["loss_sum"] / max(1, r["windows"])
+        return dict(loss=float(sum(float(v) for v in task)), task_loss=[float(v) for v in task],
+                    accuracy=[float(v) for v in r["correct"] / max(1, r["windows"])], nonfinite=int(r["nonfinite"]))
+    r = model.score_rows(y, labels, gamma=gamma, window_loss=False)
+    return dict(loss=float(r.loss), task_loss=[float(v) for v in r.task_loss], accuracy=[float(v) for v in r.accuracy], nonfinite=int(r.nonfinite))
+
+
+def audit(model, x, plans=(), tol=1e-4, near_tie=1e-6, rows_out=None, labels=None, gamma=2.0):
     """The lines of the tool for a model with the exact form enabled: a list of dicts, the exact form first.  ``rows_out``: a dict that
     receives every form's rows under the form's name.  The handle's precision plan is put back to what it was."""
     import re
@@ -111,6 +129,8 @@ def audit(model, x, plans=(), tol=1e-4, near_tie=1e-6, rows_out=None):
             layers = re.search(r"fp32_layers=(\S+)", model.describe())
             line.update(seconds=dt, windows_per_s=len(x) / dt if dt > 0 else 0.0, precision="fp64" if plan is None else prec.group(1) if prec else "?",
                         fp32_layers="" if plan is None or not layers else layers.group(1))
+            if labels is not None:
+                line.update(score_fields(model, y, labels, gamma))
             lines.append(line)
             if rows_out is not None:
                 rows_out[name] = y
@@ -142,7 +162,15 @@ def main(argv=None, rows_out=None):
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
     m.load_state_dict(sd)
     m.exact(True)
-    lines = audit(m, x, args.plan_list, args.tol, args.near_tie, rows_out)
+    labels = None
+    if args.label_fn:
+        labels = np.load(args.label_fn)
+        if args.max_windows is not None:
+            labels = labels[:args.max_windows]
+        if labels.ndim != 2 or labels.shape[0] != len(x) or labels.shape[1] < m.output_size:
+            raise _lib.C3Error(f"{args.label_fn}: labels {labels.shape} do not belong to {len(x)} windows of a model with {m.output_size} outputs")
+        labels = np.ascontiguousarray(labels[:, :m.output_size], dtype=np.int8 if labels.dtype.kind in "biu" else np.float32)
+    lines = audit(m, x, args.plan_list, args.tol, args.near_tie, rows_out, labels, args.gamma)
     text = "".join(json.dumps(line) + "\n" for line in lines)
     sys.stdout.write(text)
     if args.out:

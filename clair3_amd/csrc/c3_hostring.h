@@ -181,6 +181,10 @@ struct RingInput {
     const int64_t *counts = nullptr;
     float *const *y_parts = nullptr;
     int n_parts = 0;
+    bool score = false;  // a scored batch (c3_score_submit; Sliced only): labels (batch, nout) of label_dtype; y_host may be nullptr (the rows stay
+    const void *labels = nullptr;  // on the device), loss_host too (nobody asked for the windows' values)
+    int label_dtype = C3_DTYPE_I8;
+    float *loss_host = nullptr;
 };
 static RingInput ring_input(InKind kind, const void *x, int x_dtype, int64_t batch, float *y_host, const int32_t *depth = nullptr, float *y_dev = nullptr) {
     RingInput in;
@@ -241,13 +245,14 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
     if (cand) p.start_all.bytes = n * sizeof(int32_t), p.tiles.bytes = (size_t)((in.batch + kCompactTile - 1) / kCompactTile) * sizeof(uint32_t);
     p.starts.bytes = region ? n * sizeof(int32_t) : 0, p.depth.bytes = db;
     if (rows) p.rows_tab.bytes = n * sizeof(ExpandEntry);  // (a batch packed here may need less than this bound: fill_packed_rows)
+    if (in.score) p.labels.bytes = n * m->nout * (in.label_dtype == C3_DTYPE_F32 ? sizeof(float) : 1);
     size_t end = 0;
-    for (Section *s : {&p.image, &p.cand_pos, &p.depth_in, &p.chunks, &p.starts, &p.depth, &p.start_all, &p.tiles, &p.rows_tab})
+    for (Section *s : {&p.image, &p.cand_pos, &p.depth_in, &p.chunks, &p.starts, &p.depth, &p.start_all, &p.tiles, &p.rows_tab, &p.labels})
         s->off = al(end), end = s->off + s->bytes;
     // a candidate batch stages up to its chunk table: the arrays behind it are written by the selection kernels
     p.tail = rows ? p.rows_tab.off : p.cand_pos.off;
     p.staged = cand ? p.chunks.off + p.chunks.bytes
-               : rows ? end : (p.starts.bytes + p.depth.bytes ? p.depth.off + p.depth.bytes : p.image.bytes);
+               : rows || p.labels.bytes ? end : (p.starts.bytes + p.depth.bytes ? p.depth.off + p.depth.bytes : p.image.bytes);
     p.x_cap = cand ? end : p.staged;
     // ... and its statuses and the count of kept candidates leave behind the rows
     p.y.bytes = n * m->row * sizeof(float);
@@ -258,6 +263,11 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
     if (verify) p.verify.off = in.y_dev ? 0 : al(p.y_total), p.verify.bytes = kVerifyRecordBytes, p.y_total = p.verify.off + p.verify.bytes;
     // ... and its layer records (c3_model_set_verify_layers) behind that
     if (verify && layers) p.layers.off = p.y_total, p.layers.bytes = kLayerRecordsBytes, p.y_total = p.layers.off + p.layers.bytes;
+    // ... and a scored batch's record (c3_score.h) behind everything else, the windows' values behind the record when the caller wants them
+    if (in.score) {
+        p.score.off = al(p.y_total), p.score.bytes = kScoreRecordBytes, p.y_total = p.score.off + p.score.bytes;
+        if (in.loss_host) p.losses.off = p.y_total, p.losses.bytes = n * (size_t)m->nb * sizeof(float), p.y_total = p.losses.off + p.losses.bytes;
+    }
     return p;
 }
 
@@ -284,6 +294,10 @@ static void fill_region_image(const c3_model *m, const HostSlot &sl, const RingI
 static void fill_sliced(const HostSlot &sl, const RingInput &in, const StagedBatch &p, const int32_t *depth, Filled &f) {
     if (depth) memcpy(sl.pin<char>(p.depth), depth, p.depth.bytes);
     f.src = in.x;
+}
+// a scored batch: its labels behind whatever else it stages
+static void fill_labels(const HostSlot &sl, const RingInput &in, const StagedBatch &p) {
+    if (p.labels.bytes) memcpy(sl.pin<char>(p.labels), in.labels, p.labels.bytes);
 }
 // parts: each caller buffer gets the one copy every caller buffer gets, part i behind part i - 1 in the image section
 static void fill_parts(const HostSlot &sl, const RingInput &in, const StagedBatch &p, size_t window_bytes, Filled &f) {
@@ -538,6 +552,46 @@ static void verify_layers_account(c3_model *m, const HostSlot &sl) {
     }
 }
 
+// ---- score mode (c3_score.h): the two launches on stream s over `rows` (row stride m->row) and the labels staged with the batch; the record
+// -- and the windows' values when the plan has room for them -- land in the slot's output buffer
+static int score_launch(c3_model *m, hipStream_t s, const float *rows, int stride, const void *labels, int label_dtype, int64_t batch, float *loss,
+                        uint64_t *part, ScoreRecord *out) {
+    ScoreParams sp;
+    sp.rows = rows, sp.labels = labels, sp.loss = loss, sp.part = part, sp.gamma = m->score_gamma;
+    sp.stride = stride, sp.nout = m->nout, sp.tasks = m->nb, sp.batch = (int)batch;
+    sp.label_f32 = label_dtype == C3_DTYPE_F32, sp.weighted = m->score_weighted;
+    memcpy(sp.w, m->score_w, sizeof(sp.w));
+    const int blocks = score_blocks(batch);
+    ProfScope ps(m, s, m->kind == C3_KIND_PILEUP ? "p.score" : "fa.score", 0.0, (double)batch * m->nout * (4.0 + (sp.label_f32 ? 4.0 : 1.0)));
+    hipLaunchKernelGGL(rows_score_kernel, dim3((unsigned)blocks), dim3(kScoreThreads), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rows_score_final_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)part, blocks, (int)batch, m->nb, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int run_score(c3_model *m, hipStream_t s, HostSlot &sl, const StagedBatch &p, int label_dtype, int64_t batch, const float *rows) {
+    if (!sl.score_part) HIP_TRY(hipMalloc((void **)&sl.score_part, kScorePartBytes));
+    return score_launch(m, s, rows, m->row, sl.dev<const char>(p.labels), label_dtype, batch, p.losses.bytes ? (float *)((char *)sl.dev_y + p.losses.off) : nullptr,
+                        sl.score_part, (ScoreRecord *)((char *)sl.dev_y + p.score.off));
+}
+// c3_predict_wait's reader of a scored batch: the record out of the pinned output buffer, the windows' values to where the caller wants them
+static void read_score(HostSlot &sl) {
+    const StagedBatch &p = sl.plan;
+    memcpy(&sl.score_rec, (const char *)sl.pin_y + p.score.off, sizeof(ScoreRecord));
+    if (sl.loss_host && p.losses.bytes) memcpy(sl.loss_host, (const char *)sl.pin_y + p.losses.off, p.losses.bytes);
+}
+// c3_predict_wait, a scored batch that another pass answered in the end (the range guard's re-run under either policy, verify mode's
+// escalation): scored again on the rows it is answered with, from the labels still staged; the record and the values come over again
+static int rescore(c3_model *m, HostSlot &sl, const float *rows) {
+    const StagedBatch &p = sl.plan;
+    TRY(use_lane(m, sl.lane));
+    hipStream_t s = lane(m).stream;
+    TRY(run_score(m, s, sl, p, sl.label_dtype, sl.batch, rows));
+    HIP_TRY(hipMemcpyAsync((char *)sl.pin_y + p.score.off, (const char *)sl.dev_y + p.score.off, p.y_total - p.score.off, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---- launch, on the active lane's stream: the selection in front of a candidate batch, the forward pass, the rows on their way out
 static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p) {
     hipStream_t s = lane(m).stream;
@@ -563,12 +617,21 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
     TRY(rc_product);
     if (in.y_dev && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, in.y_dev, in.batch * m->row, m->range_flag);
+    const bool rows_home = in.score && !in.y_host;  // (a scored batch whose caller wants no rows: scanned here like rows that stay on the device)
+    if (rows_home && f16)
+        hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, sl.dev_y, in.batch * m->row, m->range_flag);
     if (p.verify.bytes) TRY(shadow_pass(m, sl, in, p));
+    if (p.score.bytes) TRY(run_score(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
     // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
     // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
-    hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                       in.y_dev ? (p.verify.bytes + p.layers.bytes) / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+    if (rows_home) {  // only the records (a verified batch: from its verify record on) and the windows' values leave
+        const size_t from = p.verify.bytes ? p.verify.off : p.score.off;
+        hipLaunchKernelGGL(host_copy_kernel, dim3(rows_out_grid(p.y_total - from)), dim3(256), 0, s, (const uint4 *)((const char *)sl.dev_y + from),
+                           (uint4 *)((char *)sl.pin_y + from), (p.y_total - from + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+    } else
+        hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
+                           in.y_dev ? (p.verify.bytes + p.layers.bytes) / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_out, s));
     sl.used_f16 = f16;
@@ -585,15 +648,17 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
     sl.n_parts = in.kind == InKind::Parts ? in.n_parts : 0;
     for (int i = 0; i < sl.n_parts; ++i) sl.part_count[i] = in.counts[i], sl.part_y[i] = in.y_parts[i];
     sl.pack_epoch = m->pack_epoch;
+    sl.scored = in.score, sl.rows_home = in.score && !in.y_host, sl.label_dtype = in.label_dtype, sl.loss_host = in.loss_host;
+    sl.score_rec = ScoreRecord{}, sl.score_rec.tasks = m->nb;  // (a batch of no windows: what c3_score_wait reports)
     sl.busy = true;
 }
 
 static int predict_submit(c3_model *m, RingInput in, int slot) {
     TRY(ring_ready(m, slot));
     if (in.batch < 0) return fail("negative batch");
-    if (in.kind != InKind::Parts && in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev))) return fail("null buffer");  // (parts: checked one by one at the entry)
+    if (in.kind != InKind::Parts && in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev && !in.score))) return fail("null buffer");  // (parts: checked one by one at the entry)
     HIP_TRY(hipSetDevice(m->device));
-    if (in.kind == InKind::Sliced && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && in.x_dtype == C3_DTYPE_I8) in.kind = InKind::PackedHere;
+    if (in.kind == InKind::Sliced && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && in.x_dtype == C3_DTYPE_I8 && !in.score) in.kind = InKind::PackedHere;  // (a scored batch stays sliced)
     HostSlot &sl = m->slot[slot];
     // A small batch runs in the next lane (c3_model.h Lane): its own workspace and kernel stream, so that it overlaps the batches before it
     // on the chip; keep mode and profiling stay in one lane -- and so does a batch that fills the chip by itself: two of those side by side
@@ -613,7 +678,7 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
         TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes + p.layers.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
         switch (in.kind) {
-        case InKind::Sliced: fill_sliced(sl, in, p, depth, f); break;
+        case InKind::Sliced: fill_sliced(sl, in, p, depth, f), fill_labels(sl, in, p); break;
         case InKind::Region: fill_region(m, sl, in, p, depth, f); break;
         case InKind::Candidates: fill_candidates(m, sl, in, p, depth, f); break;
         case InKind::Rows: fill_rows(m, sl, in, p, f); break;
@@ -670,7 +735,7 @@ static bool range_recalibrates(const c3_model *m) {
 // what c3_predict_wait reads of a batch the fp16x3 kernels computed: its copy of the range flag, and its rows where they came to this host
 static bool slot_out_of_range(const HostSlot &sl) {
     bool bad = *sl.pin_flag != 0;  // a conv stage produced a value near the fp16 range (kF16Range), or the device scan found a non-finite row
-    if (!sl.y_dev_out) {
+    if (!sl.y_dev_out && !sl.rows_home) {
         const uint32_t *u = reinterpret_cast<const uint32_t *>(sl.pin_y);
         for (size_t i = 0, n = sl.plan.y.bytes / 4; i < n; ++i) bad |= (u[i] & 0x7f800000u) == 0x7f800000u;
     }
@@ -689,7 +754,7 @@ static int range_guard_stale_rerun(c3_model *m, HostSlot &sl, bool *bad) {
                                   sl.dev<const ExpandEntry>(p.rows_tab));
     m->tap_call_off = 0;
     TRY(rc);
-    if (sl.y_dev_out) {
+    if (sl.y_dev_out || sl.rows_home) {
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((sl.batch * m->row + 255) / 256)), dim3(256), 0, s, y, sl.batch * m->row, m->range_flag);
         HIP_TRY(hipGetLastError());
     } else HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, s));
@@ -727,18 +792,25 @@ int c3_predict_wait(c3_model *m, int slot) {
         const auto rerun = range_recalibrates(m) ? range_guard_recalibrate : range_guard_rerun;
         TRY(rerun(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sl.tap_off,
                   sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
-        if (!sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
+        if (!sl.y_dev_out && !sl.rows_home) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
         HIP_TRY(hipStreamSynchronize(lane(m).stream));
     }
+    const float *answered = guarded ? sl.dev_y : nullptr;  // a scored batch: the rows of the pass that answers it, where another pass than the first does
     if (sl.verified) {  // the range guard keeps priority: a batch it answered counts as skipped
         if (!guarded) verify_layers_account(m, sl);
         if (guarded) ++m->vstats.batches_skipped;
         else if (verify_account(m, sl)) {  // escalate: the batch is answered with its rows on the fp32 forms, decoder columns included
             TRY(use_lane(m, sl.lane));
             if (sl.y_dev_out) HIP_TRY(hipMemcpyAsync(sl.y_dev_out, sl.shadow, p.y.bytes, hipMemcpyDeviceToDevice, lane(m).stream));
-            else HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.shadow, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
+            else if (!sl.rows_home) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.shadow, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
             HIP_TRY(hipStreamSynchronize(lane(m).stream));
+            answered = sl.shadow;
         }
+    }
+    if (sl.scored) {  // the record and the windows' values, of the rows the batch is answered with
+        if (answered) TRY(rescore(m, sl, answered));
+        read_score(sl);
+        if (sl.rows_home) return 0;
     }
     if (sl.y_dev_out) return 0;
     if (sl.cand) {  // rows [0, kept) are the result; the rest belong to the surplus windows of dropped candidates
@@ -1160,6 +1232,123 @@ int c3_decode_columns(c3_model *m, const float *y_host, int64_t batch, float *ro
     hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, lane(m).stream, dp);
     HIP_TRY(hipGetLastError());
     TRY(d2h_staged(rows_host, rows, total, lane(m).stream));
+    return 0;
+}
+
+// ---- score mode (c3_score.h): the setting and the entries ----
+int c3_model_set_score(c3_model *m, int enable, float gamma, const float *class_weights) {
+    if (!m) return fail("null model");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (!enable) {
+        m->score_on = false;
+        return 0;
+    }
+    if (!(gamma >= 0.f) || !std::isfinite(gamma)) return fail("gamma must be a finite number >= 0, got %g", (double)gamma);
+    for (int c = 0; class_weights && c < m->nout; ++c)
+        if (!std::isfinite(class_weights[c])) return fail("class weight %d is not finite (%g)", c, (double)class_weights[c]);
+    m->score_on = true, m->score_gamma = (double)gamma, m->score_weighted = class_weights != nullptr;
+    for (int c = 0; c < kScoreMaxCols; ++c) m->score_w[c] = class_weights && c < m->nout ? class_weights[c] : 1.f;
+    return 0;
+}
+// what every score entry refuses first
+static int score_args_ok(const c3_model *m, int label_dtype, int64_t batch, const char *who) {
+    if (!m) return fail("null model");
+    if (!m->score_on) return fail("%s: score mode is off for this handle: call c3_model_set_score first", who);
+    if (label_dtype != C3_DTYPE_I8 && label_dtype != C3_DTYPE_F32) return fail("%s: labels must be int8 or float32 (got dtype %d)", who, label_dtype);
+    if (batch < 0) return fail("negative batch");
+    if (batch > ((int64_t)1 << 30)) return fail("%s: too many windows for one call (%lld)", who, (long long)batch);
+    return 0;
+}
+static void score_result(const c3_model *m, const ScoreRecord &r, c3_score_result *out) {
+    *out = c3_score_result{};
+    out->windows = r.windows, out->tasks = m->nb, out->nonfinite = r.nonfinite;
+    for (int k = 0; k < 4; ++k) out->loss_sum[k] = r.loss_sum[k], out->correct[k] = r.correct[k];
+}
+int c3_score_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const void *labels_host, int label_dtype, float *y_host,
+                    float *loss_host, int slot) {
+    TRY(score_args_ok(m, label_dtype, batch, "c3_score_submit"));
+    if (batch > 0 && !labels_host) return fail("null buffer: labels");
+    RingInput in = ring_input(InKind::Sliced, x_host, x_dtype, batch, y_host);
+    in.score = true, in.labels = labels_host, in.label_dtype = label_dtype, in.loss_host = loss_host;
+    return predict_submit(m, in, slot);
+}
+int c3_score_wait(c3_model *m, int slot, c3_score_result *out) {
+    TRY(ring_ready(m, slot, false));
+    if (!out) return fail("null argument: out");
+    HostSlot &sl = m->slot[slot];
+    if (!sl.busy) return fail("slot %d has nothing in flight", slot);
+    if (!sl.scored) return fail("slot %d holds a batch that is not scored: c3_predict_wait completes it", slot);
+    TRY(c3_predict_wait(m, slot));
+    score_result(m, sl.score_rec, out);
+    return 0;
+}
+// blocking: a batch of two chunks or more (predict_chunk) travels as chunks through three slots of the ring; the chunks' records are added up
+// here in chunk order (the sums of a batch therefore depend on the cut at the level of double rounding, the windows' values do not)
+int c3_score(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const void *labels_host, int label_dtype, float *y_host, float *loss_host,
+             c3_score_result *out) {
+    TRY(score_args_ok(m, label_dtype, batch, "c3_score"));
+    if (!out) return fail("null argument: out");
+    const int64_t chunk = predict_chunk(m);
+    if (chunk <= 0 || batch < 2 * chunk) {
+        TRY(c3_score_submit(m, x_host, x_dtype, batch, labels_host, label_dtype, y_host, loss_host, 0));
+        return c3_score_wait(m, 0, out);
+    }
+    constexpr int kRing = 3;
+    const int64_t wbytes = c3_model_window_bytes(m, x_dtype), lbytes = (int64_t)m->nout * (label_dtype == C3_DTYPE_F32 ? 4 : 1);
+    c3_score_result total = c3_score_result{}, one;
+    total.tasks = m->nb;
+    auto add = [&](const c3_score_result &r) {
+        total.windows += r.windows, total.nonfinite += r.nonfinite;
+        for (int k = 0; k < 4; ++k) total.loss_sum[k] += r.loss_sum[k], total.correct[k] += r.correct[k];
+    };
+    int64_t n_sub = 0, n_done = 0;
+    int rc = 0;
+    for (int64_t off = 0; off < batch && rc == 0; ++n_sub) {
+        const int64_t take = batch - off < 2 * chunk ? batch - off : chunk;  // (a tail shorter than a chunk joins the last one)
+        if (n_sub - n_done == kRing && (rc = c3_score_wait(m, (int)(n_done++ % kRing), &one)) == 0) add(one);
+        if (rc == 0)
+            rc = c3_score_submit(m, (const char *)x_host + off * wbytes, x_dtype, take, (const char *)labels_host + off * lbytes, label_dtype,
+                                 y_host ? y_host + off * m->row : nullptr, loss_host ? loss_host + off * m->nb : nullptr, (int)(n_sub % kRing));
+        if (rc != 0) break;
+        off += take;
+    }
+    const std::string first_error = rc != 0 ? g_err : std::string();
+    for (; n_done < n_sub; ++n_done) {  // drain, also after an error: no slot stays busy behind a failed call
+        const int r = c3_score_wait(m, (int)(n_done % kRing), &one);
+        if (r == 0 && rc == 0) add(one);
+        if (rc == 0) rc = r;
+    }
+    if (!first_error.empty()) g_err = first_error;
+    if (rc == 0) *out = total;
+    return rc;
+}
+// given probability rows (the reference's, the exact form's rounded, adversarial ones) without a forward pass: rows, labels, partials,
+// record and values in the handle's decoder scratch, the two launches in the first lane
+int c3_score_rows(c3_model *m, const float *rows_host, int row_floats, int64_t batch, const void *labels_host, int label_dtype, c3_score_result *out,
+                  float *loss_host) {
+    TRY(score_args_ok(m, label_dtype, batch, "c3_score_rows"));
+    if (!out) return fail("null argument: out");
+    if (row_floats < m->nout) return fail("c3_score_rows: rows of %d floats are shorter than the %d probabilities of this model", row_floats, m->nout);
+    ScoreRecord rec = ScoreRecord{};
+    if (batch == 0) return score_result(m, rec, out), 0;
+    if (!rows_host || !labels_host) return fail("null buffer: rows / labels");
+    HIP_TRY(hipSetDevice(m->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t yb = (size_t)batch * row_floats * sizeof(float), lb = (size_t)batch * m->nout * (label_dtype == C3_DTYPE_F32 ? 4 : 1);
+    const size_t vb = (size_t)batch * m->nb * sizeof(float);
+    const size_t l_at = al(yb), p_at = al(l_at + lb), r_at = p_at + kScorePartBytes, v_at = r_at + kScoreRecordBytes;
+    TRY(ensure_decode_buf(m, v_at + vb));
+    TRY(use_lane(m, 0));
+    hipStream_t s = lane(m).stream;
+    char *base = (char *)m->decode_dev;
+    TRY(h2d_staged(base, rows_host, yb, s));
+    TRY(h2d_staged(base + l_at, labels_host, lb, s));
+    TRY(score_launch(m, s, (const float *)base, row_floats, base + l_at, label_dtype, batch, (float *)(base + v_at), (uint64_t *)(base + p_at),
+                     (ScoreRecord *)(base + r_at)));
+    TRY(d2h_staged(&rec, base + r_at, sizeof(rec), s));
+    if (loss_host) TRY(d2h_staged(loss_host, base + v_at, vb, s));
+    score_result(m, rec, out);
     return 0;
 }
 

@@ -15,6 +15,8 @@
 //   c3_verify.h    verify mode's two compare kernels and their record (included with the other kernels below): a selected batch of the ring
 //                  runs a second forward pass on the fp32 forms from the same staged input (c3_hostring.h shadow_pass) and the two sets of
 //                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
+//   c3_score.h     score mode's two kernels and their record: the focal loss and arg-max accuracy of a labelled batch on the rows that answer
+//                  it (c3_hostring.h run_score; the entries c3_score_submit / _wait, c3_score, c3_score_rows sit at the end of that file)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries;
 //                  the packing part of a full-alignment load (fa_pack_weights) and, on it, the range guard's policy C3_RANGE_RECALIBRATE: a trip
@@ -60,6 +62,7 @@
 #include "c3_l4.h"
 #include "c3_dense.h"
 #include "c3_verify.h"
+#include "c3_score.h"
 
 using namespace c3;
 
@@ -159,6 +162,7 @@ struct StagedBatch {
     Section tiles;      // candidates: the compaction tiles' counts
     Section rows_tab;   // a rows batch: one ExpandEntry per window.  A batch packed here (C3HIP_PACK_ROWS=1) by ONE range moves it, `tail`
                         // and `staged` down behind the rows it found (fill_packed_rows) -- the only values settled after the plan
+    Section labels;     // a scored batch (c3_score.h): its labels (batch, nout), int8 or float32 -- the last section a scored batch stages
     size_t tail = 0;    // [tail, staged): what is staged behind the image
     size_t staged = 0;  // bytes of the input buffer that cross PCIe
     size_t x_cap = 0;   // bytes the slot's input buffers must hold
@@ -168,6 +172,8 @@ struct StagedBatch {
     Section kept;       // candidates: the count of kept candidates (16 bytes from a multiple of 16)
     Section verify;     // a verified batch (c3_verify.h): its VerifyRecord, behind the kept count (rows that stay on the device: the only section)
     Section layers;     // ... with layer records (c3_model_set_verify_layers): one LayerRecord per layer in network order, behind the verify record
+    Section score;      // a scored batch (c3_score.h): its ScoreRecord, behind everything above
+    Section losses;     // ... and the windows' values [batch][tasks] float32 behind the record, when the caller asked for them
     size_t y_total = 0;
 };
 
@@ -218,6 +224,13 @@ struct HostSlot {
     uint32_t layer_kept = 0, layer_planes = 0;  // of the batch in flight: tensors the product pass produced / as planes
     bool layer_dropped = false;               // ... a buffer for them could not be allocated: the batch brings no layer record
     int layer_parts[kTapCount] = {};          // ... and the partials written per tensor so far
+    // a scored batch (c3_score.h; c3_score_submit): the score kernel's partials are the slot's, allocated on first use.  rows_home: the caller
+    // wants no rows (y_host == NULL) -- they stay in dev_y, are scanned there for the range guard, and only the record and the windows' values leave
+    bool scored = false, rows_home = false;
+    int label_dtype = 0;
+    float *loss_host = nullptr;
+    uint64_t *score_part = nullptr;
+    ScoreRecord score_rec = {};  // of the batch c3_predict_wait completed last (c3_score_wait hands it over)
     // a section of the staged batch on the device / in the pinned input buffer (nullptr: the batch has none)
     template <class T> T *dev(const Section &s) const { return s.bytes ? (T *)((char *)dev_x + s.off) : nullptr; }
     template <class T> T *pin(const Section &s) const { return s.bytes ? (T *)((char *)pin_x + s.off) : nullptr; }
@@ -406,6 +419,12 @@ struct c3_model {
     HostSlot *layer_slot = nullptr;          // ... this slot's batch with layer records
     int64_t layer_batch = 0;                 // ... of this many windows
     const uint32_t *layer_kept_count = nullptr;  // ... a candidate batch: the device word with its kept count
+
+    // ---- score mode (c3_model_set_score, c3_score.h): off = nothing allocated, nothing launched ----
+    bool score_on = false;
+    double score_gamma = 2.0;
+    bool score_weighted = false;
+    float score_w[kScoreMaxCols] = {};  // class weights in the row's column layout
 
     // ---- calibration (c3_calibrate.h; full alignment): off = nothing allocated, nothing launched, a load packs what it packs without it ----
     int census_pass = 0;              // forward_device is enqueuing a census pass: tap() takes the channels' maxima instead of copying

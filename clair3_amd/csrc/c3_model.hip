@@ -13,7 +13,7 @@
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.4 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.5 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -433,6 +433,8 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
         if (m->verify_layers) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), ",layers:1");
     }
     if (m->exact.want) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " exact=1");  // only while the exact form is enabled (c3_exact.h)
+    if (m->score_on)  // only while score mode is enabled (c3_score.h)
+        snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " score=gamma:%g,weights:%d", m->score_gamma, (int)m->score_weighted);
     return 0;
 }
 
@@ -482,6 +484,7 @@ int c3_model_destroy(c3_model *m) {
         if (sl.dev_y) (void)hipFree(sl.dev_y);
         if (sl.shadow) (void)hipFree(sl.shadow);
         if (sl.layer_part) (void)hipFree(sl.layer_part);
+        if (sl.score_part) (void)hipFree(sl.score_part);
         for (float *p : sl.layer_buf)
             if (p) (void)hipFree(p);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);

@@ -6,6 +6,7 @@
 pass runs in hand-written HIP kernels (libc3hip.so) instead of ATen.  PyTorch is used only to read
 checkpoints and, optionally, to own device tensors handed to ``model(X)``.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -36,6 +37,25 @@ class _CandidateBatch:
         self.n_rows = C.c_int64(-1)
 
 
+_LABEL_DTYPE = {np.dtype(np.int8): _lib.DTYPE_I8, np.dtype(np.float32): _lib.DTYPE_F32}
+
+# what score() / wait_score() / score_rows() return: ``loss`` the sum over the tasks of the batch means (what the reference's validation pass
+# adds up per batch, clair3/Train.py:236-240), ``task_loss`` the batch mean per task, ``accuracy`` per task the share of windows whose arg-max
+# of p is the arg-max of y, ``windows``, ``nonfinite`` the windows that held a probability that is not finite; ``window_loss`` (B, tasks)
+# float32 and ``rows`` (B, row_size) float32 when asked for, else None; ``loss_sum`` / ``correct`` the record's own totals
+ScoreResult = collections.namedtuple("ScoreResult", "loss task_loss accuracy windows nonfinite window_loss rows loss_sum correct")
+
+
+def _score_result(rec, window_loss=None, rows=None):
+    t, n = rec.tasks, max(1, rec.windows)
+    loss_sum, correct = np.array(rec.loss_sum[:t], dtype=np.float64), np.array(rec.correct[:t], dtype=np.int64)
+    task_loss = loss_sum / n
+    total = 0.0
+    for v in task_loss:  # in task order
+        total += float(v)
+    return ScoreResult(total, task_loss, correct / n, int(rec.windows), int(rec.nonfinite), window_loss, rows, loss_sum, correct)
+
+
 class _HipModel:
     KIND = None
     DEFAULT_CHANNELS = None
@@ -58,6 +78,7 @@ class _HipModel:
         self._lowering = None   # calibration (set_calibration): the channel lowering a handle created anew takes along ...
         self._cal_meta = None   # ... and (cap_log2, windows) of the calibration it came from, for save_calibration
         self._exact = False     # the exact form (exact()): a handle created anew takes the setting along
+        self._score = None      # score mode (score_mode): (gamma, class weights or None) a handle created anew takes along
         self._range_policy = None  # the range-guard policy (range_policy): (policy, max_recalibrations) a handle created anew takes along
         self._recal_seen = 0       # recalibrations of the handle whose lowering self._lowering already mirrors (_sync_recalibration)
         self._calibration_file = None  # C3HIP_CALIBRATION of a model built without a checkpoint (predict.calibration_from_env): applied by the first load
@@ -103,6 +124,8 @@ class _HipModel:
                 _lib.check(_lib.lib().c3_model_set_calibration_origin(self._handle, *self._cal_meta), "c3_model_set_calibration_origin")
         if self._exact:
             _lib.check(_lib.lib().c3_model_set_exact(self._handle, 1), "c3_model_set_exact")
+        if self._score is not None:
+            self._set_score(*self._score)
         if self._range_policy is not None:  # (before the load: under "recalibrate" it keeps the tensors)
             _lib.check(_lib.lib().c3_model_set_range_policy(self._handle, *self._range_policy), "c3_model_set_range_policy")
         if sd is not None:
@@ -610,6 +633,96 @@ class _HipModel:
             raise _lib.C3Error(f"{path}: made for another checkpoint (its channel exponents k0 differ from the loaded checkpoint's)")
         self.set_calibration(f["lowering"], reload=True, cap_log2=f["cap_log2"], windows=f["windows"])
         return self
+
+    # ---- score mode: focal loss and accuracy of labelled windows on the device (c3_model_set_score) ----
+    def _set_score(self, gamma, weights):
+        _lib.check(_lib.lib().c3_model_set_score(self._handle, 1, gamma, None if weights is None else weights.ctypes.data), "c3_model_set_score")
+
+    def score_mode(self, gamma=2.0, class_weights=None, enable=True):
+        """Enable score mode with the reference's ``gamma`` and class weights (output_size floats in the row's column layout, e.g.
+        evaluate.class_weights; None = none).  score(), submit_score() and score_rows() set it themselves when their arguments differ from
+        what is in force; enable=False switches it off."""
+        self._need_handle()
+        if not enable:
+            _lib.check(_lib.lib().c3_model_set_score(self._handle, 0, 0.0, None), "c3_model_set_score")
+            self._score = None
+            return self
+        try:
+            gamma = float(gamma)
+        except (TypeError, ValueError) as e:
+            raise _lib.C3Error(f"gamma must be a number >= 0, got {gamma!r}") from e
+        w = None
+        if class_weights is not None:
+            w = np.ascontiguousarray(class_weights, dtype=np.float32)
+            if w.shape != (self.output_size,):
+                raise _lib.C3Error(f"class_weights must hold {self.output_size} entries, got shape {w.shape}")
+        self._set_score(gamma, w)
+        self._score = (gamma, w)
+        return self
+
+    def _score_setting(self, gamma, class_weights):
+        cur = self._score
+        same = cur is not None and cur[0] == float(gamma) and ((cur[1] is None) == (class_weights is None)) and \
+            (class_weights is None or np.array_equal(cur[1], np.asarray(class_weights, dtype=np.float32)))
+        if not same:
+            self.score_mode(gamma, class_weights)
+
+    def _labels(self, labels, n):
+        labels = np.ascontiguousarray(labels)
+        dt = _LABEL_DTYPE.get(labels.dtype)
+        if dt is None:
+            raise _lib.C3Error(f"unsupported label dtype {labels.dtype} (int8 / float32 expected)")
+        if labels.shape != (n, self.output_size):
+            raise _lib.C3Error(f"labels must be {(n, self.output_size)} in the row's column layout, got {labels.shape}")
+        return labels, dt
+
+    def submit_score(self, x, labels, slot=0, class_weights=None, gamma=2.0, window_loss=False, rows=False):
+        """Asynchronous half of score() (c3_score_submit); returns a ticket for wait_score()."""
+        self._need_handle()
+        self._score_setting(gamma, class_weights)
+        x, dt = self._window_batch(x)
+        labels, ldt = self._labels(labels, x.shape[0])
+        y = np.empty((x.shape[0], self.row_size), dtype=np.float32) if rows else None
+        wl = np.empty((x.shape[0], 4 if self.add_indel_length else 2), dtype=np.float32) if window_loss else None
+        _lib.check(_lib.lib().c3_score_submit(self._handle, x.ctypes.data, dt, x.shape[0], labels.ctypes.data, ldt,
+                                              None if y is None else y.ctypes.data, None if wl is None else wl.ctypes.data, slot), "c3_score_submit")
+        return slot, y, wl
+
+    def wait_score(self, ticket):
+        slot, y, wl = ticket
+        rec = _lib.ScoreResult()
+        _lib.check(_lib.lib().c3_score_wait(self._handle, slot, C.byref(rec)), "c3_score_wait")
+        return _score_result(rec, wl, y)
+
+    def score(self, x, labels, class_weights=None, gamma=2.0, window_loss=False, rows=False):
+        """The reference's validation loss of the labelled windows ``x`` (clair3/Train.py:87-107, :210-257): forward pass, focal loss per task,
+        arg-max accuracy, all on the device (c3_score; blocking).  labels: (B, output_size) int8 or float32 in the row's column layout.
+        Without rows=True the probabilities never leave the device.  Returns a ScoreResult."""
+        self._need_handle()
+        self._score_setting(gamma, class_weights)
+        x, dt = self._window_batch(x)
+        labels, ldt = self._labels(labels, x.shape[0])
+        y = np.empty((x.shape[0], self.row_size), dtype=np.float32) if rows else None
+        wl = np.empty((x.shape[0], 4 if self.add_indel_length else 2), dtype=np.float32) if window_loss else None
+        rec = _lib.ScoreResult()
+        _lib.check(_lib.lib().c3_score(self._handle, x.ctypes.data, dt, x.shape[0], labels.ctypes.data, ldt, None if y is None else y.ctypes.data,
+                                       None if wl is None else wl.ctypes.data, C.byref(rec)), "c3_score")
+        return _score_result(rec, wl, y)
+
+    def score_rows(self, rows, labels, class_weights=None, gamma=2.0, window_loss=True):
+        """score() of given float32 probability rows (B, >= output_size) without a forward pass (c3_score_rows): the reference's rows, the
+        exact form's rounded to float32, adversarial ones."""
+        self._need_handle()
+        self._score_setting(gamma, class_weights)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] < self.output_size:
+            raise _lib.C3Error(f"rows must be (B, >= {self.output_size}) float32, got {rows.shape}")
+        labels, ldt = self._labels(labels, rows.shape[0])
+        wl = np.empty((rows.shape[0], 4 if self.add_indel_length else 2), dtype=np.float32) if window_loss else None
+        rec = _lib.ScoreResult()
+        _lib.check(_lib.lib().c3_score_rows(self._handle, rows.ctypes.data, rows.shape[1], rows.shape[0], labels.ctypes.data, ldt, C.byref(rec),
+                                            None if wl is None else wl.ctypes.data), "c3_score_rows")
+        return _score_result(rec, wl, None)
 
     # ---- the exact form: the network in fp64 from end to end on the device (c3_predict_exact; DESIGN.md 4) ----
     def exact(self, enable=True):

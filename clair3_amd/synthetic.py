@@ -429,3 +429,62 @@ def make_windows(kind, batch, seed=0, recipe="realistic", channels=None):
     if kind == PILEUP:
         return make_pileup_windows(batch, seed, recipe, channels=channels or PILEUP_CHANNELS)
     return make_fa_windows(batch, seed, recipe, channels=channels or FA_CHANNELS)
+
+
+# ---- score mode in numpy: the rule of csrc/c3_score.h for callers without a GPU ----
+def head_slices(nout):
+    """the (lo, hi) column ranges of the tasks a row of ``nout`` probabilities holds"""
+    out, lo = [], 0
+    for n in HEAD_SIZES:
+        if lo >= nout:
+            break
+        out.append((lo, lo + n))
+        lo += n
+    return out
+
+
+def focal_scores(rows, labels, gamma=2.0, class_weights=None):
+    """The reference's focal loss (clair3/Train.py:87-107) and the arg-max accuracy of labelled rows, in float64 -- the rule the device
+    evaluates (c3_score_rows, Clair3_P/F.score).  rows: (B, >= nout) probabilities, float32 (clamped in float32 as the reference clamps them:
+    q = min(max(p, 1e-9f), 1.0f)) or float64 (the exact form's: clamped in double at the same two float32 constants); labels: (B, nout) in
+    the row's column layout, any numeric dtype, hard or soft; class_weights: nout floats or None.  Per window and task
+    L_t = sum_c w_c y_c (-ln q_c) (1 - q_c)^gamma y_c, one chain over the columns in ascending order.  Returns a dict: ``window_loss``
+    (B, tasks) float64, ``loss_sum`` (tasks,) their sums in window order, ``correct`` (tasks,) windows whose arg-max of p is the arg-max of y
+    (first maximum; a NaN is never one), ``nonfinite`` windows holding a probability that is not finite, ``windows``, ``tasks``."""
+    labels = np.asarray(labels)
+    nout = labels.shape[1]
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or labels.ndim != 2 or rows.shape[0] != labels.shape[0] or rows.shape[1] < nout or nout not in (24, 90):
+        raise ValueError(f"rows {rows.shape} and labels {labels.shape} do not belong together")
+    p = rows[:, :nout]
+    lo_c, hi_c = np.float32(1e-9), np.float32(1.0)
+    if p.dtype != np.float64:
+        p = p.astype(np.float32, copy=False)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.where(p < lo_c, lo_c, np.where(p > hi_c, hi_c, p)).astype(np.float64)  # (a NaN stays a NaN)
+        y = labels.astype(np.float64)
+        rest = 1.0 - q
+        terms = (-y * np.log(q)) * ((rest * rest if gamma == 2 else np.power(rest, float(gamma))) * y)
+        if class_weights is not None:
+            w = np.asarray(class_weights, dtype=np.float32).astype(np.float64)
+            if w.shape != (nout,):
+                raise ValueError(f"class_weights must hold {nout} entries, got shape {w.shape}")
+            terms = terms * w[None, :]
+    heads = head_slices(nout)
+    B = len(p)
+    window_loss = np.zeros((B, len(heads)), dtype=np.float64)
+    correct = np.zeros(len(heads), dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        for t, (lo, hi) in enumerate(heads):
+            acc = np.zeros(B, dtype=np.float64)
+            for c in range(lo, hi):  # one chain in column order
+                acc = acc + terms[:, c]
+            window_loss[:, t] = acc
+            pa = np.where(np.isnan(p[:, lo:hi]), -np.inf, p[:, lo:hi]).argmax(1) if B else np.zeros(0, np.int64)
+            ya = np.where(np.isnan(y[:, lo:hi]), -np.inf, y[:, lo:hi]).argmax(1) if B else np.zeros(0, np.int64)
+            correct[t] = int((pa == ya).sum())
+    loss_sum = np.zeros(len(heads), dtype=np.float64)
+    for b in range(B):  # in window order
+        loss_sum = loss_sum + window_loss[b]
+    return dict(window_loss=window_loss, loss_sum=loss_sum, correct=correct, nonfinite=int((~np.isfinite(p)).any(1).sum()) if B else 0,
+                windows=B, tasks=len(heads))

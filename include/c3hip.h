@@ -613,6 +613,43 @@ int c3_debug_tap(c3_model *m, const char *names);
  * fusing kernel, when the call's form produced no such tensor (act0 inside res1a, act8 inside res3b). */
 int c3_debug_tap_fetch(c3_model *m, const char *name, int64_t first, int64_t windows, float *host_out, int64_t n_floats);
 
+/* ---- score mode: focal loss and arg-max accuracy of labelled windows, evaluated on the device ----
+ * The reference's validation pass (clair3/Train.py:87-107 FocalLoss.forward, :210-257 _run_epoch with train=False) on the rows of a batch
+ * where they are.  Labels: (batch, c3_model_output_size()) in the row's own column layout [21|3|33|33], C3_DTYPE_I8 or C3_DTYPE_F32 (soft
+ * labels work).  Per window and task t: L_t = sum_c w_c * y_c * (-ln q_c) * (1 - q_c)^gamma * y_c with q = min(max(p, 1e-9f), 1.0f) --
+ * evaluated in double from the float32 probabilities, the window's value rounded once to float32, the unrounded values summed in a
+ * fixed order: the record of a batch is bit-identical across slots, lanes and runs.
+ *   c3_model_set_score  enable != 0: gamma >= 0 and class_weights (c3_model_output_size() floats in the row's column layout, or NULL = none)
+ *                       apply to every later score entry; enable == 0: off.  Never enabled: nothing is allocated or launched and
+ *                       c3_model_describe is what it was; enabled, it gains " score=gamma:<g>,weights:<0|1>".  Refused while a submit is pending.
+ *   c3_score_submit     c3_predict_submit of sliced windows plus their labels; y_host may be NULL (the rows then do not cross PCIe: only the
+ *                       record, and the windows' values if asked for, do), loss_host ([batch][tasks] floats) may be NULL.  The buffers
+ *                       x_host and labels_host may be reused when it returns.  Same ring, lanes and range guard as every batch: a batch the
+ *                       range guard re-runs (either policy) or verify mode escalates is scored again on the rows it is answered with.
+ *   c3_score_wait       completes it: c3_predict_wait plus the batch's record.  (c3_predict_wait alone also completes a scored batch.)
+ *   c3_score            blocking; a batch of two chunks (C3HIP_PREDICT_CHUNK) or more travels as chunks whose records are added in chunk order
+ *   c3_score_rows       scores given probability rows (row_floats >= c3_model_output_size() floats each; the first columns count) without a
+ *                       forward pass: the reference's rows, the exact form's, adversarial ones
+ * A window with a non-finite probability is not hidden: its values are reported as they come out (a NaN passes the clamp) and `nonfinite`
+ * counts it.  arg-max: the first maximum, the lowest index on ties, a NaN never.
+ * Errors: a handle without c3_model_set_score, a label dtype other than int8 / float32, gamma < 0 or not finite, a class weight that is not finite. */
+typedef struct {
+    int64_t windows;
+    int32_t tasks;       /* 2, or 4 with the indel-length heads */
+    int32_t reserved;
+    double loss_sum[4];  /* per task: sum over the windows of L_t (the batch mean is loss_sum[t] / windows) */
+    int64_t correct[4];  /* per task: windows whose arg-max of p equals the arg-max of y */
+    int64_t nonfinite;   /* windows with a probability that is not finite */
+} c3_score_result;
+int c3_model_set_score(c3_model *m, int enable, float gamma, const float *class_weights);
+int c3_score_submit(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const void *labels_host, int label_dtype, float *y_host,
+                    float *loss_host, int slot);
+int c3_score_wait(c3_model *m, int slot, c3_score_result *out);
+int c3_score(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const void *labels_host, int label_dtype, float *y_host, float *loss_host,
+             c3_score_result *out);
+int c3_score_rows(c3_model *m, const float *rows_host, int row_floats, int64_t batch, const void *labels_host, int label_dtype, c3_score_result *out,
+                  float *loss_host);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
