@@ -32,13 +32,18 @@ EXPORTS = (
     "c3_model_calibrate", "c3_model_calibrate_reset", "c3_model_calibration_census", "c3_model_calibration_solve",
     "c3_model_set_channel_lowering", "c3_model_set_calibration_origin", "c3_model_channel_exps", "c3_calibration_rule",
     "c3_model_set_exact", "c3_predict_exact", "c3_exact_fetch",
+    "c3_model_set_answer", "c3_model_set_verify_reference", "c3_model_verify_extra",
     "c3_model_set_range_policy", "c3_range_policy_check", "c3_model_range_stats",
     "c3_predict_submit_parts", "c3_predict_parts",
     "c3_model_set_score", "c3_score_submit", "c3_score_wait", "c3_score", "c3_score_rows",
 )
 MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
-VERIFY_REPORT, VERIFY_ESCALATE = 0, 1
+VERIFY_REPORT, VERIFY_ESCALATE, VERIFY_REPLACE = 0, 1, 2
+VERIFY_POLICY = {VERIFY_REPORT: "report", VERIFY_ESCALATE: "escalate", VERIFY_REPLACE: "replace"}
+# what verify mode compares with (C3_VERIFY_REF_*) and what answers a batch of the ring (C3_ANSWER_*)
+VERIFY_REF = {"fp32": 0, "exact": 1}
+ANSWER = {"product": 0, "exact": 1}
 # policy of the range guard (C3_RANGE_* in include/c3hip.h)
 RANGE_STICKY, RANGE_RECALIBRATE = 0, 1
 # status of a layer of verify mode's layer records (C3_VERIFY_LAYER_* in include/c3hip.h)
@@ -71,6 +76,12 @@ class VerifyStats(C.Structure):
                 ("label_diffs", C.c_int64 * 4), ("near_ties", C.c_int64 * 4), ("escalations", C.c_int64),
                 ("max_abs_diff", C.c_float), ("head_max_abs_diff", C.c_float * 4), ("tol", C.c_float), ("near_tie", C.c_float),
                 ("every", C.c_int32), ("policy", C.c_int32)]
+
+
+class VerifyExtra(C.Structure):
+    """c3_verify_extra (include/c3hip.h)"""
+    _fields_ = [("reference", C.c_int32), ("reserved", C.c_int32), ("rows_replaced", C.c_int64), ("batches_with_replacements", C.c_int64),
+                ("max_abs_diff_f64", C.c_double)]
 
 
 class VerifyLayer(C.Structure):
@@ -206,6 +217,9 @@ def lib():
     L.c3_model_set_exact.argtypes = [C.c_void_p, C.c_int]
     L.c3_predict_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
     L.c3_exact_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    L.c3_model_set_answer.argtypes = [C.c_void_p, C.c_int]
+    L.c3_model_set_verify_reference.argtypes = [C.c_void_p, C.c_int]
+    L.c3_model_verify_extra.argtypes = [C.c_void_p, C.POINTER(VerifyExtra)]
     L.c3_model_set_range_policy.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.c3_range_policy_check.argtypes = [C.c_char_p]
     L.c3_model_range_stats.argtypes = [C.c_void_p, C.POINTER(RangeStats)]

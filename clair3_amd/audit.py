@@ -13,6 +13,11 @@ With ``--label_fn L.npy`` (labels (N, 24|90) in the row's column layout, one-hot
 the unit the checkpoint was trained in: ``loss`` (the reference's validation loss, clair3/Train.py:87-107 and :236-240: the sum over the
 tasks of the mean focal loss), ``task_loss`` and ``accuracy`` per task and ``nonfinite`` -- the forms' float32 rows scored on the device
 (score mode, c3_score_rows), the exact form's double rows by the same rule in numpy (synthetic.focal_scores).
+With ``--on-ring`` the same table is measured where a job runs: every form's rows travel through the submit / wait ring with verify mode
+on every batch and the exact form as its reference (model.verify(reference="exact")), and the line is what the DEVICE compared --
+``max_abs_err`` the double maximum (verify_extra), the per-head maxima its float32 roundings, ``worst_batch`` / ``worst_row`` instead of
+``worst_window``, ``batches_checked`` / ``batches_skipped``; ``seconds`` then include the exact pass.  The rows are the same rows, so
+``max_abs_err``, ``rows_over_tol``, ``label_diffs`` and ``near_ties`` are those of the table without it.
 """
 import json
 import sys
@@ -80,6 +85,8 @@ def parse_args(argv=None):
     ap.add_argument("--platform", default="ont")
     ap.add_argument("--enable_dwell_time", action="store_true")
     ap.add_argument("--out", default=None, help="write the lines here as well")
+    ap.add_argument("--on-ring", dest="on_ring", action="store_true",
+                    help="measure through the submit / wait ring with verify mode against the exact form (the device's comparison)")
     args = ap.parse_args(argv)
     if not args.tol > 0 or not np.isfinite(args.tol):
         raise _lib.C3Error(f"--tol must be > 0, got {args.tol}")
@@ -139,6 +146,43 @@ def audit(model, x, plans=(), tol=1e-4, near_tie=1e-6, rows_out=None, labels=Non
     return lines
 
 
+def audit_on_ring(model, x, plans=(), tol=1e-4, near_tie=1e-6, rows_out=None):
+    """The lines of ``--on-ring`` for a model with the exact form enabled: one dict per form (none, all, the plans), taken from the totals of
+    verify mode with the exact form as its reference after one predict_numpy of the sample.  Verify mode, its reference and the precision
+    plan are put back to what they were."""
+    import re
+    before, verify, ref, with_layers = ",".join(model.layer_precision()), model._verify, model._verify_ref, model._verify_layers
+    heads = 4 if model.output_size == 90 else 2
+    lines = []
+    try:
+        for name, plan in [("none", ""), ("all", "all")] + [(p, p) for p in plans]:
+            model.layer_precision(plan)
+            model.verify(every=1, tol=tol, near_tie=near_tie, reference="exact")
+            model.predict_numpy(x)  # (the first call of a form pays its workspace and its kernels' load)
+            model.verify_reset()
+            t0 = time.perf_counter()
+            y = model.predict_numpy(x)
+            dt = time.perf_counter() - t0
+            st, ex = model.verify_stats(), model.verify_extra()
+            prec = re.search(r"precision=(\S+)", model.describe())
+            layers = re.search(r"fp32_layers=(\S+)", model.describe())
+            lines.append(dict(form=name, on_ring=True, windows=int(st["windows_checked"]), tol=float(st["tol"]), near_tie=float(st["near_tie"]),
+                              max_abs_err=ex["max_abs_diff_f64"], worst_batch=int(st["worst_batch"]), worst_row=int(st["worst_row"]),
+                              rows_over_tol=int(st["rows_over_tol"]), head_max_abs_err=[float(v) for v in st["head_max_abs_diff"][:heads]],
+                              label_diffs=[int(v) for v in st["label_diffs"][:heads]], near_ties=[int(v) for v in st["near_ties"][:heads]],
+                              batches_checked=int(st["batches_checked"]), batches_skipped=int(st["batches_skipped"]), seconds=dt,
+                              windows_per_s=len(x) / dt if dt > 0 else 0.0, precision=prec.group(1) if prec else "?",
+                              fp32_layers=layers.group(1) if layers else ""))
+            if rows_out is not None:
+                rows_out[name] = y
+    finally:
+        model.layer_precision(before)
+        every, vtol, vtie, policy = verify if verify is not None else (0, 1e-4, 1e-6, _lib.VERIFY_REPORT)
+        model.verify(every=every, tol=vtol, near_tie=vtie, escalate=policy == _lib.VERIFY_ESCALATE, replace=policy == _lib.VERIFY_REPLACE,
+                     layers=with_layers, reference=ref)
+    return lines
+
+
 def main(argv=None, rows_out=None):
     args = parse_args(argv)  # (a bad plan name is refused here, before any device call)
     import os
@@ -170,7 +214,10 @@ def main(argv=None, rows_out=None):
         if labels.ndim != 2 or labels.shape[0] != len(x) or labels.shape[1] < m.output_size:
             raise _lib.C3Error(f"{args.label_fn}: labels {labels.shape} do not belong to {len(x)} windows of a model with {m.output_size} outputs")
         labels = np.ascontiguousarray(labels[:, :m.output_size], dtype=np.int8 if labels.dtype.kind in "biu" else np.float32)
-    lines = audit(m, x, args.plan_list, args.tol, args.near_tie, rows_out, labels, args.gamma)
+    if args.on_ring:
+        lines = audit_on_ring(m, x, args.plan_list, args.tol, args.near_tie, rows_out)
+    else:
+        lines = audit(m, x, args.plan_list, args.tol, args.near_tie, rows_out, labels, args.gamma)
     text = "".join(json.dumps(line) + "\n" for line in lines)
     sys.stdout.write(text)
     if args.out:

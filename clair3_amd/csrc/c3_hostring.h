@@ -416,6 +416,14 @@ static int queue_input(c3_model *m, const HostSlot &sl, const StagedBatch &p, co
     return 0;
 }
 
+// ---- the exact form on the ring (c3_exact.h, included behind this file): the pass that answers a batch of an exact-answer handle, verify
+// mode's second pass against the exact rows, and the repair of C3_VERIFY_REPLACE
+static int exact_ring_pass(c3_model *m, hipStream_t s, HostSlot &sl, const StagedBatch &p, int x_dtype, int64_t batch, float *y, double *keep64, bool layers);
+static int exact_shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, const StagedBatch &p);
+static int verify_replace_launch(c3_model *m, hipStream_t s, HostSlot &sl, const RingInput &in, const StagedBatch &p, const double *ref64);
+// the depths the product and fp32 forms see of a staged batch: none where they were staged for the exact form's gather only (StagedBatch::gather_only)
+static const int32_t *ring_depth(const HostSlot &sl, const StagedBatch &p) { return p.gather_only ? nullptr : sl.dev<const int32_t>(p.depth); }
+
 // ---- verify mode (c3_verify.h): which batches, the second pass, what c3_predict_wait does with the record
 // The submits with batch > 0 are numbered; number k is selected when k % every == 0.  A selected batch that cannot be verified counts as skipped.
 // verify_select only LOOKS (true: this batch runs the second pass); verify_count numbers the submit once it is in flight, so that a submit
@@ -484,7 +492,7 @@ static int shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, const Sta
     const bool f16 = m->f16_ok, planes = lane(m).last_planes;
     m->f16_ok = false;
     if (p.layers.bytes) m->layer_pass = 2;  // every layer's compare launch goes behind the launch that wrote it (c3_forward.h layer_tap)
-    const int rc = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, sl.shadow, sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth),
+    const int rc = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, sl.shadow, sl.dev<const int32_t>(p.starts), ring_depth(sl, p),
                                   sl.dev<const ExpandEntry>(p.rows_tab));
     m->f16_ok = f16, lane(m).last_planes = planes, m->choice = reported, m->layer_pass = 0;
     TRY(rc);
@@ -510,12 +518,25 @@ static int shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, const Sta
     hipLaunchKernelGGL(rows_compare_final_kernel, dim3(1), dim3(64), 0, s, (const VerifyRecord *)cp.part, blocks, cp.kept, (int)in.batch,
                        (VerifyRecord *)((char *)sl.dev_y + p.verify.off));
     HIP_TRY(hipGetLastError());
+    if (m->verify_policy == C3_VERIFY_REPLACE) TRY(verify_replace_launch(m, s, sl, in, p, nullptr));
     return 0;
 }
 // c3_predict_wait, a verified batch the range guard did not answer: the record joins the totals; true = the policy escalates this batch
 static bool verify_account(c3_model *m, const HostSlot &sl) {
-    const VerifyRecord &r = *(const VerifyRecord *)((const char *)sl.pin_y + sl.plan.verify.off);
+    const char *rec = (const char *)sl.pin_y + sl.plan.verify.off;
+    const VerifyRecord &r = *(const VerifyRecord *)rec;
     c3_verify_stats &t = m->vstats;
+    const bool ref_exact = m->verify_ref == C3_VERIFY_REF_EXACT;  // (neither setting changes while a batch is in flight)
+    if (ref_exact) {  // the double maximum behind the record (c3_exact.h)
+        double d;
+        memcpy(&d, rec + kVerifyMax64At, sizeof(d));
+        m->vextra.max_abs_diff_f64 = std::max(m->vextra.max_abs_diff_f64, d);
+    }
+    if (m->verify_policy == C3_VERIFY_REPLACE) {  // ... and the rows repaired on the device
+        uint32_t n;
+        memcpy(&n, rec + kVerifyReplacedAt, sizeof(n));
+        m->vextra.rows_replaced += n, m->vextra.batches_with_replacements += n > 0;
+    }
     ++t.batches_checked, t.windows_checked += r.n, t.rows_over_tol += r.rows_over;
     if (t.worst_batch < 0 || r.max_abs > t.max_abs_diff) t.worst_batch = sl.verify_ordinal, t.worst_row = r.worst_row, t.max_abs_diff = r.max_abs;
     int64_t labels = 0;
@@ -526,8 +547,9 @@ static bool verify_account(c3_model *m, const HostSlot &sl) {
     if (m->verify_policy != C3_VERIFY_ESCALATE || (r.rows_over == 0 && labels == 0)) return false;
     ++t.escalations;
     if (m->f16_ok)
-        fprintf(stderr, "libc3hip: verify mode: fp16x3 rows differ from the fp32 forms (max |d| = %.3g, %u rows beyond %.3g, %lld labels); this handle "
-                        "continues on fp32 matrix instructions\n", (double)r.max_abs, r.rows_over, (double)m->verify_tol, (long long)labels);
+        fprintf(stderr, "libc3hip: verify mode: fp16x3 rows differ from the %s (max |d| = %.3g, %u rows beyond %.3g, %lld labels); this handle "
+                        "continues on fp32 matrix instructions\n", ref_exact ? "exact form" : "fp32 forms", (double)r.max_abs, r.rows_over, (double)m->verify_tol,
+                (long long)labels);
     m->f16_ok = false, m->precision = "fp32-verify";
     return true;
 }
@@ -605,14 +627,16 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
         sp.img_cols = in.n_cols;
         TRY(run_select(m, s, sp));
     }
-    const bool f16 = m->f16_ok;
+    const bool exact = m->answer_exact;  // the batch is answered by the exact form (c3_exact.h): no product kernel, the range flag neither raised nor read
+    const bool f16 = m->f16_ok && !exact;
     if (p.layers.bytes) {  // layer records: the product pass keeps its layer outputs in the slot (c3_forward.h layer_tap)
         TRY(ensure_layers(m, sl, in.batch));
         m->layer_slot = &sl, m->layer_batch = in.batch, m->layer_pass = 1;
         m->layer_kept_count = in.kind == InKind::Candidates ? (const uint32_t *)((const char *)sl.dev_y + p.kept.off) : nullptr;
     }
-    const int rc_product = forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, sl.dev<const int32_t>(p.starts),
-                                          sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab));
+    const int rc_product = exact ? exact_ring_pass(m, s, sl, p, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, nullptr, false)
+                                 : forward_device(m, s, sl.dev_x, in.x_dtype, in.batch, in.y_dev ? in.y_dev : sl.dev_y, sl.dev<const int32_t>(p.starts),
+                                                  ring_depth(sl, p), sl.dev<const ExpandEntry>(p.rows_tab));
     m->layer_pass = 0;
     TRY(rc_product);
     if (in.y_dev && f16)  // rows that stay on the device are scanned there (bit 1 of the flag: a non-finite row)
@@ -620,7 +644,7 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
     const bool rows_home = in.score && !in.y_host;  // (a scored batch whose caller wants no rows: scanned here like rows that stay on the device)
     if (rows_home && f16)
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, sl.dev_y, in.batch * m->row, m->range_flag);
-    if (p.verify.bytes) TRY(shadow_pass(m, sl, in, p));
+    if (p.verify.bytes) TRY(m->verify_ref == C3_VERIFY_REF_EXACT ? exact_shadow_pass(m, sl, in, p) : shadow_pass(m, sl, in, p));
     if (p.score.bytes) TRY(run_score(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
     // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
@@ -657,6 +681,10 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
     TRY(ring_ready(m, slot));
     if (in.batch < 0) return fail("negative batch");
     if (in.kind != InKind::Parts && in.batch > 0 && (!in.x || (!in.y_host && !in.y_dev && !in.score))) return fail("null buffer");  // (parts: checked one by one at the entry)
+    // the exact form gathers the windows of a region with the int32 pre-pass of c3_rescale.h: an int8 region matrix cannot be read by it
+    const bool region_kind = in.kind == InKind::Region || in.kind == InKind::Candidates, exact_can = !(region_kind && in.x_dtype == C3_DTYPE_I8);
+    if (m->answer_exact && !exact_can)
+        return fail("the exact form is refused for an int8 region matrix: its windows are gathered by the int32 pre-pass -- pass int32 / int64 counts, or sliced windows");
     HIP_TRY(hipSetDevice(m->device));
     if (in.kind == InKind::Sliced && m->pack_rows && m->kind == C3_KIND_FULL_ALIGNMENT && in.x_dtype == C3_DTYPE_I8 && !in.score) in.kind = InKind::PackedHere;  // (a scored batch stays sliced)
     HostSlot &sl = m->slot[slot];
@@ -671,8 +699,17 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
     for (int k = 0; k < kHostSlots; ++k) alone &= !m->slot[k].busy;
     const LaneSharing shared_chip_forms(m, in.batch, in_lane && !alone);
     const int32_t *depth = deep_depths(m, in);
-    const bool verify = verify_select(m, in.batch, true, &sl.verify_ordinal);
+    // (an exact-answer batch is skipped like a batch of a handle on the fp32 forms; so is a batch the exact reference cannot read)
+    const bool verify = verify_select(m, in.batch, !m->answer_exact && (m->verify_ref != C3_VERIFY_REF_EXACT || exact_can), &sl.verify_ordinal);
+    // a region / candidate batch the exact form reads always stages depths -- the caller's, or zeros: the pre-pass then is the plain gather
+    std::vector<int32_t> no_depth;
+    bool gather_only = false;
+    if (region_kind && !depth && in.batch > 0 && (m->answer_exact || (verify && m->verify_ref == C3_VERIFY_REF_EXACT))) {
+        if (!in.depth) no_depth.assign((size_t)in.batch, 0);
+        depth = in.depth ? in.depth : no_depth.data(), gather_only = true;
+    }
     StagedBatch p = plan_batch(m, in, depth != nullptr, verify, m->verify_layers);
+    p.gather_only = gather_only;
     Filled f;
     if (in.batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
@@ -750,7 +787,7 @@ static int range_guard_stale_rerun(c3_model *m, HostSlot &sl, bool *bad) {
     hipStream_t s = lane(m).stream;
     float *y = sl.y_dev_out ? sl.y_dev_out : sl.dev_y;
     m->tap_call_off = sl.tap_off;
-    const int rc = forward_device(m, s, sl.dev_x, sl.x_dtype, sl.batch, y, sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth),
+    const int rc = forward_device(m, s, sl.dev_x, sl.x_dtype, sl.batch, y, sl.dev<const int32_t>(p.starts), ring_depth(sl, p),
                                   sl.dev<const ExpandEntry>(p.rows_tab));
     m->tap_call_off = 0;
     TRY(rc);
@@ -791,7 +828,7 @@ int c3_predict_wait(c3_model *m, int slot) {
         TRY(use_lane(m, sl.lane));
         const auto rerun = range_recalibrates(m) ? range_guard_recalibrate : range_guard_rerun;
         TRY(rerun(m, lane(m).stream, sl.dev_x, sl.x_dtype, sl.batch, sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sl.tap_off,
-                  sl.dev<const int32_t>(p.starts), sl.dev<const int32_t>(p.depth), sl.dev<const ExpandEntry>(p.rows_tab)));
+                  sl.dev<const int32_t>(p.starts), ring_depth(sl, p), sl.dev<const ExpandEntry>(p.rows_tab)));
         if (!sl.y_dev_out && !sl.rows_home) HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.y.bytes, hipMemcpyDeviceToHost, lane(m).stream));
         HIP_TRY(hipStreamSynchronize(lane(m).stream));
     }
@@ -1109,6 +1146,7 @@ static void verify_layers_zero(c3_model *m) {
 static void verify_zero(c3_model *m) {
     m->vstats = c3_verify_stats{};
     m->vstats.worst_batch = -1;
+    m->vextra = c3_verify_extra{};
     verify_layers_zero(m);
 }
 int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int policy) {
@@ -1116,7 +1154,8 @@ int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int p
     if (every < 0) return fail("every must be >= 0 (0 = off), got %d", every);
     if (!(tol > 0.f)) return fail("tol must be > 0, got %g", (double)tol);
     if (!(near_tie >= 0.f)) return fail("near_tie must be >= 0, got %g", (double)near_tie);
-    if (policy != C3_VERIFY_REPORT && policy != C3_VERIFY_ESCALATE) return fail("policy must be C3_VERIFY_REPORT or C3_VERIFY_ESCALATE, got %d", policy);
+    if (policy != C3_VERIFY_REPORT && policy != C3_VERIFY_ESCALATE && policy != C3_VERIFY_REPLACE)
+        return fail("policy must be C3_VERIFY_REPORT, C3_VERIFY_ESCALATE or C3_VERIFY_REPLACE, got %d", policy);
     for (const HostSlot &sl : m->slot)
         if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
     if (every > 0 && !m->verify_seen) verify_zero(m);

@@ -21,7 +21,8 @@
 //   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries;
 //                  the packing part of a full-alignment load (fa_pack_weights) and, on it, the range guard's policy C3_RANGE_RECALIBRATE: a trip
 //                  takes the census during its fp32 re-run, solves, packs again and stays on the product forms (range_guard_recalibrate)
-//   c3_exact.h     the exact form: both networks in fp64 on the device, its kernels, workspace and entries (c3_predict_exact, c3_exact_fetch)
+//   c3_exact.h     the exact form: both networks in fp64 on the device, its kernels, workspace and entries (c3_predict_exact, c3_exact_fetch);
+//                  on the ring: exact_ring_pass (c3_model_set_answer), exact_shadow_pass (c3_model_set_verify_reference), verify_replace_launch
 //   c3_model.hip   create / geometry / device-resident entries / describe / destroy
 // Every layer has exactly two forms: the product (fp16x3 split products on the 16-bit matrix instructions) and
 // one fp32-MFMA form that the range guard falls back to (and that C3HIP_FP32=1 selects from the start).
@@ -175,6 +176,8 @@ struct StagedBatch {
     Section score;      // a scored batch (c3_score.h): its ScoreRecord, behind everything above
     Section losses;     // ... and the windows' values [batch][tasks] float32 behind the record, when the caller asked for them
     size_t y_total = 0;
+    bool gather_only = false;  // a region / candidate batch the exact form reads (c3_exact.h exact_ring_pass): `depth` is staged (zeros where the
+                               // caller gave none) only so that the pre-pass of c3_rescale.h gathers its windows; the product forms do not see it
 };
 
 constexpr int kMaxParts = 64;  // host buffers one staged batch may be assembled from (C3_MAX_PARTS)
@@ -215,6 +218,9 @@ struct HostSlot {
     int64_t verify_ordinal = 0;  // which submit of the handle this batch was (c3_verify_stats.worst_batch)
     float *shadow = nullptr;
     size_t shadow_bytes = 0, shadow_part = 0;  // shadow_part: offset of the partials
+    // ... against the exact form (C3_VERIFY_REF_EXACT): the float32 rounding of the exact rows at the front of `shadow` (what an escalated or
+    // repaired batch is answered with), the fp64 rows of the whole batch at shadow_rows64, the fp64 compare kernel's partials at shadow_part
+    size_t shadow_rows64 = 0;
     // ... with layer records: the product pass's layer outputs of the whole batch (copied behind the producing launches like a tap's, never
     // into a user's tap buffers) and the layer compare kernel's partials.  The slot's like the shadow rows, allocated on first use
     float *layer_buf[kTapCount] = {};
@@ -274,6 +280,10 @@ struct ExactState {
     double *act[9] = {}, *spp = nullptr, *gx1 = nullptr, *h1 = nullptr, *gx2 = nullptr, *h2 = nullptr;
     double *l4 = nullptr, *l5 = nullptr, *logit = nullptr, *y = nullptr;
     int64_t last_n = 0;  // windows of the last pass of the last call (c3_exact_fetch)
+    // on the ring (exact_ring_pass): ONE workspace for all lanes, so the passes of different lanes are put in order by this event, recorded
+    // behind each pass and waited on by the next; created when the exact form is first used on the ring
+    hipEvent_t ring_ev = nullptr;
+    bool ring_recorded = false;
 };
 // a tensor of the last c3_model_load as the handle keeps it while the range-guard policy is RECALIBRATE
 struct KeptTensor {
@@ -407,6 +417,9 @@ struct c3_model {
     float verify_tol = 1e-4f, verify_near_tie = 1e-6f;
     int verify_policy = C3_VERIFY_REPORT;
     bool verify_seen = false;  // verify mode is or was on: c3_model_describe ends on verify=...
+    int verify_ref = C3_VERIFY_REF_FP32;  // c3_model_set_verify_reference: what a selected batch is compared with
+    c3_verify_extra vextra = {};          // the totals that c3_verify_stats has no room for (reference is filled in when read)
+    bool answer_exact = false;            // c3_model_set_answer(C3_ANSWER_EXACT): every batch of the ring is answered by the exact form
     c3_verify_stats vstats = {};  // totals since the last load / reset (batches_submitted doubles as the selection counter)
     // ... layer records (c3_model_set_verify_layers): off = nothing allocated, nothing launched, a verified batch laid out as without it
     bool verify_layers = false;

@@ -13,7 +13,7 @@
 
 extern "C" {
 
-const char *c3_version(void) { return "c3hip 0.5.5 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
+const char *c3_version(void) { return "c3hip 0.5.6 (gfx950, fp32 data, fp16x3 split matrix products) srchash:" C3HIP_SRC_HASH; }
 const char *c3_last_error(void) { return g_err.c_str(); }
 
 int c3_device_count(void) {
@@ -383,7 +383,7 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
     if (m->kind == C3_KIND_PILEUP)
         snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s lstm1=%s proj2=%s lstm2=%s on_fp32=%d precision=%s lstm_wmax=%.4g lstm_hh_norm=%.4g auto_fp32_at=%.4g "
                  "ring_lanes=%d lane_max_batch=%lld max_depth=%d rescaled=%lld candidates=%lld kept=%lld chunks=%lld", m->sharing,
-                 stores, m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
+                 stores, m->choice.lstm1, m->choice.proj2, m->choice.lstm2, (int)!m->f16_ok, m->answer_exact ? "exact" : m->precision, (double)m->lstm_wmax, (double)m->lstm_hh_norm,
                  (double)(m->precision_forced ? 0.f : m->auto_fp32_at), m->ring_lanes, (long long)m->lane_max_batch, m->max_depth,
                  (long long)m->rescaled, (long long)m->cand_n, (long long)m->cand_kept, (long long)m->cand_chunks);
     else {
@@ -406,7 +406,7 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
         snprintf(buf, (size_t)n, "sharing=%d plane_stores=%s conv_stack=%s stride1=%s conv3=%s conv5=%s on_fp32=%d ring_lanes=%d lane_max_batch=%lld "
                  "precision=%s wino_form=%s fa_tail=%s wave_prio=%s rows_windows=%lld rows_shipped=%lld pack_rows=%d", m->sharing,
                  stores, m->choice.fa, m->choice.s1, m->choice.s2[0], m->choice.s2[1], (int)!m->f16_ok, m->ring_lanes, (long long)m->lane_max_batch,
-                 m->precision, wf[0] ? wf : "-", m->choice.fa_tail, wp[0] ? wp : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
+                 m->answer_exact ? "exact" : m->precision, wf[0] ? wf : "-", m->choice.fa_tail, wp[0] ? wp : "-", (long long)m->rows_windows, (long long)m->rows_shipped, (int)m->pack_rows);
     }
     if (m->fp32_plan | m->fp32_auto) {  // only while a precision plan is in force (c3_model.h layer_f16)
         const size_t at = strlen(buf);
@@ -426,11 +426,12 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
         const size_t at = strlen(buf);
         snprintf(buf + at, (size_t)n - at, " verify=every:%d,policy:%s,tol:%.3g,submitted:%lld,checked:%lld,skipped:%lld,windows:%lld,max_abs_diff:%.3g,"
                  "rows_over_tol:%lld,label_diffs:%lld,near_ties:%lld,escalations:%lld", m->verify_every,
-                 m->verify_policy == C3_VERIFY_ESCALATE ? "escalate" : "report", (double)m->verify_tol, (long long)t.batches_submitted,
+                 m->verify_policy == C3_VERIFY_ESCALATE ? "escalate" : m->verify_policy == C3_VERIFY_REPLACE ? "replace" : "report", (double)m->verify_tol, (long long)t.batches_submitted,
                  (long long)t.batches_checked, (long long)t.batches_skipped, (long long)t.windows_checked, (double)t.max_abs_diff,
                  (long long)t.rows_over_tol, (long long)(t.label_diffs[0] + t.label_diffs[1] + t.label_diffs[2] + t.label_diffs[3]),
                  (long long)(t.near_ties[0] + t.near_ties[1] + t.near_ties[2] + t.near_ties[3]), (long long)t.escalations);
         if (m->verify_layers) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), ",layers:1");
+        if (m->verify_ref == C3_VERIFY_REF_EXACT) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), ",ref:exact");  // only while the reference is the exact form
     }
     if (m->exact.want) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " exact=1");  // only while the exact form is enabled (c3_exact.h)
     if (m->score_on)  // only while score mode is enabled (c3_score.h)
@@ -452,6 +453,7 @@ int c3_model_destroy(c3_model *m) {
     free_all_workspaces(m);
     exact_free_workspace(m);
     exact_free_weights(m);
+    if (m->exact.ring_ev) (void)hipEventDestroy(m->exact.ring_ev);
     for (const Lane &L : m->lanes)
         if (L.stream) (void)hipStreamDestroy(L.stream);
     float *ws[] = {m->proj_w[0], m->proj_w[1], m->proj_b[0], m->proj_b[1], m->whh[0], m->whh[1], m->whh16[0], m->whh16[1],

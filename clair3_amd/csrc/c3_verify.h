@@ -26,6 +26,9 @@ namespace c3 {
 constexpr int kVerifyThreads = 256;     // 64 rows per workgroup and pass
 constexpr int kVerifyMaxBlocks = 1024;  // partials of one batch (a larger batch: every workgroup takes several passes)
 constexpr size_t kVerifyRecordBytes = 256;  // the record's section of a staged batch (a multiple of 256 like every section)
+// ... behind the record in that section (c3_exact.h writes them, c3_predict_wait reads them): the double maximum of a comparison with
+// the exact rows, and the count of rows C3_VERIFY_REPLACE overwrote
+constexpr size_t kVerifyMax64At = 64, kVerifyReplacedAt = 72;
 
 struct VerifyRecord {  // 16 words: a workgroup's partial, and the batch's record as c3_predict_wait reads it
     float max_abs;

@@ -78,6 +78,8 @@ class _HipModel:
         self._lowering = None   # calibration (set_calibration): the channel lowering a handle created anew takes along ...
         self._cal_meta = None   # ... and (cap_log2, windows) of the calibration it came from, for save_calibration
         self._exact = False     # the exact form (exact()): a handle created anew takes the setting along
+        self._answer = "product"      # what answers a batch of the ring (answer()) ...
+        self._verify_ref = "fp32"     # ... and what verify mode compares with (verify(reference=)): both need the exact form, both travel with it
         self._score = None      # score mode (score_mode): (gamma, class weights or None) a handle created anew takes along
         self._range_policy = None  # the range-guard policy (range_policy): (policy, max_recalibrations) a handle created anew takes along
         self._recal_seen = 0       # recalibrations of the handle whose lowering self._lowering already mirrors (_sync_recalibration)
@@ -210,6 +212,12 @@ class _HipModel:
         if rc != 0:
             raise _lib.C3Error(f"Error(s) in loading state_dict for {type(self).__name__}: {_lib.last_error()}")
         self._recal_seen = 0
+        # what needs the double weights on the device (answer(), verify(reference="exact")) and was asked for before this load placed them,
+        # or of a handle created anew: the library keeps both across reloads, so setting them again changes nothing
+        if self._verify_ref != "fp32":
+            _lib.check(_lib.lib().c3_model_set_verify_reference(self._handle, _lib.VERIFY_REF[self._verify_ref]), "c3_model_set_verify_reference")
+        if self._answer != "product":
+            _lib.check(_lib.lib().c3_model_set_answer(self._handle, _lib.ANSWER[self._answer]), "c3_model_set_answer")
 
     # ---- the forward pass ----
     def __call__(self, x):
@@ -377,8 +385,10 @@ class _HipModel:
 
     # ---- verify mode (c3_model_set_verify) ----
     @staticmethod
-    def _verify_args(every, tol, near_tie, escalate):
+    def _verify_args(every, tol, near_tie, escalate, replace=False):
         """(every, tol, near_tie, policy) as the C ABI takes them; anything it would refuse is refused here with the same words"""
+        if escalate and replace:
+            raise _lib.C3Error("escalate and replace are two policies: choose one")
         if isinstance(every, bool) or not isinstance(every, (int, np.integer)):
             raise _lib.C3Error(f"every must be an integer >= 0 (0 = off), got {every!r}")
         if every < 0 or every > 2 ** 31 - 1:
@@ -391,25 +401,55 @@ class _HipModel:
             raise _lib.C3Error(f"tol must be > 0, got {tol}")
         if not near_tie >= 0 or not np.isfinite(near_tie):
             raise _lib.C3Error(f"near_tie must be >= 0, got {near_tie}")
-        return int(every), tol, near_tie, _lib.VERIFY_ESCALATE if escalate else _lib.VERIFY_REPORT
+        return int(every), tol, near_tie, _lib.VERIFY_ESCALATE if escalate else _lib.VERIFY_REPLACE if replace else _lib.VERIFY_REPORT
 
     def verify(self, every=1, tol=1e-4, near_tie=1e-6, escalate=False, layers=False):
+        """Verify mode as the base of the model classes states it: the call below with the reference left what it is and no row repaired.
+        The model classes (Clair3_P, Clair3_F) take the two further keywords: _RingVerify.verify."""
+        return self._verify_with(every, tol, near_tie, escalate, layers, self._verify_ref, False)
+
+    def _verify_with(self, every, tol, near_tie, escalate, layers, reference, replace):
         """Verify mode: every ``every``-th batch of the submit / wait ring (predict_numpy, submit and everything built on them) also runs on the
         fp32-MFMA forms from the same staged input and the two sets of rows are compared on the device (c3_model_set_verify).  ``tol`` and
         ``near_tie`` default to the project's own gates (north_star's 1e-4, tests/util.py NEAR_TIE).  escalate=False: the rows stay the
         fp16x3 ones, bit for bit; escalate=True: a batch that disagrees is answered with its fp32 rows and the handle continues on the
         fp32 forms.  every=0 switches it off.  verify_stats() reads the totals.  layers=True: every compared batch also compares the
-        two forms layer by layer on the device (c3_model_set_verify_layers); verify_layers() reads that table."""
-        args = self._verify_args(every, tol, near_tie, escalate)
+        two forms layer by layer on the device (c3_model_set_verify_layers); verify_layers() reads that table.
+        reference="exact": a selected batch runs the exact form (exact()) instead of the fp32 forms and is compared with its fp64 rows
+        (c3_model_set_verify_reference; with layers=True the product layers are compared with the exact layers); verify_extra() reads the
+        double maximum.  replace=True (with either
+        reference; not together with escalate): only the rows that disagree are overwritten with the reference's rows, every other row
+        stays the product row and the handle stays on the forms it was on (C3_VERIFY_REPLACE)."""
+        if not isinstance(replace, (bool, np.bool_)):
+            raise _lib.C3Error(f"replace must be True or False, got {replace!r}")
+        args = self._verify_args(every, tol, near_tie, escalate, replace)
         if not isinstance(layers, (bool, np.bool_)):
             raise _lib.C3Error(f"layers must be True or False, got {layers!r}")
+        if reference not in _lib.VERIFY_REF:
+            raise _lib.C3Error(f"reference must be 'fp32' or 'exact', got {reference!r}")
         if self._handle is None:  # (a call that fails leaves nothing behind for a later .to(device) to apply)
             raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        if reference != self._verify_ref:  # (in front of everything else: refused, it leaves the setting what it was)
+            if self._pending_sd is not None or reference == "fp32":  # (no weights yet: the first load sets it, behind the double weights)
+                _lib.check(_lib.lib().c3_model_set_verify_reference(self._handle, _lib.VERIFY_REF[reference]), "c3_model_set_verify_reference")
+            elif not self._exact:
+                raise _lib.C3Error("reference='exact' needs the exact form: call exact() first")
+            self._verify_ref = reference
         _lib.check(_lib.lib().c3_model_set_verify(self._handle, *args), "c3_model_set_verify")
         _lib.check(_lib.lib().c3_model_set_verify_layers(self._handle, int(layers)), "c3_model_set_verify_layers")
         self._verify = args  # a handle created anew by .to(another device) takes the setting along
         self._verify_layers = bool(layers)
         return self
+
+    def verify_extra(self):
+        """what verify_stats() has no room for (c3_model_verify_extra), since the last load / verify_reset(): ``reference`` ("fp32" | "exact"),
+        ``rows_replaced`` and ``batches_with_replacements`` of verify(replace=True), ``max_abs_diff_f64`` of verify(reference="exact")"""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        ex = _lib.VerifyExtra()
+        _lib.check(_lib.lib().c3_model_verify_extra(self._handle, C.byref(ex)), "c3_model_verify_extra")
+        return dict(reference="exact" if ex.reference == _lib.VERIFY_REF["exact"] else "fp32", rows_replaced=int(ex.rows_replaced),
+                    batches_with_replacements=int(ex.batches_with_replacements), max_abs_diff_f64=float(ex.max_abs_diff_f64))
 
     def verify_stats(self):
         """the totals of verify mode since the last load / verify_reset() as a dict (c3_model_verify_stats; include/c3hip.h names the fields)"""
@@ -421,7 +461,7 @@ class _HipModel:
         for name, _ in _lib.VerifyStats._fields_:
             v = getattr(st, name)
             out[name] = list(v) if hasattr(v, "__len__") else v
-        out["policy"] = "escalate" if st.policy == _lib.VERIFY_ESCALATE else "report"
+        out["policy"] = _lib.VERIFY_POLICY.get(st.policy, "report")
         return out
 
     def verify_layers(self):
@@ -738,6 +778,21 @@ class _HipModel:
             self._load(self._pending_sd)
         return self
 
+    def answer(self, form="exact"):
+        """What answers the batches of the submit / wait ring (c3_model_set_answer): "exact" -- predict_numpy, submit / wait and everything
+        built on them (depths, regions, candidates, rows, parts, submit_dev, score mode) return the float32 rounding of the exact rows,
+        decoder columns computed from them; no product kernel runs, describe() says precision=exact, verify mode skips such batches --
+        or "product", the default.  Needs exact(); forward() and forward(checked=True) stay the product forms."""
+        if form not in _lib.ANSWER:
+            raise _lib.C3Error(f"form must be 'exact' or 'product', got {form!r}")
+        self._need_handle()
+        if self._pending_sd is not None or form == "product":
+            _lib.check(_lib.lib().c3_model_set_answer(self._handle, _lib.ANSWER[form]), "c3_model_set_answer")
+        elif not self._exact:  # (no weights yet: the first load sets it, behind the double weights -- which exact() must have asked for)
+            raise _lib.C3Error("answer('exact') needs the exact form: call exact() first")
+        self._answer = form
+        return self
+
     def predict_exact(self, x):
         """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;
         blocking; windows only).  Whatever precision, plan or calibration the handle runs does not enter."""
@@ -821,7 +876,16 @@ class _HipModel:
             pass
 
 
-class Clair3_P(_HipModel):
+class _RingVerify(_HipModel):
+    """verify mode of the model classes: the base's call and, behind its keywords, what the exact form on the ring added"""
+
+    def verify(self, every=1, tol=1e-4, near_tie=1e-6, escalate=False, layers=False, reference="fp32", replace=False):
+        """_HipModel._verify_with says what every keyword does.  The defaults keep the call what it was: the fp32 forms as the reference,
+        no row repaired."""
+        return self._verify_with(every, tol, near_tie, escalate, layers, reference, replace)
+
+
+class Clair3_P(_RingVerify):
     """Pileup network: 2 x bidirectional LSTM + FC heads (reference: clair3/model.py:58-161)."""
     KIND = _lib.KIND_PILEUP
     DEFAULT_CHANNELS = 18  # shared/param_p.py:32-36
@@ -908,7 +972,7 @@ class Clair3_P(_HipModel):
         return slot, out
 
 
-class Clair3_F(_HipModel):
+class Clair3_F(_RingVerify):
     """Full-alignment network: residual 3x3-conv stack + pyramid pooling + FC heads (clair3/model.py:282-416)."""
     KIND = _lib.KIND_FULL_ALIGNMENT
     DEFAULT_CHANNELS = 8  # shared/param_f.py:24-31 (9 with --enable_dwell_time)

@@ -40,19 +40,55 @@ def _load_torch_checkpoint(model, checkpoint_path, device=None):
     calibration_from_env(model)
     verify_from_env(model)
     exact_from_env(model)
+    answer_from_env(model)
     range_guard_from_env(model)
+
+
+def parse_answer_env(value):
+    """C3HIP_ANSWER=exact | product -> "exact" | "product"; None when unset or empty.  Anything else raises."""
+    value = (value or "").strip().lower()
+    if not value:
+        return None
+    if value not in _lib.ANSWER:
+        raise _lib.C3Error(f"C3HIP_ANSWER must be exact or product, got {value!r}")
+    return value
+
+
+def parse_verify_ref_env(value):
+    """C3HIP_VERIFY_REF=exact | fp32 -> "exact" | "fp32"; None when unset or empty.  Anything else raises."""
+    value = (value or "").strip().lower()
+    if not value:
+        return None
+    if value not in _lib.VERIFY_REF:
+        raise _lib.C3Error(f"C3HIP_VERIFY_REF must be exact or fp32, got {value!r}")
+    return value
 
 
 def exact_from_env(model):
     """C3HIP_EXACT=1: the model takes the exact form along where it is built (model.exact(): the double weights travel with its loads);
-    unset, empty or 0: the model is left alone.  Anything else raises."""
+    unset, empty or 0: the model is left alone.  Anything else raises.  C3HIP_ANSWER=exact and C3HIP_VERIFY_REF=exact (with C3HIP_VERIFY
+    on) imply it, as C3HIP_EXACT=1 does."""
     import os
     value = (os.environ.get("C3HIP_EXACT") or "").strip()
-    if value in ("", "0"):
-        return False
-    if value != "1":
+    answer = parse_answer_env(os.environ.get("C3HIP_ANSWER"))
+    ref = parse_verify_ref_env(os.environ.get("C3HIP_VERIFY_REF"))
+    implied = answer == "exact" or (ref == "exact" and parse_verify_env(os.environ.get("C3HIP_VERIFY")) is not None)
+    if value not in ("", "0", "1"):
         raise _lib.C3Error(f"C3HIP_EXACT must be 0 or 1, got {value!r}")
+    if value != "1" and (not implied or getattr(model, "_exact", False)):  # (implied only: verify_from_env may have enabled it already)
+        return False
     model.exact(True)
+    return True
+
+
+def answer_from_env(model):
+    """C3HIP_ANSWER=exact: the model answers the batches of the ring from the exact form where it is built (model.answer()); product, unset
+    or empty: the model is left alone.  Called behind exact_from_env, which placed the double weights."""
+    import os
+    answer = parse_answer_env(os.environ.get("C3HIP_ANSWER"))
+    if answer != "exact":
+        return False
+    model.answer("exact")
     return True
 
 
@@ -74,12 +110,13 @@ def calibration_from_env(model):
 
 
 def parse_verify_env(value, tol=None):
-    """C3HIP_VERIFY=<n> | <n>,escalate (and C3HIP_VERIFY_TOL=<tol>) -> the keyword arguments of ``model.verify``; None when unset, empty or
-    0.  Anything else that is not such a setting raises: a job asked to verify must not run unverified because of a typo."""
+    """C3HIP_VERIFY=<n> | <n>,escalate | <n>,replace (and C3HIP_VERIFY_TOL=<tol>) -> the keyword arguments of ``model.verify``; None when
+    unset, empty or 0.  Anything else that is not such a setting raises: a job asked to verify must not run unverified because of a typo.
+    ``replace`` appears among the keywords only when the word is used: without it the result is what it always was."""
     if value is None or not value.strip():
         return None
     parts = [p.strip().lower() for p in value.split(",")]
-    if len(parts) > 2 or (len(parts) == 2 and parts[1] not in ("escalate", "report")):
+    if len(parts) > 2 or (len(parts) == 2 and parts[1] not in ("escalate", "report", "replace")):
         raise _lib.C3Error(f"C3HIP_VERIFY must be <n> or <n>,escalate (every n-th batch; 0 = off), got {value!r}")
     try:
         every = int(parts[0])
@@ -88,6 +125,8 @@ def parse_verify_env(value, tol=None):
     if every < 0:
         raise _lib.C3Error(f"C3HIP_VERIFY: n must be >= 0, got {every}")
     kw = dict(every=every, escalate=len(parts) == 2 and parts[1] == "escalate")
+    if len(parts) == 2 and parts[1] == "replace":
+        kw["replace"] = True
     if tol is not None and tol.strip():
         try:
             kw["tol"] = float(tol)
@@ -111,6 +150,11 @@ def verify_from_env(model):
         return False
     if os.environ.get("C3HIP_VERIFY_LAYERS", "").strip().lower() not in ("", "0", "false", "no", "off"):
         kw["layers"] = True  # (only when set: without it the call is what it was; _report_verified follows the handle, not the environment)
+    ref = parse_verify_ref_env(os.environ.get("C3HIP_VERIFY_REF"))
+    if ref is not None and ref != "fp32":
+        kw["reference"] = ref  # (only when the reference is not the default's)
+        if not getattr(model, "_exact", False):
+            model.exact(True)  # (the reference needs the double weights: implied, as by C3HIP_EXACT=1)
     model.verify(**kw)
     if not any(v is model for v in _VERIFIED):
         import atexit
@@ -125,11 +169,15 @@ def verify_summary(model):
     import re
     st = model.verify_stats()
     prec = re.search(r"precision=(\S+)", model.describe())
-    return ("[clair3_amd] verify: precision={} every={} policy={} tol={:g} batches submitted={} checked={} skipped={} windows={} "
+    line = ("[clair3_amd] verify: precision={} every={} policy={} tol={:g} batches submitted={} checked={} skipped={} windows={} "
             "max_abs_diff={:.3g} per_head={} worst=(batch {}, row {}) rows_over_tol={} label_diffs={} near_ties={} escalations={}").format(
         prec.group(1) if prec else "?", st["every"], st["policy"], st["tol"], st["batches_submitted"], st["batches_checked"],
         st["batches_skipped"], st["windows_checked"], st["max_abs_diff"], "/".join(f"{v:.3g}" for v in st["head_max_abs_diff"]),
         st["worst_batch"], st["worst_row"], st["rows_over_tol"], st["label_diffs"], st["near_ties"], st["escalations"])
+    extra = model.verify_extra() if hasattr(model, "verify_extra") else None
+    if extra is not None and extra["reference"] == "exact":  # (at the end, and only then: the line is otherwise what it always was)
+        line += " ref=exact replaced={}".format(extra["rows_replaced"])
+    return line
 
 
 # the suite's layer gate (tests/test_caller_inputs_gpu.py LAYER_TOL): a layer whose rel = max_abs_diff / max(1, ref_max_abs) exceeds it is marked
@@ -312,6 +360,7 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
         calibration_from_env(m)
         verify_from_env(m)
         exact_from_env(m)
+        answer_from_env(m)
         range_guard_from_env(m)
     return m
 

@@ -98,6 +98,8 @@ class Server:
         out = dict(kind=name, row_size=int(m.row_size), output_size=int(m.output_size), input_channels=int(m.input_channels),
                    add_indel_length=bool(m.add_indel_length), decoder=bool(getattr(m, "_decode_cols", False)),
                    geometry=list(geometry) if geometry else None, sha256=None)
+        # what answers a batch and what verify mode compares with (model.answer(), model.verify(reference=)): "product" / "fp32" unless asked otherwise
+        out.update(answer=getattr(m, "_answer", "product"), verify_reference=getattr(m, "_verify_ref", "fp32"))
         out.update(self.info.get(name, {}))
         return out
 
@@ -240,7 +242,9 @@ class Server:
         elif op == "stats":
             with self.cond:
                 conn.send(dict(ok=True, paused=self.paused, stats={k: dict(v, seconds=dict(v["seconds"])) for k, v in self.stats.items()},
-                               waiting={k: len(q) for k, q in self.queue.items()}))
+                               waiting={k: len(q) for k, q in self.queue.items()},
+                               answer={k: getattr(m, "_answer", "product") for k, m in self.models.items()},
+                               verify_reference={k: getattr(m, "_verify_ref", "fp32") for k, m in self.models.items()}))
         elif op in ("pause", "resume"):
             with self.cond:
                 self.paused = op == "pause"

@@ -587,6 +587,58 @@ int c3_model_range_stats(c3_model *m, c3_range_stats *out);
 int c3_model_set_exact(c3_model *m, int enable);
 int c3_predict_exact(c3_model *m, const void *x_host, int x_dtype, int64_t batch, double *y_host);
 int c3_exact_fetch(c3_model *m, const char *name, int64_t first, int64_t windows, double *host_out, int64_t n_doubles);
+
+/* ---- the exact form on the submit / wait ring: what answers a batch, what verify mode compares with (csrc/c3_exact.h) ----
+ * The exact pass reads a batch of the ring where the product forms read it -- the staged windows; windows with depths and the windows of a
+ * region or candidate batch as the pre-pass of c3_rescale.h writes them into the lane's buffer (without a deep window it is a plain gather);
+ * occupied rows as c3_expand.h expands them; parts as the one batch they are -- on the batch's lane stream, cut into passes of
+ * C3HIP_EXACT_CHUNK windows in the handle's ONE exact workspace (passes of different lanes are put in order by an event).  A small kernel
+ * rounds the fp64 rows to float32 (round to nearest even) into the slot's row buffer; decoder columns, score mode and the rows' way back
+ * (parts, c3_predict_submit_dev) are what they are for product rows.  A window's float32 exact row is bit-identical whatever batch, chunk,
+ * lane or input kind it travelled in: it is (float)c3_predict_exact of that window.  A candidate batch computes a row for every candidate
+ * slot, as the product forms do; rows [0, kept) are the result.  An int8 REGION matrix is refused (the gather is the int32 pre-pass).
+ *   c3_model_set_answer   C3_ANSWER_EXACT: every batch of the ring -- c3_predict, c3_predict_submit and everything built on it: depths,
+ *                         regions, candidates, rows, parts, c3_predict_submit_dev, score mode -- is answered by the float32 rounding of its
+ *                         exact rows, decoder columns computed from those rows.  No product or fp32 kernel is launched for such a batch, the
+ *                         range flag is neither raised nor read, verify mode skips it (counted in batches_skipped, like a batch of a handle
+ *                         on the fp32 forms).  c3_model_describe reports precision=exact; set back to C3_ANSWER_PRODUCT it reports what it
+ *                         reported before and the rows are bit for bit those of a handle that never had it set.  Refused unless the last
+ *                         c3_model_load placed the double weights (c3_model_set_exact), and while a c3_predict_submit is pending; it
+ *                         survives a reload that keeps the exact form, and c3_model_set_exact(m, 0) is refused while it is set.
+ *                         c3_predict_device and c3_predict_device_checked stay exactly what they are: the product forms on the caller's stream
+ *   c3_model_set_verify_reference   C3_VERIFY_REF_EXACT: a batch verify mode selects runs the exact pass in place of the fp32 pass, and the
+ *                         rows are compared with the fp64 rows: |(double)a - b| in double, the arg-max and the top-2 gap of the EXACT row,
+ *                         tol and near_tie compared as doubles; the float fields of c3_verify_stats are the round-to-nearest floats of the
+ *                         double maxima, the double maximum itself is c3_verify_extra.max_abs_diff_f64.  Skip rules, numbering, totals and
+ *                         reset are unchanged (a selected int8 region batch counts as skipped).  C3_VERIFY_ESCALATE answers the tripping
+ *                         batch with its float32 exact rows and continues on the fp32 forms as before.  Refused without the double
+ *                         weights and while a submit is pending.  With c3_model_set_verify_layers a compared batch compares the product
+ *                         layers with the EXACT layers (the tensors c3_exact_fetch names; every one exists, the pileup gx2 included),
+ *                         pass by pass behind the exact pass that wrote them: |(double)a - b| in double, the record's floats the roundings
+ *                         of the double maxima; FUSED stays what it is for the product side.  c3_model_describe ends its verify=... text
+ *                         on ,ref:exact while the reference is exact
+ *   C3_VERIFY_REPLACE     third policy of c3_model_set_verify, with either reference: behind the comparison a small kernel overwrites every
+ *                         row that is over tol, or has an arg-max difference outside near-ties in any head, with the reference's row (the
+ *                         fp32-form row, or the float32 rounding of the exact row); every other row stays bit for bit the product row, the
+ *                         handle stays on the forms it was on.  Decoder columns are recomputed for the batch from the rows as they then
+ *                         are (the columns of untouched rows do not change).  It works on the device in front of the rows' copy-out, so
+ *                         rows left on the device (c3_predict_submit_dev), parts and score mode see the repaired rows.  A candidate batch:
+ *                         rows [0, kept) only
+ *   c3_model_verify_extra the totals c3_verify_stats has no room for (that struct keeps its size), since the last load / reset */
+#define C3_ANSWER_PRODUCT 0
+#define C3_ANSWER_EXACT 1
+int c3_model_set_answer(c3_model *m, int form);
+#define C3_VERIFY_REF_FP32 0
+#define C3_VERIFY_REF_EXACT 1
+int c3_model_set_verify_reference(c3_model *m, int ref);
+#define C3_VERIFY_REPLACE 2 /* third value of c3_model_set_verify's policy */
+typedef struct {
+    int32_t reference, reserved;        /* C3_VERIFY_REF_* in force */
+    int64_t rows_replaced;              /* C3_VERIFY_REPLACE: rows overwritten with the reference's ... */
+    int64_t batches_with_replacements;  /* ... in this many batches */
+    double max_abs_diff_f64;            /* C3_VERIFY_REF_EXACT: the largest |(double)a - b| of the compared rows (0 under REF_FP32) */
+} c3_verify_extra;
+int c3_model_verify_extra(c3_model *m, c3_verify_extra *out);
 int c3_model_describe(c3_model *m, char *buf, int buf_bytes);
 /* blocks until everything enqueued on the model's own stream has finished */
 int c3_model_synchronize(c3_model *m);
