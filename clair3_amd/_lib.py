@@ -36,6 +36,7 @@ EXPORTS = (
     "c3_model_set_range_policy", "c3_range_policy_check", "c3_model_range_stats",
     "c3_predict_submit_parts", "c3_predict_parts",
     "c3_model_set_score", "c3_score_submit", "c3_score_wait", "c3_score", "c3_score_rows",
+    "c3_model_set_score_census", "c3_score_census_read", "c3_score_census_reset",
 )
 MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
@@ -102,6 +103,13 @@ class ScoreResult(C.Structure):
     """c3_score_result (include/c3hip.h)"""
     _fields_ = [("windows", C.c_int64), ("tasks", C.c_int32), ("reserved", C.c_int32), ("loss_sum", C.c_double * 4),
                 ("correct", C.c_int64 * 4), ("nonfinite", C.c_int64)]
+
+
+class ScoreCensus(C.Structure):
+    """c3_score_census (include/c3hip.h)"""
+    _fields_ = [("windows", C.c_int64), ("tasks", C.c_int32), ("reserved", C.c_int32), ("confusion", C.c_int64 * 2628),
+                ("rel_windows", (C.c_int64 * 20) * 4), ("rel_correct", (C.c_int64 * 20) * 4), ("rel_conf_q32", (C.c_int64 * 20) * 4),
+                ("rel_skipped", C.c_int64 * 4), ("gap_below", (C.c_int64 * 6) * 4)]
 
 
 class C3Error(RuntimeError):
@@ -228,6 +236,9 @@ def lib():
     L.c3_score_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(ScoreResult)]
     L.c3_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ScoreResult)]
     L.c3_score_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.POINTER(ScoreResult), C.c_void_p]
+    L.c3_model_set_score_census.argtypes = [C.c_void_p, C.c_int]
+    L.c3_score_census_read.argtypes = [C.c_void_p, C.POINTER(ScoreCensus)]
+    L.c3_score_census_reset.argtypes = [C.c_void_p]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

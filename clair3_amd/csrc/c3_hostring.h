@@ -267,6 +267,8 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
     if (in.score) {
         p.score.off = al(p.y_total), p.score.bytes = kScoreRecordBytes, p.y_total = p.score.off + p.score.bytes;
         if (in.loss_host) p.losses.off = p.y_total, p.losses.bytes = n * (size_t)m->nb * sizeof(float), p.y_total = p.losses.off + p.losses.bytes;
+        // ... and, only while the handle's census is on (c3_census.h), the batch's table behind those
+        if (m->score_census_on) p.census.off = al(p.y_total), p.census.bytes = kScoreCensusBytes, p.y_total = p.census.off + p.census.bytes;
     }
     return p;
 }
@@ -596,11 +598,46 @@ static int run_score(c3_model *m, hipStream_t s, HostSlot &sl, const StagedBatch
     return score_launch(m, s, rows, m->row, sl.dev<const char>(p.labels), label_dtype, batch, p.losses.bytes ? (float *)((char *)sl.dev_y + p.losses.off) : nullptr,
                         sl.score_part, (ScoreRecord *)((char *)sl.dev_y + p.score.off));
 }
-// c3_predict_wait's reader of a scored batch: the record out of the pinned output buffer, the windows' values to where the caller wants them
-static void read_score(HostSlot &sl) {
+// ---- the census of score mode (c3_census.h): the batch's table is zeroed and filled on stream s, behind the score kernels and from the same
+// rows and labels; a re-run rewrites it, so nothing accumulates on the device
+static int census_launch(c3_model *m, hipStream_t s, const float *rows, int stride, const void *labels, int label_dtype, int64_t batch,
+                         ScoreCensusTable *out) {
+    ScoreCensusParams cp;
+    cp.rows = rows, cp.labels = labels, cp.out = out;
+    cp.stride = stride, cp.nout = m->nout, cp.batch = (int)batch, cp.label_f32 = label_dtype == C3_DTYPE_F32;
+    ProfScope ps(m, s, m->kind == C3_KIND_PILEUP ? "p.census" : "fa.census", 0.0, (double)batch * m->nout * (4.0 + (cp.label_f32 ? 4.0 : 1.0)));
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(ScoreCensusTable), s));
+    hipLaunchKernelGGL(rows_census_kernel, dim3((unsigned)score_census_blocks(batch)), dim3(kScoreCensusThreads), 0, s, cp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int run_census(c3_model *m, hipStream_t s, HostSlot &sl, const StagedBatch &p, int label_dtype, int64_t batch, const float *rows) {
+    return census_launch(m, s, rows, m->row, sl.dev<const char>(p.labels), label_dtype, batch, (ScoreCensusTable *)((char *)sl.dev_y + p.census.off));
+}
+// one completed batch of `windows` windows joins the handle's totals: 32-bit counts widened here
+static void census_add(c3_score_census &total, const ScoreCensusTable &t, int64_t windows, int tasks) {
+    total.windows += windows, total.tasks = tasks;
+    for (int i = 0; i < kScoreCensusCells; ++i) total.confusion[i] += t.confusion[i];
+    for (int h = 0; h < 4; ++h) {
+        for (int b = 0; b < kScoreCensusBins; ++b) {
+            total.rel_windows[h][b] += t.rel_windows[h][b], total.rel_correct[h][b] += t.rel_correct[h][b];
+            total.rel_conf_q32[h][b] += (int64_t)t.rel_conf_q32[h][b];
+        }
+        total.rel_skipped[h] += t.rel_skipped[h];
+        for (int k = 0; k < kScoreCensusGaps; ++k) total.gap_below[h][k] += t.gap_below[h][k];
+    }
+}
+// c3_predict_wait's reader of a scored batch: the record out of the pinned output buffer, the windows' values to where the caller wants them,
+// the batch's census table into the handle's totals -- once per completed batch, whoever waits for it
+static void read_score(HostSlot &sl, c3_model *m = nullptr) {
     const StagedBatch &p = sl.plan;
     memcpy(&sl.score_rec, (const char *)sl.pin_y + p.score.off, sizeof(ScoreRecord));
     if (sl.loss_host && p.losses.bytes) memcpy(sl.loss_host, (const char *)sl.pin_y + p.losses.off, p.losses.bytes);
+    if (m && p.census.bytes) {
+        ScoreCensusTable t;
+        memcpy(&t, (const char *)sl.pin_y + p.census.off, sizeof(t));
+        census_add(m->score_census, t, sl.batch, m->nb);
+    }
 }
 // c3_predict_wait, a scored batch that another pass answered in the end (the range guard's re-run under either policy, verify mode's
 // escalation): scored again on the rows it is answered with, from the labels still staged; the record and the values come over again
@@ -609,6 +646,7 @@ static int rescore(c3_model *m, HostSlot &sl, const float *rows) {
     TRY(use_lane(m, sl.lane));
     hipStream_t s = lane(m).stream;
     TRY(run_score(m, s, sl, p, sl.label_dtype, sl.batch, rows));
+    if (p.census.bytes) TRY(run_census(m, s, sl, p, sl.label_dtype, sl.batch, rows));
     HIP_TRY(hipMemcpyAsync((char *)sl.pin_y + p.score.off, (const char *)sl.dev_y + p.score.off, p.y_total - p.score.off, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
@@ -646,6 +684,7 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
         hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((in.batch * m->row + 255) / 256)), dim3(256), 0, s, sl.dev_y, in.batch * m->row, m->range_flag);
     if (p.verify.bytes) TRY(m->verify_ref == C3_VERIFY_REF_EXACT ? exact_shadow_pass(m, sl, in, p) : shadow_pass(m, sl, in, p));
     if (p.score.bytes) TRY(run_score(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
+    if (p.census.bytes) TRY(run_census(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
     // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
     // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
@@ -846,7 +885,7 @@ int c3_predict_wait(c3_model *m, int slot) {
     }
     if (sl.scored) {  // the record and the windows' values, of the rows the batch is answered with
         if (answered) TRY(rescore(m, sl, answered));
-        read_score(sl);
+        read_score(sl, m);
         if (sl.rows_home) return 0;
     }
     if (sl.y_dev_out) return 0;
@@ -1280,7 +1319,7 @@ int c3_model_set_score(c3_model *m, int enable, float gamma, const float *class_
     for (const HostSlot &sl : m->slot)
         if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
     if (!enable) {
-        m->score_on = false;
+        m->score_on = m->score_census_on = false;  // (the census needs score mode; its totals stay readable)
         return 0;
     }
     if (!(gamma >= 0.f) || !std::isfinite(gamma)) return fail("gamma must be a finite number >= 0, got %g", (double)gamma);
@@ -1288,6 +1327,33 @@ int c3_model_set_score(c3_model *m, int enable, float gamma, const float *class_
         if (!std::isfinite(class_weights[c])) return fail("class weight %d is not finite (%g)", c, (double)class_weights[c]);
     m->score_on = true, m->score_gamma = (double)gamma, m->score_weighted = class_weights != nullptr;
     for (int c = 0; c < kScoreMaxCols; ++c) m->score_w[c] = class_weights && c < m->nout ? class_weights[c] : 1.f;
+    return 0;
+}
+// ---- ... and its census (c3_census.h) ----
+int c3_model_set_score_census(c3_model *m, int enable) {
+    if (!m) return fail("null model");
+    if (!m->score_on) return fail("c3_model_set_score_census: score mode is off for this handle: call c3_model_set_score first");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    m->score_census_on = enable != 0;
+    if (enable && !m->score_census_seen) m->score_census_seen = true, m->score_census = c3_score_census{}, m->score_census.tasks = m->nb;
+    return 0;
+}
+static int census_entry_ok(const c3_model *m, const char *who) {
+    if (!m) return fail("null model");
+    if (!m->score_on) return fail("%s: score mode is off for this handle: call c3_model_set_score first", who);
+    if (!m->score_census_seen) return fail("%s: the census was never enabled on this handle: call c3_model_set_score_census first", who);
+    return 0;
+}
+int c3_score_census_read(c3_model *m, c3_score_census *out) {
+    TRY(census_entry_ok(m, "c3_score_census_read"));
+    if (!out) return fail("null argument: out");
+    *out = m->score_census;
+    return 0;
+}
+int c3_score_census_reset(c3_model *m) {
+    TRY(census_entry_ok(m, "c3_score_census_reset"));
+    m->score_census = c3_score_census{}, m->score_census.tasks = m->nb;
     return 0;
 }
 // what every score entry refuses first
@@ -1377,7 +1443,8 @@ int c3_score_rows(c3_model *m, const float *rows_host, int row_floats, int64_t b
     const size_t yb = (size_t)batch * row_floats * sizeof(float), lb = (size_t)batch * m->nout * (label_dtype == C3_DTYPE_F32 ? 4 : 1);
     const size_t vb = (size_t)batch * m->nb * sizeof(float);
     const size_t l_at = al(yb), p_at = al(l_at + lb), r_at = p_at + kScorePartBytes, v_at = r_at + kScoreRecordBytes;
-    TRY(ensure_decode_buf(m, v_at + vb));
+    const size_t c_at = al(v_at + vb), cb = m->score_census_on ? sizeof(ScoreCensusTable) : 0;  // (the census: its table behind the values)
+    TRY(ensure_decode_buf(m, cb ? c_at + cb : v_at + vb));
     TRY(use_lane(m, 0));
     hipStream_t s = lane(m).stream;
     char *base = (char *)m->decode_dev;
@@ -1385,8 +1452,14 @@ int c3_score_rows(c3_model *m, const float *rows_host, int row_floats, int64_t b
     TRY(h2d_staged(base + l_at, labels_host, lb, s));
     TRY(score_launch(m, s, (const float *)base, row_floats, base + l_at, label_dtype, batch, (float *)(base + v_at), (uint64_t *)(base + p_at),
                      (ScoreRecord *)(base + r_at)));
+    if (cb) TRY(census_launch(m, s, (const float *)base, row_floats, base + l_at, label_dtype, batch, (ScoreCensusTable *)(base + c_at)));
     TRY(d2h_staged(&rec, base + r_at, sizeof(rec), s));
     if (loss_host) TRY(d2h_staged(loss_host, base + v_at, vb, s));
+    if (cb) {
+        ScoreCensusTable t;
+        TRY(d2h_staged(&t, base + c_at, sizeof(t), s));
+        census_add(m->score_census, t, batch, m->nb);
+    }
     score_result(m, rec, out);
     return 0;
 }

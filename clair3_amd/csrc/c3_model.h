@@ -17,6 +17,8 @@
 //                  rows are compared on the device; with c3_model_set_verify_layers also the two forms' outputs of every layer (layer_compare_kernel)
 //   c3_score.h     score mode's two kernels and their record: the focal loss and arg-max accuracy of a labelled batch on the rows that answer
 //                  it (c3_hostring.h run_score; the entries c3_score_submit / _wait, c3_score, c3_score_rows sit at the end of that file)
+//   c3_census.h    score mode's census: the kernel that counts a scored batch's confusion, reliability and gap tables from the same rows, and
+//                  the batch's table (c3_hostring.h run_census; the entries c3_model_set_score_census, c3_score_census_read / _reset)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries;
 //                  the packing part of a full-alignment load (fa_pack_weights) and, on it, the range guard's policy C3_RANGE_RECALIBRATE: a trip
@@ -64,6 +66,7 @@
 #include "c3_dense.h"
 #include "c3_verify.h"
 #include "c3_score.h"
+#include "c3_census.h"
 
 using namespace c3;
 
@@ -175,6 +178,7 @@ struct StagedBatch {
     Section layers;     // ... with layer records (c3_model_set_verify_layers): one LayerRecord per layer in network order, behind the verify record
     Section score;      // a scored batch (c3_score.h): its ScoreRecord, behind everything above
     Section losses;     // ... and the windows' values [batch][tasks] float32 behind the record, when the caller asked for them
+    Section census;     // ... and the batch's ScoreCensusTable (c3_census.h) behind those, from a multiple of 256 bytes: only with the census on
     size_t y_total = 0;
     bool gather_only = false;  // a region / candidate batch the exact form reads (c3_exact.h exact_ring_pass): `depth` is staged (zeros where the
                                // caller gave none) only so that the pre-pass of c3_rescale.h gathers its windows; the product forms do not see it
@@ -438,6 +442,9 @@ struct c3_model {
     double score_gamma = 2.0;
     bool score_weighted = false;
     float score_w[kScoreMaxCols] = {};  // class weights in the row's column layout
+    // ... and its census (c3_model_set_score_census, c3_census.h): off = no section in a staged batch, nothing launched, nothing copied
+    bool score_census_on = false, score_census_seen = false;  // seen: is or was on -- c3_score_census_read / _reset answer
+    c3_score_census score_census = {};                        // totals of the completed batches since the last reset
 
     // ---- calibration (c3_calibrate.h; full alignment): off = nothing allocated, nothing launched, a load packs what it packs without it ----
     int census_pass = 0;              // forward_device is enqueuing a census pass: tap() takes the channels' maxima instead of copying

@@ -435,7 +435,8 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
     }
     if (m->exact.want) snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " exact=1");  // only while the exact form is enabled (c3_exact.h)
     if (m->score_on)  // only while score mode is enabled (c3_score.h)
-        snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " score=gamma:%g,weights:%d", m->score_gamma, (int)m->score_weighted);
+        snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " score=gamma:%g,weights:%d%s", m->score_gamma, (int)m->score_weighted,
+                 m->score_census_on ? ",census:1" : "");
     return 0;
 }
 

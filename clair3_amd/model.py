@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import synthetic as syn
 
 _NP_DTYPE = {np.dtype(np.int8): _lib.DTYPE_I8, np.dtype(np.int32): _lib.DTYPE_I32}
 
@@ -81,6 +82,7 @@ class _HipModel:
         self._answer = "product"      # what answers a batch of the ring (answer()) ...
         self._verify_ref = "fp32"     # ... and what verify mode compares with (verify(reference=)): both need the exact form, both travel with it
         self._score = None      # score mode (score_mode): (gamma, class weights or None) a handle created anew takes along
+        self._score_census = False  # ... and its census (score_census): on or off travels too, the totals belong to the handle
         self._range_policy = None  # the range-guard policy (range_policy): (policy, max_recalibrations) a handle created anew takes along
         self._recal_seen = 0       # recalibrations of the handle whose lowering self._lowering already mirrors (_sync_recalibration)
         self._calibration_file = None  # C3HIP_CALIBRATION of a model built without a checkpoint (predict.calibration_from_env): applied by the first load
@@ -128,6 +130,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_exact(self._handle, 1), "c3_model_set_exact")
         if self._score is not None:
             self._set_score(*self._score)
+            if self._score_census:
+                _lib.check(_lib.lib().c3_model_set_score_census(self._handle, 1), "c3_model_set_score_census")
         if self._range_policy is not None:  # (before the load: under "recalibrate" it keeps the tensors)
             _lib.check(_lib.lib().c3_model_set_range_policy(self._handle, *self._range_policy), "c3_model_set_range_policy")
         if sd is not None:
@@ -685,7 +689,7 @@ class _HipModel:
         self._need_handle()
         if not enable:
             _lib.check(_lib.lib().c3_model_set_score(self._handle, 0, 0.0, None), "c3_model_set_score")
-            self._score = None
+            self._score, self._score_census = None, False  # (the census needs score mode)
             return self
         try:
             gamma = float(gamma)
@@ -763,6 +767,38 @@ class _HipModel:
         _lib.check(_lib.lib().c3_score_rows(self._handle, rows.ctypes.data, rows.shape[1], rows.shape[0], labels.ctypes.data, ldt, C.byref(rec),
                                             None if wl is None else wl.ctypes.data), "c3_score_rows")
         return _score_result(rec, wl, None)
+
+    # ---- ... and its census: confusion, reliability and near-tie tables of the scored windows (c3_model_set_score_census) ----
+    def score_census(self, enable=True):
+        """Switch the census of score mode on or off: while on, every scored batch (score, submit_score / wait_score, score_rows) adds its
+        windows to the handle's tables, counted on the device from the rows the batch is answered with.  Enables score mode with its defaults
+        when it is off; refused while a submit is pending."""
+        if not isinstance(enable, (bool, np.bool_)):
+            raise _lib.C3Error(f"enable must be True or False, got {enable!r}")
+        self._need_handle()
+        if enable and self._score is None:
+            self.score_mode()
+        _lib.check(_lib.lib().c3_model_set_score_census(self._handle, int(enable)), "c3_model_set_score_census")
+        self._score_census = bool(enable)
+        return self
+
+    def census(self):
+        """The census since the last census_reset() (c3_score_census_read) as a synthetic.Census: ``confusion`` four (K, K) int64 arrays
+        [truth][pred], ``rel_windows`` / ``rel_correct`` / ``rel_conf_q32`` (4, 20), ``rel_skipped`` (4,), ``gap_below`` (4, 6), ``windows``,
+        ``tasks``.  evaluate.census_report turns it into accuracy, precision / recall / F1 and the calibration error."""
+        self._need_handle()
+        rec = _lib.ScoreCensus()
+        _lib.check(_lib.lib().c3_score_census_read(self._handle, C.byref(rec)), "c3_score_census_read")
+        flat = np.ctypeslib.as_array(rec.confusion).astype(np.int64)
+        conf = [flat[o:o + k * k].reshape(k, k).copy() for o, k in zip(syn.CENSUS_CELL_OFF, syn.HEAD_SIZES)]
+        arr = lambda a: np.ctypeslib.as_array(a).astype(np.int64)  # noqa: E731
+        return syn.Census(int(rec.windows), int(rec.tasks), conf, arr(rec.rel_windows), arr(rec.rel_correct), arr(rec.rel_conf_q32),
+                          arr(rec.rel_skipped), arr(rec.gap_below))
+
+    def census_reset(self):
+        self._need_handle()
+        _lib.check(_lib.lib().c3_score_census_reset(self._handle), "c3_score_census_reset")
+        return self
 
     # ---- the exact form: the network in fp64 from end to end on the device (c3_predict_exact; DESIGN.md 4) ----
     def exact(self, enable=True):

@@ -9,6 +9,7 @@ state_dict key names / shapes follow the reference modules:
   Clair3_P -- /root/reference/clair3/model.py:96-125
   Clair3_F -- /root/reference/clair3/model.py:317-365 (+ BasicConv2D :183-197, BasicBlock :200-235)
 """
+import collections
 from collections import OrderedDict
 
 import numpy as np
@@ -488,3 +489,60 @@ def focal_scores(rows, labels, gamma=2.0, class_weights=None):
         loss_sum = loss_sum + window_loss[b]
     return dict(window_loss=window_loss, loss_sum=loss_sum, correct=correct, nonfinite=int((~np.isfinite(p)).any(1).sum()) if B else 0,
                 windows=B, tasks=len(heads))
+
+
+# ---- score mode's census in numpy: the rule of csrc/c3_census.h, whose definitions these constants repeat (tests/test_score_census.py
+# holds them against that header) ----
+CENSUS_BINS = 20                                                                  # kScoreCensusBins
+CENSUS_GAP_THR = np.array([1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1], dtype=np.float32)  # score_census_gap_thr
+CENSUS_CONF_UNIT = 2.0 ** 32                                                      # kScoreCensusConfUnit
+CENSUS_CELL_OFF = (0, 441, 450, 1539)                                             # kScoreCensusCellOff: task t's K_t x K_t cells of c3_score_census.confusion
+
+# what score_census and Clair3_P/F.census() return: ``confusion`` four (K_t, K_t) int64 arrays [truth][pred]; ``rel_windows``, ``rel_correct``,
+# ``rel_conf_q32`` (4, 20) int64; ``rel_skipped`` (4,); ``gap_below`` (4, 6), cumulative.  The tables of tasks a model lacks are zero.
+Census = collections.namedtuple("Census", "windows tasks confusion rel_windows rel_correct rel_conf_q32 rel_skipped gap_below")
+
+
+def empty_census(tasks=0):
+    return Census(0, tasks, [np.zeros((k, k), np.int64) for k in HEAD_SIZES], np.zeros((4, CENSUS_BINS), np.int64),
+                  np.zeros((4, CENSUS_BINS), np.int64), np.zeros((4, CENSUS_BINS), np.int64), np.zeros(4, np.int64),
+                  np.zeros((4, len(CENSUS_GAP_THR)), np.int64))
+
+
+def score_census(rows, labels):
+    """The census of score mode (c3_model_set_score_census; csrc/c3_census.h states the rule and its constants) of labelled float32 rows:
+    per task the confusion table of arg-max(y) against arg-max(p) -- the arg-maxima of focal_scores' ``correct`` -- the reliability table
+    over 20 confidence bins with fixed-point confidence sums, and the cumulative counts of windows whose best two probabilities lie closer
+    than 1e-6 .. 1e-1.  rows: (B, >= nout) float32 probabilities as they come out (not clamped); labels: (B, nout).  Returns a Census."""
+    labels = np.asarray(labels)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or labels.ndim != 2 or rows.shape[0] != labels.shape[0] or rows.shape[1] < labels.shape[1] or labels.shape[1] not in (24, 90):
+        raise ValueError(f"rows {rows.shape} and labels {labels.shape} do not belong together")
+    nout = labels.shape[1]
+    p_all, y_all = rows[:, :nout].astype(np.float32, copy=False), labels.astype(np.float32)
+    heads = head_slices(nout)
+    B = len(p_all)
+    out = empty_census(len(heads))._replace(windows=B)
+    if B == 0:
+        return out
+    at = np.arange(B)
+    for t, (lo, hi) in enumerate(heads):
+        p = np.where(np.isnan(p_all[:, lo:hi]), np.float32(-np.inf), p_all[:, lo:hi])  # a NaN is never a maximum
+        y = np.where(np.isnan(y_all[:, lo:hi]), np.float32(-np.inf), y_all[:, lo:hi])
+        pred, truth = p.argmax(1), y.argmax(1)  # the first maximum; index 0 when nothing exceeds -inf
+        np.add.at(out.confusion[t], (truth, pred), 1)
+        conf = p[at, pred]  # -inf when the head is all NaN
+        others = p.copy()
+        others[at, pred] = -np.inf
+        second = others.max(1)
+        with np.errstate(invalid="ignore"):
+            gap = conf - second  # float32
+            ok = np.isfinite(conf) & (conf >= 0) & (conf <= 1)
+            b = np.minimum(CENSUS_BINS - 1, (conf[ok] * np.float32(CENSUS_BINS)).astype(np.int64))
+            np.add.at(out.rel_windows[t], b, 1)
+            np.add.at(out.rel_correct[t], b, (pred == truth)[ok].astype(np.int64))
+            np.add.at(out.rel_conf_q32[t], b, np.rint(conf[ok].astype(np.float64) * CENSUS_CONF_UNIT).astype(np.int64))
+            out.rel_skipped[t] = int((~ok).sum())
+            for k, thr in enumerate(CENSUS_GAP_THR):
+                out.gap_below[t, k] = int((gap < thr).sum())
+    return out

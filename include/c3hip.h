@@ -702,6 +702,39 @@ int c3_score(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const 
 int c3_score_rows(c3_model *m, const float *rows_host, int row_floats, int64_t batch, const void *labels_host, int label_dtype, c3_score_result *out,
                   float *loss_host);
 
+/* ---- score mode's census: per-class confusion, reliability and near-tie tables of the scored windows, counted on the device ----
+ * Replaces asking for every row (rows of 96 - 360 B per window across PCIe) and counting on the host; the reference has nothing of the
+ * kind (clair3/Train.py:210-257 returns a loss).  The rule, with its bins, thresholds and fixed-point unit: clair3_amd/csrc/c3_census.h;
+ * in numpy: synthetic.score_census.  Per window and task t (K_t = 21, 3, 33, 33 classes), from the float32 probabilities as they come out:
+ *   confusion     [truth][pred] += 1 with the arg-maxima the `correct` count of c3_score_result compares: sum == windows, trace == correct[t]
+ *   rel_*         conf = p[pred]; finite and in [0, 1]: bin b = min(19, (int)(conf * 20.0f)), rel_windows[t][b] += 1, rel_correct[t][b] +=
+ *                 (pred == truth), rel_conf_q32[t][b] += (int64)rint(conf * 2^32) (mean confidence of a bin: rel_conf_q32 / 2^32 /
+ *                 rel_windows); otherwise rel_skipped[t] += 1
+ *   gap_below     gap = conf - (the best probability among the other classes), float32; [t][k] += (gap < 1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1),
+ *                 cumulative; a NaN or infinite gap is counted nowhere
+ * Integers throughout: the totals do not depend on chunking, slots, lanes or the order of anything.
+ *   c3_model_set_score_census  enable != 0: every later scored batch (c3_score_submit / _wait, c3_score, c3_score_rows) fills a table on
+ *                       the device behind its record, from the rows it is answered with (a batch the range guard re-runs or verify mode
+ *                       escalates or repairs is counted once, on those rows), and whichever of c3_score_wait / c3_predict_wait completes
+ *                       it adds the table to the handle's totals.  Needs c3_model_set_score; refused while a submit is pending.
+ *                       c3_model_describe's score field then ends on ",census:1".  Off (the default): no section in a staged batch, no
+ *                       launch, no byte copied -- a scored batch is what it was.  On: one memset and one launch per batch and 12032 bytes more
+ *                       on the batch's way back.
+ *   c3_score_census_read   the totals since the last reset (a 24-column model has two tasks: the tables of the other two stay zero)
+ *   c3_score_census_reset  zeroes them
+ * Errors: a null handle, a null `out`, a handle without score mode, read or reset on a handle that never enabled the census. */
+typedef struct {
+    int64_t windows;
+    int32_t tasks, reserved;
+    int64_t confusion[2628];      /* task t from offset 0, 441, 450, 1539: [truth][pred], K_t x K_t */
+    int64_t rel_windows[4][20], rel_correct[4][20], rel_conf_q32[4][20];
+    int64_t rel_skipped[4];
+    int64_t gap_below[4][6];
+} c3_score_census;
+int c3_model_set_score_census(c3_model *m, int enable);
+int c3_score_census_read(c3_model *m, c3_score_census *out);
+int c3_score_census_reset(c3_model *m);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
