@@ -37,6 +37,7 @@ EXPORTS = (
     "c3_predict_submit_parts", "c3_predict_parts",
     "c3_model_set_score", "c3_score_submit", "c3_score_wait", "c3_score", "c3_score_rows",
     "c3_model_set_score_census", "c3_score_census_read", "c3_score_census_reset",
+    "c3_model_set_refine", "c3_model_refine_stats", "c3_model_refine_reset", "c3_refine_select",
 )
 MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
@@ -110,6 +111,13 @@ class ScoreCensus(C.Structure):
     _fields_ = [("windows", C.c_int64), ("tasks", C.c_int32), ("reserved", C.c_int32), ("confusion", C.c_int64 * 2628),
                 ("rel_windows", (C.c_int64 * 20) * 4), ("rel_correct", (C.c_int64 * 20) * 4), ("rel_conf_q32", (C.c_int64 * 20) * 4),
                 ("rel_skipped", C.c_int64 * 4), ("gap_below", (C.c_int64 * 6) * 4)]
+
+
+class RefineStats(C.Structure):
+    """c3_refine_stats (include/c3hip.h)"""
+    _fields_ = [("batches", C.c_int64), ("batches_refined", C.c_int64), ("batches_skipped", C.c_int64), ("windows", C.c_int64),
+                ("windows_selected", C.c_int64), ("windows_changed", C.c_int64), ("head_selected", C.c_int64 * 4),
+                ("decoder_selected", C.c_int64), ("min_gap", C.c_float * 4), ("max_abs_diff", C.c_float), ("gap", C.c_float)]
 
 
 class C3Error(RuntimeError):
@@ -239,6 +247,10 @@ def lib():
     L.c3_model_set_score_census.argtypes = [C.c_void_p, C.c_int]
     L.c3_score_census_read.argtypes = [C.c_void_p, C.POINTER(ScoreCensus)]
     L.c3_score_census_reset.argtypes = [C.c_void_p]
+    L.c3_model_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.c3_model_refine_stats.argtypes = [C.c_void_p, C.POINTER(RefineStats)]
+    L.c3_model_refine_reset.argtypes = [C.c_void_p]
+    L.c3_refine_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
     L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

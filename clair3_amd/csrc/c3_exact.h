@@ -746,6 +746,62 @@ static int exact_ring_pass(c3_model *m, hipStream_t s, HostSlot &sl, const Stage
     return 0;
 }
 
+// Refine mode's second pass (c3_refine.h; c3_hostring.h refine_account calls it from c3_predict_wait): the n_sel selected windows of the batch
+// that came home in slot sl, in the batch's lane.  Per pass of C3HIP_EXACT_CHUNK windows: gathered from the staged image into the exact
+// form's own window buffer (ExactState::x, the handle's: grown on demand, freed with it), exact_pass, the rows rounded to float32 into the
+// handle's compact row buffer; then the decoder columns of those rows, the scatter into the batch's rows -- in the slot, or in the caller's
+// device buffer --, the repaired rows and the record on their way to the pinned buffer, one synchronize.  Ordered behind the passes of other
+// lanes by ExactState::ring_ev as exact_ring_pass is
+static int refine_pass(c3_model *m, HostSlot &sl, int64_t n_sel) {
+    ExactState &E = m->exact;
+    const StagedBatch &p = sl.plan;
+    if (!E.loaded) return fail("refine mode: the exact form was not enabled at the last load: c3_model_set_exact(m, 1), then c3_model_load");
+    TRY(use_lane(m, sl.lane));
+    hipStream_t s = lane(m).stream;
+    char *section = (char *)sl.dev_y + p.refine.off;
+    const int32_t *index = (const int32_t *)(section + kRefineRecordBytes);
+    const int64_t chunk = exact_chunk(m), wbytes = c3_model_window_bytes(m, sl.x_dtype);
+    TRY(exact_ensure_workspace(m, std::min(n_sel, chunk), sl.x_dtype == C3_DTYPE_I32 ? 4 : 1));
+    const size_t row_bytes = (size_t)n_sel * m->row * sizeof(float);
+    if (row_bytes > m->refine_rows_bytes) {  // (every earlier second pass ended with a synchronize: nothing reads the smaller one)
+        if (m->refine_rows) (void)hipFree(m->refine_rows);
+        m->refine_rows = nullptr, m->refine_rows_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&m->refine_rows, row_bytes));
+        m->refine_rows_bytes = row_bytes;
+    }
+    if (!E.ring_ev) HIP_TRY(hipEventCreateWithFlags(&E.ring_ev, hipEventDisableTiming));
+    if (E.ring_recorded) HIP_TRY(hipStreamWaitEvent(s, E.ring_ev, 0));
+    for (int64_t off = 0; off < n_sel; off += chunk) {
+        const int64_t n = std::min(chunk, n_sel - off);
+        if (wbytes % 8 == 0) hipLaunchKernelGGL(refine_gather_kernel<8>, dim3((unsigned)n), dim3(256), 0, s, (const char *)sl.dev_x, index + off, (char *)E.x, wbytes);
+        else hipLaunchKernelGGL(refine_gather_kernel<1>, dim3((unsigned)n), dim3(256), 0, s, (const char *)sl.dev_x, index + off, (char *)E.x, wbytes);
+        HIP_TRY(hipGetLastError());
+        TRY(exact_pass(m, s, E.x, sl.x_dtype, n));
+        hipLaunchKernelGGL(exact_rows_to_f32_kernel<>, dim3((unsigned)((n * m->nout + 255) / 256)), dim3(256), 0, s, (const double *)E.y,
+                           m->refine_rows + off * m->row, (double *)nullptr, n, m->nout, m->row);
+        HIP_TRY(hipGetLastError());
+        E.last_n = n;
+    }
+    HIP_TRY(hipEventRecord(E.ring_ev, s));
+    E.ring_recorded = true;
+    if (m->row > m->nout) {  // decoder columns of the refined rows, from their refined probabilities
+        DecodeParams dp{m->refine_rows, m->row, nullptr, nullptr, nullptr, nullptr, m->refine_rows + m->nout, (int)n_sel, m->nout == 90 ? 1 : 0};
+        hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((n_sel + 3) / 4)), dim3(256), 0, s, dp);
+        HIP_TRY(hipGetLastError());
+    }
+    RefineScatterParams sp;
+    sp.refined = m->refine_rows, sp.index = index, sp.rows = sl.y_dev_out ? sl.y_dev_out : sl.dev_y, sp.rec = (RefineRecord *)section;
+    sp.stride = m->row, sp.nout = m->nout, sp.n = (int)n_sel;
+    hipLaunchKernelGGL(refine_scatter_kernel, dim3(refine_blocks(n_sel)), dim3(kRefineThreads), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    // rows that came to this host: the batch's rows and its record again (one transfer: the sections lie behind each other); rows that stay on
+    // the device: the record
+    if (sl.y_dev_out) HIP_TRY(hipMemcpyAsync((char *)sl.pin_y + p.refine.off, section, kRefineRecordBytes, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(hipMemcpyAsync(sl.pin_y, sl.dev_y, p.refine.off + kRefineRecordBytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // C3_VERIFY_REPLACE behind the comparison (either reference): the rows under test are repaired where they are, in front of their copy-out;
 // the count lands in the verify record's section.  ref64: the exact rows (nullptr: the reference is the fp32 rows at the front of sl.shadow)
 static int verify_replace_launch(c3_model *m, hipStream_t s, HostSlot &sl, const RingInput &in, const StagedBatch &p, const double *ref64) {
@@ -823,6 +879,7 @@ int c3_model_set_exact(c3_model *m, int enable) {
     if (!enable && m->answer_exact) return fail("c3_model_set_exact: the handle answers from the exact form: c3_model_set_answer(m, C3_ANSWER_PRODUCT) first");
     if (!enable && m->verify_ref == C3_VERIFY_REF_EXACT)
         return fail("c3_model_set_exact: verify mode's reference is the exact form: c3_model_set_verify_reference(m, C3_VERIFY_REF_FP32) first");
+    if (!enable && m->refine_on) return fail("c3_model_set_exact: refine mode answers near-ties from the exact form: c3_model_set_refine(m, 0, 0) first");
     m->exact.want = enable != 0;
     return 0;
 }

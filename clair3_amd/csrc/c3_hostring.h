@@ -234,7 +234,7 @@ static const int32_t *deep_depths(c3_model *m, const RingInput &in) {
 
 // THE layout of a staged batch (c3_model.h StagedBatch), for every kind: nothing else computes an offset.  The kernels' alignment
 // assumptions hang on it: sections from multiples of 256 bytes, the 8-byte pieces of expand_rows_kernel, the 16-byte pieces of host_copy_kernel
-static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth, bool verify = false, bool layers = false) {
+static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_depth, bool verify = false, bool layers = false, bool refine = false) {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const bool cand = in.kind == InKind::Candidates, region = cand || in.kind == InKind::Region, rows = is_rows(in.kind);
     const size_t n = (size_t)in.batch, db = with_depth ? n * sizeof(int32_t) : 0;
@@ -270,6 +270,11 @@ static StagedBatch plan_batch(const c3_model *m, const RingInput &in, bool with_
         // ... and, only while the handle's census is on (c3_census.h), the batch's table behind those
         if (m->score_census_on) p.census.off = al(p.y_total), p.census.bytes = kScoreCensusBytes, p.y_total = p.census.off + p.census.bytes;
     }
+    // ... and, only while refine mode is on and covers the batch (c3_refine.h; never together with a verify record), its record and the list of
+    // selected windows behind everything else; rows that stay on the device: all the slot's output buffer holds
+    if (refine)
+        p.refine.off = in.y_dev ? 0 : al(p.y_total), p.refine.bytes = kRefineRecordBytes + ((n * sizeof(int32_t) + 15) & ~(size_t)15),
+        p.y_total = p.refine.off + p.refine.bytes;
     return p;
 }
 
@@ -425,6 +430,66 @@ static int exact_shadow_pass(c3_model *m, HostSlot &sl, const RingInput &in, con
 static int verify_replace_launch(c3_model *m, hipStream_t s, HostSlot &sl, const RingInput &in, const StagedBatch &p, const double *ref64);
 // the depths the product and fp32 forms see of a staged batch: none where they were staged for the exact form's gather only (StagedBatch::gather_only)
 static const int32_t *ring_depth(const HostSlot &sl, const StagedBatch &p) { return p.gather_only ? nullptr : sl.dev<const int32_t>(p.depth); }
+
+// ---- refine mode (c3_refine.h): the selection behind the product pass, and what c3_predict_wait does with its record
+// the two selection launches on stream s over `rows` (row stride `stride`): the windows' minimum gaps, bits and the workgroups' partials into
+// `scratch` (RefineScratch(batch).bytes), the record and the ascending list of selected windows into `section`
+static int refine_select_launch(hipStream_t s, const float *rows, int stride, int nout, int64_t batch, float gap, void *scratch, void *section) {
+    const RefineScratch at(batch);
+    RefineGapParams gp;
+    gp.rows = rows, gp.min_gap = (float *)scratch, gp.bits = (uint8_t *)scratch + at.bits_at, gp.part = (RefinePart *)((char *)scratch + at.part_at);
+    gp.stride = stride, gp.nout = nout, gp.batch = (int)batch, gp.gap = gap;
+    const unsigned blocks = refine_blocks(batch);
+    hipLaunchKernelGGL(rows_gap_kernel, dim3(blocks), dim3(kRefineThreads), 0, s, gp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refine_compact_kernel, dim3(blocks), dim3(64), 0, s, (const uint8_t *)gp.bits, (const RefinePart *)gp.part, (int)batch,
+                       (int32_t *)((char *)section + kRefineRecordBytes), (RefineRecord *)section);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// which batches the mode covers (c3_model_set_refine in include/c3hip.h lists the ones it does not: they count as skipped)
+static bool refine_covers(const c3_model *m, const RingInput &in) {
+    return m->refine_on && in.batch > 0 && in.batch <= kRefineMaxBatch && (in.kind == InKind::Sliced || in.kind == InKind::Parts) && !in.depth &&
+           !in.score && !m->answer_exact;
+}
+static int run_refine_select(c3_model *m, hipStream_t s, HostSlot &sl, const StagedBatch &p, int64_t batch, const float *rows) {
+    const RefineScratch at(batch);
+    if (at.bytes > sl.refine_scratch_bytes) {  // (the slot is free: nothing reads the buffer)
+        if (sl.refine_scratch) (void)hipFree(sl.refine_scratch);
+        sl.refine_scratch = nullptr, sl.refine_scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&sl.refine_scratch, at.bytes));
+        sl.refine_scratch_bytes = at.bytes;
+    }
+    ProfScope ps(m, s, m->kind == C3_KIND_PILEUP ? "p.refine" : "fa.refine", 0.0, (double)batch * m->row * 4.0);
+    return refine_select_launch(s, rows, m->row, m->nout, batch, m->refine_gap, sl.refine_scratch, (char *)sl.dev_y + p.refine.off);
+}
+// the second pass over the selected windows of a batch that came home (c3_exact.h, behind exact_pass)
+static int refine_pass(c3_model *m, HostSlot &sl, int64_t n_sel);
+static void refine_zero(c3_model *m) {
+    m->rfstats = c3_refine_stats{};
+    for (float &g : m->rfstats.min_gap) g = INFINITY;
+}
+// c3_predict_wait, a batch submitted while the mode was on: it joins the totals; one with selected windows runs its second pass here, in its
+// lane.  The range guard keeps priority: a batch it answered is not refined
+static int refine_account(c3_model *m, HostSlot &sl, bool guarded) {
+    const StagedBatch &p = sl.plan;
+    c3_refine_stats &t = m->rfstats;
+    ++t.batches;
+    if (!p.refine.bytes || guarded) return ++t.batches_skipped, 0;
+    const RefineRecord *r = (const RefineRecord *)((const char *)sl.pin_y + p.refine.off);
+    if (r->windows != (uint32_t)sl.batch || r->selected > r->windows)
+        return fail("internal: the refine record counts %u of %u windows selected in a batch of %lld", r->selected, r->windows, (long long)sl.batch);
+    if (r->selected > 0) {
+        TRY(refine_pass(m, sl, r->selected));  // (the record comes home again, with what the scatter kernel counted)
+        ++t.batches_refined;
+    }
+    t.windows += r->windows, t.windows_selected += r->selected, t.windows_changed += r->changed, t.decoder_selected += r->decoder;
+    for (int k = 0; k < 4; ++k) t.head_selected[k] += r->head[k], t.min_gap[k] = std::min(t.min_gap[k], r->min_gap[k]);
+    float d;
+    memcpy(&d, &r->max_diff_bits, sizeof(d));
+    t.max_abs_diff = std::max(t.max_abs_diff, d);
+    return 0;
+}
 
 // ---- verify mode (c3_verify.h): which batches, the second pass, what c3_predict_wait does with the record
 // The submits with batch > 0 are numbered; number k is selected when k % every == 0.  A selected batch that cannot be verified counts as skipped.
@@ -685,6 +750,7 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
     if (p.verify.bytes) TRY(m->verify_ref == C3_VERIFY_REF_EXACT ? exact_shadow_pass(m, sl, in, p) : shadow_pass(m, sl, in, p));
     if (p.score.bytes) TRY(run_score(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
     if (p.census.bytes) TRY(run_census(m, s, sl, p, in.label_dtype, in.batch, sl.dev_y));
+    if (p.refine.bytes) TRY(run_refine_select(m, s, sl, p, in.batch, in.y_dev ? in.y_dev : sl.dev_y));
     // the rows (96 - 484 B per window) and the range flag leave through a copy kernel on the COMPUTE stream, whatever the
     // batch: handing them to a transfer stream (event, cross-queue wait, two DMA copies, event) cost the compute queue
     // ~75 us per batch -- 538 k -> 647 k windows/s host to host at B = 256 (profiles/r03_e_d2h_by_kernel.txt)
@@ -694,7 +760,7 @@ static int launch_batch(c3_model *m, HostSlot &sl, const RingInput &in, const St
                            (uint4 *)((char *)sl.pin_y + from), (p.y_total - from + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
     } else
         hipLaunchKernelGGL(host_copy_kernel, dim3(in.y_dev ? 1 : rows_out_grid(p.y_total)), dim3(256), 0, s, (const uint4 *)sl.dev_y, (uint4 *)sl.pin_y,
-                           in.y_dev ? (p.verify.bytes + p.layers.bytes) / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
+                           in.y_dev ? (p.verify.bytes + p.layers.bytes + p.refine.bytes) / 16 : (p.y_total + 15) / 16, (const uint32_t *)m->range_flag, sl.pin_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_out, s));
     sl.used_f16 = f16;
@@ -713,6 +779,7 @@ static void record_batch(const c3_model *m, HostSlot &sl, const RingInput &in, c
     sl.pack_epoch = m->pack_epoch;
     sl.scored = in.score, sl.rows_home = in.score && !in.y_host, sl.label_dtype = in.label_dtype, sl.loss_host = in.loss_host;
     sl.score_rec = ScoreRecord{}, sl.score_rec.tasks = m->nb;  // (a batch of no windows: what c3_score_wait reports)
+    sl.refine_on = m->refine_on;
     sl.busy = true;
 }
 
@@ -747,12 +814,12 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         if (!in.depth) no_depth.assign((size_t)in.batch, 0);
         depth = in.depth ? in.depth : no_depth.data(), gather_only = true;
     }
-    StagedBatch p = plan_batch(m, in, depth != nullptr, verify, m->verify_layers);
+    StagedBatch p = plan_batch(m, in, depth != nullptr, verify, m->verify_layers, refine_covers(m, in));
     p.gather_only = gather_only;
     Filled f;
     if (in.batch > 0) {
         // the slot becomes busy only once everything has been queued: a failure on the way leaves it free
-        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes + p.layers.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
+        TRY(ensure_slot(sl, p.x_cap, in.y_dev ? p.verify.bytes + p.layers.bytes + p.refine.bytes : p.y_total));  // (rows that stay on the device need no slot buffers)
         switch (in.kind) {
         case InKind::Sliced: fill_sliced(sl, in, p, depth, f), fill_labels(sl, in, p); break;
         case InKind::Region: fill_region(m, sl, in, p, depth, f); break;
@@ -883,6 +950,7 @@ int c3_predict_wait(c3_model *m, int slot) {
             answered = sl.shadow;
         }
     }
+    if (sl.refine_on) TRY(refine_account(m, sl, guarded));  // refine mode (c3_refine.h): the windows near a tie are answered by the exact form
     if (sl.scored) {  // the record and the windows' values, of the rows the batch is answered with
         if (answered) TRY(rescore(m, sl, answered));
         read_score(sl, m);
@@ -1197,6 +1265,8 @@ int c3_model_set_verify(c3_model *m, int every, float tol, float near_tie, int p
         return fail("policy must be C3_VERIFY_REPORT, C3_VERIFY_ESCALATE or C3_VERIFY_REPLACE, got %d", policy);
     for (const HostSlot &sl : m->slot)
         if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (every > 0 && m->refine_on)
+        return fail("c3_model_set_verify: refine mode is on for this handle (c3_model_set_refine) and the two own the same rows: switch it off first");
     if (every > 0 && !m->verify_seen) verify_zero(m);
     m->verify_every = every, m->verify_tol = tol, m->verify_near_tie = near_tie, m->verify_policy = policy;
     m->verify_seen |= every > 0;
@@ -1240,6 +1310,39 @@ int c3_model_verify_layers(c3_model *m, c3_verify_layer *out, int max_entries) {
         out[k].status = out[k].batches > 0 ? C3_VERIFY_LAYER_COMPARED : m->vlayer_batches > 0 ? C3_VERIFY_LAYER_FUSED : C3_VERIFY_LAYER_NONE;
     }
     return nl;
+}
+
+// ---- refine mode (c3_refine.h): the setting and the totals; the selection alone is c3_refine_select, behind the decoder entries ----
+int c3_model_set_refine(c3_model *m, int enable, float gap) {
+    if (!m) return fail("null model");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    if (!enable) {
+        m->refine_on = false;
+        return 0;
+    }
+    if (!(gap >= 0.f) || !std::isfinite(gap)) return fail("c3_model_set_refine: gap must be a finite number >= 0, got %g", (double)gap);
+    if (m->verify_every > 0)
+        return fail("c3_model_set_refine: verify mode is on for this handle (c3_model_set_verify) and the two own the same rows: switch it off first");
+    if (!m->exact.loaded)
+        return fail("c3_model_set_refine: the exact form was not enabled at the last load: c3_model_set_exact(m, 1), then c3_model_load");
+    if (!m->refine_seen) refine_zero(m);
+    m->refine_on = m->refine_seen = true, m->refine_gap = gap;
+    return 0;
+}
+int c3_model_refine_stats(c3_model *m, c3_refine_stats *out) {
+    if (!m || !out) return fail("null argument");
+    if (!m->refine_seen) refine_zero(m);
+    *out = m->rfstats;
+    out->gap = m->refine_gap;
+    return 0;
+}
+int c3_model_refine_reset(c3_model *m) {
+    if (!m) return fail("null model");
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    refine_zero(m);
+    return 0;
 }
 
 // the handle's scratch buffer of the two decoder entries below: grown, never shrunk
@@ -1310,6 +1413,38 @@ int c3_decode_columns(c3_model *m, const float *y_host, int64_t batch, float *ro
     hipLaunchKernelGGL(outcome_maxima_kernel<true>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, lane(m).stream, dp);
     HIP_TRY(hipGetLastError());
     TRY(d2h_staged(rows_host, rows, total, lane(m).stream));
+    return 0;
+}
+
+// refine mode's selection on rows the caller brings (hand-made corners, another form's rows) without a forward pass: rows, scratch, record
+// and list in the handle's decoder scratch, the two launches in the first lane
+int c3_refine_select(c3_model *m, const float *rows_host, int row_floats, int64_t batch, float gap, int32_t *index_out, int64_t *n_out, float *gaps_out) {
+    if (!m) return fail("null model");
+    if (!n_out) return fail("null argument: n_out");
+    if (batch < 0) return fail("negative batch");
+    if (batch > kRefineMaxBatch) return fail("c3_refine_select: too many windows for one call (%lld)", (long long)batch);
+    if (row_floats != m->nout && row_floats != m->nout + kDecodeCols)
+        return fail("c3_refine_select: rows of %d floats: this model has %d probabilities, %d with the decoder columns", row_floats, m->nout, m->nout + kDecodeCols);
+    if (!(gap >= 0.f) || !std::isfinite(gap)) return fail("c3_refine_select: gap must be a finite number >= 0, got %g", (double)gap);
+    *n_out = 0;
+    if (batch == 0) return 0;
+    if (!rows_host || !index_out) return fail("null buffer: rows / index_out");
+    HIP_TRY(hipSetDevice(m->device));
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const RefineScratch at(batch);
+    const size_t yb = (size_t)batch * row_floats * sizeof(float), s_at = al(yb), r_at = al(s_at + at.bytes);
+    TRY(ensure_decode_buf(m, r_at + kRefineRecordBytes + (size_t)batch * sizeof(int32_t)));
+    TRY(use_lane(m, 0));
+    hipStream_t s = lane(m).stream;
+    char *base = (char *)m->decode_dev;
+    TRY(h2d_staged(base, rows_host, yb, s));
+    TRY(refine_select_launch(s, (const float *)base, row_floats, m->nout, batch, gap, base + s_at, base + r_at));
+    RefineRecord rec;
+    TRY(d2h_staged(&rec, base + r_at, sizeof(rec), s));
+    if (rec.windows != (uint32_t)batch || rec.selected > rec.windows) return fail("internal: the refine record counts %u of %u windows selected", rec.selected, rec.windows);
+    if (rec.selected) TRY(d2h_staged(index_out, base + r_at + kRefineRecordBytes, (size_t)rec.selected * sizeof(int32_t), s));
+    if (gaps_out) TRY(d2h_staged(gaps_out, base + s_at, (size_t)batch * sizeof(float), s));
+    *n_out = rec.selected;
     return 0;
 }
 

@@ -19,6 +19,8 @@
 //                  it (c3_hostring.h run_score; the entries c3_score_submit / _wait, c3_score, c3_score_rows sit at the end of that file)
 //   c3_census.h    score mode's census: the kernel that counts a scored batch's confusion, reliability and gap tables from the same rows, and
 //                  the batch's table (c3_hostring.h run_census; the entries c3_model_set_score_census, c3_score_census_read / _reset)
+//   c3_refine.h    refine mode: the kernels that find the windows of a batch near a tie, gather them for the exact form and put the refined
+//                  rows back (c3_hostring.h run_refine_select, c3_predict_wait; c3_exact.h refine_pass; the entries c3_model_set_refine, ...)
 //   c3_debug.h     c3_debug_* / c3_profile_* (parity tests, bench.py)
 //   c3_calibrate.h full alignment: channel exponents calibrated from observed activations -- the census kernel and pass, the rule, the entries;
 //                  the packing part of a full-alignment load (fa_pack_weights) and, on it, the range guard's policy C3_RANGE_RECALIBRATE: a trip
@@ -67,6 +69,7 @@
 #include "c3_verify.h"
 #include "c3_score.h"
 #include "c3_census.h"
+#include "c3_refine.h"
 
 using namespace c3;
 
@@ -179,6 +182,8 @@ struct StagedBatch {
     Section score;      // a scored batch (c3_score.h): its ScoreRecord, behind everything above
     Section losses;     // ... and the windows' values [batch][tasks] float32 behind the record, when the caller asked for them
     Section census;     // ... and the batch's ScoreCensusTable (c3_census.h) behind those, from a multiple of 256 bytes: only with the census on
+    Section refine;     // refine mode (c3_refine.h): the batch's RefineRecord and int32[batch] selected windows behind everything above (rows that stay
+                        // on the device: the only section) -- only while the mode is on, for a batch it covers
     size_t y_total = 0;
     bool gather_only = false;  // a region / candidate batch the exact form reads (c3_exact.h exact_ring_pass): `depth` is staged (zeros where the
                                // caller gave none) only so that the pre-pass of c3_rescale.h gathers its windows; the product forms do not see it
@@ -241,6 +246,11 @@ struct HostSlot {
     float *loss_host = nullptr;
     uint64_t *score_part = nullptr;
     ScoreRecord score_rec = {};  // of the batch c3_predict_wait completed last (c3_score_wait hands it over)
+    // refine mode (c3_refine.h): refine_on -- the mode was on when the batch in flight was submitted (it counts in the totals, refined or
+    // skipped); the selection's scratch (RefineScratch) is the slot's, allocated on first use
+    bool refine_on = false;
+    void *refine_scratch = nullptr;
+    size_t refine_scratch_bytes = 0;
     // a section of the staged batch on the device / in the pinned input buffer (nullptr: the batch has none)
     template <class T> T *dev(const Section &s) const { return s.bytes ? (T *)((char *)dev_x + s.off) : nullptr; }
     template <class T> T *pin(const Section &s) const { return s.bytes ? (T *)((char *)pin_x + s.off) : nullptr; }
@@ -445,6 +455,13 @@ struct c3_model {
     // ... and its census (c3_model_set_score_census, c3_census.h): off = no section in a staged batch, nothing launched, nothing copied
     bool score_census_on = false, score_census_seen = false;  // seen: is or was on -- c3_score_census_read / _reset answer
     c3_score_census score_census = {};                        // totals of the completed batches since the last reset
+
+    // ---- refine mode (c3_model_set_refine, c3_refine.h): off = no section in a staged batch, nothing allocated, launched or copied ----
+    bool refine_on = false, refine_seen = false;  // seen: is or was on (the totals start with it)
+    float refine_gap = 0.f;
+    c3_refine_stats rfstats = {};     // totals since the last load / reset (gap is filled in when read)
+    float *refine_rows = nullptr;     // device: the refined rows of the batch c3_predict_wait is completing; grown on demand, freed with the handle
+    size_t refine_rows_bytes = 0;
 
     // ---- calibration (c3_calibrate.h; full alignment): off = nothing allocated, nothing launched, a load packs what it packs without it ----
     int census_pass = 0;              // forward_device is enqueuing a census pass: tap() takes the channels' maxima instead of copying

@@ -313,6 +313,7 @@ int c3_model_load(c3_model *m, const c3_tensor_desc *tensors, int n_tensors) {
     HIP_TRY(hipMemset(m->range_flag, 0, 256));
     HIP_TRY(hipDeviceSynchronize());  // (the handle's streams are non-blocking: the flag is zero before any of them runs again)
     verify_zero(m);  // verify mode: the totals were about the weights before; the setting stays
+    refine_zero(m);  // refine mode: likewise
     m->layer_exp_ok = false;  // (layer records: the channel exponents are these weights')
     // the range-guard policy (c3_calibrate.h): the setting stays, the totals start again, and under RECALIBRATE the tensors are kept for its repacks
     m->rstats = c3_range_stats{}, m->pack_epoch = 0;
@@ -437,6 +438,9 @@ int c3_model_describe(c3_model *m, char *buf, int n) {
     if (m->score_on)  // only while score mode is enabled (c3_score.h)
         snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " score=gamma:%g,weights:%d%s", m->score_gamma, (int)m->score_weighted,
                  m->score_census_on ? ",census:1" : "");
+    if (m->refine_on)  // only while refine mode is on (c3_refine.h)
+        snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " refine=gap:%g,windows:%lld,selected:%lld,changed:%lld", (double)m->refine_gap,
+                 (long long)m->rfstats.windows, (long long)m->rfstats.windows_selected, (long long)m->rfstats.windows_changed);
     return 0;
 }
 
@@ -469,6 +473,7 @@ int c3_model_destroy(c3_model *m) {
     if (m->range_flag) (void)hipFree(m->range_flag);
     if (m->layer_exp) (void)hipFree(m->layer_exp);
     if (m->census_dev) (void)hipFree(m->census_dev);
+    if (m->refine_rows) (void)hipFree(m->refine_rows);
     if (m->pin_flag) (void)hipHostFree(m->pin_flag);
     for (int l = 0; l < 9; ++l) {
         if (m->conv_w[l]) (void)hipFree(m->conv_w[l]);
@@ -488,6 +493,7 @@ int c3_model_destroy(c3_model *m) {
         if (sl.shadow) (void)hipFree(sl.shadow);
         if (sl.layer_part) (void)hipFree(sl.layer_part);
         if (sl.score_part) (void)hipFree(sl.score_part);
+        if (sl.refine_scratch) (void)hipFree(sl.refine_scratch);
         for (float *p : sl.layer_buf)
             if (p) (void)hipFree(p);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);

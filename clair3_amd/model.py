@@ -81,6 +81,7 @@ class _HipModel:
         self._exact = False     # the exact form (exact()): a handle created anew takes the setting along
         self._answer = "product"      # what answers a batch of the ring (answer()) ...
         self._verify_ref = "fp32"     # ... and what verify mode compares with (verify(reference=)): both need the exact form, both travel with it
+        self._refine = None     # refine mode (refine): the gap, or None = off; needs the exact form and travels with it
         self._score = None      # score mode (score_mode): (gamma, class weights or None) a handle created anew takes along
         self._score_census = False  # ... and its census (score_census): on or off travels too, the totals belong to the handle
         self._range_policy = None  # the range-guard policy (range_policy): (policy, max_recalibrations) a handle created anew takes along
@@ -222,6 +223,8 @@ class _HipModel:
             _lib.check(_lib.lib().c3_model_set_verify_reference(self._handle, _lib.VERIFY_REF[self._verify_ref]), "c3_model_set_verify_reference")
         if self._answer != "product":
             _lib.check(_lib.lib().c3_model_set_answer(self._handle, _lib.ANSWER[self._answer]), "c3_model_set_answer")
+        if self._refine is not None:  # (refine mode needs them too)
+            _lib.check(_lib.lib().c3_model_set_refine(self._handle, 1, self._refine), "c3_model_set_refine")
 
     # ---- the forward pass ----
     def __call__(self, x):
@@ -433,6 +436,8 @@ class _HipModel:
             raise _lib.C3Error(f"reference must be 'fp32' or 'exact', got {reference!r}")
         if self._handle is None:  # (a call that fails leaves nothing behind for a later .to(device) to apply)
             raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        if args[0] > 0 and self._refine is not None:
+            raise _lib.C3Error("verify() is refused while refine mode is on (refine()): the two own the same rows")
         if reference != self._verify_ref:  # (in front of everything else: refused, it leaves the setting what it was)
             if self._pending_sd is not None or reference == "fp32":  # (no weights yet: the first load sets it, behind the double weights)
                 _lib.check(_lib.lib().c3_model_set_verify_reference(self._handle, _lib.VERIFY_REF[reference]), "c3_model_set_verify_reference")
@@ -828,6 +833,65 @@ class _HipModel:
             raise _lib.C3Error("answer('exact') needs the exact form: call exact() first")
         self._answer = form
         return self
+
+    # ---- refine mode: the windows near a tie are answered by the exact form (c3_model_set_refine) ----
+    def refine(self, gap=1e-4, enable=True):
+        """Refine mode: every batch of sliced windows (predict_numpy and its chunks, submit / wait, submit_parts, submit_dev) is answered by
+        the product forms as without it; the windows whose row lies within ``gap`` of a tie -- in a head, or with decoder columns on among
+        the decoder's class maxima (synthetic.refine_gaps states the rule) -- then run through the exact form, and their rows and decoder
+        columns become the float32 rounding of the exact ones.  Every other row stays the product row, bit for bit.  ``gap`` defaults to
+        verify mode's tol, far above the forms' row error: every label is then the exact form's.  Needs exact(); refused while verify mode
+        is on (the two own the same rows) or a submit is pending.  refine_stats() reads the totals; enable=False switches it off."""
+        if not isinstance(enable, (bool, np.bool_)):
+            raise _lib.C3Error(f"enable must be True or False, got {enable!r}")
+        self._need_handle()
+        if not enable:
+            _lib.check(_lib.lib().c3_model_set_refine(self._handle, 0, 0.0), "c3_model_set_refine")
+            self._refine = None
+            return self
+        try:
+            gap = float(gap)
+        except (TypeError, ValueError) as e:
+            raise _lib.C3Error(f"gap must be a number >= 0, got {gap!r}") from e
+        if not gap >= 0 or not np.isfinite(np.float32(gap)):
+            raise _lib.C3Error(f"gap must be a finite number >= 0, got {gap}")
+        if self._pending_sd is not None:
+            _lib.check(_lib.lib().c3_model_set_refine(self._handle, 1, gap), "c3_model_set_refine")
+        elif not self._exact:  # (no weights yet: the first load sets it, behind the double weights -- which exact() must have asked for)
+            raise _lib.C3Error("refine() needs the exact form: call exact() first")
+        elif self._verify is not None and self._verify[0] > 0:
+            raise _lib.C3Error("refine() is refused while verify mode is on: the two own the same rows")
+        self._refine = gap
+        return self
+
+    def refine_stats(self):
+        """the totals of refine mode since the last load / refine_reset() as a dict (c3_model_refine_stats; include/c3hip.h names the fields)"""
+        self._need_handle()
+        st = _lib.RefineStats()
+        _lib.check(_lib.lib().c3_model_refine_stats(self._handle, C.byref(st)), "c3_model_refine_stats")
+        out = {}
+        for name, _ in _lib.RefineStats._fields_:
+            v = getattr(st, name)
+            out[name] = list(v) if hasattr(v, "__len__") else v
+        return out
+
+    def refine_reset(self):
+        self._need_handle()
+        _lib.check(_lib.lib().c3_model_refine_reset(self._handle), "c3_model_refine_reset")
+        return self
+
+    def refine_select(self, rows, gap):
+        """refine mode's selection alone on given rows (c3_refine_select), float32 (B, output_size) or (B, output_size + DECODE_COLS) with the
+        decoder columns filled in: (index int32 ascending, min_gap float32 (B,)) -- what synthetic.refine_select gives."""
+        self._need_handle()
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2:
+            raise _lib.C3Error(f"rows must be (B, row_floats) float32, got {rows.shape}")
+        n = rows.shape[0]
+        index, gaps, count = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32), C.c_int64(0)
+        _lib.check(_lib.lib().c3_refine_select(self._handle, rows.ctypes.data, rows.shape[1], n, float(gap), index.ctypes.data, C.byref(count),
+                                               gaps.ctypes.data), "c3_refine_select")
+        return index[:count.value].copy(), gaps
 
     def predict_exact(self, x):
         """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;

@@ -34,13 +34,14 @@ def _read_checkpoint(checkpoint_path):
 
 def _load_torch_checkpoint(model, checkpoint_path, device=None):
     """clair3/CallVariantsFromCffi.py:19-28: append '.pt' when missing, deserialise, accept a bare state_dict or {"state_dict": ...},
-    strict load; then what the environment asks of a model where it is built (C3HIP_CALIBRATION, C3HIP_VERIFY)."""
+    strict load; then what the environment asks of a model where it is built (C3HIP_CALIBRATION, C3HIP_VERIFY, C3HIP_REFINE)."""
     model.load_state_dict(_read_checkpoint(checkpoint_path))
     _register_current(model)
     calibration_from_env(model)
     verify_from_env(model)
     exact_from_env(model)
     answer_from_env(model)
+    refine_from_env(model)
     range_guard_from_env(model)
 
 
@@ -73,6 +74,7 @@ def exact_from_env(model):
     answer = parse_answer_env(os.environ.get("C3HIP_ANSWER"))
     ref = parse_verify_ref_env(os.environ.get("C3HIP_VERIFY_REF"))
     implied = answer == "exact" or (ref == "exact" and parse_verify_env(os.environ.get("C3HIP_VERIFY")) is not None)
+    implied = implied or parse_refine_env(os.environ.get("C3HIP_REFINE")) is not None  # (refine mode answers near-ties from the exact form)
     if value not in ("", "0", "1"):
         raise _lib.C3Error(f"C3HIP_EXACT must be 0 or 1, got {value!r}")
     if value != "1" and (not implied or getattr(model, "_exact", False)):  # (implied only: verify_from_env may have enabled it already)
@@ -90,6 +92,63 @@ def answer_from_env(model):
         return False
     model.answer("exact")
     return True
+
+
+def parse_refine_env(value):
+    """C3HIP_REFINE=<gap> -> the gap of ``model.refine`` as a float; None when unset, empty or 0.  Anything that is not a number >= 0
+    raises: a job asked to refine its near-ties must not run unrefined because of a typo."""
+    if value is None or not value.strip():
+        return None
+    try:
+        gap = float(value)
+    except ValueError as e:
+        raise _lib.C3Error(f"C3HIP_REFINE must be a gap >= 0 (0 = off), got {value!r}") from e
+    if not gap >= 0 or not np.isfinite(gap):
+        raise _lib.C3Error(f"C3HIP_REFINE must be a gap >= 0 (0 = off), got {value!r}")
+    return gap if gap > 0 else None
+
+
+# models of this process that run in refine mode because the environment said so: their totals go to stderr when the process ends
+_REFINED = []
+
+
+def refine_from_env(model):
+    """C3HIP_REFINE=<gap>: refine mode where the model is built (model.refine(gap); README), behind exact_from_env, which placed the double
+    weights it implies.  Together with C3HIP_VERIFY it raises: the two own the same rows.  In a worker process one summary line per such
+    model goes to stderr at exit; stdout and the VCF stay untouched."""
+    import os
+    gap = parse_refine_env(os.environ.get("C3HIP_REFINE"))
+    if gap is None:
+        return False
+    if parse_verify_env(os.environ.get("C3HIP_VERIFY")) is not None:
+        raise _lib.C3Error("C3HIP_REFINE and C3HIP_VERIFY are both set: refine mode and verify mode own the same rows, choose one")
+    model.refine(gap)
+    if not any(v is model for v in _REFINED):
+        import atexit
+        if not _REFINED:
+            atexit.register(_report_refined)
+        _REFINED.append(model)  # (held until the process ends, like _VERIFIED)
+    return True
+
+
+def refine_summary(model):
+    """the line a worker leaves on stderr: the totals of refine mode (INTEGRATION.md 8 says how to read it)"""
+    st = model.refine_stats()
+    return ("[clair3_amd] refine: gap={:g} batches={} refined={} skipped={} windows={} selected={} changed={} per_head={} decoder={} "
+            "min_gap={} max_abs_diff={:.3g}").format(
+        st["gap"], st["batches"], st["batches_refined"], st["batches_skipped"], st["windows"], st["windows_selected"], st["windows_changed"],
+        "/".join(str(v) for v in st["head_selected"]), st["decoder_selected"], "/".join(f"{v:.3g}" for v in st["min_gap"]), st["max_abs_diff"])
+
+
+def _report_refined():
+    import sys
+    for model in _REFINED:
+        if model._handle is None:
+            continue
+        try:
+            print(refine_summary(model), file=sys.stderr)
+        except Exception as e:  # noqa: BLE001  (the process is ending: say it, do not raise)
+            print(f"[clair3_amd] refine: no summary ({e})", file=sys.stderr)
 
 
 def calibration_from_env(model):
@@ -361,6 +420,7 @@ def build_model(pileup, add_indel_length, platform="ont", enable_dwell_time=Fals
         verify_from_env(m)
         exact_from_env(m)
         answer_from_env(m)
+        refine_from_env(m)
         range_guard_from_env(m)
     return m
 

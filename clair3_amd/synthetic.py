@@ -546,3 +546,52 @@ def score_census(rows, labels):
             for k, thr in enumerate(CENSUS_GAP_THR):
                 out.gap_below[t, k] = int((gap < thr).sum())
     return out
+
+
+# ---- refine mode in numpy: the rule of csrc/c3_refine.h (tests/test_refine.py holds the two together) ----
+DECODE_COLS = 31  # kDecodeCols (csrc/c3_decode.h)
+
+
+def _top2_gap(v):
+    """largest minus second-largest value of every row of ``v`` in float32: 0 when the maximum occurs twice, NaN when the row holds a NaN"""
+    s = np.sort(v.astype(np.float32, copy=False), axis=1)  # (a NaN sorts behind everything: the difference is then a NaN)
+    with np.errstate(invalid="ignore"):
+        return (s[:, -1] - s[:, -2]).astype(np.float32)
+
+
+def refine_gaps(rows, nout, columns=None):
+    """The gaps refine mode looks at (c3_model_set_refine; csrc/c3_refine.h states the rule), (B, 5) float32: columns 0 .. 3 the top-2 gap of
+    every head of the ``nout`` probabilities (+inf for a head the row does not have), column 4 the decoder gap -- for every reference base
+    A, C, G, T that does not take the early exit (bit b of decoder column 22) the top-2 gap among decoder column 9 + b and columns 0 .. 8,
+    the minimum over those bases; +inf when all four take it or the rows carry no decoder columns.  columns: None = the rows carry them iff
+    they are wider than ``nout``; False = ignore them."""
+    rows = np.asarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or nout not in (24, 90) or rows.shape[1] not in (nout, nout + DECODE_COLS):
+        raise ValueError(f"rows {rows.shape} are not rows of {nout} probabilities with or without the {DECODE_COLS} decoder columns")
+    has_cols = rows.shape[1] > nout
+    if columns is None:
+        columns = has_cols
+    if columns and not has_cols:
+        raise ValueError("columns=True needs rows with the decoder columns")
+    out = np.full((len(rows), 5), np.inf, dtype=np.float32)
+    if len(rows) == 0:
+        return out
+    for h, (lo, hi) in enumerate(head_slices(nout)):
+        out[:, h] = _top2_gap(rows[:, lo:hi])
+    if columns:
+        cols = rows[:, nout:]
+        with np.errstate(invalid="ignore"):
+            early = np.nan_to_num(cols[:, 22], nan=0.0, posinf=0.0, neginf=0.0).astype(np.int64)
+        per_base = [np.where(early >> b & 1, np.float32(np.inf), _top2_gap(np.concatenate([cols[:, 9 + b:10 + b], cols[:, 0:9]], axis=1)))
+                    for b in range(4)]
+        out[:, 4] = np.fmin.reduce(np.stack(per_base), axis=0)  # (a NaN gap of one base is left out, as refine_select leaves a NaN head gap out)
+    return out
+
+
+def refine_select(rows, nout, gap, columns=None):
+    """(index, min_gap) of refine mode's selection (c3_refine_select): the windows any of whose gaps is <= ``gap`` in float32, ascending, as
+    int32; and every window's minimum gap with NaN gaps left out (NaN when all of them are).  A NaN gap selects nothing."""
+    g = refine_gaps(rows, nout, columns)
+    with np.errstate(invalid="ignore"):
+        sel = (g <= np.float32(gap)).any(axis=1)
+    return np.flatnonzero(sel).astype(np.int32), np.fmin.reduce(g, axis=1) if len(g) else np.zeros(0, np.float32)

@@ -735,6 +735,55 @@ int c3_model_set_score_census(c3_model *m, int enable);
 int c3_score_census_read(c3_model *m, c3_score_census *out);
 int c3_score_census_reset(c3_model *m);
 
+/* ---- refine mode: the windows of a batch that sit near a tie are answered by the exact form ----
+ * Labels of the product forms and of the fp64 oracle agree outside near-ties; at a near-tie the label depends on which form computed the
+ * row.  With refine mode on, the product pass answers a batch as it does without it, two launches behind it measure per window how close
+ * the row is to a tie, and c3_predict_wait runs ONLY the windows within `gap` of one through the exact form (c3_predict_exact's arithmetic)
+ * and replaces their rows -- probabilities and decoder columns -- by the float32 rounding of the exact ones.  Every other row stays the
+ * product row, bit for bit.  With `gap` far above the forms' row error (1e-6 .. 8.5e-6 in the suite; the default of the Python layer is
+ * 1e-4) every arg-max of a returned row is the arg-max of the exact row.
+ * The rule (clair3_amd/csrc/c3_refine.h; in numpy: synthetic.refine_gaps / refine_select), all in float32:
+ *   head gap     per head (21 | 3 | 33 | 33 columns): the largest minus the second-largest value, 0 when the maximum occurs twice
+ *   decoder gap  only with decoder columns on: for every reference base A, C, G, T that does not take the early exit (bit b of decoder
+ *                column 22) the same gap among the ten class maxima -- decoder column 9 + b and columns 0 .. 8 --, the minimum over those bases
+ *   selected     iff any of these gaps is <= gap.  A NaN gap selects nothing: a non-finite row is the range guard's business
+ * Stated limit: near-ties inside one outcome class list are caught only through the head gaps they are products of.
+ *   c3_model_set_refine  enable != 0: every later batch of sliced windows without depths (c3_predict and its chunks, c3_predict_submit,
+ *                       c3_predict_submit_parts, c3_predict_submit_dev) is refined; gap must be finite and >= 0.  Needs the exact form
+ *                       loaded (c3_model_set_exact, then c3_model_load) and verify mode off -- the two own the same rows, and
+ *                       c3_model_set_verify(every > 0) is refused while refine mode is on.  Refused while a submit is pending.  A load keeps
+ *                       the setting and starts the totals again.  Batches that are NOT refined and count in batches_skipped: one the range guard
+ *                       answered, a scored batch, a batch of an exact-answer handle, a batch with depths, a region, candidate, rows or
+ *                       packed-rows batch, a batch of more than 2^22 windows.  Off (the default): no section in a staged batch, nothing
+ *                       allocated, launched or copied.  On: two launches per batch and 256 + 4 * batch bytes more on its way back; a batch
+ *                       with selected windows adds the exact passes over them to its c3_predict_wait.
+ *                       c3_model_describe gains " refine=gap:<g>,windows:<n>,selected:<n>,changed:<n>" only while the mode is on.
+ *   c3_model_refine_stats   the totals since the last load / reset
+ *   c3_model_refine_reset   zeroes them
+ *   c3_refine_select    the selection alone on rows the caller brings (row_floats == c3_model_output_size(), or that + C3_DECODE_COLS with the
+ *                       decoder columns filled in): index_out (batch entries of room) receives the selected windows in ascending order, *n_out
+ *                       their number, gaps_out (batch floats, may be NULL) every window's minimum gap (NaN gaps left out; NaN when all are).
+ *                       Needs neither the mode nor the exact form.
+ * Errors: a null handle or argument, a gap that is negative or not finite, refine with verify mode on, refine without the exact form. */
+typedef struct {
+    int64_t batches;            /* completed batches of windows while the mode was on = refined + skipped + those with nothing selected */
+    int64_t batches_refined;    /* ... with at least one window answered by the exact form */
+    int64_t batches_skipped;
+    int64_t windows;            /* windows of the batches that were not skipped */
+    int64_t windows_selected;   /* ... answered by the exact form */
+    int64_t windows_changed;    /* ... in which the arg-max of a head changed between the product row and the exact float32 row */
+    int64_t head_selected[4];   /* windows with g_h <= gap, per head */
+    int64_t decoder_selected;   /* windows with the decoder gap <= gap */
+    float min_gap[4];           /* per head: the smallest gap seen (+inf: none) */
+    float max_abs_diff;         /* max |exact float32 - product| over the refined probabilities */
+    float gap;                  /* the setting (0 when the mode was never on) */
+} c3_refine_stats;
+int c3_model_set_refine(c3_model *m, int enable, float gap);
+int c3_model_refine_stats(c3_model *m, c3_refine_stats *out);
+int c3_model_refine_reset(c3_model *m);
+int c3_refine_select(c3_model *m, const float *rows_host, int row_floats, int64_t batch, float gap, int32_t *index_out, int64_t *n_out,
+                     float *gaps_out);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
