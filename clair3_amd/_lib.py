@@ -38,7 +38,10 @@ EXPORTS = (
     "c3_model_set_score", "c3_score_submit", "c3_score_wait", "c3_score", "c3_score_rows",
     "c3_model_set_score_census", "c3_score_census_read", "c3_score_census_reset",
     "c3_model_set_refine", "c3_model_refine_stats", "c3_model_refine_reset", "c3_refine_select",
+    "c3_jackknife_rows", "c3_jackknife", "c3_jackknife_reduce",
 )
+# layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
+JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
 MAX_PARTS = 64  # C3_MAX_PARTS (include/c3hip.h)
 # policy of verify mode (C3_VERIFY_* in include/c3hip.h)
 VERIFY_REPORT, VERIFY_ESCALATE, VERIFY_REPLACE = 0, 1, 2
@@ -118,6 +121,18 @@ class RefineStats(C.Structure):
     _fields_ = [("batches", C.c_int64), ("batches_refined", C.c_int64), ("batches_skipped", C.c_int64), ("windows", C.c_int64),
                 ("windows_selected", C.c_int64), ("windows_changed", C.c_int64), ("head_selected", C.c_int64 * 4),
                 ("decoder_selected", C.c_int64), ("min_gap", C.c_float * 4), ("max_abs_diff", C.c_float), ("gap", C.c_float)]
+
+
+class JackknifeWindow(C.Structure):
+    """c3_jackknife_window (include/c3hip.h); synthetic.JACKKNIFE_DTYPE is the same record as a numpy dtype"""
+    _fields_ = [("reads", C.c_int32), ("nonfinite", C.c_int32), ("flips", C.c_int32 * 4), ("decision_flips", C.c_int32 * 4),
+                ("lean_read", C.c_int32 * 4), ("lean_drop", C.c_float * 4), ("max_delta", C.c_float), ("reserved", C.c_int32)]
+
+
+class JackknifeInfo(C.Structure):
+    """c3_jackknife_info (include/c3hip.h)"""
+    _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
+                ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
 
 
 class C3Error(RuntimeError):
@@ -251,7 +266,11 @@ def lib():
     L.c3_model_refine_stats.argtypes = [C.c_void_p, C.POINTER(RefineStats)]
     L.c3_model_refine_reset.argtypes = [C.c_void_p]
     L.c3_refine_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
-    L.c3_outcome_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.c3_jackknife_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(JackknifeInfo)]
+    L.c3_jackknife.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(JackknifeInfo)]
+    L.c3_jackknife_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]
     L.c3_model_destroy.argtypes = [C.c_void_p]

@@ -491,6 +491,10 @@ struct c3_model {
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
 
+    // ---- jackknife mode (c3_jackknife_rows, c3_jackknife.h): never called = nothing allocated, nothing launched ----
+    void *jackknife_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows and its records; grown on demand
+    size_t jackknife_bytes = 0;
+
     // ---- workspaces and kernel streams: the lanes (Lane above; lane(m) is the active one) ----
     Lane lanes[kMaxLanes];
     int lane_cur = 0;

@@ -893,6 +893,37 @@ class _HipModel:
                                                gaps.ctypes.data), "c3_refine_select")
         return index[:count.value].copy(), gaps
 
+    # ---- jackknife mode: the reduction alone (c3_jackknife_reduce; Clair3_F.jackknife / jackknife_rows run the network) ----
+    @staticmethod
+    def _jackknife_layout(layout):
+        if layout not in _lib.JACKKNIFE_LAYOUT:
+            raise _lib.C3Error(f"layout must be 'recentre' or 'in_place', got {layout!r}")
+        return _lib.JACKKNIFE_LAYOUT[layout]
+
+    def jackknife_reduce(self, base_rows, variant_rows, counts, drops=False):
+        """The records of jackknife mode for rows the caller holds (c3_jackknife_reduce): ``base_rows`` (B, row) float32, ``variant_rows``
+        (sum(counts), row) the rows of every window's leave-one-read-out variants in window order, read order; row = output_size, or that
+        + DECODE_COLS with the decoder columns filled in.  Returns a dict: ``rows`` (B,) of synthetic.JACKKNIFE_DTYPE, ``counts``, and with
+        drops=True ``drops`` (sum(counts), 4) float32 -- what synthetic.jackknife_records gives.  Needs no weights."""
+        self._need_handle()
+        base = np.ascontiguousarray(base_rows, dtype=np.float32)
+        var = np.ascontiguousarray(variant_rows, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if base.ndim != 2 or var.ndim != 2 or var.shape[1] != base.shape[1]:
+            raise _lib.C3Error(f"base rows (B, row) and variant rows (n, row) float32 expected, got {base.shape} and {var.shape}")
+        if counts.shape != (len(base),):
+            raise _lib.C3Error(f"counts must hold one entry per window: shape {counts.shape} for {len(base)} windows")
+        if (counts >= 0).all() and int(counts.sum(dtype=np.int64)) != len(var):
+            raise _lib.C3Error(f"counts add up to {int(counts.sum(dtype=np.int64))} variants, {len(var)} rows given")
+        rec = np.zeros(len(base), dtype=syn.JACKKNIFE_DTYPE)
+        d = np.zeros((len(var), 4), dtype=np.float32) if drops else None
+        _lib.check(_lib.lib().c3_jackknife_reduce(self._handle, base.ctypes.data, var.ctypes.data, base.shape[1], counts.ctypes.data, len(base),
+                                                  rec.ctypes.data, None if d is None else d.ctypes.data), "c3_jackknife_reduce")
+        out = dict(rows=rec, counts=counts)
+        if drops:
+            out["drops"] = d
+        return out
+
     def predict_exact(self, x):
         """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;
         blocking; windows only).  Whatever precision, plan or calibration the handle runs does not enter."""
@@ -1106,6 +1137,56 @@ class Clair3_F(_RingVerify):
         _lib.check(_lib.lib().c3_predict_rows(self._handle, rows.ctypes.data, None if firsts is None else firsts.ctypes.data, counts.ctypes.data,
                                               len(counts), y.ctypes.data), "c3_predict_rows")
         return y
+
+    # ---- jackknife mode: does a call survive when one read of its window is taken away? (c3_jackknife_rows) ----
+    def _jackknife_out(self, counts, y, rec, drops, variant_rows, info):
+        out = dict(rows=rec, counts=counts, base_rows=y, on_fp32=bool(info.on_fp32), passes=int(info.passes), bytes_staged=int(info.bytes_staged),
+                   expand_us=float(info.expand_us), reduce_us=float(info.reduce_us))
+        if drops is not None:
+            out["drops"] = drops
+        if variant_rows is not None:
+            out["variant_rows"] = variant_rows
+        return out
+
+    def jackknife_rows(self, rows, counts, firsts=None, layout="recentre", drops=False, variant_rows=False):
+        """Leave-one-read-out stability of windows handed over as their occupied rows (predict_rows's arguments; c3_jackknife_rows): for
+        every window the device builds its counts[b] variants -- the window without one row of its run, laid out again by the reference's
+        padding rule ("recentre") or left where the run starts ("in_place") --, runs them through the forward pass beside the window itself
+        and reduces their rows to one record.  Returns a dict: ``rows`` (B,) of synthetic.JACKKNIFE_DTYPE (reads, nonfinite, flips per head,
+        decision_flips per reference base, lean_read / lean_drop per head, max_delta), ``counts``, ``base_rows`` -- bit for bit
+        predict_rows(rows, counts, firsts) --, ``on_fp32`` (the range guard met the call and it ran on the fp32 forms; the handle stays as it
+        was), ``passes``, ``bytes_staged``, ``expand_us`` / ``reduce_us`` (device time of the two kernels' launches); with drops=True ``drops`` (sum(counts), 4), with variant_rows=True ``variant_rows``
+        (sum(counts), row_size).  synthetic.leave_one_out / jackknife_records are the same in numpy."""
+        code = self._jackknife_layout(layout)
+        rows, counts, firsts, y = self._rows_args(rows, counts, firsts)
+        total = int(np.clip(counts, 0, None).sum(dtype=np.int64))
+        rec = np.zeros(len(counts), dtype=syn.JACKKNIFE_DTYPE)
+        d = np.zeros((total, 4), dtype=np.float32) if drops else None
+        v = np.zeros((total, self.row_size), dtype=np.float32) if variant_rows else None
+        info = _lib.JackknifeInfo()
+        _lib.check(_lib.lib().c3_jackknife_rows(self._handle, rows.ctypes.data, None if firsts is None else firsts.ctypes.data, counts.ctypes.data,
+                                                len(counts), code, y.ctypes.data, rec.ctypes.data, None if d is None else d.ctypes.data,
+                                                None if v is None else v.ctypes.data, C.byref(info)), "c3_jackknife_rows")
+        return self._jackknife_out(counts, y, rec, d, v, info)
+
+    def jackknife(self, x, layout="recentre", drops=False, variant_rows=False):
+        """jackknife_rows of dense int8 windows (c3_jackknife): every window's run -- from its first to its last non-zero row -- is found on
+        the host as synthetic.pack_fa_rows finds it, and its first row is the run's own.  ``counts`` of the result are the runs' lengths."""
+        code = self._jackknife_layout(layout)
+        self._need_handle()
+        x, dt = self._window_batch(x)
+        if x.ndim != 4:
+            raise _lib.C3Error(f"windows (B, depth, positions, C) expected, got shape {x.shape}")
+        _, _, counts = syn.pack_fa_rows(x)
+        total = int(counts.sum(dtype=np.int64))
+        y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
+        rec = np.zeros(len(x), dtype=syn.JACKKNIFE_DTYPE)
+        d = np.zeros((total, 4), dtype=np.float32) if drops else None
+        v = np.zeros((total, self.row_size), dtype=np.float32) if variant_rows else None
+        info = _lib.JackknifeInfo()
+        _lib.check(_lib.lib().c3_jackknife(self._handle, x.ctypes.data, dt, x.shape[0], code, y.ctypes.data, rec.ctypes.data,
+                                           None if d is None else d.ctypes.data, None if v is None else v.ctypes.data, C.byref(info)), "c3_jackknife")
+        return self._jackknife_out(counts, y, rec, d, v, info)
 
     def submit_rows(self, rows, counts, firsts=None, slot=0):
         """Asynchronous half of predict_rows (c3_predict_submit_rows); returns a handle for wait()."""

@@ -595,3 +595,91 @@ def refine_select(rows, nout, gap, columns=None):
     with np.errstate(invalid="ignore"):
         sel = (g <= np.float32(gap)).any(axis=1)
     return np.flatnonzero(sel).astype(np.int32), np.fmin.reduce(g, axis=1) if len(g) else np.zeros(0, np.float32)
+
+
+# ---- jackknife mode in numpy: the definitions of csrc/c3_jackknife.h (tests/test_jackknife.py holds the two together) ----
+JACKKNIFE_LAYOUTS = ("recentre", "in_place")  # C3_JACKKNIFE_RECENTRE, C3_JACKKNIFE_IN_PLACE
+# c3_jackknife_window (include/c3hip.h), 80 bytes
+JACKKNIFE_DTYPE = np.dtype([("reads", "<i4"), ("nonfinite", "<i4"), ("flips", "<i4", (4,)), ("decision_flips", "<i4", (4,)),
+                            ("lean_read", "<i4", (4,)), ("lean_drop", "<f4", (4,)), ("max_delta", "<f4"), ("reserved", "<i4")])
+
+
+def leave_one_out(rows, counts, firsts=None, depth=FA_DEPTH_ONT, layout="recentre"):
+    """The leave-one-read-out variants of windows given as their occupied rows (pad_fa_rows's arguments), dense, (sum(counts), depth,
+    positions, C) int8 in the order of c3_jackknife_rows: window after window, variant j of a window being the window without row j of its
+    run.  layout "recentre": the counts[b] - 1 rows that stay are laid out by the reference's padding rule for THAT count, first =
+    (depth - (counts[b] - 1)) // 2; "in_place": they start where the base window's run starts (firsts[b], or its centred first)."""
+    if layout not in JACKKNIFE_LAYOUTS:
+        raise ValueError(f"layout must be one of {JACKKNIFE_LAYOUTS}, got {layout!r}")
+    rows = np.asarray(rows)
+    counts = np.asarray(counts, dtype=np.int64)
+    pad_fa_rows(rows, counts, firsts, depth)  # (its checks)
+    base_first = (depth - counts) // 2 if firsts is None else np.asarray(firsts, dtype=np.int64)
+    src = np.r_[0, np.cumsum(counts)]
+    v_rows, v_counts, v_firsts = [], [], []
+    for b in range(len(counts)):
+        run = rows[src[b]:src[b + 1]]
+        for j in range(int(counts[b])):
+            v_rows.append(np.delete(run, j, axis=0))
+            v_counts.append(counts[b] - 1)
+            v_firsts.append(base_first[b] if layout == "in_place" else (depth - (counts[b] - 1)) // 2)
+    flat = np.concatenate(v_rows) if v_rows else np.zeros((0,) + rows.shape[1:], dtype=rows.dtype)
+    return pad_fa_rows(flat, np.asarray(v_counts, dtype=np.int64), np.asarray(v_firsts, dtype=np.int64), depth)
+
+
+def _first_argmax(v):
+    """arg-max of every row of ``v`` by the rule of the census and of refine mode: the first maximum, a NaN never, index 0 when nothing
+    exceeds -inf"""
+    return np.where(np.isnan(v), np.float32(-np.inf), v).argmax(1) if len(v) else np.zeros(0, np.int64)
+
+
+def jackknife_records(base_rows, variant_rows, counts, nout, columns=None):
+    """(records, drops) of jackknife mode (c3_jackknife_reduce; csrc/c3_jackknife.h states the definitions): ``base_rows`` (B, row) float32,
+    ``variant_rows`` (sum(counts), row) the rows of every window's variants in window order, read order; row = nout or nout + DECODE_COLS.
+    records: (B,) of JACKKNIFE_DTYPE; drops: (sum(counts), 4) float32, y[t_h] - v_j[t_h].  columns: None = the rows carry decoder columns
+    iff they are wider than ``nout``; False = ignore them."""
+    base = np.asarray(base_rows, dtype=np.float32)
+    var = np.asarray(variant_rows, dtype=np.float32)
+    counts = np.asarray(counts, dtype=np.int64)
+    if base.ndim != 2 or var.ndim != 2 or nout not in (24, 90) or base.shape[1] not in (nout, nout + DECODE_COLS) or var.shape[1] != base.shape[1]:
+        raise ValueError(f"base rows {base.shape} and variant rows {var.shape} are not rows of {nout} probabilities with or without the decoder columns")
+    if counts.shape != (len(base),) or (counts < 0).any() or int(counts.sum()) != len(var):
+        raise ValueError(f"counts must hold one entry >= 0 per window and add up to the {len(var)} variant rows given")
+    has_cols = base.shape[1] > nout
+    if columns is None:
+        columns = has_cols
+    if columns and not has_cols:
+        raise ValueError("columns=True needs rows with the decoder columns")
+    heads = head_slices(nout)
+    rec = np.zeros(len(base), dtype=JACKKNIFE_DTYPE)
+    rec["lean_read"] = -1
+    drops = np.zeros((len(var), 4), dtype=np.float32)
+    at = np.r_[0, np.cumsum(counts)]
+    for b in range(len(base)):
+        y, v = base[b], var[at[b]:at[b + 1]]
+        n = len(v)
+        rec["reads"][b] = n
+        if n == 0:
+            continue
+        finite = np.isfinite(v[:, :nout]).all(axis=1)
+        rec["nonfinite"][b] = int((~finite).sum())
+        with np.errstate(invalid="ignore"):
+            delta = np.abs(v[finite, :nout] - y[None, :nout])  # float32
+            delta = delta[~np.isnan(delta)]
+            rec["max_delta"][b] = delta.max() if delta.size else np.float32(0)
+            for h, (lo, hi) in enumerate(heads):
+                t = lo + int(_first_argmax(y[None, lo:hi])[0])
+                rec["flips"][b, h] = int((lo + _first_argmax(v[:, lo:hi]) != t).sum())
+                d = (y[t] - v[:, t]).astype(np.float32)  # one float32 subtraction
+                drops[at[b]:at[b + 1], h] = d
+                ok = finite & ~np.isnan(d)
+                if ok.any():
+                    j = int(np.where(ok, d, np.float32(-np.inf)).argmax())  # the first of the largest: -0 and +0 are a tie
+                    if not ok[j]:  # (every candidate is -inf and a variant that is none comes first)
+                        j = int(np.flatnonzero(ok)[0])
+                    rec["lean_read"][b, h] = j
+                    rec["lean_drop"][b, h] = d[j] + np.float32(0)  # (a zero drop is reported as +0)
+            if columns:
+                for k in range(4):
+                    rec["decision_flips"][b, k] = int((v[:, nout + 23 + k] != y[nout + 23 + k]).sum())
+    return rec, drops

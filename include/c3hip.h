@@ -784,6 +784,73 @@ int c3_model_refine_reset(c3_model *m);
 int c3_refine_select(c3_model *m, const float *rows_host, int row_floats, int64_t batch, float gap, int32_t *index_out, int64_t *n_out,
                      float *gaps_out);
 
+/* ---- jackknife mode: the leave-one-read-out stability of full-alignment calls ("Jackknife mode") ----
+ * Verify, score and refine mode measure what the ARITHMETIC can do to a label; this measures what the INPUT does.  The unit is the read: a
+ * window handed over as its occupied rows (c3_predict_rows) has n = row_count[b] reads, and variant j of it is the window without row j of
+ * its run.  The device builds the n variants of every window from the rows staged once, runs them through the unchanged forward pass beside
+ * the window itself -- the forms the handle is on: its plan, C3HIP_FP32, its calibration -- and reduces their rows to one record per window.
+ * An instrument like c3_predict_exact, not a path of a pipeline: blocking, in the first lane, and nothing is allocated, launched or planned
+ * unless one of these entries is called.
+ * The definitions (clair3_amd/csrc/c3_jackknife.h; in numpy: synthetic.leave_one_out / jackknife_records), y the window's own row:
+ *   layout      C3_JACKKNIFE_RECENTRE: the n - 1 rows that stay start at dense row (depth - (n - 1)) / 2 -- the reference's padding rule
+ *               (row_first == NULL above) applied to the variant's own count, the window its producer would have laid out without that read.
+ *               C3_JACKKNIFE_IN_PLACE: they start at the base window's first row.  The base window sits where row_first / the centring rule
+ *               puts it, exactly as in c3_predict_rows.  A row of the run is a read whatever it holds: an interior all-zero row is a variant too;
+ *               n = 1 has one variant, the all-zero window; n = 0 gives the all-zero record with lean_read = -1
+ *   arg-max     of a head (21 | 3 | 33 | 33 columns): the first maximum by `>` from -inf on -- the lowest index on ties, a NaN never, the head's
+ *               first column when nothing exceeds -inf: the rule of the census and of refine mode
+ *   a NaN       or an infinity among a variant's probabilities: the variant counts in `nonfinite` and, by the arg-max rule, in flips and
+ *               decision_flips; it is left out of lean_read / lean_drop and of max_delta.  A drop that is a NaN (the base row's own value is
+ *               one) is never the largest; a zero drop that leans is reported as +0 */
+#define C3_JACKKNIFE_RECENTRE 0
+#define C3_JACKKNIFE_IN_PLACE 1
+typedef struct c3_jackknife_window {   /* 80 bytes */
+    int32_t reads;              /* n */
+    int32_t nonfinite;          /* variants with a non-finite probability in their first nout columns */
+    int32_t flips[4];           /* per head h: variants whose arg-max in h differs from the base row's (heads the model lacks: 0) */
+    int32_t decision_flips[4];  /* rows with decoder columns: per reference base A C G T, variants whose decoder column 23 + b differs
+                                   from the base row's; without decoder columns: 0 */
+    int32_t lean_read[4];       /* per head: the j with the largest drop = y[t] - v_j[t], t the base arg-max of the head;
+                                   lowest j on ties; -1 when no variant is finite (and for a head the model lacks) */
+    float   lean_drop[4];       /* that drop (one float32 subtraction; may be negative); 0 with lean_read = -1 */
+    float   max_delta;          /* max over finite variants and the first nout columns of |v_j[c] - y[c]| (float32) */
+    int32_t reserved;
+} c3_jackknife_window;
+/* what a call did (the trailing argument of the two entries that run the network; may be NULL) */
+typedef struct {
+    int64_t windows, variants;  /* of the call */
+    int64_t passes;             /* the call is cut into passes of C3HIP_JACKKNIFE_CHUNK windows (env; default 64, 0 = never cut) */
+    int64_t bytes_staged;       /* host to device: the occupied rows and the tables */
+    int32_t on_fp32;            /* 1: the range guard met a pass and that pass ran again on the fp32 forms (below) */
+    int32_t reserved;
+    float expand_us, reduce_us; /* device time of the call's jackknife_expand_kernel / jackknife_reduce_kernel launches (HIP events, summed) */
+} c3_jackknife_info;
+/*   c3_jackknife_rows    the arguments of c3_predict_rows.  Cut into passes of C3HIP_JACKKNIFE_CHUNK windows; a window's variants never
+ *                        straddle a pass, they may straddle a micro-batch of 2048 dense windows.  Per pass the occupied rows and one table
+ *                        (the windows themselves first, then every window's variants in window order, read order) are staged once, the dense
+ *                        windows are built micro-batch by micro-batch in front of the forward pass, the rows stay in a buffer of the handle,
+ *                        the reduction runs behind the last micro-batch and the host waits once, for the records.
+ *                          y_host            (may be NULL) [batch][row]: bit for bit c3_predict_rows of the same arguments
+ *                          out               [batch] records
+ *                          drops_out         (may be NULL) [sum(row_count)][4] float32: y[t_h] - v_j[t_h] per variant and head (0: no such head)
+ *                          variant_rows_out  (may be NULL) [sum(row_count)][row]: the variants' rows, for tests and tools
+ *                        The handle is left as it was: c3_model_describe, the tap buffers of the last call, a profile being taken, the totals
+ *                        of verify / refine / score mode and rows_windows= do not see the call.  Range guard: a handle on the fp16x3 forms whose
+ *                        range flag is up behind a pass (or that returned a non-finite row) runs THAT PASS again on the fp32-MFMA forms for this
+ *                        call alone; the device flag is put back to zero, the handle stays on its forms, info->on_fp32 says so.
+ *   c3_jackknife         dense int8 windows: every window's run is found on the host as c3_pack_rows finds it, its first row is the run's own.
+ *   c3_jackknife_reduce  the reduction alone on rows the caller holds (row_floats == c3_model_output_size(), or that + C3_DECODE_COLS):
+ *                        base_rows [batch][row_floats], variant_rows [sum(row_count)][row_floats].  Needs no weights; serves both kinds.
+ * Refused before anything is queued: a pileup handle and a handle without weights (the two entries that run the network), null buffers with
+ * batch > 0, a negative count, first < 0, first + count > depth, a layout other than the two, a submit pending on any slot of the ring, a
+ * handle that answers from the exact form (c3_model_set_answer), row_floats that is neither of the two.  batch == 0 launches nothing. */
+int c3_jackknife_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, int layout,
+                      float *y_host, c3_jackknife_window *out, float *drops_out, float *variant_rows_out, c3_jackknife_info *info);
+int c3_jackknife(c3_model *m, const void *x_host, int x_dtype, int64_t batch, int layout, float *y_host, c3_jackknife_window *out,
+                 float *drops_out, float *variant_rows_out, c3_jackknife_info *info);
+int c3_jackknife_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, const int32_t *row_count,
+                        int64_t batch, c3_jackknife_window *out, float *drops_out);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
