@@ -39,6 +39,7 @@ EXPORTS = (
     "c3_model_set_score_census", "c3_score_census_read", "c3_score_census_reset",
     "c3_model_set_refine", "c3_model_refine_stats", "c3_model_refine_reset", "c3_refine_select",
     "c3_jackknife_rows", "c3_jackknife", "c3_jackknife_reduce",
+    "c3_subsample_rows", "c3_subsample", "c3_subsample_reduce",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -131,6 +132,23 @@ class JackknifeWindow(C.Structure):
 
 class JackknifeInfo(C.Structure):
     """c3_jackknife_info (include/c3hip.h)"""
+    _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
+                ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
+
+
+class SubsampleLevel(C.Structure):
+    """c3_subsample_level (include/c3hip.h); synthetic.SUBSAMPLE_LEVEL_DTYPE is the same record as a numpy dtype"""
+    _fields_ = [("keep", C.c_int32), ("run", C.c_int32), ("nonfinite", C.c_int32), ("decision_flips", C.c_int32), ("flips", C.c_int32 * 4),
+                ("min_kept", C.c_float * 4)]
+
+
+class SubsampleWindow(C.Structure):
+    """c3_subsample_window (include/c3hip.h); synthetic.SUBSAMPLE_WINDOW_DTYPE is the same record as a numpy dtype"""
+    _fields_ = [("reads", C.c_int32), ("levels_run", C.c_int32), ("hold_level", C.c_int32 * 4), ("hold_decision", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SubsampleInfo(C.Structure):
+    """c3_subsample_info (include/c3hip.h)"""
     _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
                 ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
 
@@ -270,6 +288,12 @@ def lib():
                                     C.POINTER(JackknifeInfo)]
     L.c3_jackknife.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(JackknifeInfo)]
     L.c3_jackknife_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.c3_subsample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SubsampleInfo)]
+    L.c3_subsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SubsampleInfo)]
+    L.c3_subsample_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -495,6 +495,10 @@ struct c3_model {
     void *jackknife_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows and its records; grown on demand
     size_t jackknife_bytes = 0;
 
+    // ---- subsample mode (c3_subsample_rows, c3_subsample.h): never called = nothing allocated, nothing launched ----
+    void *subsample_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows, its records and masks; grown on demand
+    size_t subsample_bytes = 0;
+
     // ---- workspaces and kernel streams: the lanes (Lane above; lane(m) is the active one) ----
     Lane lanes[kMaxLanes];
     int lane_cur = 0;

@@ -924,6 +924,47 @@ class _HipModel:
             out["drops"] = d
         return out
 
+    # ---- subsample mode: the reduction alone (c3_subsample_reduce; Clair3_F.subsample / subsample_rows run the network) ----
+    @staticmethod
+    def _subsample_plan(depths, replicates, seed=0):
+        """(depths int32 [L], replicates, seed) as the C ABI takes them, refused here as the library refuses them"""
+        try:
+            d = np.ascontiguousarray([int(v) for v in depths], dtype=np.int32)
+        except (TypeError, ValueError, OverflowError):
+            raise _lib.C3Error(f"depths must be a sequence of integers, got {depths!r}") from None
+        if not 1 <= len(d) <= syn.SUBSAMPLE_MAX_LEVELS:
+            raise _lib.C3Error(f"levels: 1 .. {syn.SUBSAMPLE_MAX_LEVELS} target depths expected, got {len(d)}")
+        if d[0] < 1 or (np.diff(d.astype(np.int64)) <= 0).any():
+            raise _lib.C3Error(f"depths must be >= 1 and strictly increasing, got {d.tolist()}")
+        if isinstance(replicates, bool) or not isinstance(replicates, (int, np.integer)) or not 1 <= replicates <= syn.SUBSAMPLE_MAX_REPLICATES:
+            raise _lib.C3Error(f"replicates must be an integer in 1 .. {syn.SUBSAMPLE_MAX_REPLICATES}, got {replicates!r}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+            raise _lib.C3Error(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        return d, int(replicates), int(seed)
+
+    def subsample_reduce(self, base_rows, variant_rows, counts, depths=(10, 20, 30, 40), replicates=8):
+        """The records of subsample mode for rows the caller holds (c3_subsample_reduce): ``base_rows`` (B, row) float32, ``variant_rows``
+        (variants, row) the rows of every window's variants in the rule's order -- window by window, level by level (only levels with
+        D_l < counts[w]), replicate by replicate; row = output_size, or that + DECODE_COLS with the decoder columns filled in.  Returns a
+        dict: ``levels`` (B, L) of synthetic.SUBSAMPLE_LEVEL_DTYPE, ``rows`` (B,) of synthetic.SUBSAMPLE_WINDOW_DTYPE, ``counts`` -- what
+        synthetic.subsample_records gives.  Needs no weights."""
+        d, replicates, _ = self._subsample_plan(depths, replicates)
+        self._need_handle()
+        base = np.ascontiguousarray(base_rows, dtype=np.float32)
+        var = np.ascontiguousarray(variant_rows, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if base.ndim != 2 or var.ndim != 2 or var.shape[1] != base.shape[1]:
+            raise _lib.C3Error(f"base rows (B, row) and variant rows (n, row) float32 expected, got {base.shape} and {var.shape}")
+        if counts.shape != (len(base),):
+            raise _lib.C3Error(f"counts must hold one entry per window: shape {counts.shape} for {len(base)} windows")
+        if (counts >= 0).all() and int(syn.subsample_variant_counts(counts, d, replicates).sum()) != len(var):
+            raise _lib.C3Error(f"the plan has {int(syn.subsample_variant_counts(counts, d, replicates).sum())} variants, {len(var)} rows given")
+        lev = np.zeros((len(base), len(d)), dtype=syn.SUBSAMPLE_LEVEL_DTYPE)
+        rec = np.zeros(len(base), dtype=syn.SUBSAMPLE_WINDOW_DTYPE)
+        _lib.check(_lib.lib().c3_subsample_reduce(self._handle, base.ctypes.data, var.ctypes.data, base.shape[1], counts.ctypes.data, len(base),
+                                                  d.ctypes.data, len(d), replicates, rec.ctypes.data, lev.ctypes.data), "c3_subsample_reduce")
+        return dict(levels=lev, rows=rec, counts=counts)
+
     def predict_exact(self, x):
         """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;
         blocking; windows only).  Whatever precision, plan or calibration the handle runs does not enter."""
@@ -1187,6 +1228,58 @@ class Clair3_F(_RingVerify):
         _lib.check(_lib.lib().c3_jackknife(self._handle, x.ctypes.data, dt, x.shape[0], code, y.ctypes.data, rec.ctypes.data,
                                            None if d is None else d.ctypes.data, None if v is None else v.ctypes.data, C.byref(info)), "c3_jackknife")
         return self._jackknife_out(counts, y, rec, d, v, info)
+
+    # ---- subsample mode: at what coverage does a call hold? (c3_subsample_rows) ----
+    def _subsample_call(self, entry, head, counts, y, plan, layout, masks, variant_rows):
+        d, replicates, seed = plan
+        total = int(syn.subsample_variant_counts(np.clip(counts, 0, None), d, replicates).sum())
+        lev = np.zeros((len(counts), len(d)), dtype=syn.SUBSAMPLE_LEVEL_DTYPE)
+        rec = np.zeros(len(counts), dtype=syn.SUBSAMPLE_WINDOW_DTYPE)
+        mk = np.zeros((total, 2), dtype=np.uint64) if masks else None
+        v = np.zeros((total, self.row_size), dtype=np.float32) if variant_rows else None
+        info = _lib.SubsampleInfo()
+        _lib.check(getattr(_lib.lib(), entry)(self._handle, *head, len(counts), d.ctypes.data, len(d), replicates, seed, layout, y.ctypes.data,
+                                              rec.ctypes.data, lev.ctypes.data, None if mk is None else mk.ctypes.data,
+                                              None if v is None else v.ctypes.data, C.byref(info)), entry)
+        out = dict(levels=lev, rows=rec, counts=counts, base_rows=y, depths=d, replicates=replicates, seed=seed, variants=int(info.variants),
+                   on_fp32=bool(info.on_fp32), passes=int(info.passes), bytes_staged=int(info.bytes_staged), expand_us=float(info.expand_us),
+                   reduce_us=float(info.reduce_us))
+        if masks:
+            out["masks"] = mk
+        if variant_rows:
+            out["variant_rows"] = v
+        return out
+
+    def subsample_rows(self, rows, counts, firsts=None, depths=(10, 20, 30, 40), replicates=8, seed=0, layout="recentre", masks=False,
+                       variant_rows=False):
+        """Stability under random read subsampling of windows handed over as their occupied rows (predict_rows's arguments;
+        c3_subsample_rows): for every target depth D of ``depths`` (1 .. 8 of them, strictly increasing) below a window's counts[w] the device
+        draws ``replicates`` (1 .. 32) subsets of D of its reads from a counter hash of ``seed`` -- nested from level to level --, lays them
+        out by the reference's padding rule ("recentre") or where the run starts ("in_place"), runs them through the forward pass beside the
+        window itself and reduces their rows.  Returns a dict: ``levels`` (B, L) of synthetic.SUBSAMPLE_LEVEL_DTYPE (keep, run, nonfinite,
+        decision_flips, flips and min_kept per head), ``rows`` (B,) of synthetic.SUBSAMPLE_WINDOW_DTYPE (reads, levels_run, hold_level per
+        head, hold_decision), ``counts``, ``base_rows`` -- bit for bit predict_rows(rows, counts, firsts) --, ``variants``, ``on_fp32``,
+        ``passes``, ``bytes_staged``, ``expand_us`` / ``reduce_us``; with masks=True ``masks`` (variants, 2) uint64, bit j = read j kept,
+        with variant_rows=True ``variant_rows`` (variants, row_size).  synthetic.subsample_masks / subsample_variants /
+        subsample_records are the same in numpy."""
+        code = self._jackknife_layout(layout)
+        plan = self._subsample_plan(depths, replicates, seed)
+        rows, counts, firsts, y = self._rows_args(rows, counts, firsts)
+        head = (rows.ctypes.data, None if firsts is None else firsts.ctypes.data, counts.ctypes.data)
+        return self._subsample_call("c3_subsample_rows", head, counts, y, plan, code, masks, variant_rows)
+
+    def subsample(self, x, depths=(10, 20, 30, 40), replicates=8, seed=0, layout="recentre", masks=False, variant_rows=False):
+        """subsample_rows of dense int8 windows (c3_subsample): every window's run -- from its first to its last non-zero row -- is found on
+        the host as synthetic.pack_fa_rows finds it, and its first row is the run's own.  ``counts`` of the result are the runs' lengths."""
+        code = self._jackknife_layout(layout)
+        plan = self._subsample_plan(depths, replicates, seed)
+        self._need_handle()
+        x, dt = self._window_batch(x)
+        if x.ndim != 4:
+            raise _lib.C3Error(f"windows (B, depth, positions, C) expected, got shape {x.shape}")
+        _, _, counts = syn.pack_fa_rows(x)
+        y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
+        return self._subsample_call("c3_subsample", (x.ctypes.data, dt), counts, y, plan, code, masks, variant_rows)
 
     def submit_rows(self, rows, counts, firsts=None, slot=0):
         """Asynchronous half of predict_rows (c3_predict_submit_rows); returns a handle for wait()."""

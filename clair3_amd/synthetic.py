@@ -683,3 +683,153 @@ def jackknife_records(base_rows, variant_rows, counts, nout, columns=None):
                 for k in range(4):
                     rec["decision_flips"][b, k] = int((v[:, nout + 23 + k] != y[nout + 23 + k]).sum())
     return rec, drops
+
+
+# ---- subsample mode in numpy: the rule of csrc/c3_subsample.h (tests/test_subsample.py holds the two together) ----
+# c3_subsample_level (48 bytes) and c3_subsample_window (32 bytes) of include/c3hip.h
+SUBSAMPLE_LEVEL_DTYPE = np.dtype([("keep", "<i4"), ("run", "<i4"), ("nonfinite", "<i4"), ("decision_flips", "<i4"), ("flips", "<i4", (4,)),
+                                  ("min_kept", "<f4", (4,))])
+SUBSAMPLE_WINDOW_DTYPE = np.dtype([("reads", "<i4"), ("levels_run", "<i4"), ("hold_level", "<i4", (4,)), ("hold_decision", "<i4"), ("reserved", "<i4")])
+SUBSAMPLE_MAX_LEVELS, SUBSAMPLE_MAX_REPLICATES, SUBSAMPLE_MAX_DEPTH = 8, 32, 128
+_M64 = (1 << 64) - 1
+
+
+def subsample_mix(z):
+    """the SplitMix64 finaliser on a uint64 array (arithmetic mod 2^64)"""
+    z = np.asarray(z, dtype=np.uint64).copy()
+    z ^= z >> np.uint64(30)
+    z *= np.uint64(0xBF58476D1CE4E5B9)
+    z ^= z >> np.uint64(27)
+    z *= np.uint64(0x94D049BB133111EB)
+    z ^= z >> np.uint64(31)
+    return z
+
+
+def subsample_keys(seed, w, r, n, depth, replicates):
+    """(n,) uint64: key(w, r, j) = mix(seed + 0x9E3779B97F4A7C15 * (1 + (w * R + r) * depth + j)) for the reads j < n of window ``w`` (its
+    index in the call) in replicate ``r``; ``depth`` is the handle's"""
+    first = (1 + (int(w) * int(replicates) + int(r)) * int(depth)) & _M64
+    counter = np.uint64(first) + np.arange(int(n), dtype=np.uint64)
+    return subsample_mix(np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * counter)
+
+
+def subsample_rank(keys, k):
+    """(n,) bool: the ``k`` reads of smallest (key, j) -- rank by key, the lowest j first on equal keys"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    mask = np.zeros(len(keys), dtype=bool)
+    mask[np.argsort(keys, kind="stable")[:max(int(k), 0)]] = True
+    return mask
+
+
+def _subsample_plan(counts, depths, replicates):
+    counts = np.asarray(counts, dtype=np.int64)
+    depths = [int(d) for d in depths]
+    if counts.ndim != 1 or (counts < 0).any():
+        raise ValueError("counts (B,) >= 0 expected")
+    if not 1 <= len(depths) <= SUBSAMPLE_MAX_LEVELS or depths[0] < 1 or any(b <= a for a, b in zip(depths, depths[1:])):
+        raise ValueError(f"1 .. {SUBSAMPLE_MAX_LEVELS} strictly increasing target depths >= 1 expected, got {depths}")
+    if not 1 <= int(replicates) <= SUBSAMPLE_MAX_REPLICATES:
+        raise ValueError(f"replicates must lie in 1 .. {SUBSAMPLE_MAX_REPLICATES}, got {replicates}")
+    return counts, depths, int(replicates)
+
+
+def subsample_variant_counts(counts, depths, replicates):
+    """(B,) int64: the variants of every window -- ``replicates`` per level with D_l < counts[w]"""
+    counts, depths, R = _subsample_plan(counts, depths, replicates)
+    return R * (np.asarray(depths, dtype=np.int64)[None, :] < counts[:, None]).sum(axis=1)
+
+
+def subsample_masks(counts, depths, replicates, seed, depth):
+    """(variants, 2) uint64: the kept-read bitmask of every variant in the rule's order -- window by window, level by level (only levels with
+    D_l < counts[w]: k == n is not run), replicate by replicate --, bit j of the pair = read j kept (j < 64 in word 0)"""
+    counts, depths, R = _subsample_plan(counts, depths, replicates)
+    if (counts > depth).any() or depth > SUBSAMPLE_MAX_DEPTH:
+        raise ValueError(f"counts must lie in [0, {depth}] and the depth in [1, {SUBSAMPLE_MAX_DEPTH}]")
+    out = []
+    for w, n in enumerate(counts):
+        keys = [subsample_keys(seed, w, r, n, depth, R) for r in range(R)]
+        for k in depths:
+            if k >= n:
+                continue
+            for r in range(R):
+                bits = sum(1 << int(j) for j in np.flatnonzero(subsample_rank(keys[r], k)))
+                out.append((bits & _M64, bits >> 64))
+    return np.array(out, dtype=np.uint64).reshape(len(out), 2)
+
+
+def subsample_variants(rows, counts, firsts=None, depths=(10, 20, 30, 40), replicates=8, seed=0, depth=FA_DEPTH_ONT, layout="recentre"):
+    """The variants of subsample mode of windows given as their occupied rows (pad_fa_rows's arguments), dense, (variants, depth, positions, C)
+    int8 in the rule's order.  A variant keeps the reads its mask names, in read order; layout "recentre": they start at dense row
+    (depth - k) // 2; "in_place": where the base window's run starts (firsts[w], or its centred first)."""
+    if layout not in JACKKNIFE_LAYOUTS:
+        raise ValueError(f"layout must be one of {JACKKNIFE_LAYOUTS}, got {layout!r}")
+    rows = np.asarray(rows)
+    counts, depths, R = _subsample_plan(counts, depths, replicates)
+    pad_fa_rows(rows, counts, firsts, depth)  # (its checks)
+    base_first = (depth - counts) // 2 if firsts is None else np.asarray(firsts, dtype=np.int64)
+    masks = subsample_masks(counts, depths, R, seed, depth)
+    src = np.r_[0, np.cumsum(counts)]
+    v_rows, v_counts, v_firsts, at = [], [], [], 0
+    for w, n in enumerate(counts):
+        run = rows[src[w]:src[w + 1]]
+        for k in depths:
+            if k >= n:
+                continue
+            for r in range(R):
+                bits = int(masks[at, 0]) | int(masks[at, 1]) << 64
+                v_rows.append(run[[j for j in range(n) if bits >> j & 1]])
+                v_counts.append(k)
+                v_firsts.append(base_first[w] if layout == "in_place" else (depth - k) // 2)
+                at += 1
+    flat = np.concatenate(v_rows) if v_rows else np.zeros((0,) + rows.shape[1:], dtype=rows.dtype)
+    return pad_fa_rows(flat, np.asarray(v_counts, dtype=np.int64), np.asarray(v_firsts, dtype=np.int64), depth)
+
+
+def subsample_records(base_rows, variant_rows, counts, depths, replicates, nout):
+    """(levels, windows) of subsample mode (c3_subsample_reduce; csrc/c3_subsample.h states the rule): ``base_rows`` (B, row) float32,
+    ``variant_rows`` (variants, row) in the rule's order; row = nout or nout + DECODE_COLS.  levels: (B, L) of SUBSAMPLE_LEVEL_DTYPE;
+    windows: (B,) of SUBSAMPLE_WINDOW_DTYPE."""
+    base = np.asarray(base_rows, dtype=np.float32)
+    var = np.asarray(variant_rows, dtype=np.float32)
+    counts, depths, R = _subsample_plan(counts, depths, replicates)
+    if base.ndim != 2 or var.ndim != 2 or nout not in (24, 90) or base.shape[1] not in (nout, nout + DECODE_COLS) or var.shape[1] != base.shape[1]:
+        raise ValueError(f"base rows {base.shape} and variant rows {var.shape} are not rows of {nout} probabilities with or without the decoder columns")
+    per_window = subsample_variant_counts(counts, depths, R)
+    if counts.shape != (len(base),) or int(per_window.sum()) != len(var):
+        raise ValueError(f"counts must hold one entry per window and the plan's {int(per_window.sum())} variants must be the {len(var)} rows given")
+    columns = base.shape[1] > nout
+    heads = head_slices(nout)
+    L = len(depths)
+    lev = np.zeros((len(base), L), dtype=SUBSAMPLE_LEVEL_DTYPE)
+    win = np.zeros(len(base), dtype=SUBSAMPLE_WINDOW_DTYPE)
+    at = 0
+    for b in range(len(base)):
+        y, n = base[b], int(counts[b])
+        t = [lo + int(_first_argmax(y[None, lo:hi])[0]) for lo, hi in heads]
+        win["reads"][b] = n
+        for l, d in enumerate(depths):
+            k = min(n, d)
+            rec = lev[b, l]
+            rec["keep"] = k
+            for h in range(len(heads)):
+                rec["min_kept"][h] = y[t[h]]
+            if k == n:
+                continue
+            v = var[at:at + R]
+            at += R
+            rec["run"] = R
+            win["levels_run"][b] += 1
+            finite = np.isfinite(v[:, :nout]).all(axis=1)
+            rec["nonfinite"] = int((~finite).sum())
+            for h, (lo, hi) in enumerate(heads):
+                rec["flips"][h] = int((lo + _first_argmax(v[:, lo:hi]) != t[h]).sum())
+                if finite.any():
+                    kept = v[finite, t[h]]
+                    rec["min_kept"][h] = kept[int(np.argmin(kept))]  # the first of the smallest: -0 and +0 are a tie
+                if rec["flips"][h]:
+                    win["hold_level"][b, h] = l + 1
+            if columns:
+                rec["decision_flips"] = int((v[:, nout + 23:nout + 27] != y[None, nout + 23:nout + 27]).any(axis=1).sum())
+                if rec["decision_flips"]:
+                    win["hold_decision"][b] = l + 1
+    return lev, win

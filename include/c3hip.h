@@ -851,6 +851,79 @@ int c3_jackknife(c3_model *m, const void *x_host, int x_dtype, int64_t batch, in
 int c3_jackknife_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, const int32_t *row_count,
                         int64_t batch, c3_jackknife_window *out, float *drops_out);
 
+/* ---- subsample mode: full-alignment calls under random read subsampling ("Subsample mode") ----
+ * Jackknife mode takes ONE read away; this asks at what coverage a call holds.  A window handed over as its occupied rows has n =
+ * row_count[w] reads.  The call names `levels` target depths D_0 < .. < D_{L-1} (1 <= L <= 8, every D >= 1), `replicates` R (1 <= R <= 32)
+ * and a seed; for every level with D_l < n the device builds R variants of the window, each keeping D_l of its reads -- the subsets are
+ * decided ON THE DEVICE from a stateless counter hash --, runs them through the unchanged forward pass beside the window itself (the forms
+ * the handle is on) and reduces their rows to one record per (window, level) and one per window.  An instrument like jackknife mode:
+ * blocking, in the first lane, and nothing is allocated, launched or planned unless one of these entries is called.
+ * The rule (clair3_amd/csrc/c3_subsample.h states it once; in numpy: synthetic.subsample_keys / subsample_masks / subsample_variants /
+ * subsample_records), w the window's index in the CALL:
+ *   keys        key(w, r, j) = mix(seed + 0x9E3779B97F4A7C15 * (1 + (w * R + r) * depth + j)) mod 2^64, mix the SplitMix64 finaliser; the
+ *               key does not depend on the level, so a replicate's subsets are nested
+ *   selection   k = min(n, D_l); k == n: the level is not run for that window (it holds by definition); k < n: replicate r keeps the k reads
+ *               of smallest (key, j), in read order.  Without replacement
+ *   layout      C3_JACKKNIFE_RECENTRE: the kept rows start at dense row (depth - k) / 2; C3_JACKKNIFE_IN_PLACE: at the base window's first row
+ *   order       of the variants: window by window, level by level (only levels that ran), replicate by replicate
+ *   a NaN       or an infinity among a variant's probabilities: the variant counts in `nonfinite` and, by the arg-max rule of jackknife
+ *               mode, in flips and decision_flips; it is left out of min_kept */
+typedef struct c3_subsample_level {    /* 48 bytes; [batch][levels] */
+    int32_t keep;               /* k = min(n, D_l) */
+    int32_t run;                /* R, or 0 when k == n */
+    int32_t nonfinite;          /* variants with a non-finite probability in their first nout columns */
+    int32_t decision_flips;     /* rows with decoder columns: variants in which any of the decoder columns 23 .. 26 differs from the base
+                                   row's; without decoder columns: 0 */
+    int32_t flips[4];           /* per head h: variants whose arg-max in h differs from the base row's (heads the model lacks: 0) */
+    float   min_kept[4];        /* per head: min over the level's finite variants of v[t_h], t_h the base arg-max of the head; the bits of
+                                   the base row's y[t_h] when no finite variant ran; 0 for a head the model lacks */
+} c3_subsample_level;
+typedef struct c3_subsample_window {   /* 32 bytes */
+    int32_t reads;              /* n */
+    int32_t levels_run;
+    int32_t hold_level[4];      /* per head: the lowest level index l with flips[h] == 0 at l and at every deeper level (levels that did not
+                                   run hold); `levels` when the deepest level itself flips; 0 for a head the model lacks */
+    int32_t hold_decision;      /* the same over decision_flips */
+    int32_t reserved;
+} c3_subsample_window;
+/* what a call did (the trailing argument of the two entries that run the network; may be NULL) */
+typedef struct {
+    int64_t windows, variants;  /* of the call */
+    int64_t passes;             /* the call is cut into passes of C3HIP_SUBSAMPLE_CHUNK windows (env; default 64, 0 = never cut) */
+    int64_t bytes_staged;       /* host to device: the occupied rows and the tables */
+    int32_t on_fp32;            /* 1: the range guard met a pass and that pass ran again on the fp32 forms */
+    int32_t reserved;
+    float expand_us, reduce_us; /* device time of the call's subsample_expand_kernel / subsample_reduce_kernel launches (HIP events, summed) */
+} c3_subsample_info;
+/*   c3_subsample_rows    the window arguments of c3_predict_rows.  Cut into passes of C3HIP_SUBSAMPLE_CHUNK windows (read at every call); a
+ *                        window's variants never straddle a pass, and because the hash uses the call's window index the results do not
+ *                        depend on the cut.  Per pass the occupied rows and one table are staged once, the dense windows are built
+ *                        micro-batch by micro-batch in front of the forward pass, the reduction runs behind the last one and the host waits
+ *                        once, for the records.
+ *                          y_host            (may be NULL) [batch][row]: bit for bit c3_predict_rows of the same arguments
+ *                          out               [batch] window records;  levels_out  [batch][levels] level records
+ *                          masks_out         (may be NULL) [variants][2] uint64: bit j of the pair = read j kept
+ *                          variant_rows_out  (may be NULL) [variants][row]: the variants' rows, for tests and tools
+ *                        The handle is left as it was, and the range guard behaves as in c3_jackknife_rows: a pass beyond the fp16 range runs
+ *                        again on the fp32-MFMA forms for this call alone, info->on_fp32 says so.
+ *   c3_subsample         dense int8 windows: every window's run is found on the host as c3_jackknife finds it.
+ *   c3_subsample_reduce  the reduction alone on rows the caller holds (row_floats == c3_model_output_size(), or that + C3_DECODE_COLS):
+ *                        base_rows [batch][row_floats], variant_rows [variants][row_floats] in the rule's order.  Needs no weights; serves
+ *                        both kinds.
+ * Refused before anything is queued: a null model; a pileup handle, a handle without weights, a handle deeper than 128 rows (the two
+ * entries that run the network); a submit pending on any slot of the ring; a handle that answers from the exact form; a layout other than
+ * the two; levels outside 1 .. 8; depths not strictly increasing or below 1; replicates outside 1 .. 32; a negative count, first < 0,
+ * first + count > depth; null required buffers; row_floats that is neither of the two.  batch == 0 launches nothing. */
+int c3_subsample_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch,
+                      const int32_t *depths, int levels, int replicates, uint64_t seed, int layout, float *y_host, c3_subsample_window *out,
+                      c3_subsample_level *levels_out, uint64_t *masks_out, float *variant_rows_out, c3_subsample_info *info);
+int c3_subsample(c3_model *m, const void *x_host, int x_dtype, int64_t batch, const int32_t *depths, int levels, int replicates,
+                 uint64_t seed, int layout, float *y_host, c3_subsample_window *out, c3_subsample_level *levels_out, uint64_t *masks_out,
+                 float *variant_rows_out, c3_subsample_info *info);
+int c3_subsample_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, const int32_t *row_count,
+                        int64_t batch, const int32_t *depths, int levels, int replicates, c3_subsample_window *out,
+                        c3_subsample_level *levels_out);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
