@@ -40,6 +40,7 @@ EXPORTS = (
     "c3_model_set_refine", "c3_model_refine_stats", "c3_model_refine_reset", "c3_refine_select",
     "c3_jackknife_rows", "c3_jackknife", "c3_jackknife_reduce",
     "c3_subsample_rows", "c3_subsample", "c3_subsample_reduce",
+    "c3_occlude", "c3_occlude_rows", "c3_occlude_reduce",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -149,6 +150,22 @@ class SubsampleWindow(C.Structure):
 
 class SubsampleInfo(C.Structure):
     """c3_subsample_info (include/c3hip.h)"""
+    _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
+                ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
+
+
+# what occlusion mode sets to zero (C3_OCCLUDE_* in include/c3hip.h)
+OCCLUDE_WHAT = {"channels": 1, "bands": 2, "both": 3}
+
+
+class OccludeWindow(C.Structure):
+    """c3_occlude_window (include/c3hip.h); synthetic.OCCLUDE_DTYPE is the same record as a numpy dtype"""
+    _fields_ = [("variants", C.c_int32), ("nonfinite", C.c_int32), ("flips", C.c_int32 * 4 * 2), ("decision_flips", C.c_int32 * 4 * 2),
+                ("lean", C.c_int32 * 4 * 2), ("lean_drop", C.c_float * 4 * 2), ("max_delta", C.c_float), ("reserved", C.c_int32)]
+
+
+class OccludeInfo(C.Structure):
+    """c3_occlude_info (include/c3hip.h)"""
     _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
                 ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
 
@@ -292,6 +309,11 @@ def lib():
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SubsampleInfo)]
     L.c3_subsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SubsampleInfo)]
+    L.c3_occlude.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(OccludeInfo)]
+    L.c3_occlude_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(OccludeInfo)]
+    L.c3_occlude_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
     L.c3_subsample_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

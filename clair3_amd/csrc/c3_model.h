@@ -277,6 +277,8 @@ struct Lane {
     int64_t xr_cap = 0;     // windows it holds
     int8_t *xe = nullptr;   // dense int8 windows of a micro-batch that came as occupied rows (c3_expand.h); allocated on first use
     int64_t xe_cap = 0;     // windows it holds
+    void *xo = nullptr;     // dense pileup windows of a micro-batch that occlusion mode builds (c3_occlude.h); allocated on first use
+    int64_t xo_cap = 0;     // int32 windows it holds
 };
 // ---- the exact form (c3_exact.h): never enabled = nothing allocated, uploaded or launched ----
 struct ExactState {
@@ -498,6 +500,10 @@ struct c3_model {
     // ---- subsample mode (c3_subsample_rows, c3_subsample.h): never called = nothing allocated, nothing launched ----
     void *subsample_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows, its records and masks; grown on demand
     size_t subsample_bytes = 0;
+
+    // ---- occlusion mode (c3_occlude, c3_occlude.h): never called = nothing allocated, nothing launched ----
+    void *occlude_dev = nullptr;  // a pass's staged input, its table, the rows of its dense windows, its records and drops; grown on demand
+    size_t occlude_bytes = 0;
 
     // ---- workspaces and kernel streams: the lanes (Lane above; lane(m) is the active one) ----
     Lane lanes[kMaxLanes];
@@ -721,6 +727,8 @@ static void free_workspace(Lane &L) {
     L.xr = nullptr, L.xr_cap = 0;
     if (L.xe) (void)hipFree(L.xe);
     L.xe = nullptr, L.xe_cap = 0;
+    if (L.xo) (void)hipFree(L.xo);
+    L.xo = nullptr, L.xo_cap = 0;
 }
 static void free_all_workspaces(c3_model *m) {  // every lane's (geometry change, destruction)
     for (Lane &L : m->lanes) free_workspace(L);

@@ -965,6 +965,77 @@ class _HipModel:
                                                   d.ctypes.data, len(d), replicates, rec.ctypes.data, lev.ctypes.data), "c3_subsample_reduce")
         return dict(levels=lev, rows=rec, counts=counts)
 
+    # ---- occlusion mode: which channels and columns a call leans on (c3_occlude, c3_occlude_rows, c3_occlude_reduce) ----
+    def _occlude_plan(self, what, band):
+        """(the code of ``what``, band, channels of group 0, bands of group 1) for the handle's geometry"""
+        if what not in _lib.OCCLUDE_WHAT:
+            raise _lib.C3Error(f"what must be 'channels', 'bands' or 'both', got {what!r}")
+        positions = (self._geometry or (89, 33))[1]
+        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 1 <= band <= positions:
+            raise _lib.C3Error(f"band must be an integer in 1 .. {positions}, got {band!r}")
+        nc, nb = syn.occlude_groups(positions, self.input_channels, what, int(band))
+        return _lib.OCCLUDE_WHAT[what], int(band), nc, nb
+
+    def _occlude_call(self, entry, head, batch, plan, drops, variant_rows, extra):
+        code, band, nc, nb = plan
+        K = nc + nb
+        y = np.empty((batch, self.row_size), dtype=np.float32)
+        rec = np.zeros(batch, dtype=syn.OCCLUDE_DTYPE)
+        d = np.zeros((batch, K, 4), dtype=np.float32) if drops else None
+        v = np.zeros((batch * K, self.row_size), dtype=np.float32) if variant_rows else None
+        info = _lib.OccludeInfo()
+        _lib.check(getattr(_lib.lib(), entry)(self._handle, *head, batch, code, band, y.ctypes.data, rec.ctypes.data,
+                                              None if d is None else d.ctypes.data, None if v is None else v.ctypes.data, C.byref(info)), entry)
+        out = dict(rows=rec, base_rows=y, channels=nc, bands=nb, band=band, on_fp32=bool(info.on_fp32), passes=int(info.passes),
+                   bytes_staged=int(info.bytes_staged), expand_us=float(info.expand_us), reduce_us=float(info.reduce_us), **extra)
+        if drops:
+            out["drops"] = d
+        if variant_rows:
+            out["variant_rows"] = v
+        return out
+
+    def occlude(self, x, what="both", band=1, drops=False, variant_rows=False):
+        """Which input channels and which columns the calls of the dense windows ``x`` lean on (c3_occlude; either network): for every window
+        the device builds K variants -- the window with one channel set to zero (what "channels" or "both": C of them), the window with the
+        columns [k * band, (k + 1) * band) set to zero ("bands" or "both": ceil(P / band)) --, runs them through the forward pass beside the
+        window itself and reduces their rows to one record.  Returns a dict: ``rows`` (B,) of synthetic.OCCLUDE_DTYPE (variants, nonfinite;
+        per group [0 = channels, 1 = bands]: flips per head, decision_flips per reference base, lean / lean_drop per head; max_delta),
+        ``base_rows`` -- bit for bit predict_numpy(x) --, ``channels``, ``bands`` (the two groups' sizes), ``band``, ``on_fp32`` (full
+        alignment: the range guard met the call and it ran on the fp32 forms; the handle stays as it was), ``passes``, ``bytes_staged``,
+        ``expand_us`` / ``reduce_us``; with drops=True ``drops`` (B, K, 4), the map of every variant's drop in every head, with
+        variant_rows=True ``variant_rows`` (B * K, row_size).  synthetic.occlude_variants / occlude_records are the same in numpy."""
+        plan = self._occlude_plan(what, band)
+        self._need_handle()
+        x, dt = self._window_batch(x)
+        extra = {}
+        if self.KIND == _lib.KIND_FULL_ALIGNMENT:
+            if x.ndim != 4:
+                raise _lib.C3Error(f"windows (B, depth, positions, C) expected, got shape {x.shape}")
+            extra["counts"] = syn.pack_fa_rows(x)[2]
+        return self._occlude_call("c3_occlude", (x.ctypes.data, dt), x.shape[0], plan, drops, variant_rows, extra)
+
+    def occlude_reduce(self, base_rows, variant_rows, channels, bands, drops=False):
+        """The records of occlusion mode for rows the caller holds (c3_occlude_reduce): ``base_rows`` (B, row) float32, ``variant_rows``
+        (B * (channels + bands), row) every window's variants, group 0 then group 1; row = output_size, or that + DECODE_COLS with the
+        decoder columns filled in.  Returns a dict: ``rows`` (B,) of synthetic.OCCLUDE_DTYPE, ``channels``, ``bands``, and with drops=True
+        ``drops`` (B, K, 4) -- what synthetic.occlude_records gives.  Needs no weights."""
+        self._need_handle()
+        base = np.ascontiguousarray(base_rows, dtype=np.float32)
+        var = np.ascontiguousarray(variant_rows, dtype=np.float32)
+        channels, bands = int(channels), int(bands)
+        if base.ndim != 2 or var.ndim != 2 or var.shape[1] != base.shape[1]:
+            raise _lib.C3Error(f"base rows (B, row) and variant rows (n, row) float32 expected, got {base.shape} and {var.shape}")
+        if channels >= 0 and bands >= 0 and len(var) != len(base) * (channels + bands):
+            raise _lib.C3Error(f"{len(base)} windows of {channels + bands} variants need {len(base) * (channels + bands)} variant rows, {len(var)} given")
+        rec = np.zeros(len(base), dtype=syn.OCCLUDE_DTYPE)
+        d = np.zeros((len(base), max(channels + bands, 0), 4), dtype=np.float32) if drops else None
+        _lib.check(_lib.lib().c3_occlude_reduce(self._handle, base.ctypes.data, var.ctypes.data, base.shape[1], channels, bands, len(base),
+                                                rec.ctypes.data, None if d is None else d.ctypes.data), "c3_occlude_reduce")
+        out = dict(rows=rec, channels=channels, bands=bands)
+        if drops:
+            out["drops"] = d
+        return out
+
     def predict_exact(self, x):
         """float64 (B, 24|90): the rows of the windows ``x`` in the arithmetic of the fp64 oracle, computed on the device (c3_predict_exact;
         blocking; windows only).  Whatever precision, plan or calibration the handle runs does not enter."""
@@ -1280,6 +1351,14 @@ class Clair3_F(_RingVerify):
         _, _, counts = syn.pack_fa_rows(x)
         y = np.empty((x.shape[0], self.row_size), dtype=np.float32)
         return self._subsample_call("c3_subsample", (x.ctypes.data, dt), counts, y, plan, code, masks, variant_rows)
+
+    def occlude_rows(self, rows, counts, firsts=None, what="both", band=1, drops=False, variant_rows=False):
+        """occlude() of windows handed over as their occupied rows (predict_rows's arguments; c3_occlude_rows): the variants keep the run
+        where ``firsts`` or the centring rule puts it.  ``base_rows`` of the result are bit for bit predict_rows(rows, counts, firsts)."""
+        plan = self._occlude_plan(what, band)
+        rows, counts, firsts, _ = self._rows_args(rows, counts, firsts)
+        head = (rows.ctypes.data, None if firsts is None else firsts.ctypes.data, counts.ctypes.data)
+        return self._occlude_call("c3_occlude_rows", head, len(counts), plan, drops, variant_rows, dict(counts=counts))
 
     def submit_rows(self, rows, counts, firsts=None, slot=0):
         """Asynchronous half of predict_rows (c3_predict_submit_rows); returns a handle for wait()."""

@@ -833,3 +833,68 @@ def subsample_records(base_rows, variant_rows, counts, depths, replicates, nout)
                 if rec["decision_flips"]:
                     win["hold_decision"][b] = l + 1
     return lev, win
+
+
+# ---- occlusion mode in numpy: the definitions of csrc/c3_occlude.h (tests/test_occlude.py holds the two together) ----
+OCCLUDE_WHAT = {"channels": 1, "bands": 2, "both": 3}  # C3_OCCLUDE_CHANNELS, C3_OCCLUDE_BANDS, both
+# c3_occlude_window (include/c3hip.h), 144 bytes; [g]: group 0 = channels, group 1 = bands
+OCCLUDE_DTYPE = np.dtype([("variants", "<i4"), ("nonfinite", "<i4"), ("flips", "<i4", (2, 4)), ("decision_flips", "<i4", (2, 4)),
+                          ("lean", "<i4", (2, 4)), ("lean_drop", "<f4", (2, 4)), ("max_delta", "<f4"), ("reserved", "<i4")])
+
+
+def occlude_groups(positions, channels, what="both", band=1):
+    """(channels of group 0, bands of group 1) of a call: C or 0, and nb = ceil(P / band) or 0"""
+    if what not in OCCLUDE_WHAT:
+        raise ValueError(f"what must be one of {tuple(OCCLUDE_WHAT)}, got {what!r}")
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 1 <= band <= positions:
+        raise ValueError(f"band must be an integer in 1 .. {positions}, got {band!r}")
+    code = OCCLUDE_WHAT[what]
+    return (channels if code & 1 else 0), (-(-positions // int(band)) if code & 2 else 0)
+
+
+def occlude_variants(x, what="both", band=1):
+    """The variants of occlusion mode of the windows ``x`` (B, ..., positions, channels) -- full-alignment (B, depth, P, C) or pileup
+    (B, P, C), any dtype --, dense, (B * K, ...) in the order of c3_occlude: window after window, for each first the C variants with one
+    channel set to zero (when what is "channels" or "both"), then the nb = ceil(P / band) variants with every channel of the columns
+    [k * band, min(P, (k + 1) * band)) set to zero (when what is "bands" or "both").  Nothing else moves."""
+    x = np.asarray(x)
+    if x.ndim < 3:
+        raise ValueError(f"windows (B, ..., positions, channels) expected, got shape {x.shape}")
+    P, C = x.shape[-2:]
+    nc, nb = occlude_groups(P, C, what, band)
+    out = np.repeat(x[:, None], nc + nb, axis=1)  # (B, K, ..., P, C), a copy
+    for c in range(nc):
+        out[:, c, ..., c] = 0
+    for k in range(nb):
+        out[:, nc + k, ..., k * band:(k + 1) * band, :] = 0
+    return out.reshape((len(x) * (nc + nb),) + x.shape[1:])
+
+
+def occlude_records(base_rows, variant_rows, channels, bands, nout):
+    """(records, drops) of occlusion mode (c3_occlude_reduce; csrc/c3_occlude.h states the definitions): ``base_rows`` (B, row) float32,
+    ``variant_rows`` (B * K, row) with K = channels + bands, every window's variants in the order of occlude_variants; ``channels`` and
+    ``bands`` are the sizes of the two groups (either may be 0); row = nout or nout + DECODE_COLS.  records: (B,) of OCCLUDE_DTYPE;
+    drops: (B, K, 4) float32, y[t_h] - v_j[t_h].  Within a group the rule is jackknife_records' with the group's members as the reads."""
+    base = np.asarray(base_rows, dtype=np.float32)
+    var = np.asarray(variant_rows, dtype=np.float32)
+    if channels < 0 or bands < 0:
+        raise ValueError(f"group sizes must be >= 0, got {channels} and {bands}")
+    K = int(channels) + int(bands)
+    if base.ndim != 2 or var.ndim != 2 or nout not in (24, 90) or base.shape[1] not in (nout, nout + DECODE_COLS) or var.shape[1] != base.shape[1]:
+        raise ValueError(f"base rows {base.shape} and variant rows {var.shape} are not rows of {nout} probabilities with or without the decoder columns")
+    if len(var) != len(base) * K:
+        raise ValueError(f"{len(base)} windows of {K} variants need {len(base) * K} variant rows, {len(var)} given")
+    B, row = base.shape
+    var = var.reshape(B, K, row)
+    rec = np.zeros(B, dtype=OCCLUDE_DTYPE)
+    rec["variants"] = K
+    rec["lean"] = -1
+    drops = np.zeros((B, K, 4), dtype=np.float32)
+    for g, (lo, n) in enumerate(((0, int(channels)), (int(channels), int(bands)))):
+        r, d = jackknife_records(base, var[:, lo:lo + n].reshape(B * n, row), np.full(B, n, np.int64), nout)
+        rec["nonfinite"] += r["nonfinite"]
+        rec["flips"][:, g], rec["decision_flips"][:, g] = r["flips"], r["decision_flips"]
+        rec["lean"][:, g], rec["lean_drop"][:, g] = r["lean_read"], r["lean_drop"]
+        rec["max_delta"] = np.maximum(rec["max_delta"], r["max_delta"])
+        drops[:, lo:lo + n] = d.reshape(B, n, 4)
+    return rec, drops

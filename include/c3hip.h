@@ -924,6 +924,90 @@ int c3_subsample_reduce(c3_model *m, const float *base_rows, const float *varian
                         int64_t batch, const int32_t *depths, int levels, int replicates, c3_subsample_window *out,
                         c3_subsample_level *levels_out);
 
+/* ---- occlusion mode: which channels and which columns a call leans on, for both networks ("Occlusion mode") ----
+ * Jackknife and subsample mode say what the READS do to a label; they refuse a pileup handle, whose windows hold counts.  This instrument
+ * is on the input side of BOTH networks: for every window of a call the device builds K variants from the window staged once -- the window
+ * with one channel set to zero, the window with one band of columns set to zero --, runs them through the unchanged forward pass beside the
+ * window itself -- the forms the handle is on: its plan, C3HIP_FP32, its calibration -- and reduces their rows to one record per window plus
+ * the complete map of drops.  Blocking, in the first lane, and nothing is allocated, launched or planned unless one of these entries is
+ * called.
+ * The definitions (clair3_amd/csrc/c3_occlude.h; in numpy: synthetic.occlude_variants / occlude_records).  A window has P positions and C
+ * channels, the handle's geometry: full alignment (depth, P, C) int8, pileup (P, C) int8 or int32.  A call names `what`
+ * (C3_OCCLUDE_CHANNELS = 1, C3_OCCLUDE_BANDS = 2, both = 3) and `band` (1 <= band <= P, columns per band); nb = ceil(P / band), band k
+ * covers the columns [k * band, min(P, (k + 1) * band)).
+ *   variants    every window of the call has the same K = (C if channels) + (nb if bands) variants, in this order: group 0, when channels
+ *               are asked for: variant c (0 <= c < C) is the window with channel c set to zero at every position, and in every read for full
+ *               alignment; group 1, when bands are asked for: variant k (0 <= k < nb) is the window with every channel of band k's columns
+ *               set to zero, in every read.  Everything else stays where it is: a full-alignment variant keeps the base window's run where
+ *               row_first / the centring rule puts it -- a read is not removed, so nothing is laid out again.  Window b's variants are the
+ *               call's variants b * K .. b * K + K - 1.  A window without reads, or an all-zero window, still has K variants: all of them
+ *               the zero window
+ *   arg-max     of a head (21 | 3 | 33 | 33 columns): the first maximum by `>` from -inf on -- the lowest index on ties, a NaN never, the
+ *               head's first column when nothing exceeds -inf: the rule of the census, of refine mode and of jackknife mode
+ *   drop        of variant j in head h: y[t_h] - v_j[t_h] in one float32 subtraction, t_h the arg-max of the window's own row y in the head;
+ *               0 for a head the model lacks
+ *   a NaN       or an infinity among a variant's first nout columns: the variant counts in `nonfinite` and, by the arg-max rule, in flips
+ *               and decision_flips; it is left out of lean / lean_drop and of max_delta.  A drop that is a NaN (the base row's own value is
+ *               one) is never the largest; a zero drop that leans is reported as +0 */
+#define C3_OCCLUDE_CHANNELS 1
+#define C3_OCCLUDE_BANDS 2
+typedef struct c3_occlude_window {        /* 144 bytes; [g]: group 0 = channels, group 1 = bands */
+    int32_t variants;                 /* K */
+    int32_t nonfinite;                /* variants with a non-finite value in their first nout columns */
+    int32_t flips[2][4];              /* [g][h]: variants of group g whose arg-max in head h differs from y's, non-finite ones included
+                                         (0 for a head the model lacks and for a group that was not asked for) */
+    int32_t decision_flips[2][4];     /* [g][r]: rows with decoder columns: variants of group g whose decoder column 23 + r compares
+                                         unequal to y's, r = A C G T; without decoder columns: 0 */
+    int32_t lean[2][4];               /* [g][h]: the index within group g (the channel c, or the band k) of the largest drop among the
+                                         finite variants whose drop is not a NaN, the lowest index on ties; -1 when there is none or the
+                                         group was not asked for */
+    float   lean_drop[2][4];          /* that drop (may be negative); 0 with lean = -1 */
+    float   max_delta;                /* max over finite variants and the first nout columns of |v_j[c] - y[c]| (float32), NaN
+                                         differences left out; 0 without any */
+    int32_t reserved;
+} c3_occlude_window;
+/* what a call did (the trailing argument of the two entries that run the network; may be NULL) */
+typedef struct {
+    int64_t windows, variants;  /* of the call */
+    int64_t passes;             /* the call is cut into passes of C3HIP_OCCLUDE_CHUNK windows (env, read at every call; default 64
+                                   full-alignment windows, 256 pileup windows; 0 = never cut) */
+    int64_t bytes_staged;       /* host to device: the occupied rows (full alignment) or the windows (pileup), and the tables */
+    int32_t on_fp32;            /* 1: the range guard met a pass and that pass ran again on the fp32 forms (below) */
+    int32_t reserved;
+    float expand_us, reduce_us; /* device time of the call's occlude_*expand_kernel / occlude_reduce_kernel launches (HIP events, summed) */
+} c3_occlude_info;
+/*   c3_occlude         dense windows of either kind.  Full alignment: every window's run is found on the host as c3_jackknife finds it and
+ *                      only the occupied rows are staged; pileup: the windows are staged as they are, int8 or int32 on their own kernels.
+ *                      Cut into passes of C3HIP_OCCLUDE_CHUNK windows; a window's variants never straddle a pass, they may straddle a
+ *                      micro-batch (2048 full-alignment, 16384 pileup dense windows); results do not depend on the cut.  Per pass the input
+ *                      and one table (the windows themselves first, then every window's K variants in window order, variant order) are
+ *                      staged once, the dense windows are built micro-batch by micro-batch in front of the forward pass, the rows stay in a
+ *                      buffer of the handle, the reduction runs behind the last micro-batch and the host waits once, for the records.
+ *                        y_host            (may be NULL) [batch][row]: bit for bit c3_predict / c3_predict_rows of the same arguments
+ *                        out               [batch] records
+ *                        drops_out         (may be NULL) [batch][K][4] float32: the map -- the drop of every variant in every head
+ *                        variant_rows_out  (may be NULL) [batch][K][row]: the variants' rows, for tests and tools
+ *                      The handle is left as it was: c3_model_describe, the tap buffers of the last call, a profile being taken, the totals
+ *                      of verify / refine / score mode and rows_windows= do not see the call.  Range guard (full alignment): a handle on
+ *                      the fp16x3 forms whose range flag is up behind a pass (or that returned a non-finite row) runs THAT PASS again on
+ *                      the fp32-MFMA forms for this call alone; the device flag is put back to zero, the handle stays on its forms,
+ *                      info->on_fp32 says so.  A pileup handle has no such guard.
+ *   c3_occlude_rows    full alignment only: the arguments of c3_predict_rows.
+ *   c3_occlude_reduce  the reduction alone on rows the caller holds (row_floats == c3_model_output_size(), or that + C3_DECODE_COLS):
+ *                      base_rows [batch][row_floats], variant_rows [batch][channels + bands][row_floats]; `channels` and `bands` are the
+ *                      sizes of the two groups, either may be 0.  Needs no weights; serves both kinds.
+ * Refused before anything is queued: a submit pending on any slot of the ring, a handle that answers from the exact form
+ * (c3_model_set_answer), a handle without weights (the two entries that run the network), null buffers with batch > 0, `what` outside
+ * 1 .. 3, `band` outside 1 .. P, a dtype the kind does not take (full alignment int8; pileup int8 or int32), c3_occlude_rows on a pileup
+ * handle, a negative count, first < 0, first + count > depth, a pass of more than INT32_MAX dense windows, row_floats that is neither of
+ * the two, a negative group size.  batch == 0 launches nothing. */
+int c3_occlude(c3_model *m, const void *x_host, int x_dtype, int64_t batch, int what, int band, float *y_host, c3_occlude_window *out,
+               float *drops_out, float *variant_rows_out, c3_occlude_info *info);
+int c3_occlude_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, int what,
+                    int band, float *y_host, c3_occlude_window *out, float *drops_out, float *variant_rows_out, c3_occlude_info *info);
+int c3_occlude_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, int channels, int bands,
+                      int64_t batch, c3_occlude_window *out, float *drops_out);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
