@@ -196,60 +196,27 @@ __global__ __launch_bounds__(64) C3_JACKKNIFE_TEXT void jackknife_reduce_kernel(
 }
 
 // ------------------------------------------------------------------------------------------ the host's plan (plain host code: tests/host/
-// jackknife_host_check.cpp drives it against buffers of exactly these sizes)
-// A call is cut into passes of `chunk` windows (0: one pass); a window's variants never straddle a pass.
-struct JackknifePass {
-    int64_t w0 = 0, windows = 0;    // the windows [w0, w0 + windows) of the call
-    int64_t row0 = 0, rows = 0;     // their occupied rows in the caller's rows: [row0, row0 + rows)
-    int64_t var0 = 0, variants = 0; // their variants among the call's: [var0, var0 + variants)
-    int64_t dense() const { return windows + variants; }  // dense windows the pass builds: base windows first, then every variant
-};
-static inline int64_t jackknife_chunk_env() {  // env C3HIP_JACKKNIFE_CHUNK: windows per pass, default 64, 0 = never cut
-    const char *e = getenv("C3HIP_JACKKNIFE_CHUNK");
-    const long long v = e ? atoll(e) : 64;
-    return v < 0 ? 64 : (int64_t)v;
+// jackknife_host_check.cpp drives it against buffers of exactly these sizes).  The pass, its cut and its layout are c3_variants.h's; one
+// variant per read
+static inline int64_t jackknife_chunk_env() { return variant_chunk_env("C3HIP_JACKKNIFE_CHUNK", 64); }  // windows per pass, 0 = never cut
+static inline std::vector<VariantPass> jackknife_cut(const int32_t *count, int64_t batch, int64_t chunk) {
+    return variant_cut(count, batch, chunk, [count](int64_t w) { return (int64_t)count[w]; });
 }
-static inline std::vector<JackknifePass> jackknife_cut(const int32_t *count, int64_t batch, int64_t chunk) {
-    std::vector<JackknifePass> out;
-    int64_t row = 0;
-    for (int64_t w = 0; w < batch;) {
-        JackknifePass ps;
-        ps.w0 = w, ps.windows = chunk > 0 ? std::min(chunk, batch - w) : batch - w, ps.row0 = row, ps.var0 = row;
-        for (int64_t i = 0; i < ps.windows; ++i) ps.rows += count[w + i];
-        ps.variants = ps.rows;  // one variant per read
-        out.push_back(ps);
-        w += ps.windows, row += ps.rows;
-    }
-    return out;
+// meta block: table | var_first | count (RunMeta); home: the 80-byte records; extra: the drops
+static inline VariantLayout jackknife_layout(const VariantPass &ps, size_t row_bytes, int row_floats, bool drops) {
+    return VariantLayout(ps, row_bytes, RunMeta(ps, sizeof(JackknifeEntry)).bytes, row_floats, (size_t)ps.windows * sizeof(c3_jackknife_window),
+                         drops ? (size_t)ps.variants * 4 * sizeof(float) : 0);
 }
-// where a pass's sections sit in the handle's jackknife buffer (every section from a multiple of 256 bytes)
-struct JackknifeLayout {
-    size_t rows_at = 0, tab_at = 0, var_first_at = 0, count_at = 0;  // staged: the occupied rows; then the meta block [tab_at, meta_end)
-    size_t meta_end = 0;
-    size_t y_at = 0, rec_at = 0, flag_at = 0, drops_at = 0, bytes = 0;  // written by the device
-    JackknifeLayout(const JackknifePass &ps, size_t row_bytes, int row_floats, bool drops) {
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        tab_at = al((size_t)ps.rows * row_bytes);
-        var_first_at = al(tab_at + (size_t)ps.dense() * sizeof(JackknifeEntry));
-        count_at = al(var_first_at + (size_t)ps.windows * sizeof(int64_t));
-        meta_end = count_at + (size_t)ps.windows * sizeof(int32_t);
-        y_at = al(meta_end);
-        rec_at = al(y_at + (size_t)ps.dense() * row_floats * sizeof(float));
-        flag_at = rec_at + (size_t)ps.windows * sizeof(c3_jackknife_window);  // (80-byte records: a multiple of 4) the pass's copy of the range flag
-        drops_at = al(flag_at + 4);
-        bytes = drops_at + (drops ? (size_t)ps.variants * 4 * sizeof(float) : 0);
-    }
-    size_t meta_bytes() const { return meta_end - tab_at; }
-};
-// the meta block of a pass as it is staged, into `meta` of L.meta_bytes() bytes: the table (base entries with skip = -1 first, then every
+// the meta block of a pass as it is staged, into `meta` of RunMeta(..).bytes bytes: the table (base entries with skip = -1 first, then every
 // window's variants in window order, read order), every window's first variant (within the pass) and its count.  first[] / count[] are the
 // call's, checked by the entry
-static inline void jackknife_fill_pass(char *meta, const JackknifeLayout &L, const JackknifePass &ps, const int32_t *first, const int32_t *count,
-                                       int depth, size_t row_bytes, int layout) {
-    memset(meta, 0, L.meta_bytes());  // (the gaps between the sections and the entries' padding)
+static inline void jackknife_fill_pass(char *meta, const VariantPass &ps, const int32_t *first, const int32_t *count, int depth, size_t row_bytes,
+                                       int layout) {
+    const RunMeta M(ps, sizeof(JackknifeEntry));
+    memset(meta, 0, M.bytes);  // (the gaps between the sections and the entries' padding)
     JackknifeEntry *tab = reinterpret_cast<JackknifeEntry *>(meta);
-    int64_t *var_first = reinterpret_cast<int64_t *>(meta + (L.var_first_at - L.tab_at));
-    int32_t *cnt = reinterpret_cast<int32_t *>(meta + (L.count_at - L.tab_at));
+    int64_t *var_first = reinterpret_cast<int64_t *>(meta + M.var_first_at);
+    int32_t *cnt = reinterpret_cast<int32_t *>(meta + M.count_at);
     int64_t row = 0, var = 0;
     for (int64_t i = 0; i < ps.windows; ++i) {
         const int32_t n = count[ps.w0 + i], f = first[ps.w0 + i];
@@ -264,201 +231,65 @@ static inline void jackknife_fill_pass(char *meta, const JackknifeLayout &L, con
 }  // namespace c3
 
 // ------------------------------------------------------------------------------------------ the entries (include/c3hip.h)
-// the handle's jackknife buffer: a pass's staged rows, its meta block, the rows of its dense windows, the records; grown, never shrunk
-static int ensure_jackknife_buf(c3_model *m, size_t bytes) {
-    if (m->jackknife_bytes >= bytes) return 0;
-    HIP_TRY(hipDeviceSynchronize());
-    if (m->jackknife_dev) (void)hipFree(m->jackknife_dev);
-    m->jackknife_dev = nullptr, m->jackknife_bytes = 0;
-    HIP_TRY(hipMalloc(&m->jackknife_dev, bytes));
-    m->jackknife_bytes = bytes;
-    return 0;
-}
-
-// HIP events around the launches of one kind, only for a caller that asks for c3_jackknife_info: mark() in front of and behind each launch
-struct JackknifeTimer {
-    bool on = false;
-    std::vector<hipEvent_t> ev;
-    void mark(hipStream_t s) {
-        hipEvent_t e;
-        if (!on || hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s);
-        ev.push_back(e);
+// the mode of variant_run (c3_variants.h).  first[] / count[]: one checked entry per window (first: the base window's)
+struct JackknifeMode {
+    static constexpr const char *chunk_var = "C3HIP_JACKKNIFE_CHUNK";
+    c3_model *m;
+    const int32_t *first, *count;
+    int where;  // C3_JACKKNIFE_RECENTRE / _IN_PLACE
+    c3_jackknife_window *out;
+    float *drops_out;
+    size_t row_bytes() const { return (size_t)m->positions * m->C; }
+    VariantLayout layout(const VariantPass &ps) const { return jackknife_layout(ps, row_bytes(), m->row, drops_out != nullptr); }
+    void fill(char *meta, const VariantPass &ps) const { jackknife_fill_pass(meta, ps, first, count, m->depth, row_bytes(), where); }
+    int expand(hipStream_t s, VariantTimer &timer, const int8_t *rows, const char *meta, char *, int64_t off, int64_t n, void *dst) const {
+        const JackknifeExpandParams ep{rows, (const JackknifeEntry *)meta + off, (int8_t *)dst, (int)n, m->positions * m->C,
+                                       (int)c3_model_window_bytes(m, C3_DTYPE_I8)};
+        if (ep.row_bytes % 8 == 0) return variant_launch(s, &timer, jackknife_expand_kernel<8>, n, kExpandThreads, ep);
+        return variant_launch(s, &timer, jackknife_expand_kernel<1>, n, kExpandThreads, ep);
     }
-    float total_us() {  // behind the stream's last synchronisation; destroys the events
-        float us = 0.f;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) us += ms * 1e3f;
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        ev.clear();
-        return us;
+    int reduce(hipStream_t s, VariantTimer &timer, const VariantPass &ps, const VariantLayout &L, char *base) const {
+        const RunMeta M(ps, sizeof(JackknifeEntry));
+        float *y = (float *)(base + L.y_at);
+        JackknifeReduceParams rp;
+        rp.base = y, rp.variants = y + ps.windows * m->row, rp.var_first = (const int64_t *)(base + L.meta_at + M.var_first_at);
+        rp.count = (const int32_t *)(base + L.meta_at + M.count_at), rp.out = (c3_jackknife_window *)(base + L.home_at);
+        rp.drops = drops_out ? (float *)(base + L.extra_at) : nullptr, rp.stride = m->row, rp.nout = m->nout, rp.batch = (int)ps.windows;
+        return variant_launch(s, &timer, jackknife_reduce_kernel, rp.batch, 64, rp);
+    }
+    int deliver(hipStream_t s, const VariantPass &ps, const char *home, const char *drops) const {
+        memcpy(out + ps.w0, home, (size_t)ps.windows * sizeof(c3_jackknife_window));
+        return drops_out && ps.variants ? d2h_staged(drops_out + ps.var0 * 4, drops, (size_t)ps.variants * 4 * sizeof(float), s) : 0;
     }
 };
 
-static int jackknife_reduce_launch(hipStream_t s, const JackknifeReduceParams &rp, JackknifeTimer *timer = nullptr) {
-    if (rp.batch <= 0) return 0;
-    if (timer) timer->mark(s);
-    hipLaunchKernelGGL(jackknife_reduce_kernel, dim3((unsigned)rp.batch), dim3(64), 0, s, rp);
-    HIP_TRY(hipGetLastError());
-    if (timer) timer->mark(s);
-    return 0;
-}
-
-// the dense windows of a pass, micro-batch by micro-batch through the forms the handle is on, their rows at y (row stride m->row)
-static int jackknife_forward(c3_model *m, hipStream_t s, const int8_t *rows, const JackknifeEntry *tab, int64_t total, float *y, JackknifeTimer &timer) {
-    TRY(ensure_workspace(m, total));
-    TRY(ensure_expand_buf(m));
-    Lane &L = lane(m);
-    const int64_t wbytes = c3_model_window_bytes(m, C3_DTYPE_I8);
-    for (int64_t off = 0; off < total; off += L.cap) {
-        const int64_t n = std::min<int64_t>(L.cap, total - off);
-        const JackknifeExpandParams ep{rows, tab + off, L.xe, (int)n, m->positions * m->C, (int)wbytes};
-        timer.mark(s);
-        if (ep.row_bytes % 8 == 0) hipLaunchKernelGGL(jackknife_expand_kernel<8>, dim3((unsigned)n), dim3(kExpandThreads), 0, s, ep);
-        else hipLaunchKernelGGL(jackknife_expand_kernel<1>, dim3((unsigned)n), dim3(kExpandThreads), 0, s, ep);
-        HIP_TRY(hipGetLastError());
-        timer.mark(s);
-        TRY(run_fa(m, s, L.xe, n, y + off * m->row));
-        L.last_n = n;
-    }
-    return 0;
-}
-
-// what every entry that runs the network refuses before anything is queued
-static int jackknife_handle(c3_model *m, const char *who) {
-    if (!m) return fail("null model");
-    if (m->kind != C3_KIND_FULL_ALIGNMENT)
-        return fail("%s: the jackknife leaves out reads of full-alignment windows: a pileup window holds counts, not reads (c3_jackknife_reduce serves its rows)", who);
-    for (const HostSlot &sl : m->slot)
-        if (sl.busy) return fail("%s: a prediction is in flight: call c3_predict_wait first", who);
-    if (m->answer_exact) return fail("%s: the handle answers from the exact form: c3_model_set_answer(m, C3_ANSWER_PRODUCT) first", who);
-    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
-    return 0;
-}
-
-// first[] / count[]: one checked entry per window (first: the base window's)
-static int jackknife_run(c3_model *m, const int8_t *rows_host, const int32_t *first, const int32_t *count, int64_t batch, int layout, float *y_host,
-                         c3_jackknife_window *out, float *drops_out, float *variant_rows_out, c3_jackknife_info *info) {
-    HIP_TRY(hipSetDevice(m->device));
-    TRY(use_lane(m, 0));
-    hipStream_t s = lane(m).stream;
-    const size_t row_bytes = (size_t)m->positions * m->C;
-    const std::vector<JackknifePass> passes = jackknife_cut(count, batch, jackknife_chunk_env());
-    size_t need = 0;
-    for (const JackknifePass &ps : passes) {
-        if (ps.dense() > INT32_MAX) return fail("c3_jackknife_rows: %lld dense windows in one pass: set C3HIP_JACKKNIFE_CHUNK", (long long)ps.dense());
-        need = std::max(need, JackknifeLayout(ps, row_bytes, m->row, drops_out != nullptr).bytes);
-    }
-    TRY(ensure_jackknife_buf(m, need));
-    // the forms the handle is on, for this call alone: what it reports, taps, profiles and counts stays as it is (c3_calibrate.h does the same)
-    const c3_model::Choices reported = m->choice;
-    const bool f16 = m->f16_ok, tap_call = m->tap_call, prof = m->prof;
-    const int64_t tap_base = m->tap_base;
-    const uint32_t tap_mask = m->tap_mask;
-    int rc = 0, on_fp32 = 0;
-    size_t staged = 0;
-    JackknifeTimer t_expand, t_reduce;
-    t_expand.on = t_reduce.on = info != nullptr;
-    std::vector<char> meta;
-    char *base = (char *)m->jackknife_dev;
-    for (const JackknifePass &ps : passes) {
-        const JackknifeLayout L(ps, row_bytes, m->row, drops_out != nullptr);
-        meta.resize(L.meta_bytes());
-        jackknife_fill_pass(meta.data(), L, ps, first, count, m->depth, row_bytes, layout);
-        if (ps.rows) rc = h2d_staged(base + L.rows_at, rows_host + (size_t)ps.row0 * row_bytes, (size_t)ps.rows * row_bytes, s);
-        if (rc == 0) rc = h2d_staged(base + L.tab_at, meta.data(), meta.size(), s);
-        if (rc) break;
-        staged += (size_t)ps.rows * row_bytes + meta.size();
-        float *y = (float *)(base + L.y_at);
-        JackknifeReduceParams rp;
-        rp.base = y, rp.variants = y + ps.windows * m->row, rp.var_first = (const int64_t *)(base + L.var_first_at);
-        rp.count = (const int32_t *)(base + L.count_at), rp.out = (c3_jackknife_window *)(base + L.rec_at);
-        rp.drops = drops_out ? (float *)(base + L.drops_at) : nullptr, rp.stride = m->row, rp.nout = m->nout, rp.batch = (int)ps.windows;
-        for (int attempt = 0; attempt < 2 && rc == 0; ++attempt) {
-            const bool guarded = f16 && attempt == 0;  // the fp16x3 forms raise the range flag; the fp32 forms of the second attempt do not look at it
-            m->f16_ok = attempt == 0 ? f16 : false, m->tap_call = true, m->prof = false, m->tap_mask = 0;
-            rc = jackknife_forward(m, s, (const int8_t *)(base + L.rows_at), (const JackknifeEntry *)(base + L.tab_at), ps.dense(), y, t_expand);
-            m->f16_ok = f16, m->tap_call = tap_call, m->prof = prof, m->tap_base = tap_base, m->tap_mask = tap_mask, m->choice = reported;
-            if (rc) break;
-            if (guarded) {  // a non-finite row raises bit 1 of the flag as in the ring
-                const int64_t nf = ps.dense() * m->row;
-                hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, y, nf, m->range_flag);
-                if (hipGetLastError() != hipSuccess) {
-                    rc = fail("c3_jackknife_rows: the scan of the rows could not be launched");
-                    break;
-                }
-            }
-            if ((rc = jackknife_reduce_launch(s, rp, &t_reduce)) != 0) break;
-            // the records and, behind them, the pass's copy of the range flag come home in one copy: the one place the host waits for the pass
-            if (hipMemcpyAsync(base + L.flag_at, m->range_flag, 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-                rc = fail("c3_jackknife_rows: hipMemcpyAsync failed");
-                break;
-            }
-            std::vector<char> home(L.flag_at + 4 - L.rec_at);
-            if ((rc = d2h_staged(home.data(), base + L.rec_at, home.size(), s)) != 0) break;
-            uint32_t flag = 0;
-            memcpy(&flag, home.data() + home.size() - 4, 4);
-            if (guarded && flag) {  // beyond the range of the fp16x3 kernels: this pass again on the fp32-MFMA forms, for this call alone
-                if (hipMemsetAsync(m->range_flag, 0, 256, s) != hipSuccess) rc = fail("c3_jackknife_rows: hipMemsetAsync failed");
-                on_fp32 = 1;
-                continue;
-            }
-            memcpy(out + ps.w0, home.data(), (size_t)ps.windows * sizeof(c3_jackknife_window));
-            if (y_host) rc = d2h_staged(y_host + ps.w0 * m->row, y, (size_t)ps.windows * m->row * sizeof(float), s);
-            if (rc == 0 && drops_out && ps.variants) rc = d2h_staged(drops_out + ps.var0 * 4, base + L.drops_at, (size_t)ps.variants * 4 * sizeof(float), s);
-            if (rc == 0 && variant_rows_out && ps.variants)
-                rc = d2h_staged(variant_rows_out + ps.var0 * m->row, y + ps.windows * m->row, (size_t)ps.variants * m->row * sizeof(float), s);
-            break;
-        }
-        if (rc) break;
-    }
-    if (rc) {
-        const std::string why = g_err;
-        (void)hipStreamSynchronize(s);
-        (void)t_expand.total_us(), (void)t_reduce.total_us();
-        return g_err = why, rc;
-    }
-    const float expand_us = t_expand.total_us(), reduce_us = t_reduce.total_us();  // (the last copy home has synchronised the stream)
-    if (info) {
-        *info = c3_jackknife_info{};
-        info->expand_us = expand_us, info->reduce_us = reduce_us;
-        info->windows = batch, info->passes = (int64_t)passes.size(), info->bytes_staged = (int64_t)staged, info->on_fp32 = on_fp32;
-        for (const JackknifePass &ps : passes) info->variants += ps.variants;
-    }
-    return 0;
-}
+// what the two entries that run the network tell a pileup handle
+static const char kJackknifeFaOnly[] =
+    "%s: the jackknife leaves out reads of full-alignment windows: a pileup window holds counts, not reads (c3_jackknife_reduce serves its rows)";
 
 extern "C" {
 
 int c3_jackknife_rows(c3_model *m, const void *rows_host, const int32_t *row_first, const int32_t *row_count, int64_t batch, int layout,
                       float *y_host, c3_jackknife_window *out, float *drops_out, float *variant_rows_out, c3_jackknife_info *info) {
-    TRY(jackknife_handle(m, "c3_jackknife_rows"));
+    TRY(variant_handle(m, "c3_jackknife_rows", kJackknifeFaOnly));
     if (batch < 0) return fail("negative batch");
     if (layout != C3_JACKKNIFE_RECENTRE && layout != C3_JACKKNIFE_IN_PLACE)
         return fail("c3_jackknife_rows: unknown layout %d (C3_JACKKNIFE_RECENTRE or C3_JACKKNIFE_IN_PLACE)", layout);
     if (batch > 0 && (!row_count || !out)) return fail("null buffer: row_count / out");
-    std::vector<int32_t> first((size_t)batch), count((size_t)batch);
+    std::vector<int32_t> first, count;
     int64_t total = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        const int32_t c = table_i32(row_count, b);
-        if (c < 0) return fail("window %lld: negative row_count %d", (long long)b, c);
-        const int32_t f = row_first ? table_i32(row_first, b) : (m->depth - c) / 2;
-        if (f < 0) return fail("window %lld: negative row_first %d", (long long)b, f);
-        if ((int64_t)f + c > m->depth)
-            return fail("window %lld: rows [%d, %lld) reach beyond the depth of %d rows", (long long)b, f, (long long)f + c, m->depth);
-        first[(size_t)b] = f, count[(size_t)b] = c, total += c;
-    }
+    TRY(checked_runs(m, row_first, row_count, batch, &first, &count, &total));
     if (total > 0 && !rows_host) return fail("null buffer: rows");
     if (info) *info = c3_jackknife_info{};
     if (batch == 0) return 0;
-    return jackknife_run(m, (const int8_t *)rows_host, first.data(), count.data(), batch, layout, y_host, out, drops_out, variant_rows_out, info);
+    const JackknifeMode mode{m, first.data(), count.data(), layout, out, drops_out};
+    return variant_run(m, "c3_jackknife_rows", (const int8_t *)rows_host, C3_DTYPE_I8, jackknife_cut(count.data(), batch, jackknife_chunk_env()), mode,
+                       y_host, variant_rows_out, info);
 }
 
 int c3_jackknife(c3_model *m, const void *x_host, int x_dtype, int64_t batch, int layout, float *y_host, c3_jackknife_window *out,
                  float *drops_out, float *variant_rows_out, c3_jackknife_info *info) {
-    TRY(jackknife_handle(m, "c3_jackknife"));
+    TRY(variant_handle(m, "c3_jackknife", kJackknifeFaOnly));
     if (batch < 0) return fail("negative batch");
     if (x_dtype != C3_DTYPE_I8) return fail("full-alignment windows must be int8 (got dtype %d)", x_dtype);
     if (layout != C3_JACKKNIFE_RECENTRE && layout != C3_JACKKNIFE_IN_PLACE)
@@ -466,22 +297,12 @@ int c3_jackknife(c3_model *m, const void *x_host, int x_dtype, int64_t batch, in
     if (batch > 0 && (!x_host || !out)) return fail("null buffer: windows / out");
     if (info) *info = c3_jackknife_info{};
     if (batch == 0) return 0;
-    // every window's run, found on the host as c3_pack_rows finds it; its first row is the run's own
-    const size_t row_bytes = (size_t)m->positions * m->C, wbytes = (size_t)m->depth * row_bytes;
-    std::vector<int32_t> first((size_t)batch), count((size_t)batch);
-    size_t total = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        occupied_run((const uint8_t *)x_host + (size_t)b * wbytes, m->depth, row_bytes, &first[(size_t)b], &count[(size_t)b]);
-        total += (size_t)count[(size_t)b];
-    }
-    std::vector<int8_t> rows(std::max<size_t>(total * row_bytes, 1));
-    size_t at = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        const size_t n = (size_t)count[(size_t)b] * row_bytes;
-        memcpy(rows.data() + at, (const char *)x_host + (size_t)b * wbytes + (size_t)first[(size_t)b] * row_bytes, n);
-        at += n;
-    }
-    return jackknife_run(m, rows.data(), first.data(), count.data(), batch, layout, y_host, out, drops_out, variant_rows_out, info);
+    std::vector<int32_t> first, count;
+    std::vector<int8_t> rows;
+    gather_runs(m, x_host, batch, &first, &count, &rows);
+    const JackknifeMode mode{m, first.data(), count.data(), layout, out, drops_out};
+    return variant_run(m, "c3_jackknife", rows.data(), C3_DTYPE_I8, jackknife_cut(count.data(), batch, jackknife_chunk_env()), mode, y_host,
+                       variant_rows_out, info);
 }
 
 int c3_jackknife_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, const int32_t *row_count, int64_t batch,
@@ -507,10 +328,10 @@ int c3_jackknife_reduce(c3_model *m, const float *base_rows, const float *varian
     const size_t rf = (size_t)row_floats * sizeof(float);
     const size_t v_at = al((size_t)batch * rf), f_at = al(v_at + (size_t)total * rf), c_at = al(f_at + (size_t)batch * 8), r_at = al(c_at + (size_t)batch * 4);
     const size_t d_at = al(r_at + (size_t)batch * sizeof(c3_jackknife_window));
-    TRY(ensure_jackknife_buf(m, d_at + (drops_out ? (size_t)total * 16 : 0)));
+    TRY(ensure_variant_buf(m, d_at + (drops_out ? (size_t)total * 16 : 0)));
     TRY(use_lane(m, 0));
     hipStream_t s = lane(m).stream;
-    char *base = (char *)m->jackknife_dev;
+    char *base = (char *)m->variant_dev;
     TRY(h2d_staged(base, base_rows, (size_t)batch * rf, s));
     if (total) TRY(h2d_staged(base + v_at, variant_rows, (size_t)total * rf, s));
     TRY(h2d_staged(base + f_at, var_first.data(), (size_t)batch * 8, s));
@@ -519,7 +340,7 @@ int c3_jackknife_reduce(c3_model *m, const float *base_rows, const float *varian
     rp.base = (const float *)base, rp.variants = (const float *)(base + v_at), rp.var_first = (const int64_t *)(base + f_at);
     rp.count = (const int32_t *)(base + c_at), rp.out = (c3_jackknife_window *)(base + r_at), rp.drops = drops_out ? (float *)(base + d_at) : nullptr;
     rp.stride = row_floats, rp.nout = m->nout, rp.batch = (int)batch;
-    TRY(jackknife_reduce_launch(s, rp));
+    TRY(variant_launch(s, nullptr, jackknife_reduce_kernel, batch, 64, rp));
     TRY(d2h_staged(out, base + r_at, (size_t)batch * sizeof(c3_jackknife_window), s));
     if (drops_out && total) TRY(d2h_staged(drops_out, base + d_at, (size_t)total * 16, s));
     return 0;

@@ -493,17 +493,9 @@ struct c3_model {
     void *decode_dev = nullptr;  // scratch of c3_outcome_maxima
     size_t decode_bytes = 0;
 
-    // ---- jackknife mode (c3_jackknife_rows, c3_jackknife.h): never called = nothing allocated, nothing launched ----
-    void *jackknife_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows and its records; grown on demand
-    size_t jackknife_bytes = 0;
-
-    // ---- subsample mode (c3_subsample_rows, c3_subsample.h): never called = nothing allocated, nothing launched ----
-    void *subsample_dev = nullptr;  // a pass's staged rows, its tables, the rows of its dense windows, its records and masks; grown on demand
-    size_t subsample_bytes = 0;
-
-    // ---- occlusion mode (c3_occlude, c3_occlude.h): never called = nothing allocated, nothing launched ----
-    void *occlude_dev = nullptr;  // a pass's staged input, its table, the rows of its dense windows, its records and drops; grown on demand
-    size_t occlude_bytes = 0;
+    // ---- the variant instruments (jackknife, subsample and occlusion mode; c3_variants.h): never called = nothing allocated, nothing launched ----
+    void *variant_dev = nullptr;  // a pass's staged input, its meta block, the rows of its dense windows, its records and drops / masks; grown on demand
+    size_t variant_bytes = 0;
 
     // ---- workspaces and kernel streams: the lanes (Lane above; lane(m) is the active one) ----
     Lane lanes[kMaxLanes];

@@ -10,6 +10,7 @@
 #include "c3_mixed.h"  // (behind every kernel of the handle without a plan: c3_forward.h says why)
 #include "c3_calibrate.h"  // (last, for the same reason)
 #include "c3_exact.h"  // (behind every other kernel: the exact form is an instrument and moves none of them)
+#include "c3_variants.h"  // (host code only: what the three modes below share)
 #include "c3_jackknife.h"  // (jackknife mode: its kernels sit in a section of their own behind `.c3_refine_text`)
 #include "c3_subsample.h"  // (subsample mode: its kernels sit in a section of their own behind `.c3_jackknife_text`)
 #include "c3_occlude.h"  // (occlusion mode: its kernels sit in a section of their own behind `.c3_subsample_text`)
@@ -477,9 +478,7 @@ int c3_model_destroy(c3_model *m) {
     if (m->layer_exp) (void)hipFree(m->layer_exp);
     if (m->census_dev) (void)hipFree(m->census_dev);
     if (m->refine_rows) (void)hipFree(m->refine_rows);
-    if (m->jackknife_dev) (void)hipFree(m->jackknife_dev);
-    if (m->subsample_dev) (void)hipFree(m->subsample_dev);
-    if (m->occlude_dev) (void)hipFree(m->occlude_dev);
+    if (m->variant_dev) (void)hipFree(m->variant_dev);
     if (m->pin_flag) (void)hipHostFree(m->pin_flag);
     for (int l = 0; l < 9; ++l) {
         if (m->conv_w[l]) (void)hipFree(m->conv_w[l]);

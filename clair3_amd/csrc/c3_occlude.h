@@ -265,56 +265,22 @@ struct OccludePlan {
         bands = what & C3_OCCLUDE_BANDS ? (P + band - 1) / band : 0;
     }
 };
-// A call is cut into passes of `chunk` windows (0: one pass); a window's variants never straddle a pass.
-struct OccludePass {
-    int64_t w0 = 0, windows = 0;     // the windows [w0, w0 + windows) of the call
-    int64_t unit0 = 0, units = 0;    // their staged units in the caller's input: occupied rows (full alignment), windows (pileup)
-    int64_t var0 = 0, variants = 0;  // their variants among the call's: [var0, var0 + variants), K a window
-    int64_t dense() const { return windows + variants; }  // dense windows the pass builds: base windows first, then every variant
-};
-// env C3HIP_OCCLUDE_CHUNK: windows per pass, 0 = never cut; default 64 full-alignment windows (jackknife mode's pass), 256 pileup windows
-// (256 * 52 dense windows stay below the pileup micro-batch of 16384)
-static inline int64_t occlude_chunk_env(int kind) {
-    const int64_t dflt = kind == C3_KIND_PILEUP ? 256 : 64;
-    const char *e = getenv("C3HIP_OCCLUDE_CHUNK");
-    const long long v = e ? atoll(e) : dflt;
-    return v < 0 ? dflt : (int64_t)v;
+// The pass, its cut and its layout are c3_variants.h's.  env C3HIP_OCCLUDE_CHUNK: windows per pass, 0 = never cut; default 64
+// full-alignment windows (jackknife mode's pass), 256 pileup windows (256 * 52 dense windows stay below the pileup micro-batch of 16384)
+static inline int64_t occlude_chunk_env(int kind) { return variant_chunk_env("C3HIP_OCCLUDE_CHUNK", kind == C3_KIND_PILEUP ? 256 : 64); }
+// count: the windows' occupied rows (full alignment), or null: one unit a window (pileup); K variants a window
+static inline std::vector<VariantPass> occlude_cut(const int32_t *count, int64_t batch, int64_t chunk, int K) {
+    return variant_cut(count, batch, chunk, [K](int64_t) { return (int64_t)K; });
 }
-// count: the windows' occupied rows (full alignment), or null: one unit a window (pileup)
-static inline std::vector<OccludePass> occlude_cut(const int32_t *count, int64_t batch, int64_t chunk, int K) {
-    std::vector<OccludePass> out;
-    int64_t unit = 0;
-    for (int64_t w = 0; w < batch;) {
-        OccludePass ps;
-        ps.w0 = w, ps.windows = chunk > 0 ? std::min(chunk, batch - w) : batch - w, ps.unit0 = unit, ps.var0 = w * K;
-        for (int64_t i = 0; i < ps.windows; ++i) ps.units += count ? count[w + i] : 1;
-        ps.variants = ps.windows * K;
-        out.push_back(ps);
-        w += ps.windows, unit += ps.units;
-    }
-    return out;
+// meta block: the table alone; home: the 144-byte records; extra: the drops
+static inline VariantLayout occlude_layout(const VariantPass &ps, size_t unit_bytes, int row_floats, bool drops) {
+    return VariantLayout(ps, unit_bytes, (size_t)ps.dense() * sizeof(OccludeEntry), row_floats, (size_t)ps.windows * sizeof(c3_occlude_window),
+                         drops ? (size_t)ps.variants * 4 * sizeof(float) : 0);
 }
-// where a pass's sections sit in the handle's occlusion buffer (every section from a multiple of 256 bytes): the staged input, the table,
-// the rows of the dense windows, the records with the pass's copy of the range flag behind them, the drops
-struct OccludeLayout {
-    size_t in_at = 0, tab_at = 0, tab_end = 0;                          // staged
-    size_t y_at = 0, rec_at = 0, flag_at = 0, drops_at = 0, bytes = 0;  // written by the device
-    OccludeLayout(const OccludePass &ps, size_t unit_bytes, int row_floats, bool drops) {
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        tab_at = al((size_t)ps.units * unit_bytes);
-        tab_end = tab_at + (size_t)ps.dense() * sizeof(OccludeEntry);
-        y_at = al(tab_end);
-        rec_at = al(y_at + (size_t)ps.dense() * row_floats * sizeof(float));
-        flag_at = rec_at + (size_t)ps.windows * sizeof(c3_occlude_window);  // (144-byte records: a multiple of 4)
-        drops_at = al(flag_at + 4);
-        bytes = drops_at + (drops ? (size_t)ps.variants * 4 * sizeof(float) : 0);
-    }
-    size_t tab_bytes() const { return tab_end - tab_at; }
-};
 // the table of a pass as it is staged, `tab` of ps.dense() entries: the base entries first (no mask), then every window's K variants in
 // window order and variant order -- channels 0 .. C - 1, then bands 0 .. nb - 1.  first[] / count[] are the call's, checked by the entry
 // (full alignment), or null (pileup: one unit of unit_bytes a window)
-static inline void occlude_fill_pass(OccludeEntry *tab, const OccludePass &ps, const OccludePlan &plan, const int32_t *first, const int32_t *count,
+static inline void occlude_fill_pass(OccludeEntry *tab, const VariantPass &ps, const OccludePlan &plan, const int32_t *first, const int32_t *count,
                                      size_t unit_bytes) {
     const int K = plan.K();
     int64_t unit = 0;
@@ -333,174 +299,47 @@ static inline void occlude_fill_pass(OccludeEntry *tab, const OccludePass &ps, c
 }  // namespace c3
 
 // ------------------------------------------------------------------------------------------ the entries (include/c3hip.h)
-// the handle's occlusion buffer: a pass's staged input, its table, the rows of its dense windows, the records, the drops; grown, never shrunk
-static int ensure_occlude_buf(c3_model *m, size_t bytes) {
-    if (m->occlude_bytes >= bytes) return 0;
-    HIP_TRY(hipDeviceSynchronize());
-    if (m->occlude_dev) (void)hipFree(m->occlude_dev);
-    m->occlude_dev = nullptr, m->occlude_bytes = 0;
-    HIP_TRY(hipMalloc(&m->occlude_dev, bytes));
-    m->occlude_bytes = bytes;
-    return 0;
-}
-
-// the active lane's buffer of dense pileup windows that occlude_pileup_expand_kernel builds, sized like the lane's buffer of rescaled
-// windows (ensure_rescale_buf): as many int32 windows as its workspace holds; allocated on first use, grown, freed with the workspace
-static int ensure_occlude_window_buf(c3_model *m) {
-    Lane &L = lane(m);
-    if (L.xo && L.xo_cap >= L.cap) return 0;
-    HIP_TRY(hipDeviceSynchronize());
-    if (L.xo) (void)hipFree(L.xo);
-    L.xo = nullptr, L.xo_cap = 0;
-    HIP_TRY(hipMalloc(&L.xo, std::max<size_t>((size_t)L.cap * m->positions * m->C * sizeof(int32_t), 256)));
-    L.xo_cap = L.cap;
-    return 0;
-}
-
-static int occlude_reduce_launch(hipStream_t s, const OccludeReduceParams &rp, JackknifeTimer *timer = nullptr) {
-    if (rp.batch <= 0) return 0;
-    if (timer) timer->mark(s);
-    hipLaunchKernelGGL(occlude_reduce_kernel, dim3((unsigned)rp.batch), dim3(64), 0, s, rp);
-    HIP_TRY(hipGetLastError());
-    if (timer) timer->mark(s);
-    return 0;
-}
-
-// the dense windows of a pass, micro-batch by micro-batch through the forms the handle is on, their rows at y (row stride m->row): the
-// micro-batch loop of jackknife_forward; int8 and int32 pileup windows stay on their own kernels, as in forward_device
-static int occlude_forward(c3_model *m, hipStream_t s, const int8_t *in, const OccludeEntry *tab, int64_t total, int x_dtype, float *y,
-                           JackknifeTimer &timer) {
-    TRY(ensure_workspace(m, total));
-    const bool fa = m->kind == C3_KIND_FULL_ALIGNMENT;
-    if (fa) TRY(ensure_expand_buf(m));
-    else TRY(ensure_occlude_window_buf(m));
-    Lane &L = lane(m);
-    const int64_t wbytes = c3_model_window_bytes(m, x_dtype);
-    for (int64_t off = 0; off < total; off += L.cap) {
-        const int64_t n = std::min<int64_t>(L.cap, total - off);
-        const OccludeExpandParams ep{in, tab + off, fa ? (void *)L.xe : L.xo, (int)n, m->positions, m->C, m->positions * m->C, (int)wbytes};
-        const dim3 grid((unsigned)n), block(kExpandThreads);
-        timer.mark(s);
-        if (fa && m->C == 8) hipLaunchKernelGGL(occlude_expand_kernel<8>, grid, block, 0, s, ep);  // (a piece is a cell only when C == 8)
-        else if (fa) hipLaunchKernelGGL(occlude_expand_kernel<1>, grid, block, 0, s, ep);
-        else if (x_dtype == C3_DTYPE_I8) hipLaunchKernelGGL(occlude_pileup_expand_kernel<int8_t>, grid, block, 0, s, ep);
-        else hipLaunchKernelGGL(occlude_pileup_expand_kernel<int32_t>, grid, block, 0, s, ep);
-        HIP_TRY(hipGetLastError());
-        timer.mark(s);
-        float *yp = y + off * m->row;
-        if (fa) TRY(run_fa(m, s, L.xe, n, yp));
-        else if (x_dtype == C3_DTYPE_I8) TRY(run_pileup_t<int8_t>(m, s, (const int8_t *)L.xo, n, yp));
-        else TRY(run_pileup_t<int32_t>(m, s, (const int32_t *)L.xo, n, yp));
-        L.last_n = n;
+// the mode of variant_run (c3_variants.h).  Full alignment: one checked first[] / count[] entry per window; pileup: the windows themselves
+// are the staged units, first = count = null
+struct OccludeMode {
+    static constexpr const char *chunk_var = "C3HIP_OCCLUDE_CHUNK";
+    c3_model *m;
+    int x_dtype;
+    const int32_t *first, *count;
+    OccludePlan plan;
+    c3_occlude_window *out;
+    float *drops_out;
+    size_t unit_bytes() const { return m->kind == C3_KIND_FULL_ALIGNMENT ? (size_t)m->positions * m->C : (size_t)c3_model_window_bytes(m, x_dtype); }
+    VariantLayout layout(const VariantPass &ps) const { return occlude_layout(ps, unit_bytes(), m->row, drops_out != nullptr); }
+    void fill(char *meta, const VariantPass &ps) const { occlude_fill_pass((OccludeEntry *)meta, ps, plan, first, count, unit_bytes()); }
+    int expand(hipStream_t s, VariantTimer &timer, const int8_t *in, const char *meta, char *, int64_t off, int64_t n, void *dst) const {
+        const bool fa = m->kind == C3_KIND_FULL_ALIGNMENT;
+        const OccludeExpandParams ep{in, (const OccludeEntry *)meta + off, dst, (int)n, m->positions, m->C, m->positions * m->C,
+                                     (int)c3_model_window_bytes(m, x_dtype)};
+        if (fa && m->C == 8) return variant_launch(s, &timer, occlude_expand_kernel<8>, n, kExpandThreads, ep);  // (a piece is a cell only when C == 8)
+        if (fa) return variant_launch(s, &timer, occlude_expand_kernel<1>, n, kExpandThreads, ep);
+        if (x_dtype == C3_DTYPE_I8) return variant_launch(s, &timer, occlude_pileup_expand_kernel<int8_t>, n, kExpandThreads, ep);
+        return variant_launch(s, &timer, occlude_pileup_expand_kernel<int32_t>, n, kExpandThreads, ep);
     }
-    return 0;
-}
+    int reduce(hipStream_t s, VariantTimer &timer, const VariantPass &ps, const VariantLayout &L, char *base) const {
+        float *y = (float *)(base + L.y_at);
+        OccludeReduceParams rp;
+        rp.base = y, rp.variants = y + ps.windows * m->row, rp.out = (c3_occlude_window *)(base + L.home_at);
+        rp.drops = drops_out ? (float *)(base + L.extra_at) : nullptr, rp.stride = m->row, rp.nout = m->nout, rp.batch = (int)ps.windows;
+        rp.channels = plan.channels, rp.bands = plan.bands;
+        return variant_launch(s, &timer, occlude_reduce_kernel, rp.batch, 64, rp);
+    }
+    int deliver(hipStream_t s, const VariantPass &ps, const char *home, const char *drops) const {
+        memcpy(out + ps.w0, home, (size_t)ps.windows * sizeof(c3_occlude_window));
+        return drops_out && ps.variants ? d2h_staged(drops_out + ps.var0 * 4, drops, (size_t)ps.variants * 4 * sizeof(float), s) : 0;
+    }
+};
 
 // what the two entries that run the network refuse before anything is queued
 static int occlude_handle(c3_model *m, const char *who, int what, int band) {
-    if (!m) return fail("null model");
-    for (const HostSlot &sl : m->slot)
-        if (sl.busy) return fail("%s: a prediction is in flight: call c3_predict_wait first", who);
-    if (m->answer_exact) return fail("%s: the handle answers from the exact form: c3_model_set_answer(m, C3_ANSWER_PRODUCT) first", who);
-    if (!m->loaded) return fail("model has no weights: call c3_model_load first");
+    TRY(variant_handle(m, who, nullptr));
     if (what < 1 || what > 3) return fail("%s: unknown `what` %d (C3_OCCLUDE_CHANNELS = 1, C3_OCCLUDE_BANDS = 2, or both = 3)", who, what);
     if (band < 1 || band > m->positions) return fail("%s: band %d outside 1 .. %d, the window's positions", who, band, m->positions);
-    return 0;
-}
-
-// in_host: the staged units of the call back to back (full alignment: the occupied rows, with one checked first[] / count[] entry per
-// window; pileup: the windows themselves, first = count = null)
-static int occlude_run(c3_model *m, const char *who, const int8_t *in_host, int x_dtype, const int32_t *first, const int32_t *count, int64_t batch,
-                       const OccludePlan &plan, float *y_host, c3_occlude_window *out, float *drops_out, float *variant_rows_out, c3_occlude_info *info) {
-    const bool fa = m->kind == C3_KIND_FULL_ALIGNMENT;
-    const size_t unit_bytes = fa ? (size_t)m->positions * m->C : (size_t)c3_model_window_bytes(m, x_dtype);
-    const int K = plan.K();
-    const std::vector<OccludePass> passes = occlude_cut(count, batch, occlude_chunk_env(m->kind), K);
-    size_t need = 0;
-    for (const OccludePass &ps : passes) {
-        if (ps.dense() > INT32_MAX) return fail("%s: %lld dense windows in one pass: set C3HIP_OCCLUDE_CHUNK", who, (long long)ps.dense());
-        need = std::max(need, OccludeLayout(ps, unit_bytes, m->row, drops_out != nullptr).bytes);
-    }
-    HIP_TRY(hipSetDevice(m->device));
-    TRY(use_lane(m, 0));
-    hipStream_t s = lane(m).stream;
-    TRY(ensure_occlude_buf(m, need));
-    // the forms the handle is on, for this call alone: what it reports, taps, profiles and counts stays as it is (jackknife_run does the same)
-    const c3_model::Choices reported = m->choice;
-    const bool f16 = m->f16_ok, tap_call = m->tap_call, prof = m->prof;
-    const int64_t tap_base = m->tap_base;
-    const uint32_t tap_mask = m->tap_mask;
-    int rc = 0, on_fp32 = 0;
-    size_t staged = 0;
-    JackknifeTimer t_expand, t_reduce;
-    t_expand.on = t_reduce.on = info != nullptr;
-    std::vector<OccludeEntry> tab;
-    char *base = (char *)m->occlude_dev;
-    for (const OccludePass &ps : passes) {
-        const OccludeLayout L(ps, unit_bytes, m->row, drops_out != nullptr);
-        tab.assign((size_t)ps.dense(), OccludeEntry{});
-        occlude_fill_pass(tab.data(), ps, plan, first, count, unit_bytes);
-        if (ps.units) rc = h2d_staged(base + L.in_at, in_host + (size_t)ps.unit0 * unit_bytes, (size_t)ps.units * unit_bytes, s);
-        if (rc == 0) rc = h2d_staged(base + L.tab_at, tab.data(), L.tab_bytes(), s);
-        if (rc) break;
-        staged += (size_t)ps.units * unit_bytes + L.tab_bytes();
-        float *y = (float *)(base + L.y_at);
-        OccludeReduceParams rp;
-        rp.base = y, rp.variants = y + ps.windows * m->row, rp.out = (c3_occlude_window *)(base + L.rec_at);
-        rp.drops = drops_out ? (float *)(base + L.drops_at) : nullptr, rp.stride = m->row, rp.nout = m->nout, rp.batch = (int)ps.windows;
-        rp.channels = plan.channels, rp.bands = plan.bands;
-        for (int attempt = 0; attempt < 2 && rc == 0; ++attempt) {
-            // full alignment: the fp16x3 forms raise the range flag; the fp32 forms of the second attempt do not look at it.  A pileup handle
-            // has no such guard
-            const bool guarded = fa && f16 && attempt == 0;
-            m->f16_ok = attempt == 0 ? f16 : false, m->tap_call = true, m->prof = false, m->tap_mask = 0;
-            rc = occlude_forward(m, s, (const int8_t *)(base + L.in_at), (const OccludeEntry *)(base + L.tab_at), ps.dense(), x_dtype, y, t_expand);
-            m->f16_ok = f16, m->tap_call = tap_call, m->prof = prof, m->tap_base = tap_base, m->tap_mask = tap_mask, m->choice = reported;
-            if (rc) break;
-            if (guarded) {  // a non-finite row raises bit 1 of the flag as in the ring
-                const int64_t nf = ps.dense() * m->row;
-                hipLaunchKernelGGL(rows_finite_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, y, nf, m->range_flag);
-                if (hipGetLastError() != hipSuccess) {
-                    rc = fail("%s: the scan of the rows could not be launched", who);
-                    break;
-                }
-            }
-            if ((rc = occlude_reduce_launch(s, rp, &t_reduce)) != 0) break;
-            // the records and, behind them, the pass's copy of the range flag come home in one copy: the one place the host waits for the pass
-            if (guarded && hipMemcpyAsync(base + L.flag_at, m->range_flag, 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-                rc = fail("%s: hipMemcpyAsync failed", who);
-                break;
-            }
-            std::vector<char> home(L.flag_at + (guarded ? 4 : 0) - L.rec_at);
-            if ((rc = d2h_staged(home.data(), base + L.rec_at, home.size(), s)) != 0) break;
-            uint32_t flag = 0;
-            if (guarded) memcpy(&flag, home.data() + home.size() - 4, 4);
-            if (guarded && flag) {  // beyond the range of the fp16x3 kernels: this pass again on the fp32-MFMA forms, for this call alone
-                if (hipMemsetAsync(m->range_flag, 0, 256, s) != hipSuccess) rc = fail("%s: hipMemsetAsync failed", who);
-                on_fp32 = 1;
-                continue;
-            }
-            memcpy(out + ps.w0, home.data(), (size_t)ps.windows * sizeof(c3_occlude_window));
-            if (y_host) rc = d2h_staged(y_host + ps.w0 * m->row, y, (size_t)ps.windows * m->row * sizeof(float), s);
-            if (rc == 0 && drops_out && ps.variants) rc = d2h_staged(drops_out + ps.var0 * 4, base + L.drops_at, (size_t)ps.variants * 4 * sizeof(float), s);
-            if (rc == 0 && variant_rows_out && ps.variants)
-                rc = d2h_staged(variant_rows_out + ps.var0 * m->row, y + ps.windows * m->row, (size_t)ps.variants * m->row * sizeof(float), s);
-            break;
-        }
-        if (rc) break;
-    }
-    if (rc) {
-        const std::string why = g_err;
-        (void)hipStreamSynchronize(s);
-        (void)t_expand.total_us(), (void)t_reduce.total_us();
-        return g_err = why, rc;
-    }
-    const float expand_us = t_expand.total_us(), reduce_us = t_reduce.total_us();  // (the last copy home has synchronised the stream)
-    if (info) {
-        *info = c3_occlude_info{};
-        info->expand_us = expand_us, info->reduce_us = reduce_us;
-        info->windows = batch, info->variants = batch * K, info->passes = (int64_t)passes.size(), info->bytes_staged = (int64_t)staged, info->on_fp32 = on_fp32;
-    }
     return 0;
 }
 
@@ -512,22 +351,15 @@ int c3_occlude_rows(c3_model *m, const void *rows_host, const int32_t *row_first
     if (m->kind != C3_KIND_FULL_ALIGNMENT) return fail("c3_occlude_rows: occupied rows are full-alignment input: a pileup handle takes its windows through c3_occlude");
     if (batch < 0) return fail("negative batch");
     if (batch > 0 && (!row_count || !out)) return fail("null buffer: row_count / out");
-    std::vector<int32_t> first((size_t)batch), count((size_t)batch);
+    std::vector<int32_t> first, count;
     int64_t total = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        const int32_t c = table_i32(row_count, b);
-        if (c < 0) return fail("window %lld: negative row_count %d", (long long)b, c);
-        const int32_t f = row_first ? table_i32(row_first, b) : (m->depth - c) / 2;
-        if (f < 0) return fail("window %lld: negative row_first %d", (long long)b, f);
-        if ((int64_t)f + c > m->depth)
-            return fail("window %lld: rows [%d, %lld) reach beyond the depth of %d rows", (long long)b, f, (long long)f + c, m->depth);
-        first[(size_t)b] = f, count[(size_t)b] = c, total += c;
-    }
+    TRY(checked_runs(m, row_first, row_count, batch, &first, &count, &total));
     if (total > 0 && !rows_host) return fail("null buffer: rows");
     if (info) *info = c3_occlude_info{};
     if (batch == 0) return 0;
-    return occlude_run(m, "c3_occlude_rows", (const int8_t *)rows_host, C3_DTYPE_I8, first.data(), count.data(), batch,
-                       OccludePlan(m->positions, m->C, what, band), y_host, out, drops_out, variant_rows_out, info);
+    const OccludeMode mode{m, C3_DTYPE_I8, first.data(), count.data(), OccludePlan(m->positions, m->C, what, band), out, drops_out};
+    return variant_run(m, "c3_occlude_rows", (const int8_t *)rows_host, C3_DTYPE_I8,
+                       occlude_cut(count.data(), batch, occlude_chunk_env(m->kind), mode.plan.K()), mode, y_host, variant_rows_out, info);
 }
 
 int c3_occlude(c3_model *m, const void *x_host, int x_dtype, int64_t batch, int what, int band, float *y_host, c3_occlude_window *out,
@@ -540,25 +372,13 @@ int c3_occlude(c3_model *m, const void *x_host, int x_dtype, int64_t batch, int 
     if (batch > 0 && (!x_host || !out)) return fail("null buffer: windows / out");
     if (info) *info = c3_occlude_info{};
     if (batch == 0) return 0;
-    const OccludePlan plan(m->positions, m->C, what, band);
-    if (m->kind == C3_KIND_PILEUP)
-        return occlude_run(m, "c3_occlude", (const int8_t *)x_host, x_dtype, nullptr, nullptr, batch, plan, y_host, out, drops_out, variant_rows_out, info);
-    // every window's run, found on the host as c3_pack_rows finds it; its first row is the run's own.  Only the occupied rows are staged
-    const size_t row_bytes = (size_t)m->positions * m->C, wbytes = (size_t)m->depth * row_bytes;
-    std::vector<int32_t> first((size_t)batch), count((size_t)batch);
-    size_t total = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        occupied_run((const uint8_t *)x_host + (size_t)b * wbytes, m->depth, row_bytes, &first[(size_t)b], &count[(size_t)b]);
-        total += (size_t)count[(size_t)b];
-    }
-    std::vector<int8_t> rows(std::max<size_t>(total * row_bytes, 1));
-    size_t at = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        const size_t n = (size_t)count[(size_t)b] * row_bytes;
-        memcpy(rows.data() + at, (const char *)x_host + (size_t)b * wbytes + (size_t)first[(size_t)b] * row_bytes, n);
-        at += n;
-    }
-    return occlude_run(m, "c3_occlude", rows.data(), C3_DTYPE_I8, first.data(), count.data(), batch, plan, y_host, out, drops_out, variant_rows_out, info);
+    std::vector<int32_t> first, count;
+    std::vector<int8_t> rows;
+    const bool fa = m->kind == C3_KIND_FULL_ALIGNMENT;
+    if (fa) gather_runs(m, x_host, batch, &first, &count, &rows);
+    const OccludeMode mode{m, x_dtype, fa ? first.data() : nullptr, fa ? count.data() : nullptr, OccludePlan(m->positions, m->C, what, band), out, drops_out};
+    return variant_run(m, "c3_occlude", fa ? rows.data() : (const int8_t *)x_host, x_dtype, occlude_cut(mode.count, batch, occlude_chunk_env(m->kind), mode.plan.K()),
+                       mode, y_host, variant_rows_out, info);
 }
 
 int c3_occlude_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, int channels, int bands, int64_t batch,
@@ -578,17 +398,17 @@ int c3_occlude_reduce(c3_model *m, const float *base_rows, const float *variant_
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t rf = (size_t)row_floats * sizeof(float);
     const size_t v_at = al((size_t)batch * rf), r_at = al(v_at + (size_t)total * rf), d_at = al(r_at + (size_t)batch * sizeof(c3_occlude_window));
-    TRY(ensure_occlude_buf(m, d_at + (drops_out ? (size_t)total * 16 : 0)));
+    TRY(ensure_variant_buf(m, d_at + (drops_out ? (size_t)total * 16 : 0)));
     TRY(use_lane(m, 0));
     hipStream_t s = lane(m).stream;
-    char *base = (char *)m->occlude_dev;
+    char *base = (char *)m->variant_dev;
     TRY(h2d_staged(base, base_rows, (size_t)batch * rf, s));
     if (total) TRY(h2d_staged(base + v_at, variant_rows, (size_t)total * rf, s));
     OccludeReduceParams rp;
     rp.base = (const float *)base, rp.variants = (const float *)(base + v_at), rp.out = (c3_occlude_window *)(base + r_at);
     rp.drops = drops_out ? (float *)(base + d_at) : nullptr, rp.stride = row_floats, rp.nout = m->nout, rp.batch = (int)batch;
     rp.channels = channels, rp.bands = bands;
-    TRY(occlude_reduce_launch(s, rp));
+    TRY(variant_launch(s, nullptr, occlude_reduce_kernel, batch, 64, rp));
     TRY(d2h_staged(out, base + r_at, (size_t)batch * sizeof(c3_occlude_window), s));
     if (drops_out && total) TRY(d2h_staged(drops_out, base + d_at, (size_t)total * 16, s));
     return 0;

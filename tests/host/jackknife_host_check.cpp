@@ -43,35 +43,37 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
     }
     std::vector<int8_t> rows((size_t)total * row_bytes);  // row r holds r + 1 in every byte (mod 127): a row names itself
     for (int64_t r = 0; r < total; ++r) memset(rows.data() + (size_t)r * row_bytes, (int)(r % 127) + 1, row_bytes);
-    const std::vector<JackknifePass> passes = jackknife_cut(count.data(), batch, chunk);
+    const std::vector<VariantPass> passes = jackknife_cut(count.data(), batch, chunk);
     // the cut: the passes tile the call, `chunk` windows each but the last, a window's variants in one pass
     CHECK((int64_t)passes.size() == (batch == 0 ? 0 : chunk > 0 ? (batch + chunk - 1) / chunk : 1));
     int64_t w = 0, row = 0, variants = 0;
     for (size_t k = 0; k < passes.size(); ++k) {
-        const JackknifePass &ps = passes[k];
-        CHECK(ps.w0 == w && ps.row0 == row && ps.var0 == row && ps.windows > 0 && (chunk == 0 || ps.windows <= chunk));
+        const VariantPass &ps = passes[k];
+        CHECK(ps.w0 == w && ps.unit0 == row && ps.var0 == row && ps.windows > 0 && (chunk == 0 || ps.windows <= chunk));
         CHECK(k + 1 == passes.size() || chunk == 0 || ps.windows == chunk);
         int64_t mine = 0;
         for (int64_t i = 0; i < ps.windows; ++i) mine += count[(size_t)(ps.w0 + i)];
-        CHECK(ps.rows == mine && ps.variants == mine && ps.dense() == ps.windows + mine);
+        CHECK(ps.units == mine && ps.variants == mine && ps.dense() == ps.windows + mine);
         // the layout: sections that do not overlap, in order, 256-aligned, inside the allocation
         for (bool drops : {false, true}) {
-            const JackknifeLayout L(ps, row_bytes, row_floats, drops);
-            CHECK(L.rows_at == 0 && L.tab_at >= (size_t)ps.rows * row_bytes && L.tab_at % 256 == 0);
-            CHECK(L.var_first_at >= L.tab_at + (size_t)ps.dense() * sizeof(JackknifeEntry) && L.var_first_at % 256 == 0);
-            CHECK(L.count_at >= L.var_first_at + (size_t)ps.windows * 8 && L.count_at % 256 == 0 && L.meta_end == L.count_at + (size_t)ps.windows * 4);
-            CHECK(L.y_at >= L.meta_end && L.y_at % 256 == 0 && L.rec_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && L.rec_at % 256 == 0);
-            CHECK(L.flag_at == L.rec_at + (size_t)ps.windows * sizeof(c3_jackknife_window) && L.drops_at >= L.flag_at + 4 && L.drops_at % 256 == 0);
-            CHECK(L.bytes == L.drops_at + (drops ? (size_t)ps.variants * 16 : 0) && L.meta_bytes() == L.meta_end - L.tab_at);
+            const VariantLayout L = jackknife_layout(ps, row_bytes, row_floats, drops);
+            const RunMeta M(ps, sizeof(JackknifeEntry));  // (offsets within the meta block, which starts at a multiple of 256 bytes)
+            CHECK(L.in_at == 0 && L.unit_bytes == row_bytes && L.meta_at >= (size_t)ps.units * row_bytes && L.meta_at % 256 == 0);
+            CHECK(M.var_first_at >= (size_t)ps.dense() * sizeof(JackknifeEntry) && (L.meta_at + M.var_first_at) % 256 == 0);
+            CHECK(M.count_at >= M.var_first_at + (size_t)ps.windows * 8 && (L.meta_at + M.count_at) % 256 == 0 && L.meta_end == L.meta_at + M.count_at + (size_t)ps.windows * 4);
+            CHECK(L.y_at >= L.meta_end && L.y_at % 256 == 0 && L.home_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && L.home_at % 256 == 0);
+            CHECK(L.flag_at == L.home_at + (size_t)ps.windows * sizeof(c3_jackknife_window) && L.extra_at >= L.flag_at + 4 && L.extra_at % 256 == 0);
+            CHECK(L.bytes == L.extra_at + (drops ? (size_t)ps.variants * 16 : 0) && L.meta_bytes == L.meta_end - L.meta_at && L.meta_bytes == M.bytes);
         }
         // the meta block, into a buffer of exactly its size
-        const JackknifeLayout L(ps, row_bytes, row_floats, false);
-        std::vector<char> meta(L.meta_bytes());
-        jackknife_fill_pass(meta.data(), L, ps, first.data(), count.data(), depth, row_bytes, layout);
+        const VariantLayout L = jackknife_layout(ps, row_bytes, row_floats, false);
+        const RunMeta M(ps, sizeof(JackknifeEntry));
+        std::vector<char> meta(L.meta_bytes);
+        jackknife_fill_pass(meta.data(), ps, first.data(), count.data(), depth, row_bytes, layout);
         const JackknifeEntry *tab = (const JackknifeEntry *)meta.data();
-        const int64_t *var_first = (const int64_t *)(meta.data() + (L.var_first_at - L.tab_at));
-        const int32_t *cnt = (const int32_t *)(meta.data() + (L.count_at - L.tab_at));
-        const std::vector<int8_t> staged(rows.begin() + (ptrdiff_t)((size_t)ps.row0 * row_bytes), rows.begin() + (ptrdiff_t)((size_t)(ps.row0 + ps.rows) * row_bytes));
+        const int64_t *var_first = (const int64_t *)(meta.data() + M.var_first_at);
+        const int32_t *cnt = (const int32_t *)(meta.data() + M.count_at);
+        const std::vector<int8_t> staged(rows.begin() + (ptrdiff_t)((size_t)ps.unit0 * row_bytes), rows.begin() + (ptrdiff_t)((size_t)(ps.unit0 + ps.units) * row_bytes));
         int64_t var = 0, r0 = 0;
         for (int64_t i = 0; i < ps.windows; ++i) {
             const int32_t n = count[(size_t)(ps.w0 + i)], f = first[(size_t)(ps.w0 + i)];
@@ -81,7 +83,7 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
             const std::vector<int8_t> base = expand(tab[i], staged, depth, row_bytes);
             for (int r = 0; r < depth; ++r) {  // the window of c3_predict_rows: row f + k is source row r0 + k
                 const bool in = r >= f && r < f + n;
-                CHECK(base[(size_t)r * row_bytes] == (in ? (int8_t)((ps.row0 + r0 + r - f) % 127 + 1) : 0) && base[(size_t)r * row_bytes + row_bytes - 1] == base[(size_t)r * row_bytes]);
+                CHECK(base[(size_t)r * row_bytes] == (in ? (int8_t)((ps.unit0 + r0 + r - f) % 127 + 1) : 0) && base[(size_t)r * row_bytes + row_bytes - 1] == base[(size_t)r * row_bytes]);
             }
             // ... then every window's variants in window order, read order
             for (int32_t j = 0; j < n; ++j) {
@@ -94,15 +96,15 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
                 for (int r = 0; r < depth; ++r) {
                     const bool in = r >= want_first && r < want_first + n - 1;
                     if (in && k == j) ++k;
-                    CHECK(v[(size_t)r * row_bytes] == (in ? (int8_t)((ps.row0 + r0 + k) % 127 + 1) : 0));
+                    CHECK(v[(size_t)r * row_bytes] == (in ? (int8_t)((ps.unit0 + r0 + k) % 127 + 1) : 0));
                     k += in;
                 }
                 if (n == 1) CHECK(std::all_of(v.begin(), v.end(), [](int8_t x) { return x == 0; }));  // the all-zero window
             }
             var += n, r0 += n;
         }
-        CHECK(var == ps.variants && r0 == ps.rows);
-        w += ps.windows, row += ps.rows, variants += ps.variants;
+        CHECK(var == ps.variants && r0 == ps.units);
+        w += ps.windows, row += ps.units, variants += ps.variants;
     }
     CHECK(w == batch && row == total && variants == total);
 }
@@ -174,7 +176,7 @@ static void entries(c3_model *pileup, c3_model *fa) {
         CHECK(c3_jackknife_reduce(m, nullptr, nullptr, m->nout, nullptr, 0, nullptr, nullptr) == 0);
     }
     CHECK(sizeof(c3_jackknife_window) == 80 && sizeof(c3_jackknife_info) == 48 && sizeof(JackknifeEntry) == 24);
-    CHECK(fa->jackknife_dev == nullptr && fa->jackknife_bytes == 0 && pileup->jackknife_dev == nullptr);  // nothing was allocated
+    CHECK(fa->variant_dev == nullptr && fa->variant_bytes == 0 && pileup->variant_dev == nullptr);  // nothing was allocated
 }
 
 int main() {

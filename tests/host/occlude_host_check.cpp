@@ -82,11 +82,11 @@ static void one_call(bool pileup, int depth, int P, int C, int item, int row_flo
     }
     std::vector<int8_t> in((size_t)total * unit_bytes);  // every byte a non-zero function of its place: what is zero was set to zero
     for (size_t i = 0; i < in.size(); ++i) in[i] = (int8_t)(i % 125 + 1);
-    const std::vector<OccludePass> passes = occlude_cut(pileup ? nullptr : count.data(), batch, chunk, K);
+    const std::vector<VariantPass> passes = occlude_cut(pileup ? nullptr : count.data(), batch, chunk, K);
     CHECK((int64_t)passes.size() == (batch == 0 ? 0 : chunk > 0 ? (batch + chunk - 1) / chunk : 1));
     int64_t w = 0, unit = 0, variants = 0;
     for (size_t k = 0; k < passes.size(); ++k) {
-        const OccludePass &ps = passes[k];
+        const VariantPass &ps = passes[k];
         CHECK(ps.w0 == w && ps.unit0 == unit && ps.var0 == w * K && ps.windows > 0 && (chunk == 0 || ps.windows <= chunk));
         CHECK(k + 1 == passes.size() || chunk == 0 || ps.windows == chunk);
         int64_t mine = 0;
@@ -94,17 +94,17 @@ static void one_call(bool pileup, int depth, int P, int C, int item, int row_flo
         CHECK(ps.units == mine && ps.variants == ps.windows * K && ps.dense() == ps.windows * (K + 1));
         // the layout: sections that do not overlap, in order, 256-aligned, inside the allocation
         for (bool drops : {false, true}) {
-            const OccludeLayout L(ps, unit_bytes, row_floats, drops);
-            CHECK(L.in_at == 0 && L.tab_at >= (size_t)ps.units * unit_bytes && L.tab_at % 256 == 0);
-            CHECK(L.tab_end == L.tab_at + (size_t)ps.dense() * sizeof(OccludeEntry) && L.tab_bytes() == (size_t)ps.dense() * 32);
-            CHECK(L.y_at >= L.tab_end && L.y_at % 256 == 0 && L.rec_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && L.rec_at % 256 == 0);
-            CHECK(L.flag_at == L.rec_at + (size_t)ps.windows * sizeof(c3_occlude_window) && L.drops_at >= L.flag_at + 4 && L.drops_at % 256 == 0);
-            CHECK(L.bytes == L.drops_at + (drops ? (size_t)ps.variants * 16 : 0));
+            const VariantLayout L = occlude_layout(ps, unit_bytes, row_floats, drops);
+            CHECK(L.in_at == 0 && L.unit_bytes == unit_bytes && L.meta_at >= (size_t)ps.units * unit_bytes && L.meta_at % 256 == 0);
+            CHECK(L.meta_end == L.meta_at + (size_t)ps.dense() * sizeof(OccludeEntry) && L.meta_bytes == (size_t)ps.dense() * 32);
+            CHECK(L.y_at >= L.meta_end && L.y_at % 256 == 0 && L.home_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && L.home_at % 256 == 0);
+            CHECK(L.flag_at == L.home_at + (size_t)ps.windows * sizeof(c3_occlude_window) && L.extra_at >= L.flag_at + 4 && L.extra_at % 256 == 0);
+            CHECK(L.bytes == L.extra_at + (drops ? (size_t)ps.variants * 16 : 0));
         }
         // the table, into a buffer of exactly its size; the staged input, a buffer of exactly the pass's
-        const OccludeLayout L(ps, unit_bytes, row_floats, false);
+        const VariantLayout L = occlude_layout(ps, unit_bytes, row_floats, false);
         std::vector<OccludeEntry> tab((size_t)ps.dense());
-        CHECK(tab.size() * sizeof(OccludeEntry) == L.tab_bytes());
+        CHECK(tab.size() * sizeof(OccludeEntry) == L.meta_bytes);
         occlude_fill_pass(tab.data(), ps, plan, pileup ? nullptr : first.data(), pileup ? nullptr : count.data(), unit_bytes);
         const std::vector<int8_t> staged(in.begin() + (ptrdiff_t)((size_t)ps.unit0 * unit_bytes), in.begin() + (ptrdiff_t)((size_t)(ps.unit0 + ps.units) * unit_bytes));
         const int rows = pileup ? 1 : depth;
@@ -219,10 +219,11 @@ static void entries(c3_model *pileup, c3_model *fa) {
     {
         const int64_t big = (int64_t)INT32_MAX / 52 + 1;  // x 52 dense windows a window
         const OccludePlan plan(33, 18, 3, 1);
-        const std::vector<OccludePass> passes = occlude_cut(nullptr, big, occlude_chunk_env(C3_KIND_PILEUP), plan.K());
+        const std::vector<VariantPass> passes = occlude_cut(nullptr, big, occlude_chunk_env(C3_KIND_PILEUP), plan.K());
         CHECK(passes.size() == 1 && passes[0].dense() > INT32_MAX);
         std::vector<c3_occlude_window> many(1);
-        CHECK(occlude_run(pileup, "c3_occlude", rows, C3_DTYPE_I8, nullptr, nullptr, big, plan, nullptr, many.data(), nullptr, nullptr, nullptr) != 0 &&
+        const OccludeMode mode{pileup, C3_DTYPE_I8, nullptr, nullptr, plan, many.data(), nullptr};
+        CHECK(variant_run(pileup, "c3_occlude", rows, C3_DTYPE_I8, passes, mode, nullptr, nullptr, nullptr) != 0 &&
               strstr(c3_last_error(), "dense windows in one pass: set C3HIP_OCCLUDE_CHUNK"));
     }
     unsetenv("C3HIP_OCCLUDE_CHUNK");
@@ -242,7 +243,7 @@ static void entries(c3_model *pileup, c3_model *fa) {
     CHECK(offsetof(c3_occlude_window, flips) == 8 && offsetof(c3_occlude_window, decision_flips) == 40 && offsetof(c3_occlude_window, lean) == 72);
     CHECK(offsetof(c3_occlude_window, lean_drop) == 104 && offsetof(c3_occlude_window, max_delta) == 136 && offsetof(c3_occlude_window, reserved) == 140);
     for (c3_model *m : {pileup, fa}) {  // nothing was allocated
-        CHECK(m->occlude_dev == nullptr && m->occlude_bytes == 0);
+        CHECK(m->variant_dev == nullptr && m->variant_bytes == 0);
         for (const Lane &L : m->lanes) CHECK(L.xo == nullptr && L.xo_cap == 0);
     }
 }

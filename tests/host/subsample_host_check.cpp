@@ -61,36 +61,39 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
     }
     std::vector<int8_t> rows((size_t)total * row_bytes);  // row r holds r + 1 in every byte (mod 127): a row names itself
     for (int64_t r = 0; r < total; ++r) memset(rows.data() + (size_t)r * row_bytes, (int)(r % 127) + 1, row_bytes);
-    const std::vector<SubsamplePass> passes = subsample_cut(count.data(), batch, chunk, plan);
+    const std::vector<VariantPass> passes = subsample_cut(count.data(), batch, chunk, plan);
     // the cut: the passes tile the call, `chunk` windows each but the last, a window's variants in one pass
     CHECK((int64_t)passes.size() == (batch == 0 ? 0 : chunk > 0 ? (batch + chunk - 1) / chunk : 1));
     int64_t w = 0, row = 0, variants = 0;
     for (size_t k = 0; k < passes.size(); ++k) {
-        const SubsamplePass &ps = passes[k];
-        CHECK(ps.w0 == w && ps.row0 == row && ps.var0 == variants && ps.windows > 0 && (chunk == 0 || ps.windows <= chunk));
+        const VariantPass &ps = passes[k];
+        CHECK(ps.w0 == w && ps.unit0 == row && ps.var0 == variants && ps.windows > 0 && (chunk == 0 || ps.windows <= chunk));
         CHECK(k + 1 == passes.size() || chunk == 0 || ps.windows == chunk);
         int64_t my_rows = 0, my_variants = 0;
         for (int64_t i = 0; i < ps.windows; ++i) my_rows += count[(size_t)(ps.w0 + i)], my_variants += plan.variants_of(count[(size_t)(ps.w0 + i)]);
-        CHECK(ps.rows == my_rows && ps.variants == my_variants && ps.dense() == ps.windows + my_variants);
+        CHECK(ps.units == my_rows && ps.variants == my_variants && ps.dense() == ps.windows + my_variants);
         // the layout: sections that do not overlap, in order, 256-aligned, inside the allocation
         for (bool masks : {false, true}) {
-            const SubsampleLayout L(ps, row_bytes, row_floats, plan.levels, masks);
-            CHECK(L.rows_at == 0 && L.tab_at >= (size_t)ps.rows * row_bytes && L.tab_at % 256 == 0);
-            CHECK(L.var_first_at >= L.tab_at + (size_t)ps.dense() * sizeof(SubsampleEntry) && L.var_first_at % 256 == 0);
-            CHECK(L.count_at >= L.var_first_at + (size_t)ps.windows * 8 && L.count_at % 256 == 0 && L.meta_end == L.count_at + (size_t)ps.windows * 4);
-            CHECK(L.y_at >= L.meta_end && L.y_at % 256 == 0 && L.lev_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && L.lev_at % 256 == 0);
-            CHECK(L.rec_at == L.lev_at + (size_t)ps.windows * plan.levels * sizeof(c3_subsample_level));
-            CHECK(L.flag_at == L.rec_at + (size_t)ps.windows * sizeof(c3_subsample_window) && L.masks_at >= L.flag_at + 4 && L.masks_at % 256 == 0);
-            CHECK(L.bytes == L.masks_at + (masks ? (size_t)ps.dense() * 16 : 0) && L.meta_bytes() == L.meta_end - L.tab_at);
+            const VariantLayout L = subsample_layout(ps, row_bytes, row_floats, plan.levels, masks);
+            const RunMeta M(ps, sizeof(SubsampleEntry));  // (offsets within the meta block, which starts at a multiple of 256 bytes)
+            const size_t lev_at = L.home_at, rec_at = lev_at + (size_t)ps.windows * plan.levels * sizeof(c3_subsample_level);  // home: levels, then windows
+            CHECK(L.in_at == 0 && L.unit_bytes == row_bytes && L.meta_at >= (size_t)ps.units * row_bytes && L.meta_at % 256 == 0);
+            CHECK(M.var_first_at >= (size_t)ps.dense() * sizeof(SubsampleEntry) && (L.meta_at + M.var_first_at) % 256 == 0);
+            CHECK(M.count_at >= M.var_first_at + (size_t)ps.windows * 8 && (L.meta_at + M.count_at) % 256 == 0 && L.meta_end == L.meta_at + M.count_at + (size_t)ps.windows * 4);
+            CHECK(L.y_at >= L.meta_end && L.y_at % 256 == 0 && lev_at >= L.y_at + (size_t)ps.dense() * row_floats * 4 && lev_at % 256 == 0);
+            CHECK(L.home_bytes == (size_t)ps.windows * (plan.levels * sizeof(c3_subsample_level) + sizeof(c3_subsample_window)));
+            CHECK(L.flag_at == rec_at + (size_t)ps.windows * sizeof(c3_subsample_window) && L.extra_at >= L.flag_at + 4 && L.extra_at % 256 == 0);
+            CHECK(L.bytes == L.extra_at + (masks ? (size_t)ps.dense() * 16 : 0) && L.meta_bytes == L.meta_end - L.meta_at && L.meta_bytes == M.bytes);
         }
         // the meta block, into a buffer of exactly its size
-        const SubsampleLayout L(ps, row_bytes, row_floats, plan.levels, false);
-        std::vector<char> meta(L.meta_bytes());
-        subsample_fill_pass(meta.data(), L, ps, first.data(), count.data(), depth, row_bytes, layout, plan);
+        const VariantLayout L = subsample_layout(ps, row_bytes, row_floats, plan.levels, false);
+        const RunMeta M(ps, sizeof(SubsampleEntry));
+        std::vector<char> meta(L.meta_bytes);
+        subsample_fill_pass(meta.data(), ps, first.data(), count.data(), depth, row_bytes, layout, plan);
         const SubsampleEntry *tab = (const SubsampleEntry *)meta.data();
-        const int64_t *var_first = (const int64_t *)(meta.data() + (L.var_first_at - L.tab_at));
-        const int32_t *cnt = (const int32_t *)(meta.data() + (L.count_at - L.tab_at));
-        const std::vector<int8_t> staged(rows.begin() + (ptrdiff_t)((size_t)ps.row0 * row_bytes), rows.begin() + (ptrdiff_t)((size_t)(ps.row0 + ps.rows) * row_bytes));
+        const int64_t *var_first = (const int64_t *)(meta.data() + M.var_first_at);
+        const int32_t *cnt = (const int32_t *)(meta.data() + M.count_at);
+        const std::vector<int8_t> staged(rows.begin() + (ptrdiff_t)((size_t)ps.unit0 * row_bytes), rows.begin() + (ptrdiff_t)((size_t)(ps.unit0 + ps.units) * row_bytes));
         int64_t var = 0, r0 = 0;
         for (int64_t i = 0; i < ps.windows; ++i) {
             const int64_t win = ps.w0 + i;
@@ -103,7 +106,7 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
             const std::vector<int8_t> base = expand(tab[i], all, staged, depth, row_bytes);
             for (int r = 0; r < depth; ++r) {  // the window of c3_predict_rows: row f + k is source row r0 + k
                 const bool in = r >= f && r < f + n;
-                CHECK(base[(size_t)r * row_bytes] == (in ? (int8_t)((ps.row0 + r0 + r - f) % 127 + 1) : 0) && base[(size_t)r * row_bytes + row_bytes - 1] == base[(size_t)r * row_bytes]);
+                CHECK(base[(size_t)r * row_bytes] == (in ? (int8_t)((ps.unit0 + r0 + r - f) % 127 + 1) : 0) && base[(size_t)r * row_bytes + row_bytes - 1] == base[(size_t)r * row_bytes]);
             }
             // ... then every window's variants: level by level (only levels below its count), replicate by replicate
             std::vector<std::vector<int32_t>> smaller((size_t)plan.replicates);  // the replicate's subset at the level before: nested
@@ -123,7 +126,7 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
                     size_t d = 0;  // the kept rows, in read order, from want_first on; zero everywhere else
                     for (int q = 0; q < depth; ++q) {
                         const bool in = q >= want_first && q < want_first + keep;
-                        CHECK(v[(size_t)q * row_bytes] == (in ? (int8_t)((ps.row0 + r0 + kept[d]) % 127 + 1) : 0));
+                        CHECK(v[(size_t)q * row_bytes] == (in ? (int8_t)((ps.unit0 + r0 + kept[d]) % 127 + 1) : 0));
                         CHECK(v[(size_t)q * row_bytes + row_bytes - 1] == v[(size_t)q * row_bytes]);
                         d += in;
                     }
@@ -133,8 +136,8 @@ static void one_call(int depth, size_t row_bytes, int row_floats, const std::vec
             CHECK(var - var_first[i] == plan.variants_of(n));
             r0 += n;
         }
-        CHECK(var == ps.variants && r0 == ps.rows);
-        w += ps.windows, row += ps.rows, variants += ps.variants;
+        CHECK(var == ps.variants && r0 == ps.units);
+        w += ps.windows, row += ps.units, variants += ps.variants;
     }
     CHECK(w == batch && row == total && variants == total_variants);
 }
@@ -146,10 +149,9 @@ static void cut_does_not_show(int depth, size_t row_bytes, const std::vector<int
     std::vector<std::vector<std::vector<int32_t>>> seen;
     for (int64_t chunk : {0, 1, 3}) {
         std::vector<std::vector<int32_t>> mine;
-        for (const SubsamplePass &ps : subsample_cut(count.data(), (int64_t)count.size(), chunk, plan)) {
-            const SubsampleLayout L(ps, row_bytes, 90, plan.levels, false);
-            std::vector<char> meta(L.meta_bytes());
-            subsample_fill_pass(meta.data(), L, ps, first.data(), count.data(), depth, row_bytes, C3_JACKKNIFE_RECENTRE, plan);
+        for (const VariantPass &ps : subsample_cut(count.data(), (int64_t)count.size(), chunk, plan)) {
+            std::vector<char> meta(subsample_layout(ps, row_bytes, 90, plan.levels, false).meta_bytes);
+            subsample_fill_pass(meta.data(), ps, first.data(), count.data(), depth, row_bytes, C3_JACKKNIFE_RECENTRE, plan);
             const SubsampleEntry *tab = (const SubsampleEntry *)meta.data();
             for (int64_t v = 0; v < ps.variants; ++v) mine.push_back(subsample_select(tab[ps.windows + v], plan, depth));
         }
@@ -264,8 +266,7 @@ static void entries(c3_model *pileup, c3_model *fa) {
     }
     CHECK(sizeof(c3_subsample_level) == 48 && sizeof(c3_subsample_window) == 32 && sizeof(c3_subsample_info) == 48 && sizeof(SubsampleEntry) == 32);
     // nothing was allocated: not by the refusals above, and never on a handle that did not call the mode
-    CHECK(fa->subsample_dev == nullptr && fa->subsample_bytes == 0 && pileup->subsample_dev == nullptr && pileup->subsample_bytes == 0);
-    CHECK(fa->jackknife_dev == nullptr && pileup->jackknife_dev == nullptr);
+    CHECK(fa->variant_dev == nullptr && fa->variant_bytes == 0 && pileup->variant_dev == nullptr && pileup->variant_bytes == 0);
 }
 
 int main() {

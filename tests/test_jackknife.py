@@ -18,6 +18,7 @@ from tests.test_abi import HEADER, declared_symbols
 
 ENTRIES = ("c3_jackknife_rows", "c3_jackknife", "c3_jackknife_reduce")
 JACKKNIFE_H = os.path.join(util.ROOT, "clair3_amd", "csrc", "c3_jackknife.h")
+VARIANTS_H = os.path.join(util.ROOT, "clair3_amd", "csrc", "c3_variants.h")  # what the mode shares with subsample and occlusion mode
 F32 = np.float32
 INF, NAN = F32(np.inf), F32(np.nan)
 
@@ -317,7 +318,8 @@ def test_definitions_of_the_kernel_header():
     assert "h == 0 ? 0 : h == 1 ? 21 : h == 2 ? 24 : 57" in src, "the heads of syn.head_slices"
     assert "p.nout + 23 + k" in src, "the decoder's first decision per reference base"
     assert "(depth - (n - 1)) / 2" in src and "C3_JACKKNIFE_IN_PLACE ? f" in src, "the two layouts"
-    assert "static_assert(sizeof(JackknifeEntry) == 24" in src and "e ? atoll(e) : 64" in src
+    assert "static_assert(sizeof(JackknifeEntry) == 24" in src and 'variant_chunk_env("C3HIP_JACKKNIFE_CHUNK", 64)' in src
+    assert "e ? atoll(e) : dflt" in open(VARIANTS_H).read(), "the switch is read in one place, with the mode's default"
     for word in ("a NaN never", "lowest j on ties", "an interior all-zero row of the run is a read too", "left out", "atomic"):
         assert word in src, word
     assert "atomicAdd" not in src and "atomicMax" not in src and "hipMemset(" not in src

@@ -413,7 +413,9 @@ def test_definitions_of_the_kernel_header():
     assert "h == 0 ? 0 : h == 1 ? 21 : h == 2 ? 24 : 57" in src, "the heads of syn.head_slices"
     assert "p.nout + 23 + q" in src, "the decoder's first decision per reference base"
     assert "(depth - k) / 2" in src and "C3_JACKKNIFE_IN_PLACE ? f" in src, "the two layouts"
-    assert "static_assert(sizeof(SubsampleEntry) == 32" in src and "e ? atoll(e) : 64" in src and "C3HIP_SUBSAMPLE_CHUNK" in src
+    variants = open(os.path.join(util.ROOT, "clair3_amd", "csrc", "c3_variants.h")).read()  # what the mode shares with the other two
+    assert "static_assert(sizeof(SubsampleEntry) == 32" in src and 'variant_chunk_env("C3HIP_SUBSAMPLE_CHUNK", 64)' in src
+    assert "e ? atoll(e) : dflt" in variants
     assert "kSubsampleMaxDepth = 128" in src and "kSubsampleMaxLevels = 8, kSubsampleMaxReplicates = 32" in src
     for word in ("a NaN never", "lowest j first on equal keys", "an interior all-zero row of\n// the run is a read too", "NOT RUN", "NESTED", "atomic"):
         assert word in src, word
@@ -421,7 +423,8 @@ def test_definitions_of_the_kernel_header():
     jk = open(os.path.join(util.ROOT, "clair3_amd", "csrc", "c3_jackknife.h")).read()
     assert "subsample" not in jk, "the mode adds nothing to c3_jackknife.h"
     hip = open(os.path.join(util.ROOT, "clair3_amd", "csrc", "c3_model.hip")).read()
-    assert hip.index('#include "c3_jackknife.h"') < hip.index('#include "c3_subsample.h"') and "hipFree(m->subsample_dev)" in hip
+    assert hip.index('#include "c3_jackknife.h"') < hip.index('#include "c3_subsample.h"') and "hipFree(m->variant_dev)" in hip
+    assert "subsample_dev" not in hip and "hipMalloc(&m->variant_dev" in variants, "one buffer for the three modes, freed with the handle"
 
 
 def test_entries_are_declared_bound_and_exported():
