@@ -41,6 +41,8 @@ EXPORTS = (
     "c3_jackknife_rows", "c3_jackknife", "c3_jackknife_reduce",
     "c3_subsample_rows", "c3_subsample", "c3_subsample_reduce",
     "c3_occlude", "c3_occlude_rows", "c3_occlude_reduce",
+    "c3_gvcf_site", "c3_gvcf_site_table", "c3_gvcf_blocks_host", "c3_gvcf_create", "c3_gvcf_destroy", "c3_gvcf_blocks_counts",
+    "c3_gvcf_blocks_region", "c3_gvcf_text", "c3_gvcf_tile_sites", "c3_gvcf_top_span", "c3_gvcf_table_depth",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -168,6 +170,20 @@ class OccludeInfo(C.Structure):
     """c3_occlude_info (include/c3hip.h)"""
     _fields_ = [("windows", C.c_int64), ("variants", C.c_int64), ("passes", C.c_int64), ("bytes_staged", C.c_int64),
                 ("on_fp32", C.c_int32), ("reserved", C.c_int32), ("expand_us", C.c_float), ("reduce_us", C.c_float)]
+
+
+GVCF_MORE = 2  # C3_GVCF_MORE (include/c3hip.h)
+
+
+class GvcfConfig(C.Structure):
+    """c3_gvcf_config (include/c3hip.h)"""
+    _fields_ = [("base_err", C.c_double), ("gq_bin_size", C.c_int32), ("bp_resolution", C.c_int32)]
+
+
+class GvcfBlock(C.Structure):
+    """c3_gvcf_block (include/c3hip.h); gvcf.BLOCK_DTYPE is the same record as a numpy dtype"""
+    _fields_ = [("pos", C.c_int64), ("end", C.c_int64), ("min_dp", C.c_int32), ("max_dp", C.c_int32), ("gq", C.c_int32), ("pl", C.c_int32 * 3),
+                ("ref", C.c_uint8), ("gt", C.c_uint8), ("per_site", C.c_uint8), ("first_n", C.c_uint8), ("reserved", C.c_int32)]
 
 
 class C3Error(RuntimeError):
@@ -316,6 +332,19 @@ def lib():
     L.c3_occlude_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
     L.c3_subsample_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]
+    L.c3_gvcf_site.argtypes = [C.POINTER(GvcfConfig), C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    L.c3_gvcf_site_table.argtypes = [C.POINTER(GvcfConfig), C.c_int, C.c_void_p]
+    L.c3_gvcf_blocks_host.argtypes = [C.POINTER(GvcfConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_int64)]
+    L.c3_gvcf_create.restype = C.c_void_p
+    L.c3_gvcf_create.argtypes = [C.c_int, C.POINTER(GvcfConfig)]
+    L.c3_gvcf_destroy.argtypes = [C.c_void_p]
+    L.c3_gvcf_blocks_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64)]
+    L.c3_gvcf_blocks_region.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.POINTER(C.c_int64)]
+    L.c3_gvcf_text.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.c3_gvcf_top_span.restype = C.c_int64
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

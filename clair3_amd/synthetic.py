@@ -898,3 +898,121 @@ def occlude_records(base_rows, variant_rows, channels, bands, nout):
         rec["max_delta"] = np.maximum(rec["max_delta"], r["max_delta"])
         drops[:, lo:lo + n] = d.reshape(B, n, 4)
     return rec, drops
+
+
+# ---- gVCF mode: the numpy mirror of csrc/c3_gvcf.h, for callers without a GPU and for the tests
+GVCF_BLOCK_DTYPE = np.dtype([("pos", "<i8"), ("end", "<i8"), ("min_dp", "<i4"), ("max_dp", "<i4"), ("gq", "<i4"), ("pl", "<i4", (3,)),
+                             ("ref", "u1"), ("gt", "u1"), ("per_site", "u1"), ("first_n", "u1"), ("reserved", "<i4")])  # c3_gvcf_block
+GVCF_MAX_DEPTH = 65535
+_GVCF_LOG_10, _GVCF_LOG_2, _GVCF_MAX_GQ = 2.3025, 0.3010, 50  # preprocess/utils.py:18-19, :360, as the reference writes them
+
+
+def gvcf_site(n_ref, n_total, base_err=0.001, gq_bin_size=5):
+    """(gq, binned_gq, validPL, (PL0, PL1, PL2)) of one site with an ACGT reference base: _cal_reference_likelihood and the PL lines of
+    reference_likelihood (preprocess/utils.py:490-568) with the Python math of mathcalculator (speedUp off), round(., 6) included."""
+    import math
+    logp, log1p = math.log(base_err) / _GVCF_LOG_10, math.log1p(-base_err) / _GVCF_LOG_10
+
+    def normalize(v):
+        m = max(v)
+        lse = round(m + math.log10(sum(pow(10.0, x - m) for x in v)), 6)
+        return [min(x - lse, 0) for x in v]
+
+    if n_total == 0:
+        l = normalize([-1.0, -1.0, -1.0])
+    else:
+        n_alts = n_total - n_ref
+        l = normalize([n_ref * log1p + n_alts * logp, -n_total * _GVCF_LOG_2, n_ref * logp + n_alts * log1p])
+    ptrue = math.pow(10, l[0])
+    gq = 50 if ptrue == 1 else round(-10 * (math.log(1 - ptrue) / _GVCF_LOG_10), 6)
+    gq = int(min(int(gq), _GVCF_MAX_GQ))
+    binned = (gq - 1) // gq_bin_size * gq_bin_size + 1 if gq >= 1 else 0
+    t = [-10 * x for x in l]
+    return gq, binned, l[0] == max(l), tuple(int(x - min(t)) for x in t)
+
+
+def gvcf_f(x):
+    """ceil(x + x * 0.3) in double: the block's largest depth may reach f(its smallest) (preprocess/utils.py:465, :476)"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.ceil(x + x * 0.3).astype(np.int64)
+
+
+def gvcf_region_counts(region, major, ref_bytes, first_major, n_sites):
+    """(n_ref, n_total) int64 [n_sites] from a region as calculate_clair3_pileup leaves it (src/clair3_pileup.c:355-371, :452-455): site j
+    takes the column whose major is first_major + j, a site without a column has 0 / 0.  The reference index is C 1, G 2, T 3, anything
+    else 0 (base2index of the upper-cased byte); the strand sums are minus the two negated reference channels, ref_count the sums minus
+    the other three bases' counts, all_alt_count the reference's running-maximum sum in index order, del 6 + 15, ins 4 + 13."""
+    region = np.asarray(region).astype(np.int64)
+    major = np.asarray(major, dtype=np.int64)
+    ref = np.frombuffer(bytes(ref_bytes), dtype=np.uint8) if isinstance(ref_bytes, (bytes, bytearray)) else np.asarray(ref_bytes, dtype=np.uint8)
+    if region.ndim != 2 or region.shape[1] != PILEUP_CHANNELS or major.shape != (len(region),) or len(ref) != n_sites:
+        raise ValueError("region (n_cols, 18), major (n_cols,), ref_bytes (n_sites,) expected")
+    n_ref, n_total = np.zeros(n_sites, np.int64), np.zeros(n_sites, np.int64)
+    site = major - first_major
+    keep = (site >= 0) & (site < n_sites)
+    m, site = region[keep], site[keep]
+    up = ref[site] & 0xDF
+    r = np.select([up == ord("C"), up == ord("G"), up == ord("T")], [1, 2, 3], 0)
+    ref_count = -(m[:, 0:4].sum(axis=1) + m[:, 9:13].sum(axis=1))  # -(negated sums) - (the other three bases), on both strands
+    alt, all_alt = np.zeros(len(m), np.int64), np.zeros(len(m), np.int64)
+    for k in range(4):
+        cur = np.where(r == k, 0, m[:, k] + m[:, 9 + k])
+        up_k = cur > alt
+        alt = np.where(up_k, cur, alt)
+        all_alt = all_alt + np.where(up_k, alt, 0)
+    n_ref[site] = ref_count
+    n_total[site] = ref_count + all_alt + m[:, 6] + m[:, 15] + m[:, 4] + m[:, 13]
+    return n_ref, n_total
+
+
+def gvcf_blocks(n_ref, n_total, ref_bytes, first_pos=0, base_err=0.001, gq_bin_size=5, bp_resolution=False):
+    """The records of make_gvcf_online / write_to_gvcf_batch (preprocess/utils.py:398-488, :577-606) as (n,) of GVCF_BLOCK_DTYPE, by the
+    reduction csrc/c3_gvcf.h states: a block from s runs on while no hard break (binned_gq, gt, is-exactly-N against the previous site)
+    lies in it and max(dp) <= gvcf_f(min(dp))."""
+    n_ref, n_total = np.asarray(n_ref, dtype=np.int64), np.asarray(n_total, dtype=np.int64)
+    ref = np.frombuffer(bytes(ref_bytes), dtype=np.uint8) if isinstance(ref_bytes, (bytes, bytearray)) else np.asarray(ref_bytes, dtype=np.uint8)
+    n = len(n_total)
+    if n_ref.shape != (n,) or ref.shape != (n,):
+        raise ValueError("n_ref, n_total and ref_bytes of one length expected")
+    if n and ((n_ref < 0).any() or (n_ref > n_total).any() or (n_total > GVCF_MAX_DEPTH).any()):
+        raise ValueError("counts must satisfy 0 <= n_ref <= n_total <= 65535")
+    pairs, inv = np.unique(np.stack([n_total, n_ref], axis=1), axis=0, return_inverse=True) if n else (np.zeros((0, 2), np.int64), np.zeros(0, np.int64))
+    recs = [gvcf_site(int(b), int(a), base_err, gq_bin_size) for a, b in pairs]
+    inv = inv.reshape(-1)
+    gq = np.array([r[0] for r in recs], np.int64)[inv] if n else np.zeros(0, np.int64)
+    binned = np.array([r[1] for r in recs], np.int64)[inv] if n else np.zeros(0, np.int64)
+    valid = np.array([r[2] for r in recs], bool)[inv] if n else np.zeros(0, bool)
+    pl = np.array([r[3] for r in recs], np.int64).reshape(-1, 3)[inv] if n else np.zeros((0, 3), np.int64)
+    acgt = np.isin(ref, np.frombuffer(b"ACGT", np.uint8))
+    gq, binned, pl = np.where(acgt, gq, 1), np.where(acgt, binned, 1), np.where(acgt[:, None], pl, 0)
+    is_n = ref == ord("N")
+    printed = np.where(acgt, ref, ord("N")).astype(np.uint8)
+    f = gvcf_f(np.arange(int(n_total.max()) + 1 if n else 1))  # by the smallest depth
+    out = []
+
+    def close(s, e, mn, mx, mgq):
+        if (bp_resolution or not valid[s]) and acgt[s]:
+            for i in range(s, e + 1):
+                out.append((first_pos + i, first_pos + i, n_total[i], n_total[i], binned[i], tuple(pl[i]), printed[i], valid[i], 1, 0, 0))
+        elif not acgt[s]:
+            out.append((first_pos + s, first_pos + e, mn, mx, 1, (0, 0, 0), ord("N"), 0, 0, 1, 0))
+        else:
+            out.append((first_pos + s, first_pos + e, mn, mx, mgq, tuple(pl[s]), printed[s], valid[s], 0, 0, 0))
+
+    s = 0
+    for i in range(n):
+        d = int(n_total[i])
+        if i == 0:
+            mn = mx = d
+            mgq = gq[i]
+            continue
+        hard = binned[i] != binned[i - 1] or valid[i] != valid[i - 1] or is_n[i] != is_n[i - 1]
+        mn2, mx2 = min(mn, d), max(mx, d)
+        if hard or mx2 > f[mn2]:
+            close(s, i - 1, mn, mx, mgq)
+            s, mn, mx, mgq = i, d, d, gq[i]
+        else:
+            mn, mx, mgq = mn2, mx2, min(mgq, gq[i])
+    if n:
+        close(s, n - 1, mn, mx, mgq)
+    return np.array(out, dtype=GVCF_BLOCK_DTYPE) if out else np.zeros(0, GVCF_BLOCK_DTYPE)

@@ -1008,6 +1008,74 @@ int c3_occlude_rows(c3_model *m, const void *rows_host, const int32_t *row_first
 int c3_occlude_reduce(c3_model *m, const float *base_rows, const float *variant_rows, int row_floats, int channels, int bands,
                       int64_t batch, c3_occlude_window *out, float *drops_out);
 
+/* ---- gVCF mode: the non-variant half of the reference's --gvcf, the <NON_REF> block records, from the per-site counts of the pileup
+ * step.  No c3_model is involved.  The rule, the argument why it is a chain of range queries, and the kernels: csrc/c3_gvcf.h.
+ * One contig per call; a depth of at most 65535; at most INT32_MAX - 1024 sites a call.
+ *   c3_gvcf_config   what variantInfoCalculator takes (preprocess/utils.py:350): p_err, gq_bin_size, bp_resolution
+ *   c3_gvcf_block    one written record (write_to_gvcf_batch :577-606): a block, or one item of a block that the reference writes item by
+ *                    item (per_site = 1: a ./. block, or any block under bp_resolution, whose first item's base is in ACGT)
+ *   c3_gvcf_site     reference_likelihood / _cal_reference_likelihood (:490-568) of one site, plain host code:
+ *                    out6 = gq, binned_gq, validPL (1: 0/0, 0: ./.), PL[3].  ref_byte is the raw reference byte: anything outside
+ *                    upper-case ACGT gives gq = binned_gq = 1 and PL 0,0,0
+ *   c3_gvcf_site_table  the same for every pair n_ref <= n_total <= depth with an ACGT base: out[6 * (n_total * (n_total + 1) / 2 + n_ref)]
+ *   c3_gvcf_blocks_host  make_gvcf_online (:398-488) and the closing write_to_gvcf_batch of the producer (preprocess/
+ *                    CreateTensorPileupFromCffi.py:419-437) over n_sites sites, sequentially on the host: needs no device.  Site j is
+ *                    position first_pos + j; n_ref / n_total [n_sites] are C3_DTYPE_I32 or C3_DTYPE_I64 (= pos_ref_count /
+ *                    pos_total_count themselves); ref_bytes [n_sites] raw reference bytes
+ *   c3_gvcf_create / c3_gvcf_destroy   a device context: a stream, workspaces that grow and never shrink, the table of site records
+ *   c3_gvcf_blocks_counts   the same records as c3_gvcf_blocks_host, on the device
+ *   c3_gvcf_blocks_region   the same from the region matrix calculate_clair3_pileup returns (src/clair3_pileup.c:355-371, :452-455 undone
+ *                    on the device): region_host (n_cols, 18) C3_DTYPE_I32 or C3_DTYPE_I64 (= plp_data.matrix), major_host = plp_data.major
+ *                    (strictly increasing, 0-based); site j takes the column whose major is first_major + j, a site without a column has
+ *                    0 / 0.  For the site the producer prints as P, the major is P when the chunk's ctg_start is not 1, P - 1 when it is
+ *                    (CreateTensorPileupFromCffi.py:413-423)
+ *   c3_gvcf_text     the lines of write_to_gvcf (:608-622) for a call's records, with its contig-end rule (END == contig_len - 1 prints
+ *                    contig_len; contig_len <= 0: the contig is not in the header).  n_sites > 0 turns the producer's empty-pileup rule on
+ *                    (CreateTensorPileupFromCffi.py:417-421, :439-440): where every record has max_dp 0, the one line of
+ *                    write_empty_pileup (:392-397) stands in their place, pos max(1, first_pos), END first_pos + n_sites.  n_sites == 0
+ *                    prints the records as they are, all-zero ones included (what make_gvcf_online itself writes for them)
+ *   c3_gvcf_tile_sites / c3_gvcf_top_span / c3_gvcf_table_depth   constants of the device path, for tests: sites per tile, sites per
+ *                    group of tiles (the last level that is walked one thread per group), rows of the device's record table
+ * Sites deeper than the table's 1024 rows (up to 65535) cost a call one copy of its counts back to the host (4 bytes a site) and a side
+ * table of the distinct deep pairs.
+ * Status: 0; 1 with c3_last_error (a negative count, n_ref > n_total, a depth above 65535, null buffers, a dtype other than the two);
+ * C3_GVCF_MORE when max_blocks (or buf_bytes) is too small: the count needed is in *n_blocks_out (*bytes_out), the first max_blocks records
+ * are written and nothing beyond them (the text: nothing).  n_sites == 0 launches nothing and gives no record. */
+#define C3_GVCF_MORE 2
+typedef struct {
+    double base_err;       /* --base_err, 0.001 */
+    int32_t gq_bin_size;   /* --gq_bin_size, 5 */
+    int32_t bp_resolution; /* --bp_resolution */
+} c3_gvcf_config;
+typedef struct c3_gvcf_block { /* 48 bytes */
+    int64_t pos, end;       /* POS and END (before the contig-end rule of the text) */
+    int32_t min_dp, max_dp; /* of the block's n_total; an item: its own */
+    int32_t gq;             /* what is printed as GQ: the block's minimum of the items' gq; an item: its binned_gq; 1 when first_n */
+    int32_t pl[3];
+    uint8_t ref;            /* the printed base: A C G T or N */
+    uint8_t gt;             /* 1: 0/0, 0: ./. */
+    uint8_t per_site;       /* 1: an item of a block written item by item */
+    uint8_t first_n;        /* 1: a block whose first item's base is outside ACGT (./., GQ 1, PL 0,0,0) */
+    int32_t reserved;
+} c3_gvcf_block;
+typedef struct c3_gvcf c3_gvcf;
+int c3_gvcf_site(const c3_gvcf_config *cfg, int64_t n_ref, int64_t n_total, int ref_byte, int32_t *out6);
+int c3_gvcf_site_table(const c3_gvcf_config *cfg, int depth, int32_t *out);
+int c3_gvcf_blocks_host(const c3_gvcf_config *cfg, const void *n_ref, const void *n_total, int dtype, const void *ref_bytes, int64_t n_sites,
+                        int64_t first_pos, c3_gvcf_block *blocks_out, int64_t max_blocks, int64_t *n_blocks_out);
+c3_gvcf *c3_gvcf_create(int device, const c3_gvcf_config *cfg);
+int c3_gvcf_destroy(c3_gvcf *g);
+int c3_gvcf_blocks_counts(c3_gvcf *g, const void *n_ref, const void *n_total, int dtype, const void *ref_bytes, int64_t n_sites, int64_t first_pos,
+                          c3_gvcf_block *blocks_out, int64_t max_blocks, int64_t *n_blocks_out);
+int c3_gvcf_blocks_region(c3_gvcf *g, const void *region_host, int x_dtype, int64_t n_cols, const int64_t *major_host, const void *ref_bytes,
+                          int64_t first_major, int64_t n_sites, int64_t first_pos, c3_gvcf_block *blocks_out, int64_t max_blocks,
+                          int64_t *n_blocks_out);
+int c3_gvcf_text(const c3_gvcf_block *blocks, int64_t n_blocks, const char *ctg_name, int64_t contig_len, int64_t first_pos, int64_t n_sites,
+                 char *buf, int64_t buf_bytes, int64_t *bytes_out);
+int c3_gvcf_tile_sites(void);
+int64_t c3_gvcf_top_span(void);
+int c3_gvcf_table_depth(void);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
