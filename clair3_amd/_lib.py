@@ -43,6 +43,8 @@ EXPORTS = (
     "c3_occlude", "c3_occlude_rows", "c3_occlude_reduce",
     "c3_gvcf_site", "c3_gvcf_site_table", "c3_gvcf_blocks_host", "c3_gvcf_create", "c3_gvcf_destroy", "c3_gvcf_blocks_counts",
     "c3_gvcf_blocks_region", "c3_gvcf_text", "c3_gvcf_tile_sites", "c3_gvcf_top_span", "c3_gvcf_table_depth",
+    "c3_pileup_create", "c3_pileup_destroy", "c3_pileup_reads", "c3_pileup_reads_host", "c3_pileup_sizes", "c3_pileup_result", "c3_pileup_stats",
+    "c3_predict_submit_pileup", "c3_predict_pileup_reads",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -184,6 +186,25 @@ class GvcfBlock(C.Structure):
     """c3_gvcf_block (include/c3hip.h); gvcf.BLOCK_DTYPE is the same record as a numpy dtype"""
     _fields_ = [("pos", C.c_int64), ("end", C.c_int64), ("min_dp", C.c_int32), ("max_dp", C.c_int32), ("gq", C.c_int32), ("pl", C.c_int32 * 3),
                 ("ref", C.c_uint8), ("gt", C.c_uint8), ("per_site", C.c_uint8), ("first_n", C.c_uint8), ("reserved", C.c_int32)]
+
+
+class ReadSetC(C.Structure):
+    """c3_read_set (include/c3hip.h)"""
+    _fields_ = [("n_reads", C.c_int64), ("pos", C.c_void_p), ("flag", C.c_void_p), ("mapq", C.c_void_p), ("cigar_first", C.c_void_p),
+                ("cigar", C.c_void_p), ("seq_first", C.c_void_p), ("seq", C.c_void_p)]
+
+
+class PileupConfig(C.Structure):
+    """c3_pileup_config (include/c3hip.h)"""
+    _fields_ = [("min_depth", C.c_int64), ("min_snp_af", C.c_float), ("min_indel_af", C.c_float), ("min_mq", C.c_int32),
+                ("max_indel_length", C.c_int32), ("call_snp_only", C.c_int32), ("gvcf", C.c_int32), ("call_ht", C.c_int32), ("reserved", C.c_int32),
+                ("hash_mask", C.c_uint64)]
+
+
+class PileupCounters(C.Structure):
+    """c3_pileup_counters (include/c3hip.h)"""
+    _fields_ = [("reads_kept", C.c_int64), ("reads_dropped", C.c_int64), ("events", C.c_int64), ("collisions", C.c_int64),
+                ("fell_back", C.c_int32), ("on_host", C.c_int32), ("kernel_ms", C.c_float * 8)]
 
 
 class C3Error(RuntimeError):
@@ -345,6 +366,16 @@ def lib():
                                         C.c_int64, C.POINTER(C.c_int64)]
     L.c3_gvcf_text.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.c3_gvcf_top_span.restype = C.c_int64
+    L.c3_pileup_create.restype = C.c_void_p
+    L.c3_pileup_create.argtypes = [C.c_int]
+    L.c3_pileup_destroy.argtypes = [C.c_void_p]
+    for fn in (L.c3_pileup_reads, L.c3_pileup_reads_host):
+        fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(PileupConfig)]
+    L.c3_pileup_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
+    L.c3_pileup_result.argtypes = [C.c_void_p] * 8
+    L.c3_pileup_stats.argtypes = [C.c_void_p, C.POINTER(PileupCounters)]
+    L.c3_predict_submit_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+    L.c3_predict_pileup_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -162,6 +162,11 @@ struct CandInput {
     std::vector<int64_t> src_col;     // ... and in the caller's matrix
     uint8_t *status_host = nullptr;
     int64_t *n_rows_host = nullptr;
+    // the region matrix already lies on this device (c3_predict_submit_pileup, c3_pileup.h): int32 columns in the order of the chunks.  Nothing
+    // of it is staged: it reaches the slot by device-to-device copies on the lane's stream, behind the event of the stream that wrote it
+    const void *dev_image = nullptr;
+    hipEvent_t dev_ready = nullptr;
+    hipEvent_t dev_taken = nullptr;  // recorded on the lane's stream behind those copies: the image's owner may overwrite it from there on
 };
 struct RingInput {
     InKind kind = InKind::Sliced;
@@ -286,6 +291,7 @@ struct Filled {
     int nrun = 0;
     struct Run { size_t off, bytes; } run[8];
     int64_t rows_shipped = 0;
+    bool no_image = false;  // the image section is filled on the device (queue_device_image): nothing of it crosses from the pinned buffer
     void prebuilt(size_t bytes) { nrun = 1, run[0] = Run{0, bytes}; }
 };
 // int64 = plp_data.matrix itself (size_t counts, src/clair3_pileup.h:113): narrowed to int32 on its way into the staging
@@ -335,6 +341,10 @@ static void fill_candidates(const c3_model *m, const HostSlot &sl, const RingInp
     memcpy(sl.pin<char>(p.cand_pos), ci.pos, p.cand_pos.bytes);
     if (depth) memcpy(sl.pin<char>(p.depth_in), depth, p.depth_in.bytes);
     memcpy(sl.pin<char>(p.chunks), ci.chunks.data(), p.chunks.bytes);
+    if (ci.dev_image) {  // (queue_device_image brings the image in)
+        f.no_image = true;
+        return;
+    }
     if (!ci.head_tail) return fill_region_image(m, sl, in, p, f);
     // head / tail windows: the image is laid out in the staging buffer chunk by chunk, positions - 1 zero columns in front of and behind
     // each (c3_select.h)
@@ -407,8 +417,9 @@ static int queue_input(c3_model *m, const HostSlot &sl, const StagedBatch &p, co
     hipStream_t s = lane(m).stream;
     if (alone && p.staged <= kKernelCopyMax && p.y_total <= kKernelCopyMax && f.nrun <= 1) {  // (the copy kernel moves ONE run: rows packed by several ranges take the transfers)
         if (f.src) StagePool::get().copy(sl.pin_x, f.src, p.image.bytes);  // (plain memcpy below 1 MB, split over the helpers above)
-        hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, s, (const uint4 *)sl.pin_x, (uint4 *)sl.dev_x, (p.staged + 15) / 16,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr);
+        const size_t from = f.no_image ? p.tail : 0;  // (a section offset: a multiple of 256)
+        hipLaunchKernelGGL(host_copy_kernel, dim3(128), dim3(256), 0, s, (const uint4 *)((const char *)sl.pin_x + from), (uint4 *)((char *)sl.dev_x + from),
+                           (p.staged - from + 15) / 16, (const uint32_t *)nullptr, (uint32_t *)nullptr);
         HIP_TRY(hipGetLastError());
     } else if (in_lane) {
         // a small batch in a lane brings its windows in on the lane's OWN stream: copy, kernels and the copy-out in order in one queue, no
@@ -420,6 +431,29 @@ static int queue_input(c3_model *m, const HostSlot &sl, const StagedBatch &p, co
         HIP_TRY(hipEventRecord(sl.ev_h2d, m->h2d_stream));
         HIP_TRY(hipStreamWaitEvent(s, sl.ev_h2d, 0));
     }
+    return 0;
+}
+
+// a candidate batch whose region matrix is on the device already: the image of fill_candidates, laid out by copies between device buffers.
+// Queued behind queue_input on the lane's stream (which brings in the tail only: Filled::no_image)
+static int queue_device_image(c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p) {
+    const CandInput &ci = *in.cand;
+    hipStream_t s = lane(m).stream;
+    if (ci.dev_ready) HIP_TRY(hipStreamWaitEvent(s, ci.dev_ready, 0));
+    if (!ci.head_tail) {
+        if (p.image.bytes) HIP_TRY(hipMemcpyAsync(sl.dev_x, ci.dev_image, p.image.bytes, hipMemcpyDeviceToDevice, s));
+        if (ci.dev_taken) HIP_TRY(hipEventRecord(ci.dev_taken, s));
+        return 0;
+    }
+    const size_t colb = (size_t)m->C * sizeof(int32_t), pad = (size_t)(m->positions - 1);
+    for (size_t k = 0; k < ci.chunks.size(); ++k) {
+        const SelectChunk &ch = ci.chunks[k];
+        const size_t n = (size_t)(ch.last - ch.first + 1), c0 = (size_t)ch.col, s0 = (size_t)ci.src_col[k];
+        HIP_TRY(hipMemsetAsync((char *)sl.dev_x + (c0 - pad) * colb, 0, pad * colb, s));
+        HIP_TRY(hipMemcpyAsync((char *)sl.dev_x + c0 * colb, (const char *)ci.dev_image + s0 * colb, n * colb, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemsetAsync((char *)sl.dev_x + (c0 + n) * colb, 0, pad * colb, s));
+    }
+    if (ci.dev_taken) HIP_TRY(hipEventRecord(ci.dev_taken, s));
     return 0;
 }
 
@@ -829,6 +863,7 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         case InKind::Parts: fill_parts(sl, in, p, (size_t)c3_model_window_bytes(m, in.x_dtype), f); break;
         }
         TRY(queue_input(m, sl, p, f, alone, in_lane));
+        if (in.cand && in.cand->dev_image) TRY(queue_device_image(m, sl, in, p));
         if (launch_batch(m, sl, in, p) != 0) {
             // refused behind its input: the slot stays free, so the next submit may stage into it at once, in ANOTHER lane's stream -- the
             // transfers queued above must have landed before that (the error message is the launch's)

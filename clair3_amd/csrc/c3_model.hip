@@ -15,6 +15,7 @@
 #include "c3_subsample.h"  // (subsample mode: its kernels sit in a section of their own behind `.c3_jackknife_text`)
 #include "c3_occlude.h"  // (occlusion mode: its kernels sit in a section of their own behind `.c3_subsample_text`)
 #include "c3_gvcf.h"  // (gVCF mode: no model; its kernels sit in a section of their own behind `.c3_occlude_text`)
+#include "c3_pileup.h"  // (pileup from reads: no model; its kernels sit in a section of their own behind `.c3_gvcf_text`)
 
 extern "C" {
 

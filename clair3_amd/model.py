@@ -1214,6 +1214,22 @@ class Clair3_P(_RingVerify):
             "c3_predict_submit_candidates")
         return slot, out
 
+    def predict_reads(self, context, head_tail=False):
+        """predict_candidates on the result a pileup_reads.Context holds (context.run(reads, start, end, ...) first): the region matrix goes
+        from the context's device buffer into the batch without visiting the host (c3_predict_pileup_reads).  Returns (rows, status) as
+        predict_candidates(counts, major, cand_pos, cand_depth) of context.fetch() does, bit for bit."""
+        out = _CandidateBatch(context.sizes()[1], self.row_size)
+        _lib.check(_lib.lib().c3_predict_pileup_reads(self._handle, context.h, int(bool(head_tail)), out.rows.ctypes.data, out.status.ctypes.data,
+                                                      C.byref(out.n_rows)), "c3_predict_pileup_reads")
+        return out.rows[:out.n_rows.value], out.status
+
+    def submit_reads(self, context, slot=0, head_tail=False):
+        """Asynchronous half of predict_reads (c3_predict_submit_pileup); wait() on the ticket returns (rows, status)."""
+        out = _CandidateBatch(context.sizes()[1], self.row_size)
+        _lib.check(_lib.lib().c3_predict_submit_pileup(self._handle, context.h, int(bool(head_tail)), out.rows.ctypes.data, out.status.ctypes.data,
+                                                       C.byref(out.n_rows), slot), "c3_predict_submit_pileup")
+        return slot, out
+
 
 class Clair3_F(_RingVerify):
     """Full-alignment network: residual 3x3-conv stack + pyramid pooling + FC heads (clair3/model.py:282-416)."""

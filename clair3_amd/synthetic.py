@@ -1016,3 +1016,212 @@ def gvcf_blocks(n_ref, n_total, ref_bytes, first_pos=0, base_err=0.001, gq_bin_s
     if n:
         close(s, n - 1, mn, mx, mgq)
     return np.array(out, dtype=GVCF_BLOCK_DTYPE) if out else np.zeros(0, GVCF_BLOCK_DTYPE)
+
+
+# ---- pileup from reads: read sets in BAM's own encoding (c3_read_set, include/c3hip.h)
+NT16 = "=ACMGRSVTWYHKDBN"  # htslib's seq_nt16_str: the letter of a 4-bit code
+CIGAR_OPS = "MIDNSHP=X"
+PILEUP_DROP_FLAGS = (0x4, 0x100, 0x800, 0x200, 0x400)  # src/medaka_bamiter.c:20
+
+
+def pack_reads(reads):
+    """A read set from a list of (pos, flag, mapq, cigar, seq): cigar a string ("12M3I4M") or a list of (op letter, length), seq a string
+    of nt16 letters.  The arrays of c3_read_set as a dict: pos, flag, mapq, cigar_first, cigar, seq_first, seq."""
+    import re
+    pos, flag, mapq, cfirst, cig, sfirst, seq = [], [], [], [0], [], [0], []
+    for p, f, q, c, s in reads:
+        if isinstance(c, str):
+            c = [(m.group(2), int(m.group(1))) for m in re.finditer(r"(\d+)([MIDNSHP=X])", c)]
+        pos.append(p), flag.append(f), mapq.append(q)
+        cig.extend(n << 4 | CIGAR_OPS.index(o) for o, n in c)
+        cfirst.append(len(cig))
+        codes = np.array([NT16.index(b) for b in s], dtype=np.uint8)
+        seq.append(_pack_nt16(codes))
+        sfirst.append(sfirst[-1] + len(seq[-1]))
+    return {"pos": np.array(pos, np.int64), "flag": np.array(flag, np.uint16), "mapq": np.array(mapq, np.uint8),
+            "cigar_first": np.array(cfirst, np.int64), "cigar": np.array(cig, np.uint32), "seq_first": np.array(sfirst, np.int64),
+            "seq": np.concatenate(seq) if seq else np.zeros(0, np.uint8)}
+
+
+def _pack_nt16(codes):
+    """4-bit codes, two per byte, high nibble first, padded to a byte"""
+    if len(codes) & 1:
+        codes = np.append(codes, np.uint8(0))
+    return (codes[0::2] << 4 | codes[1::2]).astype(np.uint8)
+
+
+def make_read_set(n_sites, depth, read_len, seed, start=2000, sub=0.01, ins=0.004, dele=0.004, soft_clip=0.2, n_op=0.0, non_acgt=0.0,
+                  filtered=0.05, low_mapq=0.05, gaps=0, hot=0.03, d_then_i=0.0, i_then_d=0.0, pad=0.0, eqx=False, ref_other=0.0, min_mq=5,
+                  hot_at=(), gap_at=()):
+    """Aligned reads over a random reference, as a dict: the arrays of pack_reads, and start, end (the region [start, start + n_sites)),
+    ref_bytes (uint8) with ref_first, and min_mq (what low_mapq is low against).  read_len: the reference span of a read, an int or
+    (low, high).  Rates per reference position of a read: sub(stitutions), ins(ertions), dele(tions), n_op (N ops), d_then_i / i_then_d
+    (a deletion directly followed by an insertion and the other way round), pad (a P op in front of an indel); non_acgt: read bases turned
+    into other nt16 codes; per read: soft_clip (S or H at either end), filtered (one of the dropped flags), low_mapq.  hot: the share of
+    reference positions that are variant sites, where half the reads carry one of a few alleles (two strings of one length, two deletion
+    lengths): what makes candidates, and shared alleles on both strands; hot_at: (position, kind, alt) of variant sites placed by hand,
+    kind 1 a SNP, 2 insertions of alt bases, 3 deletions of alt and alt + 1 bases.  gaps: stretches of the region no read covers (a read
+    that would becomes two reads, one in front of the gap and one behind it), spread over the region; gap_at: (first, behind) of gaps placed by hand.  ref_other: reference bytes that are lower case or N.  Reads reach beyond both ends of the region, some lie wholly outside, none is sorted."""
+    rng = np.random.default_rng(seed)
+    lo_len, hi_len = (read_len, read_len) if np.isscalar(read_len) else read_len
+    end = start + n_sites
+    margin = 2 * hi_len + 64
+    ref_first = max(0, start - margin)
+    ref_len = end + margin + 64 - ref_first
+    ref_codes = rng.integers(0, 4, size=ref_len)
+    ref = np.frombuffer(b"ACGT", np.uint8)[ref_codes].copy()
+    if ref_other > 0:
+        odd = rng.random(ref_len) < ref_other
+        ref[odd] = np.where(rng.random(int(odd.sum())) < 0.5, ref[odd] | 0x20, ord("N"))
+    code_of = np.array([1, 2, 4, 8], np.uint8)
+    # variant sites: kind 1 a SNP, 2 insertions, 3 deletions; each with two alleles
+    hot_kind = np.where(rng.random(ref_len) < hot, rng.integers(1, 4, size=ref_len), 0)
+    hot_alt = rng.integers(1, 4, size=ref_len)       # SNP: the alt base = ref + this (mod 4); indels: a length 1 .. 3
+    hot_seed = rng.integers(0, 1 << 30, size=ref_len)
+    for at, k, alt in hot_at:
+        hot_kind[at - ref_first], hot_alt[at - ref_first] = k, alt
+    gap_list = []
+    for g in range(gaps):
+        a = start + (g + 1) * n_sites // (gaps + 1)
+        gap_list.append((a, a + int(rng.integers(3, 30))))
+    gap_list = sorted(gap_list + [tuple(g) for g in gap_at])
+    span_lo, span_hi = ref_first + 8, end + margin - hi_len - 8
+    mean_len = (lo_len + hi_len) / 2.0
+    n_reads = max(1, int(round(depth * (span_hi + mean_len - span_lo) / mean_len)))
+    reads_pos, flags, mapqs, cfirst, cig, sfirst, seqs = [], [], [], [0], [], [0], []
+    seq_bytes = 0
+    M = CIGAR_OPS.index
+
+    def random_bases(n):
+        return code_of[rng.integers(0, 4, size=n)]
+
+    def spans():
+        """(first position, reference span) of every read; one that would cover a gap becomes two, in front of the gap and behind it"""
+        for _ in range(n_reads):
+            L = int(rng.integers(lo_len, hi_len + 1))
+            p0 = int(rng.integers(span_lo, span_hi))
+            last = p0 + L
+            for a, b in gap_list:  # (ascending)
+                if p0 < b and last > a:
+                    if a - p0 >= 30:
+                        yield p0, a - p0
+                    p0 = b
+            if last - p0 >= 30:
+                yield p0, last - p0
+
+    for p0, L in spans():
+        o = p0 - ref_first
+        q = code_of[ref_codes[o:o + L]].copy()
+        s = rng.random(L) < sub
+        q[s] = code_of[(ref_codes[o:o + L][s] + rng.integers(1, 4, size=int(s.sum()))) % 4]
+        u = rng.random(L)
+        kind = np.zeros(L, np.int8)
+        edge = 0.0
+        for code, rate in ((1, ins), (2, dele), (3, n_op), (4, d_then_i), (5, i_then_d)):
+            kind[(u >= edge) & (u < edge + rate)] = code
+            edge += rate
+        hk = hot_kind[o:o + L]
+        carry = (hk > 0) & (rng.random(L) < 0.5)
+        second = rng.random(L) < 0.4  # the site's second allele
+        snp = carry & (hk == 1)
+        q[snp] = code_of[(ref_codes[o:o + L][snp] + hot_alt[o:o + L][snp] + second[snp]) % 4]
+        kind[carry & (hk == 2)] = 6
+        kind[carry & (hk == 3)] = 7
+        kind[:2] = 0
+        kind[-12:] = 0
+        m_op = M("M") if not eqx else (M("M"), M("="), M("X"))[int(rng.integers(0, 3))]
+        ops, pieces, cur = [], [], 0
+
+        def emit_m(to):
+            nonlocal cur
+            if to > cur:
+                if ops and ops[-1][0] == m_op:
+                    ops[-1][1] += to - cur
+                else:
+                    ops.append([m_op, to - cur])
+                pieces.append(q[cur:to])
+                cur = to
+
+        def emit_i(bases):
+            ops.append([M("I"), len(bases)])
+            pieces.append(bases)
+
+        for i in np.flatnonzero(kind):
+            i = int(i)
+            if i < cur:
+                continue
+            emit_m(i + 1)
+            k = int(kind[i])
+            if pad > 0 and rng.random() < pad and k != 3:
+                ops.append([M("P"), 1])
+            room = L - 12 - cur
+            if k == 1:
+                emit_i(random_bases(int(min(1 + rng.geometric(0.5), 12))))
+            elif k == 2 and room > 0:
+                d = int(min(rng.geometric(0.5), room))
+                ops.append([M("D"), d])
+                cur += d
+            elif k == 3 and room > 0:
+                d = int(min(rng.integers(5, 40), room))
+                ops.append([M("N"), d])
+                cur += d
+            elif k == 4 and room > 0:
+                d = int(min(rng.geometric(0.5), room))
+                ops.append([M("D"), d])
+                cur += d
+                emit_i(random_bases(int(rng.integers(1, 4))))
+            elif k == 5 and room > 0:
+                emit_i(random_bases(int(rng.integers(1, 4))))
+                d = int(min(rng.geometric(0.5), room))
+                ops.append([M("D"), d])
+                cur += d
+            elif k == 6:  # the site's insertion alleles: two strings of one length
+                r2 = np.random.default_rng(int(hot_seed[o + i]) + int(second[i]))
+                emit_i(code_of[r2.integers(0, 4, size=int(hot_alt[o + i]))])
+            elif k == 7 and room > 0:  # the site's deletion alleles: two lengths
+                d = int(min(int(hot_alt[o + i]) + int(second[i]), room))
+                ops.append([M("D"), d])
+                cur += d
+        emit_m(L)
+        if non_acgt > 0:
+            for piece in pieces:
+                bad = rng.random(len(piece)) < non_acgt
+                piece[bad] = rng.choice(np.array([15, 3, 5, 0], np.uint8), size=int(bad.sum()))
+        for front in (True, False):
+            if rng.random() < soft_clip:
+                n_clip = int(rng.integers(1, 20))
+                hard = rng.random() < 0.3
+                op = [M("H") if hard else M("S"), n_clip]
+                ops.insert(0, op) if front else ops.append(op)
+                if not hard:
+                    pieces.insert(0, random_bases(n_clip)) if front else pieces.append(random_bases(n_clip))
+        flag = 16 if rng.random() < 0.5 else 0
+        if rng.random() < filtered:
+            flag |= PILEUP_DROP_FLAGS[int(rng.integers(0, 5))]
+        mapq = int(rng.integers(0, max(min_mq, 1))) if rng.random() < low_mapq else int(rng.integers(max(min_mq, 20), 61))
+        reads_pos.append(p0), flags.append(flag), mapqs.append(mapq)
+        cig.extend(n << 4 | op for op, n in ops)
+        cfirst.append(len(cig))
+        packed = _pack_nt16(np.concatenate(pieces))
+        seqs.append(packed)
+        seq_bytes += len(packed)
+        sfirst.append(seq_bytes)
+    return {"pos": np.array(reads_pos, np.int64), "flag": np.array(flags, np.uint16), "mapq": np.array(mapqs, np.uint8),
+            "cigar_first": np.array(cfirst, np.int64), "cigar": np.array(cig, np.uint32), "seq_first": np.array(sfirst, np.int64),
+            "seq": np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), "start": start, "end": end, "ref_bytes": ref, "ref_first": ref_first,
+            "min_mq": min_mq}
+
+
+def tile_read_set(rs, copies):
+    """`copies` shifted copies of a read set laid end to end: a long region at the cost of generating a short one (the rate tool)"""
+    n_sites = rs["end"] - rs["start"]
+    first, last = rs["start"] - rs["ref_first"], rs["end"] - rs["ref_first"]
+    ref = np.concatenate([rs["ref_bytes"][:first]] + [rs["ref_bytes"][first:last]] * copies + [rs["ref_bytes"][last:]])
+    out = dict(rs)
+    out["pos"] = np.concatenate([rs["pos"] + k * n_sites for k in range(copies)])
+    for name in ("flag", "mapq", "cigar", "seq"):
+        out[name] = np.tile(rs[name], copies)
+    for name, data in (("cigar_first", "cigar"), ("seq_first", "seq")):
+        out[name] = np.concatenate([rs[name][:-1] + k * len(rs[data]) for k in range(copies)] + [np.array([copies * len(rs[data])], np.int64)])
+    out["end"], out["ref_bytes"] = rs["start"] + copies * n_sites, ref
+    return out

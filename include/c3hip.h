@@ -1076,6 +1076,68 @@ int c3_gvcf_tile_sites(void);
 int64_t c3_gvcf_top_span(void);
 int c3_gvcf_table_depth(void);
 
+/* ---- pileup from reads: the region matrix, its candidates with their alt-info, and the gVCF count pair of calculate_clair3_pileup
+ * (src/clair3_pileup.c:208-461), from aligned reads as the arrays a BAM record holds.  No c3_model is involved and no file is read.
+ * The rule clause by clause, where it deliberately leaves the reference, and the kernels: csrc/c3_pileup_rule.h, csrc/c3_pileup.h.
+ *
+ *   c3_read_set       host pointers in BAM's own encoding (bam1_core_t.pos / flag / qual, bam_get_cigar, bam_get_seq); reads in any order
+ *   c3_pileup_config  calculate_clair3_pileup's arguments, and hash_mask: ANDed into the keys of the device's insertion table (all ones by
+ *                     default; 0xF makes keys collide so that the fallback to the host form can be exercised).  gvcf == 0: no count pair
+ *   c3_pileup_create / c3_pileup_destroy   a context: result buffers; with device >= 0 a stream and device buffers that grow and never shrink.
+ *                     device < 0: a context without a GPU, for c3_pileup_reads_host alone
+ *   c3_pileup_reads   the region [start, end), 0-based.  ref_bytes[i] is the reference at ref_first + i and must cover
+ *                     [start, end + max_indel_length], else the call fails before anything is queued.  Limits of one call: 2^27 sites,
+ *                     2^31 - 1 reads and CIGAR ops, 2^29 I and D ops in the kept reads, no CIGAR op of length 0.  hash_mask 0 counts
+ *                     as all ones.  The result stays in the context
+ *                     (matrix, major, candidate positions and depths on the device) until the next call
+ *   c3_pileup_reads_host   the same rule as sequential host C; the result is held by the context on the host
+ *   c3_pileup_sizes   of the held result: columns, candidates, sites of the count pair (end - start, or 0 without gvcf), bytes of text
+ *   c3_pileup_result  copies the held result out; a null pointer skips that array.  matrix (n_cols, 18) int32, major (n_cols), candidate
+ *                     positions (0-based) and depths (n_cand), n_ref / n_total (n_sites, indexed by p - start, 0 where no column exists), and
+ *                     the alt-info text: one line per candidate, each closed by '\n', no terminating NUL
+ *   c3_pileup_stats   of the last call.  fell_back: the device call found two different events under one key and answered through the host form */
+typedef struct c3_read_set {
+    int64_t n_reads;
+    const int64_t *pos;          /* [n] 0-based leftmost reference position */
+    const uint16_t *flag;        /* [n] */
+    const uint8_t *mapq;         /* [n] */
+    const int64_t *cigar_first;  /* [n + 1] offsets into cigar */
+    const uint32_t *cigar;       /* len << 4 | op, ops 0 .. 8 = MIDNSHP=X */
+    const int64_t *seq_first;    /* [n + 1] byte offsets into seq */
+    const uint8_t *seq;          /* 4-bit nt16 codes, two per byte, high nibble first, each read starting on a byte */
+} c3_read_set;
+typedef struct c3_pileup_config {
+    int64_t min_depth;
+    float min_snp_af, min_indel_af;
+    int32_t min_mq, max_indel_length;
+    int32_t call_snp_only, gvcf, call_ht, reserved;
+    uint64_t hash_mask;
+} c3_pileup_config;
+typedef struct c3_pileup_counters {
+    int64_t reads_kept, reads_dropped, events, collisions;
+    int32_t fell_back, on_host;  /* on_host: the held result is the host form's (asked for, or fallen back to) */
+    float kernel_ms[8];          /* device calls: op table, walk, indel table, reduce, site, compaction, staging in, fetch of the records */
+} c3_pileup_counters;
+typedef struct c3_pileup c3_pileup;
+c3_pileup *c3_pileup_create(int device);
+int c3_pileup_destroy(c3_pileup *p);
+int c3_pileup_reads(c3_pileup *p, const c3_read_set *reads, int64_t start, int64_t end, const void *ref_bytes, int64_t ref_first, int64_t ref_len,
+                    const c3_pileup_config *cfg);
+int c3_pileup_reads_host(c3_pileup *p, const c3_read_set *reads, int64_t start, int64_t end, const void *ref_bytes, int64_t ref_first,
+                         int64_t ref_len, const c3_pileup_config *cfg);
+int c3_pileup_sizes(c3_pileup *p, int64_t *n_cols, int64_t *n_cand, int64_t *n_sites, int64_t *text_bytes);
+int c3_pileup_result(c3_pileup *p, int32_t *matrix, int64_t *major, int64_t *cand_pos, int32_t *cand_depth, int64_t *n_ref, int64_t *n_total,
+                     char *text);
+int c3_pileup_stats(c3_pileup *p, c3_pileup_counters *out);
+/* The held result as a candidate batch of the ring: what c3_predict_submit_candidates / c3_predict_pileup_candidates compute from the arrays
+ * c3_pileup_result returns (with the candidates' depths), rows, statuses and n_rows bit for bit, without the region matrix visiting the host:
+ * it is copied from the context's device buffer into the slot on the lane's stream.  Context and model must be on one device.  A held
+ * result of the host form (asked for, or fallen back to) is staged from the host like any other.  The submit fetches nothing from the
+ * device.  The context's next c3_pileup_reads waits for the copy of the matrix, not for the batch; c3_predict_wait(m, slot) completes the
+ * batch as usual. */
+int c3_predict_submit_pileup(c3_model *m, c3_pileup *p, int head_tail, float *y_host, uint8_t *status_host, int64_t *n_rows_host, int slot);
+int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_host, uint8_t *status_host, int64_t *n_rows_host);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
