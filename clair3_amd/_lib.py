@@ -45,6 +45,8 @@ EXPORTS = (
     "c3_gvcf_blocks_region", "c3_gvcf_text", "c3_gvcf_tile_sites", "c3_gvcf_top_span", "c3_gvcf_table_depth",
     "c3_pileup_create", "c3_pileup_destroy", "c3_pileup_reads", "c3_pileup_reads_host", "c3_pileup_sizes", "c3_pileup_result", "c3_pileup_stats",
     "c3_predict_submit_pileup", "c3_predict_pileup_reads",
+    "c3_fa_reads_create", "c3_fa_reads_destroy", "c3_fa_reads", "c3_fa_reads_host", "c3_fa_reads_sizes", "c3_fa_reads_result", "c3_fa_reads_stats",
+    "c3_predict_submit_fa_reads", "c3_predict_fa_reads",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -199,6 +201,22 @@ class PileupConfig(C.Structure):
     _fields_ = [("min_depth", C.c_int64), ("min_snp_af", C.c_float), ("min_indel_af", C.c_float), ("min_mq", C.c_int32),
                 ("max_indel_length", C.c_int32), ("call_snp_only", C.c_int32), ("gvcf", C.c_int32), ("call_ht", C.c_int32), ("reserved", C.c_int32),
                 ("hash_mask", C.c_uint64)]
+
+
+class ReadExtrasC(C.Structure):
+    """c3_read_extras (include/c3hip.h)"""
+    _fields_ = [("qual_first", C.c_void_p), ("qual", C.c_void_p), ("haplotype", C.c_void_p), ("name_key", C.c_void_p)]
+
+
+class FaConfig(C.Structure):
+    """c3_fa_config (include/c3hip.h)"""
+    _fields_ = [("min_mq", C.c_int32), ("max_indel_length", C.c_int32), ("matrix_depth", C.c_int32), ("lds_reads", C.c_int32), ("seed", C.c_uint64)]
+
+
+class FaCounters(C.Structure):
+    """c3_fa_counters (include/c3hip.h)"""
+    _fields_ = [("reads_kept", C.c_int64), ("reads_dropped", C.c_int64), ("rows", C.c_int64), ("deep_windows", C.c_int64),
+                ("fell_back", C.c_int32), ("on_host", C.c_int32), ("kernel_ms", C.c_float * 8)]
 
 
 class PileupCounters(C.Structure):
@@ -376,6 +394,17 @@ def lib():
     L.c3_pileup_stats.argtypes = [C.c_void_p, C.POINTER(PileupCounters)]
     L.c3_predict_submit_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
     L.c3_predict_pileup_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    L.c3_fa_reads_create.restype = C.c_void_p
+    L.c3_fa_reads_create.argtypes = [C.c_int]
+    L.c3_fa_reads_destroy.argtypes = [C.c_void_p]
+    for fn in (L.c3_fa_reads, L.c3_fa_reads_host):
+        fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.POINTER(ReadExtrasC), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                       C.POINTER(FaConfig)]
+    L.c3_fa_reads_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3 + [C.POINTER(C.c_int32)]
+    L.c3_fa_reads_result.argtypes = [C.c_void_p] * 5
+    L.c3_fa_reads_stats.argtypes = [C.c_void_p, C.POINTER(FaCounters)]
+    L.c3_predict_submit_fa_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+    L.c3_predict_fa_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -182,6 +182,10 @@ struct RingInput {
     const CandInput *cand = nullptr;                            // Candidates
     const int32_t *row_first = nullptr, *row_count = nullptr;  // Rows
     int64_t rows_total = 0;
+    // Rows whose bytes already lie on this device (c3_predict_submit_fa_reads, c3_fa_reads.h): nothing of them is staged, they reach the slot
+    // by one device-to-device copy on the lane's stream behind dev_ready; dev_taken is recorded behind that copy (their owner may overwrite)
+    const void *dev_rows = nullptr;
+    hipEvent_t dev_ready = nullptr, dev_taken = nullptr;
     const void *const *parts = nullptr;  // Parts
     const int64_t *counts = nullptr;
     float *const *y_parts = nullptr;
@@ -369,7 +373,9 @@ static void fill_rows(const c3_model *m, const HostSlot &sl, const RingInput &in
         tab[b] = ExpandEntry{o, in.row_first ? table_i32(in.row_first, b) : (m->depth - c) / 2, c};
         o += (int64_t)c * row_bytes;
     }
-    f.src = in.x, f.rows_shipped = in.rows_total;
+    f.rows_shipped = in.rows_total;
+    if (in.dev_rows) f.no_image = true;  // (queue_device_rows brings the rows in)
+    else f.src = in.x;
 }
 // rows packed here: the scan of c3_pack_rows writes every window's run straight into the pinned buffer, split over the staging pool by window
 // ranges: range k packs back to back from where its first window would start in the dense layout (an 8-byte boundary for an even C), so no
@@ -454,6 +460,16 @@ static int queue_device_image(c3_model *m, const HostSlot &sl, const RingInput &
         HIP_TRY(hipMemsetAsync((char *)sl.dev_x + (c0 + n) * colb, 0, pad * colb, s));
     }
     if (ci.dev_taken) HIP_TRY(hipEventRecord(ci.dev_taken, s));
+    return 0;
+}
+
+// a rows batch whose rows are on the device already: the image of fill_rows by one copy between device buffers.  Queued behind queue_input
+// on the lane's stream (which brings in the row table only: Filled::no_image)
+static int queue_device_rows(c3_model *m, const HostSlot &sl, const RingInput &in, const StagedBatch &p) {
+    hipStream_t s = lane(m).stream;
+    if (in.dev_ready) HIP_TRY(hipStreamWaitEvent(s, in.dev_ready, 0));
+    if (p.image.bytes) HIP_TRY(hipMemcpyAsync(sl.dev_x, in.dev_rows, p.image.bytes, hipMemcpyDeviceToDevice, s));
+    if (in.dev_taken) HIP_TRY(hipEventRecord(in.dev_taken, s));
     return 0;
 }
 
@@ -864,6 +880,7 @@ static int predict_submit(c3_model *m, RingInput in, int slot) {
         }
         TRY(queue_input(m, sl, p, f, alone, in_lane));
         if (in.cand && in.cand->dev_image) TRY(queue_device_image(m, sl, in, p));
+        if (in.dev_rows) TRY(queue_device_rows(m, sl, in, p));
         if (launch_batch(m, sl, in, p) != 0) {
             // refused behind its input: the slot stays free, so the next submit may stage into it at once, in ANOTHER lane's stream -- the
             // transfers queued above must have landed before that (the error message is the launch's)

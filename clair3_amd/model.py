@@ -1266,6 +1266,17 @@ class Clair3_F(_RingVerify):
                                               len(counts), y.ctypes.data), "c3_predict_rows")
         return y
 
+    def predict_reads(self, context):
+        """predict_rows on the result a fa_reads.Context holds (context.run(reads, extras, centres, ...) first): the rows go from the
+        context's device buffer into the batch without visiting the host (c3_predict_fa_reads).  Returns the probability rows, one per
+        candidate, bit for bit predict_rows(rows, counts) of context.fetch().  The handle's depth must be the result's matrix_depth."""
+        if self._handle is None:
+            raise _lib.C3Error("model has no device/weights yet: call .to(device) and .load_state_dict() first")
+        y = np.empty((context.sizes()[0], self.row_size), dtype=np.float32)
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().c3_predict_fa_reads(self._handle, context.h, y.ctypes.data if y.size else None, C.byref(n)), "c3_predict_fa_reads")
+        return y
+
     # ---- jackknife mode: does a call survive when one read of its window is taken away? (c3_jackknife_rows; DESIGN.md 4) ----
     def _jackknife_out(self, counts, y, rec, drops, variant_rows, info):
         out = dict(rows=rec, counts=counts, base_rows=y, on_fp32=bool(info.on_fp32), passes=int(info.passes), bytes_staged=int(info.bytes_staged),

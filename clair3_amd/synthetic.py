@@ -1225,3 +1225,64 @@ def tile_read_set(rs, copies):
         out[name] = np.concatenate([rs[name][:-1] + k * len(rs[data]) for k in range(copies)] + [np.array([copies * len(rs[data])], np.int64)])
     out["end"], out["ref_bytes"] = rs["start"] + copies * n_sites, ref
     return out
+
+
+# ---- full alignment from reads: what a window needs beyond the read set (c3_read_extras, include/c3hip.h)
+FA_DROP_FLAGS = 2316  # SAMTOOLS_VIEW_FILTER_FLAG, src/clair3_full_alignment_dwell.h:27
+
+
+def sort_read_set(rs):
+    """The read set in coordinate order (stable), as full alignment from reads wants it: make_read_set's reads are in none.  Returns a new
+    dict; keys that are no read arrays are passed on."""
+    order = np.argsort(rs["pos"], kind="stable")
+    out = dict(rs)
+    for name in ("pos", "flag", "mapq"):
+        out[name] = rs[name][order]
+    for first, data in (("cigar_first", "cigar"), ("seq_first", "seq")):
+        pieces = [rs[data][rs[first][r]:rs[first][r + 1]] for r in order]
+        out[data] = np.concatenate(pieces) if pieces else rs[data][:0]
+        out[first] = np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.int64)
+    return out
+
+
+def query_lengths(rs):
+    """(n,) int64: the query bases every read's CIGAR consumes (M, I, S, =, X)"""
+    op, ln = rs["cigar"] & 15, (rs["cigar"] >> 4).astype(np.int64)
+    consumed = np.where(np.isin(op, (0, 1, 4, 7, 8)), ln, 0)
+    total = np.concatenate([[0], np.cumsum(consumed)])
+    return total[rs["cigar_first"][1:]] - total[rs["cigar_first"][:-1]]
+
+
+def make_read_extras(rs, seed, phased=0.6, duplicate_names=0.0):
+    """Qualities, haplotypes and name keys for the reads of ``rs`` (make_read_set / pack_reads, in the order they have there), as a dict:
+    qual_first, qual (one byte per query base, 0 .. 59), haplotype (0 with probability 1 - phased, else 1 or 2) and name_key (uint64; a
+    share ``duplicate_names`` of the reads repeats the key of an earlier read).  ``rs`` is not changed."""
+    rng = np.random.default_rng(seed)
+    n = len(rs["pos"])
+    qlen = query_lengths(rs)
+    qual_first = np.concatenate([[0], np.cumsum(qlen)]).astype(np.int64)
+    qual = rng.integers(0, 60, size=int(qual_first[-1])).astype(np.uint8)
+    hap = np.where(rng.random(n) < phased, rng.integers(1, 3, size=n), 0).astype(np.uint8)
+    key = rng.integers(1, 1 << 62, size=n).astype(np.uint64)
+    for r in np.flatnonzero(rng.random(n) < duplicate_names):
+        if r > 0:
+            key[r] = key[int(rng.integers(0, r))]
+    return {"qual_first": qual_first, "qual": qual, "haplotype": hap, "name_key": key}
+
+
+def sort_read_extras(rs, extras):
+    """``extras`` of the unsorted ``rs`` put into the order sort_read_set(rs) gives the reads"""
+    order = np.argsort(rs["pos"], kind="stable")
+    pieces = [extras["qual"][extras["qual_first"][r]:extras["qual_first"][r + 1]] for r in order]
+    return {"qual_first": np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.int64),
+            "qual": np.concatenate(pieces) if pieces else extras["qual"][:0], "haplotype": extras["haplotype"][order],
+            "name_key": extras["name_key"][order]}
+
+
+def fa_keys(seed, centre, reads):
+    """(n,) uint64: fa_key(seed, centre, read) of csrc/c3_fa_rule.h for the read indices ``reads`` -- the counter hash of subsample mode, the
+    selection being subsample_rank(keys, matrix_depth)"""
+    g = np.uint64(0x9E3779B97F4A7C15)
+    with np.errstate(over="ignore"):
+        inner = subsample_mix(np.uint64(int(seed) & _M64) + g * np.uint64((1 + int(centre)) & _M64))
+        return subsample_mix(inner + g * (np.uint64(1) + np.asarray(reads, dtype=np.uint64)))

@@ -1138,6 +1138,65 @@ int c3_pileup_stats(c3_pileup *p, c3_pileup_counters *out);
 int c3_predict_submit_pileup(c3_model *m, c3_pileup *p, int head_tail, float *y_host, uint8_t *status_host, int64_t *n_rows_host, int slot);
 int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_host, uint8_t *status_host, int64_t *n_rows_host);
 
+/* ---- full alignment from reads: the candidate windows of calculate_clair3_full_alignment (src/clair3_full_alignment_dwell.c:437-1054) from
+ * aligned reads, as each window's occupied rows and a row count: what c3_predict_submit_rows with row_first == NULL takes (the dense window is
+ * the run placed at (matrix_depth - count) / 2).  The rule clause by clause, every place where it deliberately leaves the reference, and the
+ * kernels: csrc/c3_fa_rule.h, csrc/c3_fa_reads.h.  Limits: no BAM file is read; haplotypes are an INPUT (haplotag_read with its Levenshtein
+ * realignment is not built); 8 channels only (no dwell channel); measured on synthetic reads only.
+ *
+ *   c3_read_extras    what a window needs beyond c3_read_set: one quality byte per query base (bam_get_qual; read r owns
+ *                     qual[qual_first[r] .. qual_first[r + 1]), at least as many as its CIGAR consumes), the HP tag (0 unphased, 1, 2) and,
+ *                     optionally, a 64-bit key of the read name for the duplicate-name filter (first occurrence wins; NULL: no filter)
+ *   c3_fa_config      min_mq, max_indel_length (of the alt-info text), matrix_depth (89 or 55), seed (of the selection in windows with more
+ *                     reads than matrix_depth), lds_reads: reads overlapping one candidate the device form handles (0: the kernel's table,
+ *                     1024; a smaller value lowers it so that the fallback to the host form can be exercised)
+ *   c3_fa_reads       centres: 0-based candidate positions, strictly ascending, each >= 16.  Reads must be in coordinate order.  ref_bytes[i]
+ *                     is the reference at ref_first + i and must cover [centres[0] - 16, centres[last] + 16 + max_indel_length].  Returns 0;
+ *                     C3_FA_ERR_REFSKIP when a kept read has an N op over a flanking position of a candidate; 1 for every other refusal; all
+ *                     before anything is queued.  The result stays in the context (after a device call: rows, counts and centre depths on the
+ *                     device) until the next call
+ *   c3_fa_reads_host  the same rule as sequential host C; works in a context created with device < 0
+ *   c3_fa_reads_sizes of the held result: candidates, rows (the sum of the counts), bytes of text, matrix_depth
+ *   c3_fa_reads_result   copies the held result out; a null pointer skips that array.  rows (n_rows, 33, 8) int8, counts (n_cand) int32, centre
+ *                     depths (n_cand) int32 (every kept read at the centre, not only the shown ones), the alt-info text: one line per candidate,
+ *                     closed by '\n', no terminating NUL, entries in the order of c3_pileup_result's text (X, D by length, I by length then
+ *                     bytes, R)
+ *   c3_fa_reads_stats of the last call.  fell_back: a candidate had more overlapping reads than lds_reads and the host form answered */
+#define C3_FA_ERR_REFSKIP 2
+typedef struct c3_read_extras {
+    const int64_t *qual_first;   /* [n + 1] offsets into qual */
+    const uint8_t *qual;
+    const uint8_t *haplotype;    /* [n] 0, 1, 2 */
+    const uint64_t *name_key;    /* [n] or NULL */
+} c3_read_extras;
+typedef struct c3_fa_config {
+    int32_t min_mq, max_indel_length, matrix_depth, lds_reads;
+    uint64_t seed;
+} c3_fa_config;
+typedef struct c3_fa_counters {
+    int64_t reads_kept, reads_dropped, rows, deep_windows;  /* reads_dropped: by flag, mapq or name; deep_windows: more reads than matrix_depth */
+    int32_t fell_back, on_host;
+    float kernel_ms[8];  /* device calls: staging in, op table, candidates, scan, fill, fetch of the records; two unused */
+} c3_fa_counters;
+typedef struct c3_fa_reads_ctx c3_fa_reads_ctx;
+c3_fa_reads_ctx *c3_fa_reads_create(int device);
+int c3_fa_reads_destroy(c3_fa_reads_ctx *g);
+int c3_fa_reads(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const int64_t *centres, int64_t n_cand,
+                const void *ref_bytes, int64_t ref_first, int64_t ref_len, const c3_fa_config *cfg);
+int c3_fa_reads_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const int64_t *centres, int64_t n_cand,
+                     const void *ref_bytes, int64_t ref_first, int64_t ref_len, const c3_fa_config *cfg);
+int c3_fa_reads_sizes(c3_fa_reads_ctx *g, int64_t *n_cand, int64_t *n_rows, int64_t *text_bytes, int32_t *matrix_depth);
+int c3_fa_reads_result(c3_fa_reads_ctx *g, void *rows, int32_t *counts, int32_t *depths, char *text);
+int c3_fa_reads_stats(c3_fa_reads_ctx *g, c3_fa_counters *out);
+/* The held result as a rows batch of the ring: what c3_predict_submit_rows / c3_predict_rows compute from the rows and counts
+ * c3_fa_reads_result returns (row_first == NULL), bit for bit, without the rows visiting the host: they are copied from the context's device
+ * buffer into the slot on the lane's stream; the counts (which the call fetched anyway) make the slot's row table on the host.  n_rows_host
+ * (may be NULL) receives the number of windows.  Context and model must be on one device; a held result of the host form is staged from
+ * the host.  Refused before anything is queued: a pileup handle, a 9-channel handle, a handle whose depth is not the result's
+ * matrix_depth.  The context's next c3_fa_reads waits for the copy, not for the batch; c3_predict_wait(m, slot) completes the batch. */
+int c3_predict_submit_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host, int slot);
+int c3_predict_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host);
+
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
 int c3_profile_enable(c3_model *m, int enable);
