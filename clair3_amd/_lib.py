@@ -44,8 +44,10 @@ EXPORTS = (
     "c3_gvcf_site", "c3_gvcf_site_table", "c3_gvcf_blocks_host", "c3_gvcf_create", "c3_gvcf_destroy", "c3_gvcf_blocks_counts",
     "c3_gvcf_blocks_region", "c3_gvcf_text", "c3_gvcf_tile_sites", "c3_gvcf_top_span", "c3_gvcf_table_depth",
     "c3_pileup_create", "c3_pileup_destroy", "c3_pileup_reads", "c3_pileup_reads_host", "c3_pileup_sizes", "c3_pileup_result", "c3_pileup_stats",
+    "c3_pileup_tile_sites",
     "c3_predict_submit_pileup", "c3_predict_pileup_reads",
     "c3_fa_reads_create", "c3_fa_reads_destroy", "c3_fa_reads", "c3_fa_reads_host", "c3_fa_reads_sizes", "c3_fa_reads_result", "c3_fa_reads_stats",
+    "c3_fa_lds_reads",
     "c3_predict_submit_fa_reads", "c3_predict_fa_reads",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)

@@ -425,6 +425,8 @@ int c3_fa_reads_stats(c3_fa_reads_ctx *g, c3_fa_counters *out) {
     return 0;
 }
 
+int c3_fa_lds_reads(void) { return c3::kFaLdsReads; }
+
 // ---- the chained entry: the held rows as a rows batch of the ring (c3_hostring.h).  The rows go from the context's buffer to the slot by one
 // device-to-device copy on the lane's stream; the slot's row table is made on the host from the counts, which came back with the call.  From
 // there on the batch is a batch of c3_predict_submit_rows (row_first == NULL).  A held result of the host form goes through that entry itself

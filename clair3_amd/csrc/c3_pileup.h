@@ -730,4 +730,6 @@ int c3_pileup_stats(c3_pileup *g, c3_pileup_counters *out) {
     return 0;
 }
 
+int c3_pileup_tile_sites(void) { return c3::kPileupTile; }
+
 }  // extern "C"

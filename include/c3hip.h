@@ -1095,7 +1095,8 @@ int c3_gvcf_table_depth(void);
  *   c3_pileup_result  copies the held result out; a null pointer skips that array.  matrix (n_cols, 18) int32, major (n_cols), candidate
  *                     positions (0-based) and depths (n_cand), n_ref / n_total (n_sites, indexed by p - start, 0 where no column exists), and
  *                     the alt-info text: one line per candidate, each closed by '\n', no terminating NUL
- *   c3_pileup_stats   of the last call.  fell_back: the device call found two different events under one key and answered through the host form */
+ *   c3_pileup_stats   of the last call.  fell_back: the device call found two different events under one key and answered through the host form
+ *   c3_pileup_tile_sites   a constant of the device path, for tests: sites per compaction tile, which is also the tiles one step of the scan holds */
 typedef struct c3_read_set {
     int64_t n_reads;
     const int64_t *pos;          /* [n] 0-based leftmost reference position */
@@ -1129,6 +1130,7 @@ int c3_pileup_sizes(c3_pileup *p, int64_t *n_cols, int64_t *n_cand, int64_t *n_s
 int c3_pileup_result(c3_pileup *p, int32_t *matrix, int64_t *major, int64_t *cand_pos, int32_t *cand_depth, int64_t *n_ref, int64_t *n_total,
                      char *text);
 int c3_pileup_stats(c3_pileup *p, c3_pileup_counters *out);
+int c3_pileup_tile_sites(void);
 /* The held result as a candidate batch of the ring: what c3_predict_submit_candidates / c3_predict_pileup_candidates compute from the arrays
  * c3_pileup_result returns (with the candidates' depths), rows, statuses and n_rows bit for bit, without the region matrix visiting the host:
  * it is copied from the context's device buffer into the slot on the lane's stream.  Context and model must be on one device.  A held
@@ -1161,7 +1163,8 @@ int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_h
  *                     depths (n_cand) int32 (every kept read at the centre, not only the shown ones), the alt-info text: one line per candidate,
  *                     closed by '\n', no terminating NUL, entries in the order of c3_pileup_result's text (X, D by length, I by length then
  *                     bytes, R)
- *   c3_fa_reads_stats of the last call.  fell_back: a candidate had more overlapping reads than lds_reads and the host form answered */
+ *   c3_fa_reads_stats of the last call.  fell_back: a candidate had more overlapping reads than lds_reads and the host form answered
+ *   c3_fa_lds_reads   a constant of the device path, for tests: the reads the candidate kernel's table holds (what lds_reads == 0 stands for) */
 #define C3_FA_ERR_REFSKIP 2
 typedef struct c3_read_extras {
     const int64_t *qual_first;   /* [n + 1] offsets into qual */
@@ -1188,6 +1191,7 @@ int c3_fa_reads_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read
 int c3_fa_reads_sizes(c3_fa_reads_ctx *g, int64_t *n_cand, int64_t *n_rows, int64_t *text_bytes, int32_t *matrix_depth);
 int c3_fa_reads_result(c3_fa_reads_ctx *g, void *rows, int32_t *counts, int32_t *depths, char *text);
 int c3_fa_reads_stats(c3_fa_reads_ctx *g, c3_fa_counters *out);
+int c3_fa_lds_reads(void);
 /* The held result as a rows batch of the ring: what c3_predict_submit_rows / c3_predict_rows compute from the rows and counts
  * c3_fa_reads_result returns (row_first == NULL), bit for bit, without the rows visiting the host: they are copied from the context's device
  * buffer into the slot on the lane's stream; the counts (which the call fetched anyway) make the slot's row table on the host.  n_rows_host

@@ -21,6 +21,73 @@ def read_ops(rs, r):
     return [(int(c) & 15, int(c) >> 4) for c in rs["cigar"][int(rs["cigar_first"][r]):int(rs["cigar_first"][r + 1])]]
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix(x):  # pileup_mix of csrc/c3_pileup.h: the finaliser of splitmix64
+    x ^= x >> 30
+    x = x * 0xbf58476d1ce4e5b9 & _M64
+    x ^= x >> 27
+    x = x * 0x94d049bb133111eb & _M64
+    return x ^ x >> 31
+
+
+def event_slots(rs, start, end, min_mq=5, hash_mask=_M64):
+    """The device's event table restated in Python integers (pileup_walk_kernel of csrc/c3_pileup.h): the table's size from the I and D
+    ops of the kept reads, and per distinct event its key, the slot its probe starts at and the slot linear probing gives it.  The set of
+    occupied slots under linear probing does not depend on the order of insertion; which key sits where does, so ``wrapped`` is stated on
+    what does not: more probes start at or behind some slot s than the table has slots from s to its last one -- whatever the order, one
+    of them steps from the last slot to slot 0.
+    Returns dict(cap, events, keys {event: key}, first {event: slot}, occupied, wrapped); an event is (column, reverse, is insertion, length, codes)"""
+    indel_ops, events = 0, {}
+    for r in range(len(rs["pos"])):
+        if int(rs["flag"][r]) & DROP or int(rs["mapq"][r]) < min_mq:
+            continue
+        rev = 1 if int(rs["flag"][r]) & 16 else 0
+        codes, ops = read_codes(rs, r), read_ops(rs, r)
+        p, q = int(rs["pos"][r]), 0
+        for k, (op, n) in enumerate(ops):
+            if op in (1, 2):
+                indel_ops += 1
+                j = k - 1
+                while j >= 0 and ops[j][0] == 6:
+                    j -= 1
+                if j >= 0 and ops[j][0] in (0, 7, 8, 2) and start <= p - 1 < end:
+                    total = n
+                    if op == 1:
+                        for o2, n2 in ops[k + 1:]:
+                            if o2 != 1:
+                                break
+                            total += n2
+                    ev = (p - 1 - start, rev, int(op == 1), total, tuple(int(x) for x in codes[q:q + total]) if op == 1 else ())
+                    events[ev] = events.get(ev, 0) + 1
+            if op in (0, 7, 8, 2, 3):
+                p += n
+            if op in (0, 7, 8, 1, 4):
+                q += n
+    cap = 64
+    while cap < 2 * indel_ops:
+        cap <<= 1
+    keys, first = {}, {}
+    for ev in events:
+        col, rev, ins, total, bases = ev
+        h = 0
+        for code in bases:
+            h = ((h ^ code) * 0x100000001b3 + 0x9e3779b97f4a7c15) & _M64
+        ident = col | rev << 40 | ins << 41
+        keys[ev] = (_mix(ident) ^ _mix((h + total * 0xd6e8feb86659fd93) & _M64)) & hash_mask & ~(1 << 63)
+        first[ev] = (_mix(keys[ev] ^ 0x2545f4914f6cdd1d) & 0xffffffff) & (cap - 1)
+    occupied = set()
+    for key in sorted(set(keys.values())):  # (any order gives the same set)
+        s = first[next(ev for ev in keys if keys[ev] == key)]
+        while s in occupied:
+            s = (s + 1) & (cap - 1)
+        occupied.add(s)
+    starts = [first[next(ev for ev in keys if keys[ev] == key)] for key in set(keys.values())]
+    wrapped = any(sum(t >= s for t in starts) > cap - s for s in starts)
+    return {"cap": cap, "events": events, "keys": keys, "first": first, "occupied": occupied, "wrapped": wrapped}
+
+
 def pileup(rs, start, end, ref_bytes, ref_first, min_depth=0, min_snp_af=0.0, min_indel_af=0.0, min_mq=5, max_indel_length=50,
            call_snp_only=False, gvcf=True, call_ht=False):
     ref = bytes(bytearray(ref_bytes))

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from clair3_amd import _lib, fa_reads as fa, synthetic as syn
-from tests.fa_cases import alt_counts, by_hand, generated, golden_sets
+from tests.fa_cases import (FA_DROP_BITS, FILL_LEVELS, INDEL_CENTRE, LDS, MANY, RAGGED, STEP, alt_counts, by_hand, check_fill, check_indel_rows,
+                            fill_centres, generated, golden_sets, indel_column, many_candidates, read_range, table_fill, window_numbers)
 from tests.fa_mirror import fa_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -197,6 +198,118 @@ def test_refusals(ctx):
         ctx.run(good, gex, [110], good["ref_bytes"], 0, path="device")
     # a refused call leaves no stale result behind
     assert ctx.sizes()[:2] == (0, 0)
+
+
+# ---- the read sets the device tests take to the kernels' capacity edges (tests/test_fa_reads_gpu.py): here the host form against the mirror
+# on each of them, and what each set is built to hold
+def assert_mirror(r, rs, ex, centres, **cfg):
+    rows, counts, depths, lines = fa_mirror(rs, ex, centres, rs["ref_bytes"], rs["ref_first"], **cfg)
+    assert np.array_equal(r["counts"], counts) and np.array_equal(r["depths"], depths)
+    assert r["rows"].shape == rows.shape and np.array_equal(r["rows"], rows)
+    assert lines_of(r) == lines
+
+
+@pytest.mark.parametrize("n_over", FILL_LEVELS + (LDS + 1, 88, 89, 90, 300))
+def test_table_fill_levels(ctx, n_over):
+    rs, ex, info = table_fill((n_over,))
+    c = info["centres"][0]
+    lo, hi = read_range(info, c)
+    over, at, n_alt = window_numbers(info, c)
+    assert over == n_over and 0 < n_alt < at < over and (lo, hi) == (0, len(rs["pos"]))
+    assert hi - lo >= 5 * STEP or n_over < LDS - 1
+    # no step of the compaction has a full ballot; in the range sit a read of each dropped flag bit, of a low mapq, and kept short reads in
+    # front of the window, some of them kept in the rule's own sense: inside the window of c - 56
+    taken = info["kept"] & (info["end"] > c - 16)
+    assert all(not taken[b:b + STEP].all() for b in range(lo, hi, STEP))
+    if n_over >= STEP - 1:
+        assert all((rs["flag"] & bit).any() for bit in FA_DROP_BITS) and (rs["mapq"] < 5).any()
+        assert (info["kept"] & (info["end"] <= c - 16) & (info["end"] > c - 56 - 16)).any()
+    assert set(ex["haplotype"][taken].tolist()) == {0, 1, 2} and set((rs["flag"][taken] & 16).tolist()) == {0, 16}
+    centres = fill_centres(info)
+    for depth in (89, 128, 1) if n_over == 300 else (89, 128):
+        r = run(ctx, rs, ex, centres, matrix_depth=depth, seed=depth)
+        check_fill(r, ctx.stats(), info, depth)
+        assert r["counts"][1] == min(n_over, depth) and r["depths"][1] == at
+        assert_mirror(r, rs, ex, centres, matrix_depth=depth, seed=depth)
+    if n_over in (88, 89, 90):  # the boundary of the selection: the window of c alone
+        r = run(ctx, rs, ex, [c], matrix_depth=89)
+        assert r["counts"].tolist() == [min(n_over, 89)] and ctx.stats()["deep_windows"] == (1 if n_over == 90 else 0)
+
+
+def test_two_table_fill_levels_in_one_call(ctx):
+    rs, ex, info = table_fill((LDS, 300))
+    centres = fill_centres(info)
+    assert [window_numbers(info, c)[0] for c in info["centres"]] == [LDS, 300]
+    spans = [read_range(info, c) for c in info["centres"]]
+    assert spans[0][1] == spans[1][0] and (spans[0][1] - spans[0][0]) // STEP > (spans[1][1] - spans[1][0]) // STEP
+    r = run(ctx, rs, ex, centres, matrix_depth=89)
+    check_fill(r, ctx.stats(), info, 89)
+    assert_mirror(r, rs, ex, centres, matrix_depth=89)
+
+
+INDEL_CENTRES = [INDEL_CENTRE - 16, INDEL_CENTRE, INDEL_CENTRE + 16, INDEL_CENTRE + 17]
+
+
+def test_indel_column_across_the_256_boundary(ctx):
+    rs, ex, expected, kinds = indel_column(extras=False)
+    assert len(kinds) == 700 and lines_of(run(ctx, rs, ex, INDEL_CENTRES))[1] == "131-700-G-DT 100 DTA 100 IGG 100 IGGG 100 IGGT 100 RG 200 "
+    rs, ex, expected, kinds = indel_column()
+    # what the set is for: every kind of indel on both sides of read 256, the doubled ops only behind it, one string once and behind 512
+    for kind in (("I", "G"), ("I", "GG"), ("I", "GT"), ("D", 1), ("D", 2)):
+        at = [i for i, k in enumerate(kinds) if k == kind]
+        assert min(at) < STEP and sum(i >= STEP for i in at) > 50 and sum(i >= 2 * STEP for i in at) > 20
+    assert min(i for i, k in enumerate(kinds) if k and k[0] in ("II", "ID")) > STEP
+    once = [i for i, k in enumerate(kinds) if k == ("I", "TTT")]
+    assert len(once) == 1 and once[0] > 2 * STEP and expected[1]["IGTTT"] == 1
+    assert (rs["pos"] <= INDEL_CENTRE).all() and (np.diff(rs["pos"]) >= 0).all() and len(set(rs["pos"].tolist())) == 25
+    for depth in (89, 128, 1):
+        r = run(ctx, rs, ex, INDEL_CENTRES, matrix_depth=depth, seed=3)
+        assert alt_counts(lines_of(r)[1]) == expected and r["depths"][1] == len(kinds) == 708
+        assert_mirror(r, rs, ex, INDEL_CENTRES, matrix_depth=depth, seed=3)
+        n_ins, n_del = check_indel_rows(r, expected)
+        assert depth == 1 or (n_ins > 20 and n_del > 10)
+    # the column of the indels is the last column of the left window, the first of the right one, and outside the one behind it
+    r = run(ctx, rs, ex, INDEL_CENTRES, matrix_depth=128, seed=3)
+    first = np.concatenate([[0], np.cumsum(r["counts"])])
+    assert (r["rows"][first[0]:first[1], 32, 1] == -50).any() and (r["rows"][first[2]:first[3], 0, 1] == -100).any()
+    assert not (r["rows"][first[3]:first[4], :, 1] == -50).any()
+
+
+def test_more_candidates_than_two_scan_steps(ctx):
+    tile = _lib.lib().c3_pileup_tile_sites()  # (full alignment scans its row counts with pileup's kernel: a step holds this many candidates)
+    rs, ex, centres = many_candidates(*MANY[0], **MANY[1])
+    cfg = MANY[2]
+    n_over = run(ctx, rs, ex, centres, **dict(cfg, matrix_depth=128))["counts"]  # (no window of the set holds more than 128 reads)
+    r = run(ctx, rs, ex, centres, **cfg)
+    assert len(centres) > 2 * tile and len(r["counts"]) == len(centres) and (np.diff(centres) == 1).all() and n_over.max() < 128
+    assert (r["counts"][-10:] == 0).all() and 10 < (r["counts"] == 0).sum() < 100 and r["counts"][:tile + 1].min() > 0
+    # over-deep windows in each of the scan's three steps
+    assert ctx.stats()["deep_windows"] == (n_over > 24).sum() and all((n_over[a:a + tile] > 24).sum() > 50 for a in (0, tile, 2 * tile))
+    assert np.array_equal(r["counts"], np.minimum(n_over, 24))
+    # the mirror on a hundred centres across the step (it is quadratic): the windows of a candidate do not depend on the other candidates
+    lo, hi = tile - 50, tile + 50
+    first = np.concatenate([[0], np.cumsum(r["counts"])])
+    part = {"rows": r["rows"][first[lo]:first[hi]], "counts": r["counts"][lo:hi], "depths": r["depths"][lo:hi],
+            "text": "".join(x + "\n" for x in lines_of(r)[lo:hi]).encode()}
+    assert_mirror(part, rs, ex, centres[lo:hi], **cfg)
+    # the first candidates alone: the same rows
+    for n in (tile, tile + 1):
+        r2 = run(ctx, rs, ex, centres[:n], **cfg)
+        assert np.array_equal(r2["rows"], r["rows"][:first[n]]) and np.array_equal(r2["counts"], r["counts"][:n])
+
+
+def test_the_ragged_batch_holds_what_it_is_for(ctx):
+    tile = _lib.lib().c3_pileup_tile_sites()
+    rs, ex, centres = many_candidates(*RAGGED[0], **RAGGED[1])
+    r = run(ctx, rs, ex, centres, **RAGGED[2])
+    # above a full-alignment lane's 512 windows and above one scan step; empty windows, over-deep ones, no window over the table
+    assert len(centres) >= 1100 and len(centres) > tile and (r["counts"] == 0).sum() > 10 and ctx.stats()["deep_windows"] > 100
+    assert r["counts"].max() == 55 and (r["counts"] < 55).sum() > 100 and r["depths"].max() < LDS // 4
+    lo, hi = tile - 20, tile + 20
+    first = np.concatenate([[0], np.cumsum(r["counts"])])
+    part = {"rows": r["rows"][first[lo]:first[hi]], "counts": r["counts"][lo:hi], "depths": r["depths"][lo:hi],
+            "text": "".join(x + "\n" for x in lines_of(r)[lo:hi]).encode()}
+    assert_mirror(part, rs, ex, centres[lo:hi], **RAGGED[2])
 
 
 def _case_file(path, rs, ex, centres, cfg):

@@ -1,12 +1,17 @@
 """Full alignment from reads on the device (csrc/c3_fa_reads.h): c3_fa_reads against the host form bit for bit -- rows, counts, centre depths,
 alt-info text -- on the golden sets and on generated ones, the fallback over the lowered LDS cap, buffer reuse across calls, and the chained
-predict against c3_predict_rows on the fetched rows."""
+predict against c3_predict_rows on the fetched rows.  Behind those, the capacity edges: the candidate kernel's table at 255 .. 1024 reads and
+one read over it, indels counted across its 256-read steps, more candidates than two steps of the scan, matrix_depth 1 and 128, and chained
+batches above a ring lane's size with empty windows in them and behind a real fallback."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from clair3_amd import _lib, fa_reads as fa, synthetic as syn
 from clair3_amd.model import Clair3_F, Clair3_P
-from tests.fa_cases import by_hand, generated, golden_sets
+from tests.fa_cases import (FILL_LEVELS, INDEL_CENTRE, LDS, MANY, RAGGED, STEP, alt_counts, by_hand, check_fill, check_indel_rows, fill_centres,
+                            generated, golden_sets, indel_column, many_candidates, read_range, table_fill, window_numbers)
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +119,94 @@ def test_buffer_reuse(ctx, host_ctx):
         assert_same(got, want, f"step {step}")
 
 
+# ---- the capacity edges: the read sets of tests/fa_cases.py that tests/test_fa_reads.py holds to the mirror and to their construction
+@pytest.mark.parametrize("n_over", FILL_LEVELS)
+def test_table_fill_levels(ctx, host_ctx, n_over):
+    """exactly n_over reads in the candidate kernel's table, gathered over ragged 256-read steps: every table loop, the tally, the
+    (key, index) rank and the (haplotype, index) row at 255 .. 1024 reads, sel[] filled to 89 and to 128"""
+    rs, ex, info = table_fill((n_over,))
+    centres = fill_centres(info)
+    lo, hi = read_range(info, info["centres"][0])
+    assert window_numbers(info, info["centres"][0])[0] == n_over and (hi - lo >= 5 * STEP or n_over < LDS - 1)
+    for depth in (89, 128):
+        got, want = both(ctx, host_ctx, rs, ex, centres, matrix_depth=depth, seed=depth)
+        s = ctx.stats()
+        assert not s["fell_back"] and not s["on_host"]
+        assert_same(got, want, f"{n_over} reads, matrix_depth {depth}")
+        check_fill(got, s, info, depth)
+        assert got["counts"][1] == min(n_over, depth)
+
+
+def test_one_read_more_than_the_table_holds(ctx, host_ctx):
+    rs, ex, info = table_fill((LDS + 1,))
+    centres = fill_centres(info)
+    assert window_numbers(info, info["centres"][0])[0] == LDS + 1
+    got, want = both(ctx, host_ctx, rs, ex, centres)
+    s = ctx.stats()
+    assert s["fell_back"] and s["on_host"]
+    assert_same(got, want, "over the table")
+    check_fill(got, s, info, 89)
+    # the next call on the context, at the table's own size, answers on the device again
+    rs, ex, info = table_fill((LDS,))
+    got, want = both(ctx, host_ctx, rs, ex, fill_centres(info))
+    assert_same(got, want, "the table's size behind a fallback")
+    assert not ctx.stats()["fell_back"] and not ctx.stats()["on_host"]
+
+
+@pytest.mark.parametrize("n_over", (88, 89, 90))
+def test_boundary_of_deep_selection(ctx, host_ctx, n_over):
+    rs, ex, info = table_fill((n_over,))
+    got, want = both(ctx, host_ctx, rs, ex, info["centres"], matrix_depth=89)
+    assert_same(got, want)
+    s = ctx.stats()
+    assert got["counts"].tolist() == [min(n_over, 89)] and s["deep_windows"] == (1 if n_over == 90 else 0) and not s["fell_back"]
+
+
+def test_matrix_depth_1(ctx, host_ctx):
+    rs, ex, info = table_fill((300,))
+    got, want = both(ctx, host_ctx, rs, ex, fill_centres(info), matrix_depth=1, seed=4)
+    assert_same(got, want)
+    check_fill(got, ctx.stats(), info, 1)
+    assert got["counts"].tolist() == [1, 1] and ctx.stats()["deep_windows"] == 2 and not ctx.stats()["fell_back"]
+
+
+def test_neighbouring_candidates_of_different_trip_counts(ctx, host_ctx):
+    rs, ex, info = table_fill((LDS, 300))
+    centres = fill_centres(info)
+    assert [window_numbers(info, c)[0] for c in info["centres"]] == [LDS, 300]
+    for depth in (89, 128):
+        got, want = both(ctx, host_ctx, rs, ex, centres, matrix_depth=depth)
+        assert_same(got, want)
+        check_fill(got, ctx.stats(), info, depth)
+        assert not ctx.stats()["fell_back"]
+
+
+@pytest.mark.parametrize("depth", (89, 128, 1))
+def test_indels_counted_across_the_256_boundary(ctx, host_ctx, depth):
+    rs, ex, expected, kinds = indel_column()
+    centres = [INDEL_CENTRE - 16, INDEL_CENTRE, INDEL_CENTRE + 16, INDEL_CENTRE + 17]
+    got, want = both(ctx, host_ctx, rs, ex, centres, matrix_depth=depth, seed=3)
+    assert_same(got, want)
+    assert not ctx.stats()["fell_back"] and len(kinds) > 2 * STEP
+    assert alt_counts(got["text"].decode("ascii").split("\n")[1]) == expected and got["depths"][1] == len(kinds)
+    n_ins, n_del = check_indel_rows(got, expected)
+    assert depth == 1 or (n_ins > 20 and n_del > 10)
+
+
+def test_more_candidates_than_two_scan_steps(ctx, host_ctx):
+    """the scan's second and third step, its carry and the totals behind it: the first 1024 and 1025 candidates and all of them; equal
+    rows mean that every candidate's base offset is right"""
+    tile = _lib.lib().c3_pileup_tile_sites()
+    rs, ex, centres = many_candidates(*MANY[0], **MANY[1])
+    assert len(centres) > 2 * tile
+    for n in (tile, tile + 1, len(centres)):
+        got, want = both(ctx, host_ctx, rs, ex, centres[:n], **MANY[2])
+        assert_same(got, want, f"{n} candidates")
+        s = ctx.stats()
+        assert len(got["counts"]) == n and s["deep_windows"] > 50 and s["rows"] == len(want["rows"]) and not s["fell_back"]
+    assert (got["counts"] == 0).any() and (got["counts"][2 * tile:] == MANY[2]["matrix_depth"]).any()
+
+
 @pytest.fixture(scope="module")
 def models():
     out = {}
@@ -149,6 +242,42 @@ def test_chained_predict(ctx, models, depth):
     with fa.Context(0) as c2:
         c2.run(rs, ex, centres, rs["ref_bytes"], rs["ref_first"], path="host", matrix_depth=depth, seed=5)
         assert np.array_equal(m.predict_reads(c2).view(np.uint32), want.view(np.uint32))
+
+
+def test_chained_predict_large_and_ragged(ctx, models):
+    """more windows than a ring lane takes (512) and than one step of the scan, empty windows and over-deep ones among them: the rows go
+    from the context to the slot on the device"""
+    m = models[55]
+    tile = _lib.lib().c3_pileup_tile_sites()
+    rs, ex, centres = many_candidates(*RAGGED[0], **RAGGED[1])
+    r = ctx.run(rs, ex, centres, rs["ref_bytes"], rs["ref_first"], **RAGGED[2]).fetch()
+    s = ctx.stats()
+    assert not s["on_host"] and len(centres) >= 1100 and len(centres) > tile and s["deep_windows"] > 100
+    assert (r["counts"] == 0).sum() > 10 and (r["counts"] == 55).any() and ((r["counts"] > 0) & (r["counts"] < 55)).any()
+    want = m.predict_rows(r["rows"], r["counts"])
+    got = m.predict_reads(ctx)
+    assert got.shape == want.shape == (len(centres), m.row_size) and np.isfinite(got).all()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    # through submit and wait on a slot that is not 0
+    y, n = np.empty_like(want), C.c_int64(0)
+    _lib.check(_lib.lib().c3_predict_submit_fa_reads(m._handle, ctx.h, y.ctypes.data, C.byref(n), 2), "c3_predict_submit_fa_reads")
+    got2 = m.wait((2, y))
+    assert n.value == len(centres) and np.array_equal(got2.view(np.uint32), want.view(np.uint32))
+
+
+def test_chained_predict_behind_a_real_fallback(ctx, host_ctx, models):
+    """a window of one read more than the table holds: the device context is left with the host form's result, and the chained entry
+    stages that"""
+    m = models[55]
+    rs, ex, info = table_fill((LDS + 1,))
+    centres = fill_centres(info)
+    ctx.run(rs, ex, centres, rs["ref_bytes"], rs["ref_first"], matrix_depth=55, seed=6)
+    assert ctx.stats()["fell_back"] and ctx.stats()["on_host"]
+    r = host_ctx.run(rs, ex, centres, rs["ref_bytes"], rs["ref_first"], matrix_depth=55, seed=6).fetch()
+    assert r["counts"].tolist() == [55, 55]
+    want = m.predict_rows(r["rows"], r["counts"])
+    got = m.predict_reads(ctx)
+    assert np.isfinite(got).all() and np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 def test_chained_refusals(ctx, models):

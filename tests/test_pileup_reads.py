@@ -5,7 +5,8 @@ import pytest
 
 from clair3_amd import _lib, pileup_reads as pr, synthetic as syn
 from tests import pileup_mirror as pm
-from tests.pileup_cases import FIELDS, golden_sets
+from tests.pileup_cases import FIELDS, LONG_CIGARS, MANY_CANDIDATES, WRAP_SHIFT, big_region, distinct_events, golden_sets, insertion_column
+
 
 def host(rs, start=None, end=None, **cfg):
     return pr.pileup_counts(rs, rs["start"] if start is None else start, rs["end"] if end is None else end, rs["ref_bytes"], rs["ref_first"], path="host", **cfg)
@@ -39,6 +40,7 @@ MIRROR_CASES = {
     "plain": dict(n_sites=260, depth=24, read_len=(150, 400), seed=11),
     "odd": dict(n_sites=220, depth=20, read_len=(150, 400), seed=12, n_op=0.003, non_acgt=0.03, d_then_i=0.004, i_then_d=0.004, pad=0.2, eqx=True, gaps=2,
                 ref_other=0.03),
+    "long_cigars": LONG_CIGARS,  # reads of more than 64 and more than 128 ops: the op table's carry between its steps
 }
 MIRROR_CONFIGS = {
     "defaults": dict(),
@@ -89,6 +91,93 @@ def test_a_region_inside_the_reads_and_one_beside_them():
         want = pm.pileup(rs, start, end, rs["ref_bytes"], rs["ref_first"])
         assert np.array_equal(counts, want["counts"]) and np.array_equal(major, want["major"]) and lines == want["lines"]
         assert len(n_ref) == end - start
+
+
+# ---- the read sets the device tests take to the kernels' capacity edges (tests/test_pileup_reads_gpu.py): the host form against the mirror on
+# each of them, and what each set is built to hold
+CFG = dict(min_snp_af=0.08, min_indel_af=0.15)
+
+
+def test_the_long_cigars_case_holds_what_it_is_for():
+    rs = mirror_case("long_cigars")
+    n_ops = np.diff(rs["cigar_first"])
+    assert n_ops.max() > 128 and (n_ops > 64).sum() > 10, "reads whose op table needs the carry between 64-op steps, more than once"
+    kept = ((rs["flag"] & 0xF04) == 0) & (rs["mapq"] >= 5)
+    assert (n_ops[kept] > 128).any() and (rs["pos"][kept & (n_ops > 128)] < rs["end"]).any()
+
+
+def test_a_region_of_more_tiles_than_one_scan_step():
+    rs, tile = big_region()
+    start, end, n = rs["start"], rs["end"], rs["end"] - rs["start"]
+    tiles = (n + tile - 1) // tile
+    assert tiles > tile and n % tile == 5 and tiles == tile + 3
+    step = start + tile * tile  # the first site of the scan's second step
+    for cfg in (CFG, {}):
+        counts, major, lines, (n_ref, n_total) = host(rs, **cfg)
+        cand = np.array([int(x.split("-")[0]) - 1 for x in lines])
+        assert len(n_ref) == len(n_total) == n and 1000 < len(major) < 3 * 520
+        # columns in all three clusters, across the step and in the last tile; candidates on both sides of the step
+        assert (major < start + 520).any() and ((major >= step - 250) & (major < step)).any() and ((major >= step) & (major < step + 270)).any()
+        assert (major >= end - 5).any() and major.max() == end - 1 and major.min() == start
+        assert (cand < step - 250).sum() > 10 and ((cand >= step - 250) & (cand < step)).any() and (cand >= step).sum() > 10 and (cand >= end - 420).any()
+        for a in rs["clusters"]:
+            s, e = max(start, a - 20), min(end, a + 540)
+            want = pm.pileup(rs, s, e, rs["ref_bytes"], rs["ref_first"], **cfg)
+            inside = (major >= s) & (major < e)
+            assert len(want["major"]) > 300 and np.array_equal(major[inside], want["major"]) and np.array_equal(counts[inside], want["counts"])
+            assert [x for x, p in zip(lines, cand) if s <= p < e] == want["lines"] and len(want["lines"]) > 5
+            assert np.array_equal(n_ref[s - start:e - start], want["n_ref"]) and np.array_equal(n_total[s - start:e - start], want["n_total"])
+            if cfg:  # the variants are built at allele fractions around one half: every kind is a candidate under the thresholds
+                text = "".join(want["lines"])
+                assert (" I" in text or "-I" in text) and (" D" in text or "-D" in text) and (" X" in text or "-X" in text)
+
+
+@pytest.mark.parametrize("n_ops", (32, 33))
+def test_event_table_size_on_its_boundary(n_ops):
+    rs = distinct_events(n_ops)
+    t = pm.event_slots(rs, rs["start"], rs["end"])
+    assert t["cap"] == (64 if n_ops == 32 else 128) and len(t["events"]) == n_ops and set(t["events"].values()) == {1}
+    assert len(set(t["keys"].values())) == n_ops and len(t["occupied"]) == n_ops
+    kept = ((rs["flag"] & 0xF04) == 0) & (rs["mapq"] >= 5)
+    ops = rs["cigar"] & 15
+    per_read = np.add.reduceat(((ops == 1) | (ops == 2)).astype(np.int64), rs["cigar_first"][:-1])
+    assert per_read[kept].sum() == n_ops and per_read[~kept].sum() > 0
+    with pr.Context(None) as ctx:
+        r = ctx.run(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True).fetch()
+        assert ctx.stats()["events"] == n_ops
+    want = pm.pileup(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True)
+    assert np.array_equal(r["counts"], want["counts"]) and r["text"].decode().split("\n")[:-1] == want["lines"]
+
+
+def test_a_probe_of_the_event_table_wraps():
+    """32 distinct events in 64 slots, placed so that two probes start at the last slot: one of them goes on at slot 0"""
+    rs = distinct_events(32, shift=WRAP_SHIFT)
+    t = pm.event_slots(rs, rs["start"], rs["end"])
+    assert t["cap"] == 64 and len(set(t["keys"].values())) == 32 and t["wrapped"]
+    assert sorted(t["first"].values())[-2:] == [63, 63] and 0 in t["occupied"] and 63 in t["occupied"]
+    assert not pm.event_slots(distinct_events(32), 90, 300)["wrapped"]
+    counts, major, lines, _ = host(rs, call_ht=True)
+    want = pm.pileup(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True)
+    assert np.array_equal(counts, want["counts"]) and lines == want["lines"]
+
+
+def test_one_slot_counted_a_thousand_times():
+    rs = insertion_column(n_reads=3000)
+    t = pm.event_slots(rs, rs["start"], rs["end"])
+    assert sum(t["events"].values()) == 3000 and len(t["events"]) <= 80 and max(t["events"].values()) > 1000 // 40
+    counts, major, lines, _ = host(rs, call_ht=True, **CFG)
+    col = int(np.flatnonzero(major == 149)[0])
+    assert counts[col, 4] + counts[col, 13] == 3000 and lines[0].startswith("150-3000-")
+    want = pm.pileup(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True, **CFG)
+    assert np.array_equal(counts, want["counts"]) and lines == want["lines"]
+
+
+def test_more_candidates_than_a_ring_lane_takes():
+    rs = syn.make_read_set(**MANY_CANDIDATES)
+    counts, major, lines, _ = host(rs, call_ht=True)
+    assert len(lines) == len(major) > 1024, "every column a candidate, above lane_max_batch of a pileup handle"
+    want = pm.pileup(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True)
+    assert np.array_equal(counts, want["counts"]) and lines == want["lines"]
 
 
 # ---- hand-worked columns.  Every case: the reference is written out, the reads lie at position `pos` with the CIGAR given

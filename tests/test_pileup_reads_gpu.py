@@ -1,11 +1,13 @@
 """Pileup from reads on the device (csrc/c3_pileup.h): c3_pileup_reads against the host form bit for bit -- matrix, major, candidates, depths,
 count arrays, alt-info text -- on the golden sets and on generated ones, the fallback on key collisions, buffer reuse across calls, and the
-count pair against gVCF mode's own region kernel."""
+count pair against gVCF mode's own region kernel.  Behind those, the capacity edges: a region of more tiles than one step of the scan holds,
+reads of more than 128 ops, the event table's size rule on its boundary, a probe that wraps, and a chained batch above a ring lane's size."""
 import numpy as np
 import pytest
 
 from clair3_amd import gvcf, pileup_reads as pr, synthetic as syn
-from tests.pileup_cases import golden_sets, insertion_column, one_read, take_reads
+from tests.pileup_cases import (LONG_CIGARS, MANY_CANDIDATES, WRAP_SHIFT, big_region, distinct_events, golden_sets, insertion_column, one_read,
+                                take_reads)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +57,8 @@ GENERATED = {
                                 pad=0.1, eqx=True, ref_other=0.01), {}),
     "all_filtered": (dict(n_sites=300, depth=10, read_len=150, seed=24, filtered=1.0), {}),
     "no_gvcf_call_ht": (dict(n_sites=1100, depth=20, read_len=(150, 400), seed=25), dict(gvcf=False, call_ht=True)),
+    # reads of more than 64 and more than 128 ops: the op table's carry between its 64-op steps, read by the walk
+    "long_cigars": (LONG_CIGARS, {}),
 }
 
 
@@ -75,6 +79,8 @@ def test_generated_sets(ctx, host_ctx, name):
         assert len(rs["pos"]) >= 2000 and 2000 < len(want["major"]) < 3000 and len(want["cand_pos"]) > 10 and s["events"] > 1000
     if name == "all_filtered":
         assert s["reads_kept"] == 0 and len(want["major"]) == 0 and got["text"] == b""
+    if name == "long_cigars":
+        assert np.diff(rs["cigar_first"]).max() > 128 and s["events"] > 300 and len(want["major"]) == 300
     # thresholds at zero: every column with sixteen neighbours is a candidate, every allele is printed
     got, want = both(ctx, host_ctx, rs)
     assert_same(got, want, name + " thresholds 0")
@@ -185,6 +191,75 @@ def test_chained_entry_equals_candidates_on_the_fetched_arrays(ctx, chained, hea
     ctx.run(other, other["start"], other["end"], other["ref_bytes"], other["ref_first"], call_ht=True)
     rows3, status3 = m.wait(ticket)
     assert np.array_equal(status3, want_status) and rows3.tobytes() == want_rows.tobytes()
+
+
+# ---- the capacity edges: the read sets of tests/pileup_cases.py that tests/test_pileup_reads.py holds to the mirror and to their construction
+def test_more_tiles_than_one_scan_step(ctx, host_ctx, chained):
+    """tile + 3 tiles: the scan's second step, the sums it carries across (columns and candidates of the first cluster), its totals behind
+    tile_base's last tile, a last tile of 5 sites; then the chained entry over three stretches of columns a megabase apart"""
+    rs, tile = big_region()
+    n = rs["end"] - rs["start"]
+    step = rs["start"] + tile * tile
+    assert (n + tile - 1) // tile > tile and n % tile == 5
+    for cfg in (dict(CFG), dict()):
+        got, want = both(ctx, host_ctx, rs, **cfg)
+        assert_same(got, want, f"more than {tile} tiles {cfg}")
+        s = ctx.stats()
+        assert not s["fell_back"] and not s["on_host"] and len(got["n_ref"]) == len(got["n_total"]) == n and s["events"] > 500
+        major, cand = want["major"], want["cand_pos"]
+        assert (major < rs["start"] + 520).any() and ((major >= step - 250) & (major < step)).any() and (major >= step).any() and major.max() == rs["end"] - 1
+        assert (cand < step - 250).sum() > 10 and ((cand >= step - 250) & (cand < step)).any() and (cand >= step).sum() > 10 and (cand >= rs["end"] - 420).any()
+    m = chained[1]
+    r = ctx.run(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], **CFG).fetch()
+    assert len(syn.pileup_chunks(r["major"])[0]) == 3 and len(r["cand_pos"]) > 100
+    for head_tail in (False, True):
+        want_rows, want_status = m.predict_candidates(r["counts"], r["major"], r["cand_pos"], depths=r["cand_depth"], head_tail=head_tail)
+        rows, status = m.predict_reads(ctx, head_tail=head_tail)
+        assert np.array_equal(status, want_status) and rows.shape == want_rows.shape and rows.tobytes() == want_rows.tobytes() and len(rows) > 20
+
+
+@pytest.mark.parametrize("n_ops", (32, 33))
+def test_event_table_size_on_its_boundary(ctx, host_ctx, n_ops):
+    """32 I and D ops in the kept reads: a table of 64 slots, half full; 33: 128 slots.  Every op an event of its own"""
+    rs = distinct_events(n_ops)
+    got, want = both(ctx, host_ctx, rs, call_ht=True)
+    assert_same(got, want)
+    s = ctx.stats()
+    assert s["events"] == n_ops and s["collisions"] == 0 and not s["fell_back"] and not s["on_host"] and s["reads_dropped"] == 3
+    text = want["text"].decode()
+    assert text.count(" I") + text.count("-I") == (n_ops + 1) // 2 and text.count(" D") + text.count("-D") == n_ops // 2
+
+
+def test_a_probe_of_the_event_table_wraps(ctx, host_ctx):
+    """two probes start at the last of 64 slots (tests/test_pileup_reads.py shows it from the kernel's key and slot arithmetic): one goes on at slot 0"""
+    rs = distinct_events(32, shift=WRAP_SHIFT)
+    got, want = both(ctx, host_ctx, rs, call_ht=True)
+    assert_same(got, want)
+    s = ctx.stats()
+    assert s["events"] == 32 and s["collisions"] == 0 and not s["fell_back"] and not s["on_host"]
+
+
+def test_one_slot_counted_a_thousand_times(ctx, host_ctx):
+    rs = insertion_column(n_reads=3000)
+    got, want = both(ctx, host_ctx, rs, call_ht=True, **CFG)
+    assert_same(got, want)
+    s = ctx.stats()
+    assert s["events"] == 3000 and s["collisions"] == 0 and not s["fell_back"]
+    col = int(np.flatnonzero(got["major"] == 149)[0])
+    assert got["counts"][col, 4] + got["counts"][col, 13] == 3000 and max(got["counts"][col, 5], got["counts"][col, 14]) > 1000 // 80
+
+
+@pytest.mark.parametrize("head_tail", [False, True])
+def test_chained_entry_above_the_lane_limit(ctx, chained, head_tail):
+    """every column a candidate: more than the 1024 windows a pileup lane of the ring takes"""
+    m = chained[1]
+    rs = syn.make_read_set(**MANY_CANDIDATES)
+    r = ctx.run(rs, rs["start"], rs["end"], rs["ref_bytes"], rs["ref_first"], call_ht=True).fetch()
+    assert not ctx.stats()["on_host"] and len(r["cand_pos"]) == len(r["major"]) > 1024
+    want_rows, want_status = m.predict_candidates(r["counts"], r["major"], r["cand_pos"], depths=r["cand_depth"], head_tail=head_tail)
+    rows, status = m.predict_reads(ctx, head_tail=head_tail)
+    assert np.array_equal(status, want_status) and rows.shape == want_rows.shape and rows.tobytes() == want_rows.tobytes()
+    assert len(rows) > 1024 and np.isfinite(rows).all()
 
 
 def test_chained_entry_of_a_host_result_and_of_no_candidates(ctx, host_ctx, chained):
