@@ -226,11 +226,16 @@ c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int d
 int c3_model_set_geometry(c3_model *m, int depth, int positions) {
     if (!m) return fail("null model");
     if (positions < 1 || depth < 1) return fail("bad geometry %dx%d", depth, positions);
+    if (depth == m->depth && positions == m->positions) return 0;  // (nothing changes: the workspaces and the weights stay)
+    // refused before anything is touched: the workspaces freed below are what a batch in flight computes in, and c3_predict_wait
+    // reads the handle's geometry and weights when the range guard runs a batch again
+    for (const HostSlot &sl : m->slot)
+        if (sl.busy) return fail("a prediction is in flight: call c3_predict_wait first");
+    const int K4 = m->kind == C3_KIND_PILEUP ? positions * 320 : m->K4;
+    if (K4 % kBK) return fail("unsupported geometry: L4 fan-in %d is not a multiple of %d", K4, kBK);
     HIP_TRY(hipSetDevice(m->device));
-    m->depth = depth, m->positions = positions;
-    if (m->kind == C3_KIND_PILEUP) m->K4 = positions * 320;
-    if (m->K4 % kBK) return fail("unsupported geometry: L4 fan-in %d is not a multiple of %d", m->K4, kBK);
     HIP_TRY(hipDeviceSynchronize());
+    m->depth = depth, m->positions = positions, m->K4 = K4;
     free_all_workspaces(m);
     exact_free_workspace(m);
     m->loaded = false;

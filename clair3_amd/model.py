@@ -151,9 +151,13 @@ class _HipModel:
         return self
 
     def set_geometry(self, depth=89, positions=33):
-        self._geometry = (int(depth), int(positions))
+        geometry = (int(depth), int(positions))
+        if self._handle is not None and geometry == (self._geometry or (89, 33)):
+            return self  # (the geometry the handle has: nothing to free, nothing to load again -- also with a batch in flight)
+        if self._handle is not None:  # (refused -- a batch in flight, a fan-in L4 cannot take -- the object keeps the geometry the handle has)
+            _lib.check(_lib.lib().c3_model_set_geometry(self._handle, *geometry), "c3_model_set_geometry")
+        self._geometry = geometry
         if self._handle is not None:
-            _lib.check(_lib.lib().c3_model_set_geometry(self._handle, *self._geometry), "c3_model_set_geometry")
             if self.KIND == _lib.KIND_FULL_ALIGNMENT:  # (a census counts windows of ONE geometry: the layers' shapes follow it)
                 _lib.check(_lib.lib().c3_model_calibrate_reset(self._handle), "c3_model_calibrate_reset")
             if self._pending_sd is not None:

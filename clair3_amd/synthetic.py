@@ -348,10 +348,11 @@ def make_pileup_region(n_cols, n_chunks=1, seed=0, empty_fraction=0.0, empty_run
     return region, np.cumsum(step)
 
 
-def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, depth=FA_DEPTH_ONT):
-    """(batch, 89, 33, 8|9) int8 full-alignment tensors."""
+def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, depth=FA_DEPTH_ONT, positions=NO_OF_POSITIONS):
+    """(batch, 89, 33, 8|9) int8 full-alignment tensors; ``depth`` x ``positions`` windows of the same recipe
+    for other geometries (the default call draws what it always drew)."""
     rng = np.random.default_rng(seed)
-    shape = (batch, depth, NO_OF_POSITIONS, channels)
+    shape = (batch, depth, positions, channels)
     if recipe == "uniform":
         return rng.integers(-100, 101, size=shape).astype(np.int8)
     x = np.zeros(shape, dtype=np.int16)
@@ -362,26 +363,26 @@ def make_fa_windows(batch, seed=0, recipe="realistic", channels=FA_CHANNELS, dep
         n = int(n_reads[b])
         top = (depth - n) // 2  # reads centred, zero rows above/below (clair3_full_alignment_dwell.c:139-150)
         rows = slice(top, top + n)
-        ref = base_codes[rng.integers(0, 4, size=NO_OF_POSITIONS)]
-        cover = np.ones((n, NO_OF_POSITIONS), dtype=bool)
+        ref = base_codes[rng.integers(0, 4, size=positions)]
+        cover = np.ones((n, positions), dtype=bool)
         partial = rng.random(n) < 0.1
-        starts = np.where(partial, rng.integers(0, NO_OF_POSITIONS // 2, size=n), 0)
-        ends = np.where(partial, rng.integers(NO_OF_POSITIONS // 2, NO_OF_POSITIONS, size=n), NO_OF_POSITIONS)
-        pos = np.arange(NO_OF_POSITIONS)[None, :]
+        starts = np.where(partial, rng.integers(0, positions // 2, size=n), 0)
+        ends = np.where(partial, rng.integers(positions // 2, positions, size=n), positions)
+        pos = np.arange(positions)[None, :]
         cover &= (pos >= starts[:, None]) & (pos < ends[:, None])
         hap = np.sort(rng.choice(np.array([30, 60, 90]), size=n))
         x[b, rows, :, 0] = np.where(cover, ref[None, :], 0)
-        alt = np.where(rng.random((n, NO_OF_POSITIONS)) < 0.1, alt_codes[rng.integers(0, 6, size=(n, NO_OF_POSITIONS))], 0)
+        alt = np.where(rng.random((n, positions)) < 0.1, alt_codes[rng.integers(0, 6, size=(n, positions))], 0)
         x[b, rows, :, 1] = np.where(cover, alt, 0)
         x[b, rows, :, 2] = np.where(cover, rng.choice(np.array([50, 100]), size=(n, 1)), 0)
         x[b, rows, :, 3] = np.where(cover, rng.integers(0, 101, size=(n, 1)), 0)
-        x[b, rows, :, 4] = np.where(cover, rng.integers(0, 101, size=(n, NO_OF_POSITIONS)), 0)
+        x[b, rows, :, 4] = np.where(cover, rng.integers(0, 101, size=(n, positions)), 0)
         x[b, rows, :, 5] = np.where(cover, rng.integers(0, 101, size=(n, 1)), 0)
-        ins = np.where(rng.random((n, NO_OF_POSITIONS)) < 0.03, base_codes[rng.integers(0, 4, size=(n, NO_OF_POSITIONS))], 0)
+        ins = np.where(rng.random((n, positions)) < 0.03, base_codes[rng.integers(0, 4, size=(n, positions))], 0)
         x[b, rows, :, 6] = np.where(cover, ins, 0)
         x[b, rows, :, 7] = np.where(cover, hap[:, None], 0)
         if channels > 8:  # dwell channel, zero where no base (clair3_full_alignment_dwell.c:905-911)
-            dwell = np.clip(rng.geometric(0.12, size=(n, NO_OF_POSITIONS)), 0, 127)
+            dwell = np.clip(rng.geometric(0.12, size=(n, positions)), 0, 127)
             x[b, rows, :, 8] = np.where(cover, dwell, 0)
     return x.astype(np.int8)
 

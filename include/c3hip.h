@@ -93,7 +93,9 @@ int c3_device_pci_bus_id(int device, char *buf, int buf_bytes);
 /* kind: C3_KIND_*; in_channels: 18 (pileup) / 8 or 9 (full alignment, 9 = dwell time);
  * add_indel_length: 0 -> (B,24) output, 1 -> (B,90).  Returns NULL on failure. */
 c3_model *c3_model_create(int kind, int in_channels, int add_indel_length, int device);
-/* window geometry; defaults are the ONT shapes: depth 89 (ignored for pileup), 33 positions */
+/* window geometry; defaults are the ONT shapes: depth 89 (ignored for pileup), 33 positions.  A change frees the workspaces and
+ * drops the weights (load again); the geometry the handle already has changes nothing.  Refused, with nothing touched, while a
+ * c3_predict_submit of the handle is pending. */
 int c3_model_set_geometry(c3_model *m, int depth, int positions);
 /* strict: every expected key must be present with the expected shape, unknown keys are an error.  A (re)load starts
  * the handle afresh: the range guard's flag is cleared and the precision goes back to what C3HIP_FP32 chose, else to

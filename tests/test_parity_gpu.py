@@ -20,11 +20,11 @@ pytestmark = pytest.mark.gpu
 CASES = sorted(util.manifest().keys())
 
 
-def make_model(kind, channels, add_indel, sd, keep=False, depth=None):
+def make_model(kind, channels, add_indel, sd, keep=False, depth=None, positions=syn.NO_OF_POSITIONS):
     cls = Clair3_P if kind == syn.PILEUP else Clair3_F
     m = cls(add_indel_length=add_indel, predict=True, input_channels=channels)
-    if depth and depth != syn.FA_DEPTH_ONT:
-        m.set_geometry(depth, 33)
+    if (depth and depth != syn.FA_DEPTH_ONT) or positions != syn.NO_OF_POSITIONS:
+        m.set_geometry(depth or syn.FA_DEPTH_ONT, positions)
     if keep:
         m.keep_activations(True)
     m.to("cuda:0")
