@@ -49,6 +49,8 @@ EXPORTS = (
     "c3_fa_reads_create", "c3_fa_reads_destroy", "c3_fa_reads", "c3_fa_reads_host", "c3_fa_reads_sizes", "c3_fa_reads_result", "c3_fa_reads_stats",
     "c3_fa_lds_reads",
     "c3_predict_submit_fa_reads", "c3_predict_fa_reads",
+    "c3_fa_haplotag", "c3_fa_haplotag_host", "c3_fa_haplotag_sizes", "c3_fa_haplotag_result", "c3_fa_haplotag_stats", "c3_fa_haplotag_shape",
+    "c3_fa_reads_phased", "c3_fa_reads_phased_host",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -219,6 +221,22 @@ class FaCounters(C.Structure):
     """c3_fa_counters (include/c3hip.h)"""
     _fields_ = [("reads_kept", C.c_int64), ("reads_dropped", C.c_int64), ("rows", C.c_int64), ("deep_windows", C.c_int64),
                 ("fell_back", C.c_int32), ("on_host", C.c_int32), ("kernel_ms", C.c_float * 8)]
+
+
+class PhasedVariantsC(C.Structure):
+    """c3_phased_variants (include/c3hip.h)"""
+    _fields_ = [("n", C.c_int64), ("pos", C.c_void_p), ("alt_base", C.c_void_p), ("genotype", C.c_void_p), ("phase_set", C.c_void_p)]
+
+
+class HaplotagConfig(C.Structure):
+    """c3_haplotag_config (include/c3hip.h)"""
+    _fields_ = [("min_haplotag_mq", C.c_int32), ("reserved", C.c_int32)]
+
+
+class HaplotagCounters(C.Structure):
+    """c3_haplotag_counters (include/c3hip.h)"""
+    _fields_ = [("reads_hap", C.c_int64 * 3), ("reads_low_mapq", C.c_int64), ("pairs_realigned", C.c_int64), ("pairs_allele0", C.c_int64),
+                ("on_host", C.c_int32), ("reserved", C.c_int32), ("kernel_ms", C.c_float * 8)]
 
 
 class PileupCounters(C.Structure):
@@ -407,6 +425,15 @@ def lib():
     L.c3_fa_reads_stats.argtypes = [C.c_void_p, C.POINTER(FaCounters)]
     L.c3_predict_submit_fa_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
     L.c3_predict_fa_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    for fn in (L.c3_fa_haplotag, L.c3_fa_haplotag_host):
+        fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.POINTER(PhasedVariantsC), C.c_void_p, C.c_int64, C.c_int64, C.POINTER(HaplotagConfig)]
+    L.c3_fa_haplotag_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.c3_fa_haplotag_result.argtypes = [C.c_void_p] * 4
+    L.c3_fa_haplotag_stats.argtypes = [C.c_void_p, C.POINTER(HaplotagCounters)]
+    L.c3_fa_haplotag_shape.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    for fn in (L.c3_fa_reads_phased, L.c3_fa_reads_phased_host):
+        fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.POINTER(ReadExtrasC), C.POINTER(PhasedVariantsC), C.c_void_p, C.c_int64, C.c_void_p,
+                       C.c_int64, C.c_int64, C.POINTER(FaConfig), C.POINTER(HaplotagConfig)]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

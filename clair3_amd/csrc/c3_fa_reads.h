@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "c3_fa_rule.h"
+#include "c3_hap_rule.h"
 #include "c3_pileup.h"
 
 namespace c3 {
@@ -214,13 +215,33 @@ struct c3_fa_reads_ctx {
     // grown on demand, never shrunk
     c3_pileup::Buf pos, flag, mapq, cfirst, sfirst, qfirst, cigar, seq, qual, hap, kept, read_end, premax, ref, centres, op_rpos, op_q, op_read, sel_read,
         sel_af, centre, ev_count, tiles, flags, counts, rows;
+    // haplotagging (c3_hap_reads.h): the tags of the last haplotag call, held on the host or (tags, alleles) on the device
+    hipEvent_t hev[5] = {};
+    c3::HapResult tagged;
+    bool tags_on_host = true, hap_counted = true;
+    int64_t hap_reads = 0, hap_pairs = 0, hap_ref_first = 0;  // hap_ref_first: the reference position of hap_ref's first byte
+    c3_haplotag_counters hap_stats{};
+    c3_pileup::Buf tags, alleles, vpos, valt, vgt, vps, pair_first, var_first, hap_ref;
     std::vector<c3_pileup::Buf *> bufs() {
         return {&pos, &flag, &mapq, &cfirst, &sfirst, &qfirst, &cigar, &seq, &qual, &hap, &kept, &read_end, &premax, &ref, &centres, &op_rpos, &op_q,
-                &op_read, &sel_read, &sel_af, &centre, &ev_count, &tiles, &flags, &counts, &rows};
+                &op_read, &sel_read, &sel_af, &centre, &ev_count, &tiles, &flags, &counts, &rows, &tags, &alleles, &vpos, &valt, &vgt, &vps,
+                &pair_first, &var_first, &hap_ref};
     }
 };
 
 namespace c3 {
+
+// the haplotag step of a chained call (c3_hap_reads.h): staged behind the read set, launched behind the op table; the vote kernel writes
+// g->tags, which the window kernels then read as FaView::hap
+struct HapJob {
+    const c3_phased_variants *vars;
+    const HapTables *t;
+    const uint8_t *ref;
+    int64_t ref_first;
+};
+static int hap_stage(c3_fa_reads_ctx *g, const HapJob &job, int64_t n_reads);
+static int hap_launch(c3_fa_reads_ctx *g, const HapJob &job, int64_t n_reads);
+static int hap_fetch_tags(c3_fa_reads_ctx *g);
 
 static int fa_held_on_host(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &t, const FaView &v, const int64_t *centres, int64_t n_cand,
                            const c3_fa_config &cfg) {
@@ -232,7 +253,7 @@ static int fa_held_on_host(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTa
 }
 
 static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &t, const FaView &hv, const int64_t *centres, int64_t n_cand,
-                     const c3_fa_config &cfg) {
+                     const c3_fa_config &cfg, const HapJob *job) {
     HIP_TRY(hipSetDevice(g->device));
     const int64_t nr = rs->n_reads, n_ops = t.n_ops, D = cfg.matrix_depth;
     const int64_t seq_bytes = t.sfirst[(size_t)nr], qual_bytes = t.qfirst[(size_t)nr];
@@ -242,7 +263,7 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     const Up ups[] = {{&g->pos, rs->pos, (size_t)nr * 8}, {&g->flag, rs->flag, (size_t)nr * 2}, {&g->mapq, rs->mapq, (size_t)nr},
                       {&g->cfirst, t.cfirst.data(), (size_t)(nr + 1) * 8}, {&g->sfirst, t.sfirst.data(), (size_t)(nr + 1) * 8},
                       {&g->qfirst, t.qfirst.data(), (size_t)(nr + 1) * 8}, {&g->cigar, hv.cigar, (size_t)n_ops * 4}, {&g->seq, hv.seq, (size_t)seq_bytes},
-                      {&g->qual, hv.qual, (size_t)qual_bytes}, {&g->hap, hv.hap, (size_t)nr}, {&g->kept, t.kept.data(), (size_t)nr},
+                      {&g->qual, hv.qual, (size_t)qual_bytes}, {&g->hap, hv.hap, job ? (size_t)0 : (size_t)nr}, {&g->kept, t.kept.data(), (size_t)nr},
                       {&g->read_end, t.read_end.data(), (size_t)nr * 8}, {&g->premax, t.premax.data(), (size_t)nr * 8},
                       {&g->ref, hv.ref + (ref_lo - hv.ref_first), (size_t)ref_n}, {&g->centres, centres, (size_t)n_cand * 8}};
     for (const Up &u : ups) TRY(pileup_grow(*u.b, u.bytes));
@@ -263,6 +284,7 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
         if (u.bytes) TRY(h2d_staged(u.b->p, u.src, u.bytes, st));
     if (n_ops) HIP_TRY(hipMemsetAsync(g->ev_count.p, 0, (size_t)n_ops * 4, st));
     HIP_TRY(hipMemsetAsync(g->flags.p, 0, 64, st));
+    if (job) TRY(hap_stage(g, *job, nr));
     HIP_TRY(hipEventRecord(g->ev[1], st));
     // the op table: pileup_ops_kernel as it is (its kept flag goes to op_read, which nothing here reads)
     PileupParams pp{};
@@ -271,11 +293,12 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     pp.op_read = (int32_t *)g->op_read.p, pp.cfg.min_mq = cfg.min_mq;
     pp.tiles = n_cand, pp.tile_n = (uint32_t *)g->tiles.p, pp.tile_base = pp.tile_n + 2 * n_cand;
     if (nr > 0) PILEUP_LAUNCH(pileup_ops_kernel, (nr + 3) / 4, 256, pp);
+    if (job) TRY(hap_launch(g, *job, nr));  // (its time counts under the op table here; c3_fa_haplotag_stats has it apart)
     HIP_TRY(hipEventRecord(g->ev[2], st));
     FaParams p{};
     p.v.n_reads = nr, p.v.pos = pp.pos, p.v.cigar_first = pp.cigar_first, p.v.seq_first = (const int64_t *)g->sfirst.p, p.v.qual_first = (const int64_t *)g->qfirst.p;
     p.v.read_end = (const int64_t *)g->read_end.p, p.v.premax = (const int64_t *)g->premax.p, p.v.cigar = pp.cigar, p.v.flag = pp.flag, p.v.mapq = pp.mapq;
-    p.v.seq = (const uint8_t *)g->seq.p, p.v.qual = (const uint8_t *)g->qual.p, p.v.hap = (const uint8_t *)g->hap.p, p.v.kept = (const uint8_t *)g->kept.p;
+    p.v.seq = (const uint8_t *)g->seq.p, p.v.qual = (const uint8_t *)g->qual.p, p.v.hap = (const uint8_t *)(job ? g->tags.p : g->hap.p), p.v.kept = (const uint8_t *)g->kept.p;
     p.v.op_rpos = pp.op_rpos, p.v.op_q = pp.op_q, p.v.ref = (const uint8_t *)g->ref.p, p.v.ref_first = ref_lo;
     p.centres = (const int64_t *)g->centres.p, p.n_cand = n_cand, p.depth = (int32_t)D, p.seed = cfg.seed;
     p.cap = cfg.lds_reads > 0 ? std::min<int32_t>(cfg.lds_reads, kFaLdsReads) : kFaLdsReads;
@@ -290,6 +313,7 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     HIP_TRY(hipEventRecord(g->ev[4], st));
     if (over) {  // a candidate with more overlapping reads than the table holds: the host form answers
         g->stats.fell_back = 1;
+        if (job) TRY(hap_fetch_tags(g));  // (hv.hap is g->tagged.hap: the tags are fetched once for the host form)
         return fa_held_on_host(g, rs, t, hv, centres, n_cand, cfg);
     }
     const int64_t n_rows = totals[0];
@@ -331,7 +355,7 @@ static int fa_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_read_ext
     if (n_cand == 0) return 0;
     const FaView v = fa_view(rs, ex, t, (const uint8_t *)ref_bytes, ref_first);
     if (!device) return fa_held_on_host(g, rs, t, v, centres, n_cand, *cfg);
-    return fa_device(g, rs, t, v, centres, n_cand, *cfg);
+    return fa_device(g, rs, t, v, centres, n_cand, *cfg, nullptr);
 }
 
 }  // namespace c3
@@ -352,11 +376,14 @@ c3_fa_reads_ctx *c3_fa_reads_create(int device) {
     else {
         ok = true;
         for (hipEvent_t &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+        for (hipEvent_t &e : g->hev) ok = ok && hipEventCreate(&e) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&g->taken, hipEventDisableTiming) == hipSuccess;
         if (!ok) fail("c3_fa_reads_create: hipEventCreate failed");
     }
     if (!ok) {
         for (hipEvent_t e : g->ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : g->hev)
             if (e) (void)hipEventDestroy(e);
         if (g->ready) (void)hipEventDestroy(g->ready);
         if (g->taken) (void)hipEventDestroy(g->taken);
@@ -374,6 +401,8 @@ int c3_fa_reads_destroy(c3_fa_reads_ctx *g) {
         (void)hipSetDevice(g->device);
         if (g->stream) (void)hipStreamSynchronize(g->stream), (void)hipStreamDestroy(g->stream);
         for (hipEvent_t e : g->ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : g->hev)
             if (e) (void)hipEventDestroy(e);
         if (g->ready) (void)hipEventDestroy(g->ready);
         if (g->taken) (void)hipEventDestroy(g->taken);

@@ -46,8 +46,9 @@
 //  (c) NON-ACGT BASES: kept as the tables give them: acgt2num maps every letter but C, G, T to A's counter; num2countbase_fa gives N 100,
 //      'D' (nt16 code 13) -100, every other letter 0.  The tables are indexed with letter - 'A'; for a byte outside 'A' .. 'A' + 31 (the
 //      nt16 code 0, '=', or a reference byte that is no letter) the reference reads out of bounds: here such a byte gives 0 / A.
-// NOT BUILT: reading BAM files; haplotag_read with its Levenshtein realignment (:262-422: haplotypes are an input, that function is the
-//   obvious follow-up); the dwell channel (9-channel handles are refused by the chained entry).  matrix_depth may be 1 .. 128 (the
+// HAPLOTYPES are an input of this rule; haplotag_read with its Levenshtein realignment (:262-422) is stated in c3_hap_rule.h, and
+//   c3_fa_reads_phased (c3_hap_reads.h) runs it in front of this rule in one call.
+// NOT BUILT: reading BAM files; the dwell channel (9-channel handles are refused by the chained entry).  matrix_depth may be 1 .. 128 (the
 //   reference's are 89 and 55).
 #pragma once
 #include <stdint.h>

@@ -17,6 +17,7 @@
 #include "c3_gvcf.h"  // (gVCF mode: no model; its kernels sit in a section of their own behind `.c3_occlude_text`)
 #include "c3_pileup.h"  // (pileup from reads: no model; its kernels sit in a section of their own behind `.c3_gvcf_text`)
 #include "c3_fa_reads.h"  // (full alignment from reads: its kernels sit in a section of their own behind `.c3_pileup_text`)
+#include "c3_hap_reads.h"  // (haplotagging the reads: its kernels sit in a section of their own behind `.c3_fa_text`)
 
 extern "C" {
 

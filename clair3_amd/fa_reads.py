@@ -1,7 +1,8 @@
 """Full alignment from reads: the candidate windows of the reference's calculate_clair3_full_alignment
 (src/clair3_full_alignment_dwell.c:437-1054) from aligned reads as the arrays a BAM record holds (csrc/c3_fa_rule.h states the rule and where
-it leaves the reference, csrc/c3_fa_reads.h holds the kernels).  Limits: no BAM file is read, the reads' haplotypes are an input (the
-reference's haplotag_read is not built), 8 channels only (no dwell channel).
+it leaves the reference, csrc/c3_fa_reads.h holds the kernels).  The reads' haplotypes are an input, or are computed from phased variants
+by the reference's haplotag_read (csrc/c3_hap_rule.h, csrc/c3_hap_reads.h) in the same call.  Limits: no BAM or VCF index is read, het
+SNPs only (as the reference), 8 channels only (no dwell channel).
 
     pileup_reads.ReadSet.from_arrays(...)                  c3_read_set: BAM's own encoding, reads in COORDINATE ORDER
     ReadExtras.from_arrays(qual_first, qual, haplotype, name_key=None)   c3_read_extras: a quality byte per query base, HP tag, name key
@@ -10,9 +11,16 @@ reference's haplotag_read is not built), 8 channels only (no dwell channel).
         Clair3_F.predict_rows; synthetic.pad_fa_rows(rows, counts, depth=matrix_depth) is the dense tensor
     Context(device)                                        keeps the device buffers between calls; .run .sizes .fetch .stats;
         Clair3_F.predict_reads(context) runs the held windows through the network without fetching them
+    PhasedVariants.from_arrays(pos, alt_base, genotype, phase_set) / .from_dict / .from_vcf(path, ctg_name)   c3_phased_variants: the phased
+        heterozygous SNPs of one contig, positions 0-based and strictly ascending
+    Context.haplotag(reads, variants, ref_bytes, ref_first, path=None, min_haplotag_mq=20)   uint8 tags (0, 1, 2) of every read;
+        .haplotag_pairs() the allele of every (read, variant) pair with the n + 1 offsets, .haplotag_stats()
+    Context.run(..., variants=V) / fa_windows(..., variants=V)   tag and build the windows in one call: extras need no haplotype, and on
+        the device the tags never visit the host
 
     python -m clair3_amd.fa_reads --reads X.npz --ref_fn ref.fa --ctgName c --candidates pos.txt [--chkpnt_fn M] [--output_fn F.npz]
                                   [--path device|host] [--min_mq N] [--max_indel_length N] [--matrix_depth N] [--seed N]
+                                  [--phased_vcf_fn V.vcf[.gz]]   (the reads are haplotagged from it; X.npz then needs no haplotype)
         X.npz: the seven arrays of ReadSet.from_arrays and qual_first, qual, haplotype[, name_key].  pos.txt: one 1-based position per
         line, ascending.  The alt-info lines go to stdout; --output_fn gets rows, counts, depths (and, with --chkpnt_fn, a checkpoint
         of Clair3_F, the probability rows y).
@@ -34,6 +42,7 @@ FA_POSITIONS, FA_CHANNELS = 33, 8
 ERR_REFSKIP = 2  # C3_FA_ERR_REFSKIP
 
 DEFAULTS = dict(min_mq=5, max_indel_length=50, matrix_depth=89, lds_reads=0, seed=0)
+HAP_DEFAULTS = dict(min_haplotag_mq=20)  # min_haplotag_mq, src/clair3_full_alignment_dwell.h:20
 
 
 class RefSkipError(_lib.C3Error):
@@ -67,27 +76,91 @@ class ReadExtras:
 
     def __init__(self, arrays):
         self.arrays = arrays
-        if len(arrays["qual_first"]) != len(arrays["haplotype"]) + 1:
+        if arrays["haplotype"] is None:  # (Context.run(..., variants=V) computes it)
+            if len(arrays["qual_first"]) < 1:
+                raise ValueError("qual_first of n + 1 offsets expected")
+        elif len(arrays["qual_first"]) != len(arrays["haplotype"]) + 1:
             raise ValueError("qual_first of n + 1 offsets and haplotype of n reads expected")
         if int(arrays["qual_first"][-1]) > len(arrays["qual"]):
             raise ValueError("the last offset of qual_first lies behind the end of qual")
-        if arrays["name_key"] is not None and len(arrays["name_key"]) != len(arrays["haplotype"]):
+        if arrays["name_key"] is not None and len(arrays["name_key"]) != len(arrays["qual_first"]) - 1:
             raise ValueError("name_key of n reads expected")
         self.c = _lib.ReadExtrasC(*[arrays[name].ctypes.data if arrays[name] is not None and arrays[name].size else None for name, _ in self.FIELDS])
 
     @classmethod
-    def from_arrays(cls, qual_first, qual, haplotype, name_key=None):
+    def from_arrays(cls, qual_first, qual, haplotype=None, name_key=None):
         given = dict(qual_first=qual_first, qual=qual, haplotype=haplotype, name_key=name_key)
         return cls({name: None if given[name] is None else np.ascontiguousarray(given[name], dtype=dt).reshape(-1) for name, dt in cls.FIELDS})
 
     @classmethod
     def from_dict(cls, d, names=True):
         """from the dict synthetic.make_read_extras returns, or an .npz; names=False drops the name keys (no duplicate-name filter)"""
-        has = names and "name_key" in (d.files if hasattr(d, "files") else d)
-        return cls.from_arrays(d["qual_first"], d["qual"], d["haplotype"], d["name_key"] if has else None)
+        keys = d.files if hasattr(d, "files") else d
+        has = names and "name_key" in keys
+        return cls.from_arrays(d["qual_first"], d["qual"], d["haplotype"] if "haplotype" in keys else None, d["name_key"] if has else None)
 
     def __len__(self):
-        return len(self.arrays["haplotype"])
+        return len(self.arrays["qual_first"]) - 1
+
+
+def hap_config(**cfg):
+    unknown = set(cfg) - set(HAP_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown option(s) {sorted(unknown)}; expected some of {sorted(HAP_DEFAULTS)}")
+    return _lib.HaplotagConfig(int(dict(HAP_DEFAULTS, **cfg)["min_haplotag_mq"]), 0)
+
+
+class PhasedVariants:
+    """c3_phased_variants: the phased heterozygous SNPs of one contig; the arrays are kept alive by this object"""
+    FIELDS = (("pos", np.int64), ("alt_base", np.uint8), ("genotype", np.uint8), ("phase_set", np.int32))
+
+    def __init__(self, arrays):
+        self.arrays = arrays
+        n = len(arrays["pos"])
+        if any(len(arrays[name]) != n for name, _ in self.FIELDS):
+            raise ValueError("pos, alt_base, genotype and phase_set of one length expected")
+        self.c = _lib.PhasedVariantsC(n, *[arrays[name].ctypes.data if n else None for name, _ in self.FIELDS])
+
+    @classmethod
+    def from_arrays(cls, pos, alt_base, genotype, phase_set):
+        given = dict(pos=pos, alt_base=alt_base, genotype=genotype, phase_set=phase_set)
+        if isinstance(alt_base, (bytes, str)):
+            given["alt_base"] = np.frombuffer(alt_base.encode("ascii") if isinstance(alt_base, str) else alt_base, np.uint8)
+        return cls({name: np.ascontiguousarray(given[name], dtype=dt).reshape(-1) for name, dt in cls.FIELDS})
+
+    @classmethod
+    def from_dict(cls, d):
+        """from the dict synthetic.make_phased_variants returns, or an .npz"""
+        return cls.from_arrays(d["pos"], d["alt_base"], d["genotype"], d["phase_set"])
+
+    @classmethod
+    def from_vcf(cls, path, ctg_name=None):
+        """the rule of preprocess/CreateTensorFullAlignmentFromCffi.py:84-102: plain or gzip; rows of ``ctg_name`` whose GT holds '|';
+        genotype 1 for 0|1, else 2; PS is the last field of the sample column; pos - 1.  A REF or ALT of more than one base raises
+        ValueError (the reference's cffi char would)."""
+        import gzip
+        with open(path, "rb") as fh:
+            zipped = fh.read(2) == b"\x1f\x8b"
+        pos, alt, gt, ps = [], [], [], []
+        with (gzip.open(path, "rt") if zipped else open(path, "rt")) as fh:
+            for row in fh:
+                row = row.rstrip()
+                if not row or row[0] == "#":
+                    continue
+                columns = row.strip().split("\t")
+                if ctg_name and columns[0] != ctg_name:
+                    continue
+                info = columns[9].split(":")
+                genotype, phase_set = info[0], info[-1]
+                if "|" not in genotype:
+                    continue
+                if len(columns[3]) != 1 or len(columns[4]) != 1:
+                    raise ValueError(f"{path}: {columns[0]}:{columns[1]} has REF {columns[3]} and ALT {columns[4]}: phased SNPs of one base expected")
+                pos.append(int(columns[1]) - 1), alt.append(ord(columns[4])), gt.append(1 if genotype == "0|1" else 2), ps.append(int(phase_set))
+        return cls.from_arrays(pos, alt, gt, ps)
+
+    def __len__(self):
+        return len(self.arrays["pos"])
 
 
 class Context:
@@ -119,24 +192,70 @@ class Context:
     def __exit__(self, *exc):
         self.close()
 
-    def run(self, reads, extras, centres, ref_bytes, ref_first, path=None, **cfg):
-        """one call; centres 0-based, strictly ascending.  The result stays in the context (after a device call: the rows on the device)"""
+    def _path(self, path):
+        path = path or ("host" if self.device is None else "device")
+        if path not in ("device", "host"):
+            raise ValueError(f"path={path}: expected device or host")
+        return path
+
+    def haplotag(self, reads, variants, ref_bytes, ref_first, path=None, **cfg):
+        """(n,) uint8: the tag (0, 1, 2) of every read.  The tags stay in the context (after a device call: on the device)"""
+        if not isinstance(reads, ReadSet):
+            reads = ReadSet.from_dict(reads)
+        if not isinstance(variants, PhasedVariants):
+            variants = PhasedVariants.from_dict(variants)
+        path = self._path(path)
+        ref = _ref_array(ref_bytes)
+        c = hap_config(**cfg)
+        L = _lib.lib()
+        fn, what = (L.c3_fa_haplotag, "c3_fa_haplotag") if path == "device" else (L.c3_fa_haplotag_host, "c3_fa_haplotag_host")
+        _lib.check(fn(self.h, C.byref(reads.c), C.byref(variants.c), ref.ctypes.data if ref.size else None, int(ref_first), len(ref), C.byref(c)), what)
+        return self.haplotag_pairs(pairs=False)[0]
+
+    def haplotag_pairs(self, pairs=True):
+        """(hap, alleles, pair_first) of the held tags: alleles (n_pairs,) int8 in read order, then variant order (0 none, 1 reference,
+        2 alternative), pair_first (n + 1,) int64; pairs=False: alleles is None"""
+        n, m = C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.lib().c3_fa_haplotag_sizes(self.h, C.byref(n), C.byref(m)), "c3_fa_haplotag_sizes")
+        hap, first = np.zeros(n.value, np.uint8), np.zeros(n.value + 1, np.int64)
+        alleles = np.zeros(m.value, np.int8) if pairs else None
+        _lib.check(_lib.lib().c3_fa_haplotag_result(self.h, hap.ctypes.data if hap.size else None,
+                                                    alleles.ctypes.data if pairs and alleles.size else None, first.ctypes.data), "c3_fa_haplotag_result")
+        return hap, alleles, first
+
+    def haplotag_stats(self):
+        s = _lib.HaplotagCounters()
+        _lib.check(_lib.lib().c3_fa_haplotag_stats(self.h, C.byref(s)), "c3_fa_haplotag_stats")
+        names = ("staging", "op_table", "pairs", "votes")
+        return {"reads_hap": tuple(s.reads_hap), "reads_low_mapq": s.reads_low_mapq, "pairs_realigned": s.pairs_realigned,
+                "pairs_allele0": s.pairs_allele0, "on_host": bool(s.on_host), "kernel_ms": dict(zip(names, list(s.kernel_ms)))}
+
+    def run(self, reads, extras, centres, ref_bytes, ref_first, path=None, variants=None, min_haplotag_mq=None, **cfg):
+        """one call; centres 0-based, strictly ascending.  The result stays in the context (after a device call: the rows on the device).
+        variants (PhasedVariants or a dict of its arrays): the reads are haplotagged first and the extras' haplotype is not read"""
         if not isinstance(reads, ReadSet):
             reads = ReadSet.from_dict(reads)
         if not isinstance(extras, ReadExtras):
             extras = ReadExtras.from_dict(extras)
         if len(extras) != len(reads):
             raise ValueError(f"{len(extras)} extras for {len(reads)} reads")
-        path = path or ("host" if self.device is None else "device")
-        if path not in ("device", "host"):
-            raise ValueError(f"path={path}: expected device or host")
+        path = self._path(path)
         ref = _ref_array(ref_bytes)
         centres = np.ascontiguousarray(centres, dtype=np.int64).reshape(-1)
         c = config(**cfg)
         L = _lib.lib()
-        fn, what = (L.c3_fa_reads, "c3_fa_reads") if path == "device" else (L.c3_fa_reads_host, "c3_fa_reads_host")
-        rc = fn(self.h, C.byref(reads.c), C.byref(extras.c), centres.ctypes.data if centres.size else None, len(centres),
-                ref.ctypes.data if ref.size else None, int(ref_first), len(ref), C.byref(c))
+        args = (centres.ctypes.data if centres.size else None, len(centres), ref.ctypes.data if ref.size else None, int(ref_first), len(ref), C.byref(c))
+        if variants is not None:
+            if not isinstance(variants, PhasedVariants):
+                variants = PhasedVariants.from_dict(variants)
+            hc = hap_config(**({} if min_haplotag_mq is None else {"min_haplotag_mq": min_haplotag_mq}))
+            fn, what = (L.c3_fa_reads_phased, "c3_fa_reads_phased") if path == "device" else (L.c3_fa_reads_phased_host, "c3_fa_reads_phased_host")
+            rc = fn(self.h, C.byref(reads.c), C.byref(extras.c), C.byref(variants.c), *args, C.byref(hc))
+        else:
+            if min_haplotag_mq is not None:
+                raise TypeError("min_haplotag_mq without variants")
+            fn, what = (L.c3_fa_reads, "c3_fa_reads") if path == "device" else (L.c3_fa_reads_host, "c3_fa_reads_host")
+            rc = fn(self.h, C.byref(reads.c), C.byref(extras.c), *args)
         if rc == ERR_REFSKIP:
             raise RefSkipError(f"{what}: {_lib.last_error()}")
         _lib.check(rc, what)
@@ -176,11 +295,12 @@ def _shared_context(path):
     return _contexts[key]
 
 
-def fa_windows(reads, extras, centres, ref_bytes, ref_first, path=None, context=None, **cfg):
-    """(rows, counts, depths, alt_info_list) of the candidates at ``centres`` (0-based, strictly ascending, each >= 16).  cfg: DEFAULTS above"""
+def fa_windows(reads, extras, centres, ref_bytes, ref_first, path=None, context=None, variants=None, **cfg):
+    """(rows, counts, depths, alt_info_list) of the candidates at ``centres`` (0-based, strictly ascending, each >= 16).  cfg: DEFAULTS above;
+    variants: the reads are haplotagged from them first (Context.run)"""
     path = path or default_path()
     ctx = context or _shared_context(path)
-    r = ctx.run(reads, extras, centres, ref_bytes, ref_first, path=path, **cfg).fetch()
+    r = ctx.run(reads, extras, centres, ref_bytes, ref_first, path=path, variants=variants, **cfg).fetch()
     return r["rows"], r["counts"], r["depths"], r["text"].decode("ascii").split("\n")[:-1]
 
 
@@ -194,6 +314,7 @@ def main(argv=None):
     ap.add_argument("--chkpnt_fn")
     ap.add_argument("--output_fn")
     ap.add_argument("--path", choices=("device", "host"))
+    ap.add_argument("--phased_vcf_fn", help="phased het SNPs (plain or gzip): the reads are haplotagged from them")
     for name in ("min_mq", "max_indel_length", "matrix_depth", "seed"):
         ap.add_argument("--" + name, type=int, default=DEFAULTS[name])
     a = ap.parse_args(argv)
@@ -206,7 +327,8 @@ def main(argv=None):
     cfg = dict(min_mq=a.min_mq, max_indel_length=a.max_indel_length, matrix_depth=a.matrix_depth, seed=a.seed)
     out = {}
     with Context(0 if path == "device" else None) as ctx:
-        r = ctx.run(reads, extras, centres, ref, 0, path=path, **cfg).fetch()
+        variants = PhasedVariants.from_vcf(a.phased_vcf_fn, a.ctgName) if a.phased_vcf_fn else None
+        r = ctx.run(reads, extras, centres, ref, 0, path=path, variants=variants, **cfg).fetch()
         out.update(rows=r["rows"], counts=r["counts"], depths=r["depths"])
         if a.chkpnt_fn:
             import torch

@@ -1287,3 +1287,51 @@ def fa_keys(seed, centre, reads):
     with np.errstate(over="ignore"):
         inner = subsample_mix(np.uint64(int(seed) & _M64) + g * np.uint64((1 + int(centre)) & _M64))
         return subsample_mix(inner + g * (np.uint64(1) + np.asarray(reads, dtype=np.uint64)))
+
+
+# ---- haplotagging the reads: the phased heterozygous SNPs of a contig (c3_phased_variants, include/c3hip.h)
+def make_phased_variants(rs, seed, rate=0.02, hot_at=(), dense=None, near=(), set_span=80):
+    """Phased het SNPs over the reference of ``rs`` (make_read_set / a dict with pos, cigar_first, cigar, ref_bytes, ref_first), as a dict:
+    pos (int64, 0-based, strictly ascending), alt_base (uint8 letters), genotype (uint8, 1 = 0|1, 2 = 1|0), phase_set (int32).  Sites: a
+    share ``rate`` of the reference positions; the SNP sites of ``hot_at`` (the (position, 1, alt) entries given to make_read_set: the alt
+    base is the site's first allele there, so about half the reads carry it); ``dense`` = (first, behind): a site every 2 or 3 bases in
+    that stretch; ``near``: read indices of ``rs`` -- sites at those reads' first and last bases, 9 / 10 / 11 bases inside either end,
+    just behind the end, and at, in front of and behind every I, D and N op.  Phase sets are stretches of ``set_span`` bases (a set's
+    name is its first position + 1), so that a read usually touches several.  Every site keeps 10 bases of reference in front of it and 11
+    behind, so that every context is covered."""
+    rng = np.random.default_rng(seed)
+    ref, ref_first = np.asarray(rs["ref_bytes"]), int(rs["ref_first"])
+    lo, hi = ref_first + 10, ref_first + len(ref) - 11
+    sites = {}
+    for p in np.flatnonzero(rng.random(len(ref)) < rate):
+        sites[int(p) + ref_first] = None
+    if dense is not None:
+        p = int(dense[0])
+        while p < int(dense[1]):
+            sites[p] = None
+            p += int(rng.integers(2, 4))
+    for r in near:
+        r = int(r)
+        p0 = int(rs["pos"][r])
+        at, marks = p0, [p0, p0 + 9, p0 + 10, p0 + 11]
+        for c in rs["cigar"][rs["cigar_first"][r]:rs["cigar_first"][r + 1]]:
+            op, n = int(c) & 15, int(c) >> 4
+            if op in (1, 2, 3):
+                marks += [at - 1, at, at + 1]
+            if op in (2, 3):
+                marks += [at + n - 1, at + n]
+            if op in (0, 2, 3, 7, 8):
+                at += n
+        marks += [at - 12, at - 11, at - 10, at - 1, at]
+        for p in marks:
+            sites[p] = None
+    for p, kind, alt in hot_at:
+        if kind == 1:
+            sites[int(p)] = int(alt)
+    pos = np.array(sorted(p for p in sites if lo <= p < hi), np.int64)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    ref_at = ref[pos - ref_first]
+    code = np.searchsorted(acgt, ref_at & 0xDF).clip(0, 3)  # (a byte that is no base counts as one: the alt base is some other letter)
+    shift = np.array([sites[int(p)] if sites[int(p)] is not None else int(rng.integers(1, 4)) for p in pos], np.int64).reshape(-1)
+    return {"pos": pos, "alt_base": acgt[(code + shift) % 4].astype(np.uint8), "genotype": rng.integers(1, 3, size=len(pos)).astype(np.uint8),
+            "phase_set": ((pos // set_span) * set_span + 1).astype(np.int32)}

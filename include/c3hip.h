@@ -1145,8 +1145,9 @@ int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_h
 /* ---- full alignment from reads: the candidate windows of calculate_clair3_full_alignment (src/clair3_full_alignment_dwell.c:437-1054) from
  * aligned reads, as each window's occupied rows and a row count: what c3_predict_submit_rows with row_first == NULL takes (the dense window is
  * the run placed at (matrix_depth - count) / 2).  The rule clause by clause, every place where it deliberately leaves the reference, and the
- * kernels: csrc/c3_fa_rule.h, csrc/c3_fa_reads.h.  Limits: no BAM file is read; haplotypes are an INPUT (haplotag_read with its Levenshtein
- * realignment is not built); 8 channels only (no dwell channel); measured on synthetic reads only.
+ * kernels: csrc/c3_fa_rule.h, csrc/c3_fa_reads.h.  Limits: no BAM file is read; c3_fa_reads takes the haplotypes as an INPUT (c3_fa_reads_phased,
+ * below, computes them from phased variants by the reference's haplotag_read); 8 channels only (no dwell channel); measured on synthetic
+ * reads only.
  *
  *   c3_read_extras    what a window needs beyond c3_read_set: one quality byte per query base (bam_get_qual; read r owns
  *                     qual[qual_first[r] .. qual_first[r + 1]), at least as many as its CIGAR consumes), the HP tag (0 unphased, 1, 2) and,
@@ -1202,6 +1203,66 @@ int c3_fa_lds_reads(void);
  * matrix_depth.  The context's next c3_fa_reads waits for the copy, not for the batch; c3_predict_wait(m, slot) completes the batch. */
 int c3_predict_submit_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host, int slot);
 int c3_predict_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host);
+
+/* ---- haplotagging the reads: the reference's haplotag_read (src/clair3_full_alignment_dwell.c:262-422, called at :629-632) as one host form
+ * and one device form that give the same bytes, on their own (read tags out) and chained in front of the window kernels (the tags never
+ * leave the device).  The rule clause by clause, its quirks and its one deviation: csrc/c3_hap_rule.h; the kernels: csrc/c3_hap_reads.h.
+ * Limits: het SNPs only, as the reference; no VCF or BAM indexing; measured on synthetic read sets only.
+ *
+ *   c3_phased_variants   the phased heterozygous SNPs of ONE contig: pos 0-based and strictly ascending, alt_base a byte, genotype 1 (0|1)
+ *                     or 2 (1|0), phase_set.  n == 0: every read is tagged 0
+ *   c3_haplotag_config   min_haplotag_mq: reads below it are tagged 0 (the reference's constant is 20)
+ *   c3_fa_haplotag    tags every read of the set (no flag or name filter; any read order) on the device; _host: the same rule as sequential
+ *                     host C, works in a context created with device < 0.  ref_bytes[i] is the reference at ref_first + i and must cover
+ *                     [v - 10, v + 11) of every variant v under a read that is tagged.  Refused with 1 and a message, before anything is
+ *                     queued: null arrays, positions not strictly ascending, a genotype that is not 1 or 2, an uncovered context, and
+ *                     what c3_pileup_reads refuses in a read set.  The tags stay in the context (after a device call: on the device) until
+ *                     the next haplotag call
+ *   c3_fa_haplotag_sizes   of the held tags: reads, (read, variant) pairs
+ *   c3_fa_haplotag_result  copies out the tags hap (n_reads) and, for tests and diagnostics, the allele of every pair (0 none, 1 reference,
+ *                     2 alternative) in read order, then variant order, with the n_reads + 1 offsets pair_first.  The pairs of a read: the
+ *                     variants in [pos, end) (and at end when an I op stands there); a read below the mapq has none.  A null pointer skips
+ *                     an array
+ *   c3_fa_haplotag_stats   of the held tags (a device call's are counted when asked for, from one fetch)
+ *   c3_fa_haplotag_shape   constants of the device path, for tests: pairs per workgroup of the pair kernel, pairs per step of the vote kernel
+ *   c3_fa_reads_phased   c3_fa_haplotag and c3_fa_reads in one call: extras->haplotype is not read and may be NULL.  On the device the vote
+ *                     kernel writes the array the window kernels read, on the context's stream, with no copy to the host in between; when
+ *                     the window step falls back to its host form the tags are fetched once for it.  Refuses what either call refuses.
+ *                     Afterwards c3_fa_reads_result / _sizes / _stats and c3_predict_submit_fa_reads work as after c3_fa_reads, and the
+ *                     c3_fa_haplotag_* readers as after c3_fa_haplotag
+ *   c3_fa_reads_phased_host   the same chain as sequential host C */
+typedef struct c3_phased_variants {
+    int64_t n;
+    const int64_t *pos;         /* [n] 0-based, strictly ascending */
+    const uint8_t *alt_base;    /* [n] */
+    const uint8_t *genotype;    /* [n] 1 = 0|1, 2 = 1|0 */
+    const int32_t *phase_set;   /* [n] */
+} c3_phased_variants;
+typedef struct c3_haplotag_config {
+    int32_t min_haplotag_mq, reserved;
+} c3_haplotag_config;
+typedef struct c3_haplotag_counters {
+    int64_t reads_hap[3];     /* reads tagged 0, 1, 2 (those below the mapq are among the 0s) */
+    int64_t reads_low_mapq;
+    int64_t pairs_realigned;  /* every pair of the offsets */
+    int64_t pairs_allele0;
+    int32_t on_host, reserved;
+    float kernel_ms[8];       /* device calls: staging in, op table, pairs, votes; four unused */
+} c3_haplotag_counters;
+int c3_fa_haplotag(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_phased_variants *variants, const void *ref_bytes, int64_t ref_first,
+                   int64_t ref_len, const c3_haplotag_config *cfg);
+int c3_fa_haplotag_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_phased_variants *variants, const void *ref_bytes,
+                        int64_t ref_first, int64_t ref_len, const c3_haplotag_config *cfg);
+int c3_fa_haplotag_sizes(c3_fa_reads_ctx *g, int64_t *n_reads, int64_t *n_pairs);
+int c3_fa_haplotag_result(c3_fa_reads_ctx *g, uint8_t *hap, int8_t *alleles, int64_t *pair_first);
+int c3_fa_haplotag_stats(c3_fa_reads_ctx *g, c3_haplotag_counters *out);
+int c3_fa_haplotag_shape(int32_t *pair_block, int32_t *vote_chunk);
+int c3_fa_reads_phased(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const c3_phased_variants *variants,
+                       const int64_t *centres, int64_t n_cand, const void *ref_bytes, int64_t ref_first, int64_t ref_len,
+                       const c3_fa_config *fa_cfg, const c3_haplotag_config *hap_cfg);
+int c3_fa_reads_phased_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const c3_phased_variants *variants,
+                            const int64_t *centres, int64_t n_cand, const void *ref_bytes, int64_t ref_first, int64_t ref_len,
+                            const c3_fa_config *fa_cfg, const c3_haplotag_config *hap_cfg);
 
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
