@@ -51,6 +51,7 @@ EXPORTS = (
     "c3_predict_submit_fa_reads", "c3_predict_fa_reads",
     "c3_fa_haplotag", "c3_fa_haplotag_host", "c3_fa_haplotag_sizes", "c3_fa_haplotag_result", "c3_fa_haplotag_stats", "c3_fa_haplotag_shape",
     "c3_fa_reads_phased", "c3_fa_reads_phased_host",
+    "c3_fa_reads_dwell", "c3_fa_reads_dwell_host", "c3_fa_reads_channels", "c3_fa_dwell_cum_host", "c3_fa_dwell_table", "c3_fa_dwell_step",
 )
 # layout of a leave-one-read-out variant (C3_JACKKNIFE_* in include/c3hip.h)
 JACKKNIFE_LAYOUT = {"recentre": 0, "in_place": 1}
@@ -210,6 +211,11 @@ class PileupConfig(C.Structure):
 class ReadExtrasC(C.Structure):
     """c3_read_extras (include/c3hip.h)"""
     _fields_ = [("qual_first", C.c_void_p), ("qual", C.c_void_p), ("haplotype", C.c_void_p), ("name_key", C.c_void_p)]
+
+
+class ReadMovesC(C.Structure):
+    """c3_read_moves (include/c3hip.h)"""
+    _fields_ = [("mv_first", C.c_void_p), ("mv", C.c_void_p)]
 
 
 class FaConfig(C.Structure):
@@ -434,6 +440,13 @@ def lib():
     for fn in (L.c3_fa_reads_phased, L.c3_fa_reads_phased_host):
         fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.POINTER(ReadExtrasC), C.POINTER(PhasedVariantsC), C.c_void_p, C.c_int64, C.c_void_p,
                        C.c_int64, C.c_int64, C.POINTER(FaConfig), C.POINTER(HaplotagConfig)]
+    for fn in (L.c3_fa_reads_dwell, L.c3_fa_reads_dwell_host):
+        fn.argtypes = [C.c_void_p, C.POINTER(ReadSetC), C.POINTER(ReadExtrasC), C.POINTER(ReadMovesC), C.POINTER(PhasedVariantsC), C.c_void_p,
+                       C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FaConfig), C.POINTER(HaplotagConfig)]
+    L.c3_fa_reads_channels.argtypes = [C.c_void_p]
+    L.c3_fa_dwell_cum_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    L.c3_fa_dwell_table.restype = C.c_int64
+    L.c3_fa_dwell_table.argtypes = [C.c_void_p, C.c_void_p]
     L.c3_outcome_maxima.argtypes =[C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.c3_decode_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.c3_model_synchronize.argtypes = [C.c_void_p]

@@ -17,7 +17,8 @@
 //   pileup_scan_kernel  (c3_pileup.h, shared) exclusive sums of the candidates' row counts in candidate order: rows land back to back
 //   fa_fill_kernel      one workgroup per candidate, seven rows a step, one lane per (row, column): fa_pos by binary search in the read's op
 //                       table, the row's insertions by column into LDS, channel 6 by looking left over at most 32 columns, one 8-byte store
-//                       per cell (a row is 264 contiguous bytes)
+//                       per cell (a row is 264 contiguous bytes).  One template on the channel count holds it and the 9-channel form of a
+//                       dwell call (c3_dwell.h), whose 297-byte rows are built in LDS and written out cooperatively
 // A candidate with more overlapping reads than the table holds (cfg.lds_reads lowers the cap) raises a flag: the whole call answers through
 // the host form (stats: fell_back).
 #pragma once
@@ -172,8 +173,18 @@ C3_FA_TEXT __global__ __launch_bounds__(kFaBlock) void fa_cand_kernel(FaParams p
     if (tid == 0) p.tile_n[2 * i] = (uint32_t)n_sel, p.tile_n[2 * i + 1] = deep ? 1u : 0u, p.counts[i] = n_sel;
 }
 
-C3_FA_TEXT __global__ __launch_bounds__(kFaBlock) void fa_fill_kernel(FaParams p) {
+// CH == 8: one 8-byte store per cell.  CH == 9 (cum: the dwell tables): the rows of a step, back to back in LDS, go out as bytes up to the
+// first 4-byte boundary of the step's own range, whole dwords inside it and bytes behind -- the neighbouring candidate's rows start at the
+// next byte, and no byte outside the step's rows is written
+template <int N>
+__device__ __forceinline__ uint8_t *fa_step_rows() {  // (only the 9-channel form names it: the 8-channel kernel's LDS stays as it was)
+    __shared__ uint8_t s_rows[N];
+    return s_rows;
+}
+template <int CH>
+__device__ __forceinline__ void fa_fill_rows(const FaParams &p, const int32_t *cum) {
     __shared__ int32_t s_len[kFaRowsAStep][kFaPositions], s_q[kFaRowsAStep][kFaPositions];
+    constexpr int kRowBytes = kFaPositions * CH;
     const int tid = threadIdx.x, slot = tid / kFaPositions, col = tid - slot * kFaPositions;
     const int64_t i = blockIdx.x;
     const int64_t c = p.centres[i], base = p.tile_base[2 * i];
@@ -193,11 +204,35 @@ C3_FA_TEXT __global__ __launch_bounds__(kFaBlock) void fa_fill_kernel(FaParams p
         __syncthreads();
         if (mine) {
             const int ch6 = fa_ch6(v, r, s_len[slot], s_q[slot], col);
-            p.rows[(base + row) * kFaPositions + col] = fa_cell(v, r, c - kFaFlank + col, f, p.sel_af[i * p.depth + row], ch6);
+            if constexpr (CH == 8) p.rows[(base + row) * kFaPositions + col] = fa_cell(v, r, c - kFaFlank + col, f, p.sel_af[i * p.depth + row], ch6);
+            else {
+                const FaCell9 cell = fa_cell9(v, cum, r, c - kFaFlank + col, f, p.sel_af[i * p.depth + row], ch6);
+                uint8_t *at = fa_step_rows<kFaRowsAStep * kRowBytes>() + slot * kRowBytes + col * CH;
+                for (int b = 0; b < 8; ++b) at[b] = (uint8_t)(cell.lo >> (8 * b));
+                at[8] = cell.dwell;
+            }
         }
         __syncthreads();
+        if constexpr (CH != 8) {
+            const uint8_t *s_rows = fa_step_rows<kFaRowsAStep * kRowBytes>();
+            const int n_step = n - r0 < kFaRowsAStep ? n - r0 : kFaRowsAStep, bytes = n_step * kRowBytes;
+            const int64_t first = (base + r0) * kRowBytes;
+            uint8_t *out = (uint8_t *)p.rows + first;  // (the buffer starts on a 4-byte boundary: hipMalloc)
+            int head = (int)((4 - (first & 3)) & 3);
+            head = head < bytes ? head : bytes;
+            const int words = (bytes - head) >> 2, tail = head + 4 * words;
+            if (tid < head) out[tid] = s_rows[tid];
+            for (int w = tid; w < words; w += kFaBlock) {
+                const uint8_t *b = s_rows + head + 4 * w;
+                *(uint32_t *)(out + head + 4 * w) = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+            }
+            if (tid < bytes - tail) out[tail + tid] = s_rows[tail + tid];
+            __syncthreads();
+        }
     }
 }
+
+C3_FA_TEXT __global__ __launch_bounds__(kFaBlock) void fa_fill_kernel(FaParams p) { fa_fill_rows<kFaChannels>(p, nullptr); }
 
 }  // namespace c3
 
@@ -217,6 +252,12 @@ struct c3_fa_reads_ctx {
         sel_af, centre, ev_count, tiles, flags, counts, rows;
     // haplotagging (c3_hap_reads.h): the tags of the last haplotag call, held on the host or (tags, alleles) on the device
     hipEvent_t hev[5] = {};
+    // the dwell channel (c3_dwell.h): the staged move tables and the reads' cum tables, on the device or (host form, fallback) on the host
+    hipEvent_t dev[4] = {};
+    c3_pileup::Buf mv, mfirst, cum;
+    std::vector<int32_t> cum_host;
+    bool cum_on_host = true;
+    int64_t n_cum = 0;
     c3::HapResult tagged;
     bool tags_on_host = true, hap_counted = true;
     int64_t hap_reads = 0, hap_pairs = 0, hap_ref_first = 0;  // hap_ref_first: the reference position of hap_ref's first byte
@@ -225,7 +266,7 @@ struct c3_fa_reads_ctx {
     std::vector<c3_pileup::Buf *> bufs() {
         return {&pos, &flag, &mapq, &cfirst, &sfirst, &qfirst, &cigar, &seq, &qual, &hap, &kept, &read_end, &premax, &ref, &centres, &op_rpos, &op_q,
                 &op_read, &sel_read, &sel_af, &centre, &ev_count, &tiles, &flags, &counts, &rows, &tags, &alleles, &vpos, &valt, &vgt, &vps,
-                &pair_first, &var_first, &hap_ref};
+                &pair_first, &var_first, &hap_ref, &mv, &mfirst, &cum};
     }
 };
 
@@ -243,17 +284,29 @@ static int hap_stage(c3_fa_reads_ctx *g, const HapJob &job, int64_t n_reads);
 static int hap_launch(c3_fa_reads_ctx *g, const HapJob &job, int64_t n_reads);
 static int hap_fetch_tags(c3_fa_reads_ctx *g);
 
+// the dwell channel of a call (c3_dwell.h): the move tables are staged behind the read set, the table kernel runs beside the op table, the
+// 9-channel fill kernel takes the place of fa_fill_kernel
+struct DwJob {
+    const c3_read_moves *moves;
+    const DwTables *d;
+};
+static int dw_stage(c3_fa_reads_ctx *g, const DwJob &dw, int64_t n_reads);
+static int dw_launch(c3_fa_reads_ctx *g, const DwJob &dw, int64_t n_reads);
+static int dw_fill(c3_fa_reads_ctx *g, const FaParams &p, int64_t n_cand);
+
 static int fa_held_on_host(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &t, const FaView &v, const int64_t *centres, int64_t n_cand,
-                           const c3_fa_config &cfg) {
+                           const c3_fa_config &cfg, const DwJob *dw) {
     int64_t deep = 0;
-    fa_rule_host(rs, t, v, centres, n_cand, cfg, g->host, &deep);
-    g->on_host = true, g->stats.on_host = 1, g->stats.deep_windows = deep, g->stats.rows = (int64_t)(g->host.rows.size() / kFaRowBytes);
+    if (dw) fa_dwell_tables_host(rs, dw->moves, t, *dw->d, g->cum_host), g->cum_on_host = true, g->n_cum = dw->d->n_cum;
+    fa_rule_host(rs, t, v, centres, n_cand, cfg, g->host, &deep, dw ? g->cum_host.data() : nullptr);
+    g->on_host = true, g->stats.on_host = 1, g->stats.deep_windows = deep;
+    g->stats.rows = (int64_t)(g->host.rows.size() / (size_t)(kFaPositions * g->host.channels));
     g->n_cand = n_cand, g->n_rows = g->stats.rows;
     return 0;
 }
 
 static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &t, const FaView &hv, const int64_t *centres, int64_t n_cand,
-                     const c3_fa_config &cfg, const HapJob *job) {
+                     const c3_fa_config &cfg, const HapJob *job, const DwJob *dw) {
     HIP_TRY(hipSetDevice(g->device));
     const int64_t nr = rs->n_reads, n_ops = t.n_ops, D = cfg.matrix_depth;
     const int64_t seq_bytes = t.sfirst[(size_t)nr], qual_bytes = t.qfirst[(size_t)nr];
@@ -285,6 +338,7 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     if (n_ops) HIP_TRY(hipMemsetAsync(g->ev_count.p, 0, (size_t)n_ops * 4, st));
     HIP_TRY(hipMemsetAsync(g->flags.p, 0, 64, st));
     if (job) TRY(hap_stage(g, *job, nr));
+    if (dw) TRY(dw_stage(g, *dw, nr));
     HIP_TRY(hipEventRecord(g->ev[1], st));
     // the op table: pileup_ops_kernel as it is (its kept flag goes to op_read, which nothing here reads)
     PileupParams pp{};
@@ -294,6 +348,7 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     pp.tiles = n_cand, pp.tile_n = (uint32_t *)g->tiles.p, pp.tile_base = pp.tile_n + 2 * n_cand;
     if (nr > 0) PILEUP_LAUNCH(pileup_ops_kernel, (nr + 3) / 4, 256, pp);
     if (job) TRY(hap_launch(g, *job, nr));  // (its time counts under the op table here; c3_fa_haplotag_stats has it apart)
+    if (dw) TRY(dw_launch(g, *dw, nr));     // (likewise; kernel_ms[7] has it apart)
     HIP_TRY(hipEventRecord(g->ev[2], st));
     FaParams p{};
     p.v.n_reads = nr, p.v.pos = pp.pos, p.v.cigar_first = pp.cigar_first, p.v.seq_first = (const int64_t *)g->sfirst.p, p.v.qual_first = (const int64_t *)g->qfirst.p;
@@ -314,19 +369,21 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
     if (over) {  // a candidate with more overlapping reads than the table holds: the host form answers
         g->stats.fell_back = 1;
         if (job) TRY(hap_fetch_tags(g));  // (hv.hap is g->tagged.hap: the tags are fetched once for the host form)
-        return fa_held_on_host(g, rs, t, hv, centres, n_cand, cfg);
+        return fa_held_on_host(g, rs, t, hv, centres, n_cand, cfg, dw);
     }
     const int64_t n_rows = totals[0];
-    TRY(pileup_grow(g->rows, (size_t)n_rows * kFaRowBytes));
+    TRY(pileup_grow(g->rows, (size_t)n_rows * (dw ? kDwRowBytes : kFaRowBytes)));
     p.rows = (uint64_t *)g->rows.p;
-    if (n_rows > 0) PILEUP_LAUNCH(fa_fill_kernel, n_cand, kFaBlock, p);
+    if (n_rows > 0 && dw) TRY(dw_fill(g, p, n_cand));
+    else if (n_rows > 0) PILEUP_LAUNCH(fa_fill_kernel, n_cand, kFaBlock, p);
     HIP_TRY(hipEventRecord(g->ev[5], st));
     HIP_TRY(hipEventRecord(g->ready, st));
     // the records the text is printed from, and the counts (the chained entry makes the slot's row table from them)
     std::vector<FaCentre> centre((size_t)n_cand);
     std::vector<uint32_t> ev_count((size_t)n_ops);
     g->host.clear();
-    g->host.matrix_depth = cfg.matrix_depth, g->host.count.resize((size_t)n_cand), g->host.depth.resize((size_t)n_cand);
+    g->host.matrix_depth = cfg.matrix_depth, g->host.channels = dw ? kDwChannels : kFaChannels;
+    g->host.count.resize((size_t)n_cand), g->host.depth.resize((size_t)n_cand);
     TRY(d2h_staged(g->host.count.data(), p.counts, (size_t)n_cand * 4, st));
     TRY(d2h_staged(centre.data(), p.centre, (size_t)n_cand * sizeof(FaCentre), st));
     if (n_ops) TRY(d2h_staged(ev_count.data(), p.ev_count, (size_t)n_ops * 4, st));
@@ -340,22 +397,37 @@ static int fa_device(c3_fa_reads_ctx *g, const c3_read_set *rs, const FaTables &
         HIP_TRY(hipEventElapsedTime(&ms, g->ev[k], g->ev[k + 1]));
         g->stats.kernel_ms[k] = ms;
     }
+    for (int k = 0; dw && k < 2; ++k) {  // moves staged, dwell table
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, g->dev[2 * k], g->dev[2 * k + 1]));
+        g->stats.kernel_ms[6 + k] = ms;
+    }
     return 0;
 }
 
-static int fa_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_read_extras *ex, const int64_t *centres, int64_t n_cand, const void *ref_bytes,
-                    int64_t ref_first, int64_t ref_len, const c3_fa_config *cfg, bool device, const char *what) {
-    if (!g) return fail("%s: null context", what);
-    // whatever happens below, a refusal included, the context holds no stale result
+// whatever happens next, a refusal included, the context holds no stale result
+static void fa_reset(c3_fa_reads_ctx *g) {
     g->host.clear(), g->on_host = true, g->n_cand = g->n_rows = 0, g->stats = c3_fa_counters{};
-    if (device && g->device < 0) return fail("%s: this context was created without a device (c3_fa_reads_host needs none)", what);
+    g->cum_host.clear(), g->cum_on_host = true, g->n_cum = 0;
+}
+
+static int fa_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_read_extras *ex, const int64_t *centres, int64_t n_cand, const void *ref_bytes,
+                    int64_t ref_first, int64_t ref_len, const c3_fa_config *cfg, bool device, const char *what, const c3_read_moves *moves = nullptr,
+                    bool dwell = false) {
+    if (!g) return fail("%s: null context", what);
+    fa_reset(g);
+    if (device && g->device < 0) return fail("%s: this context was created without a device (the _host entry needs none)", what);
     FaTables t;
     TRY(fa_check(rs, ex, centres, n_cand, ref_bytes, ref_first, ref_len, cfg, t));
+    DwTables d;
+    if (dwell) TRY(fa_dwell_check(moves, t, rs->n_reads, d, what));
+    const DwJob dw{moves, &d};
     g->stats.reads_kept = t.n_kept, g->stats.reads_dropped = t.n_dropped, g->host.matrix_depth = cfg->matrix_depth;
+    g->host.channels = dwell ? kDwChannels : kFaChannels;
     if (n_cand == 0) return 0;
     const FaView v = fa_view(rs, ex, t, (const uint8_t *)ref_bytes, ref_first);
-    if (!device) return fa_held_on_host(g, rs, t, v, centres, n_cand, *cfg);
-    return fa_device(g, rs, t, v, centres, n_cand, *cfg, nullptr);
+    if (!device) return fa_held_on_host(g, rs, t, v, centres, n_cand, *cfg, dwell ? &dw : nullptr);
+    return fa_device(g, rs, t, v, centres, n_cand, *cfg, nullptr, dwell ? &dw : nullptr);
 }
 
 }  // namespace c3
@@ -377,6 +449,7 @@ c3_fa_reads_ctx *c3_fa_reads_create(int device) {
         ok = true;
         for (hipEvent_t &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
         for (hipEvent_t &e : g->hev) ok = ok && hipEventCreate(&e) == hipSuccess;
+        for (hipEvent_t &e : g->dev) ok = ok && hipEventCreate(&e) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&g->ready, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&g->taken, hipEventDisableTiming) == hipSuccess;
         if (!ok) fail("c3_fa_reads_create: hipEventCreate failed");
     }
@@ -384,6 +457,8 @@ c3_fa_reads_ctx *c3_fa_reads_create(int device) {
         for (hipEvent_t e : g->ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : g->hev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : g->dev)
             if (e) (void)hipEventDestroy(e);
         if (g->ready) (void)hipEventDestroy(g->ready);
         if (g->taken) (void)hipEventDestroy(g->taken);
@@ -403,6 +478,8 @@ int c3_fa_reads_destroy(c3_fa_reads_ctx *g) {
         for (hipEvent_t e : g->ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : g->hev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : g->dev)
             if (e) (void)hipEventDestroy(e);
         if (g->ready) (void)hipEventDestroy(g->ready);
         if (g->taken) (void)hipEventDestroy(g->taken);
@@ -445,7 +522,7 @@ int c3_fa_reads_result(c3_fa_reads_ctx *g, void *rows, int32_t *counts, int32_t 
     if (!rows || g->n_rows == 0) return 0;
     if (g->on_host) return memcpy(rows, h.rows.data(), h.rows.size()), 0;
     HIP_TRY(hipSetDevice(g->device));
-    return d2h_staged(rows, g->rows.p, (size_t)g->n_rows * kFaRowBytes, g->stream);
+    return d2h_staged(rows, g->rows.p, (size_t)g->n_rows * kFaPositions * h.channels, g->stream);
 }
 
 int c3_fa_reads_stats(c3_fa_reads_ctx *g, c3_fa_counters *out) {
@@ -464,7 +541,9 @@ int c3_predict_submit_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, i
     TRY(ring_ready(m, slot));
     if (!g) return fail("c3_predict_submit_fa_reads: null context");
     if (m->kind != C3_KIND_FULL_ALIGNMENT) return fail("c3_predict_submit_fa_reads: full-alignment windows need a full-alignment model, this is a pileup handle");
-    if (m->C != kFaChannels) return fail("c3_predict_submit_fa_reads: the handle has %d channels; the windows built from reads have %d (no dwell channel)", m->C, kFaChannels);
+    if (m->C != g->host.channels)
+        return fail("c3_predict_submit_fa_reads: the handle has %d channels; the held windows have %d (c3_fa_reads builds 8, c3_fa_reads_dwell 9 with the dwell channel)",
+                    m->C, g->host.channels);
     if (m->positions != kFaPositions) return fail("c3_predict_submit_fa_reads: the handle has %d positions, the windows %d", m->positions, kFaPositions);
     if (m->depth != g->host.matrix_depth)
         return fail("c3_predict_submit_fa_reads: the handle's depth is %d rows, the held result was built for matrix_depth %d", m->depth, g->host.matrix_depth);

@@ -48,8 +48,9 @@
 //      nt16 code 0, '=', or a reference byte that is no letter) the reference reads out of bounds: here such a byte gives 0 / A.
 // HAPLOTYPES are an input of this rule; haplotag_read with its Levenshtein realignment (:262-422) is stated in c3_hap_rule.h, and
 //   c3_fa_reads_phased (c3_hap_reads.h) runs it in front of this rule in one call.
-// NOT BUILT: reading BAM files; the dwell channel (9-channel handles are refused by the chained entry).  matrix_depth may be 1 .. 128 (the
-//   reference's are 89 and 55).
+// THE DWELL CHANNEL (channel 8 of the 9-channel windows, from the reads' move tables) is stated in c3_dwell_rule.h; c3_fa_reads_dwell
+//   (c3_dwell.h) builds such windows with this rule for channels 0 .. 7, which it leaves as they are.
+// NOT BUILT: reading BAM files.  matrix_depth may be 1 .. 128 (the reference's are 89 and 55).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -137,13 +138,14 @@ C3_FA_HD bool fa_overlaps(const FaView &v, int64_t r, int64_t c) { return v.kept
 struct FaPos {
     int state;  // 0 outside the span (or inside an N op), 1 a base, 2 deleted
     int code, bq;
+    int32_t q;  // the query offset of the base (state 1)
     int32_t ins_first, ins_k, ins_len, ins_q;  // the first and the LAST I op attached (-1: none), the last one's length and query offset
     int32_t del_k, del_len;                    // the D op attached (-1: none)
     int32_t next;                              // the op behind the attached run (the read's op count: none)
 };
 C3_FA_HD FaPos fa_pos(const FaView &v, int64_t r, int64_t at) {
     FaPos f;
-    f.state = 0, f.code = 0, f.bq = 0, f.ins_first = f.ins_k = f.del_k = -1, f.ins_len = f.ins_q = f.del_len = 0, f.next = 0;
+    f.state = 0, f.code = 0, f.bq = 0, f.q = 0, f.ins_first = f.ins_k = f.del_k = -1, f.ins_len = f.ins_q = f.del_len = 0, f.next = 0;
     if (at < v.pos[r] || at >= v.read_end[r]) return f;
     int64_t a = v.cigar_first[r], b = v.cigar_first[r + 1];
     const int64_t c1 = b;
@@ -157,7 +159,7 @@ C3_FA_HD FaPos fa_pos(const FaView &v, int64_t r, int64_t at) {
     const int64_t rp = v.op_rpos[a], len = c >> 4;
     if (pileup_op_base(op)) {
         const int64_t q = v.op_q[a] + (at - rp);
-        f.state = 1, f.code = pileup_code(v.seq, v.seq_first[r], q), f.bq = fa_norm_bq(v.qual[v.qual_first[r] + q]);
+        f.state = 1, f.q = (int32_t)q, f.code = pileup_code(v.seq, v.seq_first[r], q), f.bq = fa_norm_bq(v.qual[v.qual_first[r] + q]);
     } else if (op == kOpD) f.state = 2;
     f.next = (int32_t)c1;
     if (at != rp + len - 1) return f;
@@ -311,7 +313,7 @@ static FaView fa_view(const c3_read_set *rs, const c3_read_extras *ex, const FaT
 
 // ------------------------------------------------------------------------------------------ the held result, the text, the host form
 struct FaResult {
-    int32_t matrix_depth = 0;
+    int32_t matrix_depth = 0, channels = kFaChannels;  // channels: 8, or 9 with the dwell channel (c3_dwell_rule.h)
     std::vector<int8_t> rows;
     std::vector<int32_t> count, depth;
     std::string text;
@@ -347,11 +349,15 @@ static void fa_text(const c3_read_set *rs, const FaTables &t, const int64_t *cen
     }
 }
 
-// the rule, candidate by candidate.  Checked input only (fa_check)
+C3_FA_HD int fa_dwell_value(const FaView &v, const int32_t *cum, int64_t r, const FaPos &f);  // c3_dwell_rule.h
+
+// the rule, candidate by candidate.  Checked input only (fa_check).  cum: the reads' dwell tables (c3_dwell_rule.h); with them a cell has a
+// ninth byte
 static void fa_rule_host(const c3_read_set *rs, const FaTables &t, const FaView &v, const int64_t *centres, int64_t n_cand, const c3_fa_config &cfg,
-                         FaResult &out, int64_t *deep_windows) {
+                         FaResult &out, int64_t *deep_windows, const int32_t *cum = nullptr) {
     out.clear();
-    out.matrix_depth = cfg.matrix_depth;
+    out.matrix_depth = cfg.matrix_depth, out.channels = cum ? kFaChannels + 1 : kFaChannels;
+    const size_t ch = (size_t)out.channels;
     out.count.assign((size_t)n_cand, 0), out.depth.assign((size_t)n_cand, 0);
     std::vector<FaCentre> centre((size_t)n_cand);
     std::vector<uint32_t> ev_count((size_t)t.n_ops, 0);
@@ -438,10 +444,11 @@ static void fa_rule_host(const c3_read_set *rs, const FaTables &t, const FaView 
                 ins_len[p] = shown ? f[p].ins_len : 0, ins_q[p] = shown ? f[p].ins_q : 0;
             }
             const size_t base = out.rows.size();
-            out.rows.resize(base + kFaRowBytes);
+            out.rows.resize(base + kFaPositions * ch);
             for (int p = 0; p < kFaPositions; ++p) {
                 const uint64_t cell = fa_cell(v, r, c - kFaFlank + p, f[p], af, fa_ch6(v, r, ins_len, ins_q, p));
-                for (int b = 0; b < 8; ++b) out.rows[base + (size_t)p * 8 + b] = (int8_t)(cell >> (8 * b));
+                for (int b = 0; b < 8; ++b) out.rows[base + (size_t)p * ch + b] = (int8_t)(cell >> (8 * b));
+                if (cum) out.rows[base + (size_t)p * ch + 8] = (int8_t)fa_dwell_value(v, cum, r, f[p]);
             }
         }
     }
@@ -449,3 +456,5 @@ static void fa_rule_host(const c3_read_set *rs, const FaTables &t, const FaView 
 }
 
 }  // namespace c3
+
+#include "c3_dwell_rule.h"  // (fa_dwell_value, declared above, is defined there)

@@ -209,14 +209,15 @@ static int hap_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_phased_
     return hap_device(g, rs, job);
 }
 
-// tag, then build the windows.  The window rule's checks see extras whose haplotype is the tag array of the context
+// tag, then build the windows.  The window rule's checks see extras whose haplotype is the tag array of the context.  dwell: with the
+// dwell channel from `moves` (c3_dwell.h)
 static int fa_phased_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_read_extras *ex, const c3_phased_variants *vs, const int64_t *centres,
                            int64_t n_cand, const void *ref_bytes, int64_t ref_first, int64_t ref_len, const c3_fa_config *cfg,
-                           const c3_haplotag_config *hcfg, bool device, const char *what) {
+                           const c3_haplotag_config *hcfg, bool device, const char *what, const c3_read_moves *moves = nullptr, bool dwell = false) {
     if (!g) return fail("%s: null context", what);
-    g->host.clear(), g->on_host = true, g->n_cand = g->n_rows = 0, g->stats = c3_fa_counters{};
+    fa_reset(g);
     hap_reset(g);
-    if (device && g->device < 0) return fail("%s: this context was created without a device (c3_fa_reads_phased_host needs none)", what);
+    if (device && g->device < 0) return fail("%s: this context was created without a device (the _host entry needs none)", what);
     if (!ex) return fail("%s: null extras", what);
     HapTables ht;
     TRY(hap_check(rs, vs, ref_bytes, ref_first, ref_len, hcfg, ht));
@@ -227,6 +228,11 @@ static int fa_phased_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_r
     FaTables t;
     const int rc = fa_check(rs, &with, centres, n_cand, ref_bytes, ref_first, ref_len, cfg, t);
     if (rc) return hap_reset(g), rc;
+    DwTables d;
+    if (dwell && fa_dwell_check(moves, t, rs->n_reads, d, what)) return hap_reset(g), 1;
+    const DwJob dwj{moves, &d};
+    const DwJob *dw = dwell ? &dwj : nullptr;
+    g->host.channels = dwell ? kDwChannels : kFaChannels;
     g->stats.reads_kept = t.n_kept, g->stats.reads_dropped = t.n_dropped, g->host.matrix_depth = cfg->matrix_depth;
     g->hap_stats.reads_low_mapq = ht.n_low;
     const HapJob job{vs, &ht, (const uint8_t *)ref_bytes, ref_first};
@@ -235,9 +241,9 @@ static int fa_phased_entry(c3_fa_reads_ctx *g, const c3_read_set *rs, const c3_r
         else TRY(hap_held_on_host(g, hap_view(rs, vs, ht, (const uint8_t *)ref_bytes, ref_first), ht));
         if (n_cand == 0) return 0;
         with.haplotype = rs->n_reads ? g->tagged.hap.data() : &none;  // (hap_rule_host has made a new array)
-        return fa_held_on_host(g, rs, t, fa_view(rs, &with, t, (const uint8_t *)ref_bytes, ref_first), centres, n_cand, *cfg);
+        return fa_held_on_host(g, rs, t, fa_view(rs, &with, t, (const uint8_t *)ref_bytes, ref_first), centres, n_cand, *cfg, dw);
     }
-    const int rc2 = fa_device(g, rs, t, fa_view(rs, &with, t, (const uint8_t *)ref_bytes, ref_first), centres, n_cand, *cfg, &job);
+    const int rc2 = fa_device(g, rs, t, fa_view(rs, &with, t, (const uint8_t *)ref_bytes, ref_first), centres, n_cand, *cfg, &job, dw);
     if (rc2) return rc2;
     const int span[3][2] = {{0, 1}, {2, 3}, {3, 4}};  // staging in (with the window step's), pairs, votes; the op table is the window step's
     const int slot[3] = {0, 2, 3};

@@ -18,6 +18,7 @@
 #include "c3_pileup.h"  // (pileup from reads: no model; its kernels sit in a section of their own behind `.c3_gvcf_text`)
 #include "c3_fa_reads.h"  // (full alignment from reads: its kernels sit in a section of their own behind `.c3_pileup_text`)
 #include "c3_hap_reads.h"  // (haplotagging the reads: its kernels sit in a section of their own behind `.c3_fa_text`)
+#include "c3_dwell.h"  // (the dwell channel of those windows: its kernels sit in a section of their own behind `.c3_hap_text`)
 
 extern "C" {
 

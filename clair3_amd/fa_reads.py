@@ -2,7 +2,9 @@
 (src/clair3_full_alignment_dwell.c:437-1054) from aligned reads as the arrays a BAM record holds (csrc/c3_fa_rule.h states the rule and where
 it leaves the reference, csrc/c3_fa_reads.h holds the kernels).  The reads' haplotypes are an input, or are computed from phased variants
 by the reference's haplotag_read (csrc/c3_hap_rule.h, csrc/c3_hap_reads.h) in the same call.  Limits: no BAM or VCF index is read, het
-SNPs only (as the reference), 8 channels only (no dwell channel).
+SNPs only (as the reference).  With the reads' move tables (ReadMoves) the windows have the ninth, dwell-time channel of
+--enable_dwell_time (csrc/c3_dwell_rule.h, csrc/c3_dwell.h): the caller converts any B subtype of the mv tag to int8 (only zero or
+non-zero matters), and only synthetic tables have been run so far.
 
     pileup_reads.ReadSet.from_arrays(...)                  c3_read_set: BAM's own encoding, reads in COORDINATE ORDER
     ReadExtras.from_arrays(qual_first, qual, haplotype, name_key=None)   c3_read_extras: a quality byte per query base, HP tag, name key
@@ -17,10 +19,14 @@ SNPs only (as the reference), 8 channels only (no dwell channel).
         .haplotag_pairs() the allele of every (read, variant) pair with the n + 1 offsets, .haplotag_stats()
     Context.run(..., variants=V) / fa_windows(..., variants=V)   tag and build the windows in one call: extras need no haplotype, and on
         the device the tags never visit the host
+    ReadMoves.from_arrays(mv_first, mv) / .from_dict        c3_read_moves: the mv tags of the reads back to back, element 0 the stride
+    Context.run(..., moves=M) / fa_windows(..., moves=M)   rows (n_rows, 33, 9): channel 8 is the dwell channel; with or without variants.
+        Context.dwell_table() the per-read prefix tables the cells read; Clair3_F.predict_reads(context) then needs a 9-channel model
 
     python -m clair3_amd.fa_reads --reads X.npz --ref_fn ref.fa --ctgName c --candidates pos.txt [--chkpnt_fn M] [--output_fn F.npz]
                                   [--path device|host] [--min_mq N] [--max_indel_length N] [--matrix_depth N] [--seed N]
                                   [--phased_vcf_fn V.vcf[.gz]]   (the reads are haplotagged from it; X.npz then needs no haplotype)
+                                  [--enable_dwell_time]   (X.npz also holds mv_first and mv; 9-channel windows)
         X.npz: the seven arrays of ReadSet.from_arrays and qual_first, qual, haplotype[, name_key].  pos.txt: one 1-based position per
         line, ascending.  The alt-info lines go to stdout; --output_fn gets rows, counts, depths (and, with --chkpnt_fn, a checkpoint
         of Clair3_F, the probability rows y).
@@ -101,6 +107,39 @@ class ReadExtras:
 
     def __len__(self):
         return len(self.arrays["qual_first"]) - 1
+
+
+class ReadMoves:
+    """c3_read_moves: read r owns mv[mv_first[r] : mv_first[r + 1]], its mv tag as int8 (element 0 is the stride); the arrays are kept
+    alive by this object"""
+
+    def __init__(self, mv_first, mv):
+        self.arrays = {"mv_first": mv_first, "mv": mv}
+        if len(mv_first) < 1:
+            raise ValueError("mv_first of n + 1 offsets expected")
+        if int(mv_first[-1]) > len(mv):
+            raise ValueError("the last offset of mv_first lies behind the end of mv")
+        self.c = _lib.ReadMovesC(mv_first.ctypes.data, mv.ctypes.data if mv.size else None)
+
+    @classmethod
+    def from_arrays(cls, mv_first, mv):
+        return cls(np.ascontiguousarray(mv_first, dtype=np.int64).reshape(-1), np.ascontiguousarray(mv, dtype=np.int8).reshape(-1))
+
+    @classmethod
+    def from_dict(cls, d):
+        """from the dict synthetic.make_read_moves returns, or an .npz"""
+        return cls.from_arrays(d["mv_first"], d["mv"])
+
+    def __len__(self):
+        return len(self.arrays["mv_first"]) - 1
+
+
+def dwell_cum(mv, l, reverse=False):
+    """(cum (l + 1,) int32, has_table) of one read by c3_fa_dwell_cum_host: mv its move table (element 0 the stride), l its query length"""
+    mv = np.ascontiguousarray(mv, dtype=np.int8).reshape(-1)
+    cum = np.zeros(int(l) + 1, np.int32)
+    has = _lib.lib().c3_fa_dwell_cum_host(mv.ctypes.data if mv.size else None, len(mv), int(l), int(bool(reverse)), cum.ctypes.data)
+    return cum, bool(has)
 
 
 def hap_config(**cfg):
@@ -230,9 +269,10 @@ class Context:
         return {"reads_hap": tuple(s.reads_hap), "reads_low_mapq": s.reads_low_mapq, "pairs_realigned": s.pairs_realigned,
                 "pairs_allele0": s.pairs_allele0, "on_host": bool(s.on_host), "kernel_ms": dict(zip(names, list(s.kernel_ms)))}
 
-    def run(self, reads, extras, centres, ref_bytes, ref_first, path=None, variants=None, min_haplotag_mq=None, **cfg):
+    def run(self, reads, extras, centres, ref_bytes, ref_first, path=None, variants=None, min_haplotag_mq=None, moves=None, **cfg):
         """one call; centres 0-based, strictly ascending.  The result stays in the context (after a device call: the rows on the device).
-        variants (PhasedVariants or a dict of its arrays): the reads are haplotagged first and the extras' haplotype is not read"""
+        variants (PhasedVariants or a dict of its arrays): the reads are haplotagged first and the extras' haplotype is not read.
+        moves (ReadMoves or a dict of its arrays): the windows get the dwell channel (9 channels)"""
         if not isinstance(reads, ReadSet):
             reads = ReadSet.from_dict(reads)
         if not isinstance(extras, ReadExtras):
@@ -245,9 +285,20 @@ class Context:
         c = config(**cfg)
         L = _lib.lib()
         args = (centres.ctypes.data if centres.size else None, len(centres), ref.ctypes.data if ref.size else None, int(ref_first), len(ref), C.byref(c))
-        if variants is not None:
-            if not isinstance(variants, PhasedVariants):
-                variants = PhasedVariants.from_dict(variants)
+        if variants is not None and not isinstance(variants, PhasedVariants):
+            variants = PhasedVariants.from_dict(variants)
+        if moves is not None:
+            if not isinstance(moves, ReadMoves):
+                moves = ReadMoves.from_dict(moves)
+            if len(moves) != len(reads):
+                raise ValueError(f"{len(moves)} move tables for {len(reads)} reads")
+            if variants is None and min_haplotag_mq is not None:
+                raise TypeError("min_haplotag_mq without variants")
+            hc = None if variants is None else hap_config(**({} if min_haplotag_mq is None else {"min_haplotag_mq": min_haplotag_mq}))
+            fn, what = (L.c3_fa_reads_dwell, "c3_fa_reads_dwell") if path == "device" else (L.c3_fa_reads_dwell_host, "c3_fa_reads_dwell_host")
+            rc = fn(self.h, C.byref(reads.c), C.byref(extras.c), C.byref(moves.c), None if variants is None else C.byref(variants.c), *args,
+                    None if hc is None else C.byref(hc))
+        elif variants is not None:
             hc = hap_config(**({} if min_haplotag_mq is None else {"min_haplotag_mq": min_haplotag_mq}))
             fn, what = (L.c3_fa_reads_phased, "c3_fa_reads_phased") if path == "device" else (L.c3_fa_reads_phased_host, "c3_fa_reads_phased_host")
             rc = fn(self.h, C.byref(reads.c), C.byref(extras.c), C.byref(variants.c), *args, C.byref(hc))
@@ -268,19 +319,35 @@ class Context:
         return tuple(x.value for x in v) + (d.value,)  # n_cand, n_rows, text_bytes, matrix_depth
 
     def fetch(self):
-        """dict of the held result: rows (n_rows, 33, 8) int8, counts, depths (n_cand,) int32, text (bytes: one line per candidate)"""
+        """dict of the held result: rows (n_rows, 33, 8) int8 (33, 9 after a call with moves), counts, depths (n_cand,) int32, text (bytes:
+        one line per candidate)"""
         n_cand, n_rows, text_bytes, _ = self.sizes()
-        out = {"rows": np.zeros((n_rows, FA_POSITIONS, FA_CHANNELS), np.int8), "counts": np.zeros(n_cand, np.int32), "depths": np.zeros(n_cand, np.int32)}
+        out = {"rows": np.zeros((n_rows, FA_POSITIONS, self.channels()), np.int8), "counts": np.zeros(n_cand, np.int32), "depths": np.zeros(n_cand, np.int32)}
         text = C.create_string_buffer(max(text_bytes, 1))
         ptr = [out[k].ctypes.data if out[k].size else None for k in ("rows", "counts", "depths")]
         _lib.check(_lib.lib().c3_fa_reads_result(self.h, *ptr, text), "c3_fa_reads_result")
         out["text"] = text.raw[:text_bytes]
         return out
 
+    def channels(self):
+        """8, or 9 when the held result has the dwell channel"""
+        return int(_lib.lib().c3_fa_reads_channels(self.h))
+
+    def dwell_table(self):
+        """(qual_first[n] - qual_first[0] + n,) int32: the prefix tables of the last call with moves, read r's l + 1 entries at
+        qual_first[r] - qual_first[0] + r (after a device call: fetched from the device); empty after any other call"""
+        n = int(_lib.lib().c3_fa_dwell_table(self.h, None))
+        if n < 0:
+            raise _lib.C3Error(f"c3_fa_dwell_table: {_lib.last_error()}")
+        cum = np.zeros(n, np.int32)
+        if n and _lib.lib().c3_fa_dwell_table(self.h, cum.ctypes.data) != n:
+            raise _lib.C3Error(f"c3_fa_dwell_table: {_lib.last_error()}")
+        return cum
+
     def stats(self):
         s = _lib.FaCounters()
         _lib.check(_lib.lib().c3_fa_reads_stats(self.h, C.byref(s)), "c3_fa_reads_stats")
-        names = ("staging", "op_table", "candidates", "scan", "fill", "fetch")
+        names = ("staging", "op_table", "candidates", "scan", "fill", "fetch", "moves_staged", "dwell_table")
         return {"reads_kept": s.reads_kept, "reads_dropped": s.reads_dropped, "rows": s.rows, "deep_windows": s.deep_windows,
                 "fell_back": bool(s.fell_back), "on_host": bool(s.on_host), "kernel_ms": dict(zip(names, list(s.kernel_ms)))}
 
@@ -295,12 +362,12 @@ def _shared_context(path):
     return _contexts[key]
 
 
-def fa_windows(reads, extras, centres, ref_bytes, ref_first, path=None, context=None, variants=None, **cfg):
+def fa_windows(reads, extras, centres, ref_bytes, ref_first, path=None, context=None, variants=None, moves=None, **cfg):
     """(rows, counts, depths, alt_info_list) of the candidates at ``centres`` (0-based, strictly ascending, each >= 16).  cfg: DEFAULTS above;
-    variants: the reads are haplotagged from them first (Context.run)"""
+    variants: the reads are haplotagged from them first; moves: rows with the dwell channel (Context.run)"""
     path = path or default_path()
     ctx = context or _shared_context(path)
-    r = ctx.run(reads, extras, centres, ref_bytes, ref_first, path=path, variants=variants, **cfg).fetch()
+    r = ctx.run(reads, extras, centres, ref_bytes, ref_first, path=path, variants=variants, moves=moves, **cfg).fetch()
     return r["rows"], r["counts"], r["depths"], r["text"].decode("ascii").split("\n")[:-1]
 
 
@@ -315,6 +382,7 @@ def main(argv=None):
     ap.add_argument("--output_fn")
     ap.add_argument("--path", choices=("device", "host"))
     ap.add_argument("--phased_vcf_fn", help="phased het SNPs (plain or gzip): the reads are haplotagged from them")
+    ap.add_argument("--enable_dwell_time", action="store_true", help="9-channel windows: the reads file also holds mv_first and mv")
     for name in ("min_mq", "max_indel_length", "matrix_depth", "seed"):
         ap.add_argument("--" + name, type=int, default=DEFAULTS[name])
     a = ap.parse_args(argv)
@@ -323,18 +391,19 @@ def main(argv=None):
         centres = np.array([int(line.split()[0]) - 1 for line in fh if line.strip()], np.int64)
     with np.load(a.reads) as z:
         reads, extras = ReadSet.from_dict(z), ReadExtras.from_dict(z)
+        moves = ReadMoves.from_dict(z) if a.enable_dwell_time else None
     path = a.path or default_path()
     cfg = dict(min_mq=a.min_mq, max_indel_length=a.max_indel_length, matrix_depth=a.matrix_depth, seed=a.seed)
     out = {}
     with Context(0 if path == "device" else None) as ctx:
         variants = PhasedVariants.from_vcf(a.phased_vcf_fn, a.ctgName) if a.phased_vcf_fn else None
-        r = ctx.run(reads, extras, centres, ref, 0, path=path, variants=variants, **cfg).fetch()
+        r = ctx.run(reads, extras, centres, ref, 0, path=path, variants=variants, moves=moves, **cfg).fetch()
         out.update(rows=r["rows"], counts=r["counts"], depths=r["depths"])
         if a.chkpnt_fn:
             import torch
             from .model import Clair3_F
             sd = torch.load(a.chkpnt_fn, map_location="cpu")
-            m = Clair3_F(add_indel_length=True, predict=True).to("cuda:0")
+            m = Clair3_F(add_indel_length=True, predict=True, input_channels=9 if a.enable_dwell_time else 8).to("cuda:0")
             m.eval()
             m.load_state_dict(sd.get("state_dict", sd))
             out["y"] = m.predict_reads(ctx)

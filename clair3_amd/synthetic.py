@@ -1280,6 +1280,48 @@ def sort_read_extras(rs, extras):
             "name_key": extras["name_key"][order]}
 
 
+def make_read_moves(rs, extras, seed, mean=2.2, stall=0.002, untagged=0.05, surplus=0.05, short=0.05):
+    """Nanopore move tables (the mv:B:c tag) for the reads of ``rs`` in the order they have there, as a dict: mv_first (n + 1,) int64 and mv
+    int8, read r owning mv[mv_first[r]:mv_first[r + 1]].  Element 0 of a table is the stride (5: non-zero, and it must not count); up to
+    three zeros may stand in front of the first move.  A move is 1 (now and then -1 or 5) and is followed by its zeros: about ``mean``
+    entries per base; a share ``stall`` of the bases dwells 128 .. 191 entries and a quarter of that share 256 .. 319.  A share
+    ``untagged`` of the reads has no table, a share ``surplus`` more moves than quality bytes (K > l), a share ``short`` fewer (K < l).
+    Seeded; ``rs`` and ``extras`` are not changed."""
+    rng = np.random.default_rng(seed)
+    qlen = np.diff(np.asarray(extras["qual_first"], np.int64))
+    tables = []
+    for l in qlen.tolist():
+        kind = rng.random()
+        if kind < untagged or l == 0:
+            tables.append(np.zeros(0, np.int8))
+            continue
+        k = l
+        if kind < untagged + surplus:
+            k = l + int(rng.integers(1, 6))
+        elif kind < untagged + surplus + short:
+            k = max(l - int(rng.integers(1, 6)), 0)
+        dwell = 1 + rng.poisson(max(mean - 1.0, 0.0), size=k)
+        u = rng.random(k)
+        dwell = np.where(u < stall, 128 + rng.integers(0, 64, size=k), dwell)
+        dwell = np.where(u < stall / 4, 256 + rng.integers(0, 64, size=k), dwell)
+        lead = int(rng.integers(0, 4))
+        at = 1 + lead + np.concatenate([[0], np.cumsum(dwell)]).astype(np.int64)
+        mv = np.zeros(int(at[-1]), np.int8)
+        mv[0] = 5
+        mv[at[:-1]] = np.where(rng.random(k) < 0.9, 1, np.where(rng.random(k) < 0.5, -1, 5))
+        tables.append(mv)
+    return {"mv_first": np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64),
+            "mv": np.concatenate(tables) if tables else np.zeros(0, np.int8)}
+
+
+def sort_read_moves(rs, moves):
+    """``moves`` of the unsorted ``rs`` put into the order sort_read_set(rs) gives the reads"""
+    order = np.argsort(rs["pos"], kind="stable")
+    pieces = [moves["mv"][moves["mv_first"][r]:moves["mv_first"][r + 1]] for r in order]
+    return {"mv_first": np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.int64),
+            "mv": np.concatenate(pieces) if pieces else moves["mv"][:0]}
+
+
 def fa_keys(seed, centre, reads):
     """(n,) uint64: fa_key(seed, centre, read) of csrc/c3_fa_rule.h for the read indices ``reads`` -- the counter hash of subsample mode, the
     selection being subsample_rank(keys, matrix_depth)"""

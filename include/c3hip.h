@@ -1146,8 +1146,8 @@ int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_h
  * aligned reads, as each window's occupied rows and a row count: what c3_predict_submit_rows with row_first == NULL takes (the dense window is
  * the run placed at (matrix_depth - count) / 2).  The rule clause by clause, every place where it deliberately leaves the reference, and the
  * kernels: csrc/c3_fa_rule.h, csrc/c3_fa_reads.h.  Limits: no BAM file is read; c3_fa_reads takes the haplotypes as an INPUT (c3_fa_reads_phased,
- * below, computes them from phased variants by the reference's haplotag_read); 8 channels only (no dwell channel); measured on synthetic
- * reads only.
+ * below, computes them from phased variants by the reference's haplotag_read); these entries build the 8-channel windows, c3_fa_reads_dwell
+ * (further below) the 9-channel ones with the dwell channel; measured on synthetic reads only.
  *
  *   c3_read_extras    what a window needs beyond c3_read_set: one quality byte per query base (bam_get_qual; read r owns
  *                     qual[qual_first[r] .. qual_first[r + 1]), at least as many as its CIGAR consumes), the HP tag (0 unphased, 1, 2) and,
@@ -1162,7 +1162,7 @@ int c3_predict_pileup_reads(c3_model *m, c3_pileup *p, int head_tail, float *y_h
  *                     device) until the next call
  *   c3_fa_reads_host  the same rule as sequential host C; works in a context created with device < 0
  *   c3_fa_reads_sizes of the held result: candidates, rows (the sum of the counts), bytes of text, matrix_depth
- *   c3_fa_reads_result   copies the held result out; a null pointer skips that array.  rows (n_rows, 33, 8) int8, counts (n_cand) int32, centre
+ *   c3_fa_reads_result   copies the held result out; a null pointer skips that array.  rows (n_rows, 33, 8) int8 (33, 9 after c3_fa_reads_dwell), counts (n_cand) int32, centre
  *                     depths (n_cand) int32 (every kept read at the centre, not only the shown ones), the alt-info text: one line per candidate,
  *                     closed by '\n', no terminating NUL, entries in the order of c3_pileup_result's text (X, D by length, I by length then
  *                     bytes, R)
@@ -1182,7 +1182,8 @@ typedef struct c3_fa_config {
 typedef struct c3_fa_counters {
     int64_t reads_kept, reads_dropped, rows, deep_windows;  /* reads_dropped: by flag, mapq or name; deep_windows: more reads than matrix_depth */
     int32_t fell_back, on_host;
-    float kernel_ms[8];  /* device calls: staging in, op table, candidates, scan, fill, fetch of the records; two unused */
+    float kernel_ms[8];  /* device calls: staging in, op table, candidates, scan, fill, fetch of the records; of a dwell call: moves staged
+                          * (a part of the first), dwell table (a part of the second) */
 } c3_fa_counters;
 typedef struct c3_fa_reads_ctx c3_fa_reads_ctx;
 c3_fa_reads_ctx *c3_fa_reads_create(int device);
@@ -1199,8 +1200,8 @@ int c3_fa_lds_reads(void);
  * c3_fa_reads_result returns (row_first == NULL), bit for bit, without the rows visiting the host: they are copied from the context's device
  * buffer into the slot on the lane's stream; the counts (which the call fetched anyway) make the slot's row table on the host.  n_rows_host
  * (may be NULL) receives the number of windows.  Context and model must be on one device; a held result of the host form is staged from
- * the host.  Refused before anything is queued: a pileup handle, a 9-channel handle, a handle whose depth is not the result's
- * matrix_depth.  The context's next c3_fa_reads waits for the copy, not for the batch; c3_predict_wait(m, slot) completes the batch. */
+ * the host.  Refused before anything is queued: a pileup handle, a handle whose channel count is not the held result's (9 channels
+ * against the 8 of c3_fa_reads, or 8 against the 9 of c3_fa_reads_dwell), a handle whose depth is not the result's matrix_depth.  The context's next c3_fa_reads waits for the copy, not for the batch; c3_predict_wait(m, slot) completes the batch. */
 int c3_predict_submit_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host, int slot);
 int c3_predict_fa_reads(c3_model *m, c3_fa_reads_ctx *g, float *y_host, int64_t *n_rows_host);
 
@@ -1263,6 +1264,45 @@ int c3_fa_reads_phased(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_re
 int c3_fa_reads_phased_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const c3_phased_variants *variants,
                             const int64_t *centres, int64_t n_cand, const void *ref_bytes, int64_t ref_first, int64_t ref_len,
                             const c3_fa_config *fa_cfg, const c3_haplotag_config *hap_cfg);
+
+/* ---- the dwell channel from move tables: the 9-channel windows of enable_dwell_time (src/clair3_full_alignment_dwell.c:20-74, :669-672,
+ * :730-744, :905-911).  Channel 8 of a cell is the number of signal blocks the basecaller spent on the cell's base and on the insertions
+ * attached to it, as (int8_t) of the int32 sum -- the reference's cast, no clamp (200 is stored as -56, 256 as 0).  The rule clause by
+ * clause: csrc/c3_dwell_rule.h; the kernels: csrc/c3_dwell.h.  Channels 0 .. 7, counts, depths and text are those of c3_fa_reads.  Limits:
+ * no BAM is read; the caller converts any `B` subtype of the mv tag to int8 (only zero or non-zero matters); synthetic tables only so far.
+ *
+ *   c3_read_moves     the `mv:B:c` tags of the reads of a c3_read_set, back to back: read r owns mv[mv_first[r] .. mv_first[r + 1]), element 0
+ *                     of which is the stride and is skipped.  A read without the tag owns nothing
+ *   c3_fa_reads_dwell c3_fa_reads with the dwell channel.  variants and hap_cfg are both NULL (the haplotypes come from extras, as
+ *                     c3_fa_reads takes them) or both given (the call tags the reads first, as c3_fa_reads_phased does, and the tags stay on
+ *                     the device).  Refused before anything is queued: a null moves, an mv_first that is negative or not non-decreasing,
+ *                     only one of variants and hap_cfg, and whatever c3_fa_reads (and c3_fa_reads_phased) refuses.  Afterwards
+ *                     c3_fa_reads_result returns rows (n_rows, 33, 9), and c3_predict_submit_fa_reads takes a 9-channel handle
+ *   c3_fa_reads_dwell_host   the same rule as sequential host C; works in a context created with device < 0
+ *   c3_fa_reads_channels     8 or 9: the channels of the held result's rows
+ *   c3_fa_dwell_cum_host     the per-read rule on its own: cum_out[0 .. l] with cum_out[q] the sum of the signal lengths of the query bases
+ *                     in front of q, in the order the BAM stores the bases (reverse != 0: a read with flag & 16); l: the read's quality
+ *                     bytes.  Returns 1 when the read has a table, 0 when it has none (L <= 1 or l == 0; cum_out is then all zero)
+ *   c3_fa_dwell_table the cum arrays of the last dwell call, read r at [qual_first[r] + r - qual_first[0] ..): qual_first[n] - qual_first[0]
+ *                     + n int32, from the device after a device call.  Returns that number (0 when the last call was no dwell call), -1 on
+ *                     an error; cum_out == NULL: nothing is copied
+ *   c3_fa_dwell_step  a constant of the device path, for tests: the bytes of the staged tables one step of the table kernel covers.  The
+ *                     steps of a read start at the 16-byte boundary at or in front of its table's first byte (the staged array starts at
+ *                     mv_first[0]) */
+typedef struct c3_read_moves {
+    const int64_t *mv_first;  /* [n + 1] */
+    const int8_t *mv;
+} c3_read_moves;
+int c3_fa_reads_dwell(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const c3_read_moves *moves,
+                      const c3_phased_variants *variants, const int64_t *centres, int64_t n_cand, const void *ref_bytes, int64_t ref_first,
+                      int64_t ref_len, const c3_fa_config *fa_cfg, const c3_haplotag_config *hap_cfg);
+int c3_fa_reads_dwell_host(c3_fa_reads_ctx *g, const c3_read_set *reads, const c3_read_extras *extras, const c3_read_moves *moves,
+                           const c3_phased_variants *variants, const int64_t *centres, int64_t n_cand, const void *ref_bytes, int64_t ref_first,
+                           int64_t ref_len, const c3_fa_config *fa_cfg, const c3_haplotag_config *hap_cfg);
+int c3_fa_reads_channels(c3_fa_reads_ctx *g);
+int c3_fa_dwell_cum_host(const int8_t *mv, int64_t L, int64_t l, int reverse, int32_t *cum_out);
+int64_t c3_fa_dwell_table(c3_fa_reads_ctx *g, int32_t *cum_out);
+int c3_fa_dwell_step(void);
 
 /* Per-kernel-family HIP-event timing on the launch stream.  enable=1 brackets every kernel launch with
  * hipEvents (small overhead -- keep it off when measuring whole-job throughput). */
